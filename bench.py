@@ -15,16 +15,20 @@ samples [r*S, (r+1)*S) of each super-block; every pass each rank receives the he
 right neighbour's shard (the composed ntaps-1 overlap of all four stages, ~4.4k samples =
 8.7 KB of u8) through the LIBRARY's RCCL point-to-point (sdrhip_fm_chain_halo_exchange:
 ncclSend/ncclRecv on the compute stream) and processes shard+halo; torch.distributed (gloo)
-is only the control plane.  Per-GPU work is fixed: weak scaling.  The same run also reports
-BASELINE configs[4]'s shard size (2^20 samples per GPU per pass).
+is only the control plane.  Per-GPU work is fixed: weak scaling.  With --full the same run also
+reports BASELINE configs[4]'s shard size (2^20 samples per GPU per pass).
 
-The LAST line of stdout (rank 0) is ONE JSON object of < 4 KB: the driver's contract fields plus
-`roofline` (dominant kernel = the fused convert+decimate kernel, timed with HIP events on its
-own stream inside the timed region) and `cpu_baseline` (the reference's own C kernels,
-oracle/_ref, timed on this host's cores; N=1 only) and a few short companions (configs[1]'s
-roofline, stage times, configs[4]'s shard).  Everything else the run measures (ceilings, launch-size
-sweep, host-streamed rates, power) is printed BEFORE it, one object per line prefixed `extras <name> `,
-and written to gpurun_out/bench_extras_<N>gpu.json (contract_line / emit below).
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and
+prints ONE JSON line: the driver's contract fields (`value`, `ms_per_step` = milliseconds of one
+timed step, ...) and the configuration.  --dump-outputs DIR also writes the audio of the last
+timed step (dump_outputs below).  --full adds everything else: the LAST line of stdout (rank 0)
+is then ONE JSON object of < 4 KB: the contract fields plus `roofline` (dominant kernel = the
+fused convert+decimate kernel, timed with HIP events on its own stream, in a one-pass-at-a-time
+run of its own) and `cpu_baseline` (the reference's own C kernels, oracle/_ref, timed on this
+host's cores; N=1 only) and a few short companions (configs[1]'s roofline, stage times,
+configs[4]'s shard).  Everything else a full run measures (ceilings, launch-size sweep,
+host-streamed rates, power) is printed BEFORE it, one object per line prefixed `extras <name> `,
+and written to a JSON file beside the run (contract_line / emit below).
 """
 import argparse
 import json
@@ -241,14 +245,15 @@ def contract_line(result):
         line["config"]["halo_transport"] = _short(cfg["halo_transport"], 60)
     if cfg.get("overlap"):
         line["config"]["overlap"] = _short(cfg["overlap"], 90)
-    rf = result.get("roofline") or {}
-    line["roofline"] = _pick(rf, ("bound", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_ms", "algorithmic_flops_per_launch",
-                                  "algorithmic_bytes_per_launch"))
-    line["roofline"]["kernel"] = _short(rf.get("kernel", ""), 120)
-    if rf.get("traffic_note"):
-        line["roofline"]["traffic_note"] = _short(rf["traffic_note"], 120)
-    if isinstance(rf.get("hbm"), dict):
-        line["roofline"]["hbm"] = _pick(rf["hbm"], ("achieved", "peak", "unit", "frac"))
+    rf = result.get("roofline")
+    if isinstance(rf, dict):            # a plain run times no stage on its own: no roofline
+        line["roofline"] = _pick(rf, ("bound", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_ms", "algorithmic_flops_per_launch",
+                                      "algorithmic_bytes_per_launch"))
+        line["roofline"]["kernel"] = _short(rf.get("kernel", ""), 120)
+        if rf.get("traffic_note"):
+            line["roofline"]["traffic_note"] = _short(rf["traffic_note"], 120)
+        if isinstance(rf.get("hbm"), dict):
+            line["roofline"]["hbm"] = _pick(rf["hbm"], ("achieved", "peak", "unit", "frac"))
     c1 = result.get("roofline_config1_cfloat_decimate")
     if isinstance(c1, dict):
         line["roofline_config1"] = {"kernel": _short(c1.get("kernel", ""), 60), "samples_per_launch": c1.get("samples_per_launch"), "bound": "hbm",
@@ -311,14 +316,41 @@ def contract_line(result):
     return line
 
 
+DUMP_SAMPLE = 1 << 22           # audio values --dump-outputs writes at most: 16 MB of float32 + 32 MB of float64 positions
+DUMP_SEED = 8192
+
+
+def dump_outputs(d, audio, rank=0, world=1):
+    """--dump-outputs DIR: the audio the last timed pass wrote (what a caller of sdrhip_fm_chain_run receives) as DIR/audio.npy
+    (float32), and the position of each value in that audio as DIR/audio_index.npy (float64).  Up to DUMP_SAMPLE values: all of
+    them; beyond: one value at a seeded random offset in each of DUMP_SAMPLE equal strides, so that the same arguments always
+    give the same positions.  N > 1: one pair per rank (audio_rank<r>.npy, audio_index_rank<r>.npy)."""
+    import numpy as np
+    import torch
+    n = audio.numel()
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        stride = -(-n // DUMP_SAMPLE)
+        starts = np.arange(0, n, stride, dtype=np.int64)
+        idx = np.minimum(starts + np.random.default_rng(DUMP_SEED).integers(0, stride, starts.size), n - 1)
+    vals = audio[torch.from_numpy(idx).to(audio.device)].cpu().numpy()
+    os.makedirs(d, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    np.save(os.path.join(d, f"audio{tag}.npy"), vals.astype(np.float32))
+    np.save(os.path.join(d, f"audio_index{tag}.npy"), idx.astype(np.float64))
+
+
 def emit(result, args, out=None):
     """Print the run: first the extras (every top-level object of the full result that is not on the contract line), one per
-    stdout line, each prefixed `extras ` so that no line but the last starts with `{`; the full result also goes to
-    gpurun_out/bench_extras_<N>gpu.json (what comes back from a gpurun call; copied to profiles/ by hand).  LAST: the contract line."""
+    stdout line, each prefixed `extras ` so that no line but the last starts with `{`; the full result also goes to a JSON file
+    beside the run (`extras_file` on the contract line; copied to profiles/ by hand).  LAST: the contract line.  A plain run
+    (no --full) prints the contract line alone."""
     out = out or sys.stdout
+    full = getattr(args, "full", True)
     path = None
     try:
-        if getattr(args, "no_extras", False):        # a profiling run (--no-extras) must not overwrite the full result of the run before it
+        if getattr(args, "no_extras", False) or not full:   # a plain or profiling run must not overwrite the full result of the run before it
             raise OSError("no extras collected")
         d = os.path.join(ROOT, "gpurun_out")
         os.makedirs(d, exist_ok=True)
@@ -333,7 +365,7 @@ def emit(result, args, out=None):
     order = [k for k in result if k not in ("roofline_config1_cfloat_decimate", "launch_size_sweep", "host_streamed")] + \
             ["power", "host_streamed", "launch_size_sweep", "roofline_config1_cfloat_decimate"]
     seen = set()
-    for k in order:
+    for k in (order if full else ()):
         if k in seen or k not in result or result[k] is None or k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
                                                                       "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "extras_file"):
             seen.add(k)
@@ -358,8 +390,13 @@ def main():
     ap.add_argument("--passes-per-exchange", type=int, default=1,
                     help="N > 1 ranks: exchange the halos of this many consecutive super-blocks in ONE send/recv pair, then run that many "
                          "passes (sdrhip_fm_chain_halo_exchange_batch): a launch-bound shard cannot hide a point-to-point round trip per pass")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure: CPU baseline, per-stage times and roofline (a run of their own), "
+                         "the companion workloads and the extras; a plain run sets up, warms up, times --steps steps and reports")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the audio the last step computed to DIR/*.npy (a fixed, seeded sample when large)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the contract line (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: only the contract line (profiling runs)")
     ap.add_argument("--cpu-worker", type=float, default=None, help="only the compiled CPU receiver loop, single thread, for this many seconds")
     args = ap.parse_args()
 
@@ -389,9 +426,9 @@ def main():
         plumbing_check(args, rank, world)
         return
 
-    # CPU baseline first (rank 0, N=1 only), before the GPU is touched
+    # CPU baseline first (rank 0, N=1 only, --full), before the GPU is touched
     cpu = None
-    if world == 1 and args.gpus == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.gpus == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline()
 
     import torch
@@ -464,10 +501,12 @@ def main():
     stream = torch.cuda.current_stream()
     sptr = stream.cuda_stream
 
-    def measure(blocks, steps, warmup, passes, ramp_s, timing, graph=False, do_exchange=True, data="uniform", lib_overlap=False, ppe=1):
+    def measure(blocks, steps, warmup, passes, ramp_s, timing, graph=False, do_exchange=True, data="uniform", lib_overlap=False, ppe=1,
+                keep_audio=False):
         """One configuration: `blocks` 8192-sample blocks per GPU per pass.  Returns the max-over-ranks wall time of
         `steps` steps of `passes` passes each, the per-stage HIP-event times and the plan.  graph: the chain's kernels of
-        one pass replayed from a hipGraph captured once (sdrhip_fm_chain_graph_*): one launch per pass instead of one per kernel."""
+        one pass replayed from a hipGraph captured once (sdrhip_fm_chain_graph_*): one launch per pass instead of one per kernel.
+        keep_audio: also return the audio buffer the last timed pass wrote ("audio")."""
         S_len = blocks * BLOCK
         plan = sharding.ShardPlan(chain, rank, world, S_len)          # owned outputs + halo for this rank
         gen = torch.Generator(device="cuda").manual_seed(S.SEED_IQ + rank)
@@ -624,9 +663,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        last_audio = (audio_b if lib_overlap and flip[0] else audio) if keep_audio else None
         same_audio = None
         if lib_overlap:
-            same_audio = bool(torch.equal(audio.view(torch.int32), audio_b.view(torch.int32)))
+            if args.full:
+                same_audio = bool(torch.equal(audio.view(torch.int32), audio_b.view(torch.int32)))
             chain.set_overlap(False)
             del audio_b, buf_b
         stage_ms, runs = ({}, 0)
@@ -650,7 +691,7 @@ def main():
                 crc = gathered
         # what one exchange costs on its own: back-to-back exchanges on the compute stream, nothing else queued (N > 1, RCCL only)
         exch_us = None
-        if world > 1 and do_exchange and comm is not None:
+        if world > 1 and do_exchange and comm is not None and args.full:
             pidx[0] = 0
             torch.cuda.synchronize()
             dist.barrier()
@@ -666,7 +707,8 @@ def main():
         del g_all, g_a, g_b
         del buf, audio, ws, rows, staging
         return {"elapsed": elapsed, "passes": passes, "stage_ms": stage_ms, "plan": plan, "S_len": S_len, "overlap": overlap, "crc": crc,
-                "lib_overlap": lib_overlap, "same_audio": same_audio, "rank_elapsed": rank_elapsed, "ppe": ppe, "exchange_us": exch_us}
+                "lib_overlap": lib_overlap, "same_audio": same_audio, "rank_elapsed": rank_elapsed, "ppe": ppe, "exchange_us": exch_us,
+                "audio": last_audio}
 
     def measure_in_flight(blocks, steps, warmup, nflight, do_exchange=True):
         """Launch-bound shards: `nflight` passes in flight, pass i on HIP stream i % nflight with its own input / audio
@@ -734,7 +776,7 @@ def main():
         return elapsed, passes, S_len, same
 
     dbg = (lambda m: sys.stderr.write(f"bench[{rank}]: {m}\n")) if os.environ.get("BENCH_DEBUG") else (lambda m: None)
-    extras = not args.no_extras
+    extras = args.full and not args.no_extras        # a plain run measures the headline figure only
 
     def k2c_time(x, reps=10, warm=5):
         """The cfloat-in decimate-by-8 kernel (+ seam fix-up) on 2^27 samples: mean launch time by HIP events on its stream."""
@@ -861,12 +903,15 @@ def main():
     # per-kernel durations are not blurred by co-resident kernels (BENCH_NO_LIB_OVERLAP=1: one pass at a time throughout).
     want_overlap = world == 1 and os.environ.get("BENCH_NO_LIB_OVERLAP") != "1" and args.blocks >= 2048
     events_in_region = args.blocks >= 2048 and not want_overlap
-    main_run = measure(args.blocks, args.steps, args.warmup, args.passes_per_step, 0.3, events_in_region, lib_overlap=want_overlap, ppe=max(1, args.passes_per_exchange))
+    main_run = measure(args.blocks, args.steps, args.warmup, args.passes_per_step, 0.3, events_in_region, lib_overlap=want_overlap, ppe=max(1, args.passes_per_exchange),
+                       keep_audio=args.dump_outputs is not None)
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, main_run.pop("audio"), rank, world)
     single_pass = None
-    if want_overlap:
+    if want_overlap and args.full:
         single_pass = measure(args.blocks, args.steps, 1, main_run["passes"], 0.05, True)
         main_run["stage_ms"] = single_pass["stage_ms"]
-    elif not events_in_region:
+    elif not events_in_region and args.full:
         main_run["stage_ms"] = measure(args.blocks, max(2, args.steps // 4), 1, main_run["passes"], 0.05, True)["stage_ms"]
     dbg("main measurement done")
     # the same run on a frequency-modulated carrier instead of uniform random bytes (the chip is power-limited and the power
@@ -1225,7 +1270,7 @@ def main():
         plan, S_len, passes, stage_ms = main_run["plan"], main_run["S_len"], main_run["passes"], main_run["stage_ms"]
         elapsed = main_run["elapsed"]
         total_samples = world * S_len * passes * args.steps
-        k2_s = stage_ms["decimate"] * 1e-3
+        k2_s = stage_ms.get("decimate", 0.0) * 1e-3               # no stage times in a plain run: no roofline either
         # samples the TIMED decimate launch consumed: with the overlapped halo exchange only the chain object that computes
         # [q0, q_mid) carries timing events, and it reads the rank's own shard only
         k2_n = plan.shard_len if main_run["overlap"] else plan.k2_samples
@@ -1281,7 +1326,8 @@ def main():
                                                            if comm is not None else "host memory through gloo (fallback / plumbing check)"),
                 "order": "AVX (bit-exact vs reference AVX path)",
                 "overlap": ("two passes in flight inside the library (sdrhip_fm_chain_set_overlap): consecutive runs alternate between two internal "
-                            "streams and workspace halves; both audio buffers identical: " + str(main_run["same_audio"])) if main_run["lib_overlap"]
+                            "streams and workspace halves" + ("" if main_run["same_audio"] is None else
+                                                              "; both audio buffers identical: " + str(main_run["same_audio"]))) if main_run["lib_overlap"]
                            else "none: one pass at a time on one stream",
             },
             "roofline": {
@@ -1294,7 +1340,7 @@ def main():
                 "peak_note": "f32 VALU with UNFUSED multiply and add (parity forbids FMA; MFMA is an fma chain): 256 CU x 4 SIMD x 32 lanes x 2.4 GHz",
                 "traffic": traffic,
                 **({"traffic_note": traffic_note} if traffic_note else {}),
-                "avg_launch_ms": round(stage_ms["decimate"], 5),
+                "avg_launch_ms": round(stage_ms.get("decimate", 0.0), 5),
                 "algorithmic_flops_per_launch": k2_flops,
                 "algorithmic_bytes_per_launch": k2_alg_bytes,
                 "hbm": {"achieved": round(hbm_achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(hbm_achieved / HBM_PEAK_GBS, 4),
@@ -1326,6 +1372,8 @@ def main():
             "power": power,
             "cpu_baseline": cpu,
         }
+        if "decimate" not in stage_ms:
+            result["roofline"] = None
         emit(result, args)
 
     if comm is not None:

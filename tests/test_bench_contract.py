@@ -163,3 +163,43 @@ def test_world_size_that_disagrees_with_gpus_is_refused():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--no-extras"],
                          capture_output=True, text=True, timeout=120, env=env)
     assert out.returncode == 2 and "refusing" in out.stderr
+
+
+def test_plain_run_prints_the_contract_line_alone(tmp_path, monkeypatch):
+    """A plain run (no --full) prints one JSON line and writes no extras file; its line carries no roofline it did not measure."""
+    import argparse
+    import io
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))
+    plain = {k: v for k, v in _canned_full_result().items() if k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
+                                                                      "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config")}
+    plain.update(roofline=None, cpu_baseline=None, stage_ms={})
+    buf = io.StringIO()
+    bench.emit(plain, argparse.Namespace(full=False, no_extras=False), out=buf)
+    lines = buf.getvalue().splitlines()
+    assert len(lines) == 1 and not os.listdir(str(tmp_path))
+    r = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert r[key] == plain[key], key
+    assert "roofline" not in r and "extras_file" not in r
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert '"--full"' in src and '"--dump-outputs"' in src
+
+
+def test_dump_outputs_is_a_fixed_sample_within_64_mb(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.DUMP_SAMPLE * (4 + 8) <= 64 << 20                    # float32 values + float64 positions
+    audio = torch.arange(1000, dtype=torch.float32) * 0.5
+    bench.dump_outputs(str(tmp_path / "small"), audio)
+    v, i = np.load(tmp_path / "small" / "audio.npy"), np.load(tmp_path / "small" / "audio_index.npy")
+    assert v.dtype == np.float32 and i.dtype == np.float64 and np.array_equal(v, audio.numpy())
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 64)                     # a larger output: a seeded sample, the same every time
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), audio)
+    va, ia = np.load(tmp_path / "a" / "audio.npy"), np.load(tmp_path / "a" / "audio_index.npy")
+    assert va.size <= 64 and np.array_equal(ia, np.load(tmp_path / "b" / "audio_index.npy"))
+    assert np.all(np.diff(ia) > 0) and ia[-1] < 1000 and np.array_equal(va, audio.numpy()[ia.astype(np.int64)])

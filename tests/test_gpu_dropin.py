@@ -106,7 +106,7 @@ def test_decimators_complex(hip, oracle, factor, ntaps):
 
 def test_decimate_avxrc_config2(hip, oracle, ref):
     """BASELINE configs[1]: 127 taps -> 128, /8, one 8192-sample block -> 1009 outputs;
-    also against the reference's own compiled decimateAVXRC when oracle/_ref exists."""
+    also against the reference's own compiled decimateAVXRC (oracle/_ref, or its recorded answer)."""
     x = S.cfloat_block(8192)
     h = np.concatenate([S.taps_decim127(), np.zeros(1, np.float32)])
     hd = duplicate(h)
@@ -179,15 +179,9 @@ def test_fm_demod(hip, oracle):
 def test_dc_blocker(hip, ref):
     x = S.real_block(4096)
     out, fs, fo = hip.DropIn.dc_blocker(x, 0.25, -0.5)
-    import ctypes as C
-    exp = np.empty_like(x)
-    efs, efo = C.c_float(), C.c_float()
-    ref.lib.dcBlocker.argtypes = [C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
-                                  C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    ref.lib.dcBlocker(x.size, 0.25, -0.5, C.byref(efs), C.byref(efo), x.ctypes.data_as(C.POINTER(C.c_float)),
-                      exp.ctypes.data_as(C.POINTER(C.c_float)))
+    exp, efs, efo = ref.dc_blocker(x, 0.25, -0.5)
     assert_bit_equal(out, exp, "dcBlocker")
-    assert fs == efs.value and fo == efo.value
+    assert fs == efs and fo == efo
 
 
 def test_empty_and_tiny_calls(hip, oracle):
