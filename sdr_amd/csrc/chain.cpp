@@ -20,6 +20,7 @@
 
 #include <exception>
 #include "descriptors.hpp"
+#include "host_stream.hpp"
 
 using namespace sdrhip;
 
@@ -628,18 +629,15 @@ int sdrhip_fm_chain_read_timing(sdrhip_fm_chain* c, double* ms_sum, int* runs)
 // memory, `block` samples each -- or a multiple) go in, audio blocks of exactly `block_size_out`
 // floats come out, bit-identical to what the reference's four Pipes + convert + gain yield.
 //
-// Per submission the pinned staging buffer of the current slot holds [carried tail | new samples]
-// contiguously: the tail (the ~4.4k samples earlier pushes delivered and later outputs still need) is
-// kept in a small host-side history and copied in front of the new samples by the host (8 KB), so the
-// device never shuffles it.  Then
-//   * large submissions: ONE hipMemcpyAsync H2D on the upload stream, the chain on the compute stream,
-//     one D2H on the download stream -- three HIP streams, two slots, upload of block i over compute
-//     of i-1 over download of i-2;
-//   * small submissions (<= kDirectSamples): NO copies at all -- the decimator kernel reads the pinned
-//     host buffer directly over PCIe and the last kernel writes the audio straight into pinned host
-//     memory: ONE kernel launch for a push of a few blocks (kernels_small.hip; two launches -- decimator with its seams,
-//     fused tail -- where the one-kernel chain does not apply) and one event per push instead of ~15 API calls, which is
-//     what the reference's own block size (8192 samples) needs to beat one CPU thread.
+// Slots, staging, the carried tail (~4.4k samples, 8 KB copied by the host) and the three submission routes are the
+// host-block engine's (host_stream.hpp).  This operator picks the route by the size of [carried tail | staged samples]:
+//   * large submissions (> direct_samples): the copy engines -- upload of block i over compute of i-1 over download of i-2;
+//   * from stage_samples up: one copy into device memory on the slot's own compute stream, then the chain on device memory;
+//   * a lone source block: NO copies at all -- the decimator kernel reads the pinned host buffer directly over PCIe and the
+//     last kernel writes the audio straight into pinned host memory: ONE kernel launch for a push of a few blocks
+//     (kernels_small.hip; two launches -- decimator with its seams, fused tail -- where the one-kernel chain does not apply)
+//     and one event per push instead of ~15 API calls, which is what the reference's own block size (8192 samples) needs to
+//     beat one CPU thread.
 // Results lag at most nslots - 1 submissions (sdrhip_fm_stream_flush drains); with adaptive submission (the default for
 // operators that run in place) a push that finds the next slot still busy is staged behind the earlier ones and leaves with them.
 // ---------------------------------------------------------------------------
@@ -744,18 +742,10 @@ struct sdrhip_fm_stream {
     // runs in place (round 3): such a push is one small kernel, i.e. ~20 us of latency end to end over PCIe, and the host is
     // done submitting it in ~6 -- the slots are what keeps the GPU fed.  Results then lag three pushes instead of one
     // (sdrhip_fm_stream_flush drains; SDRHIP_STREAM_SLOTS=2 restores the short lag).
-    static constexpr int kMaxSlots = 4;
-    int nslots = 2;
-    hipStream_t compute[kMaxSlots] = {nullptr, nullptr, nullptr, nullptr};   // compute[0]: copy mode; compute[si]: in-place pushes of slot si
-    hipStream_t up = nullptr, down = nullptr;
-    DevBuf din[kMaxSlots];   // device input of the slots (copy mode)
-    DevBuf ws[kMaxSlots];    // one workspace per compute stream
+    DevBuf ws[HostStream::kMaxSlots];    // one workspace per compute stream
     int64_t N = 0;         // samples received so far
     int64_t q_done = 0;    // audio outputs computed so far
-    int64_t head_cap = 0;  // samples of room in front of the staged samples (for the carried tail), multiple of 8
-    std::vector<uint8_t> hist;   // the last `head_cap` samples of the stream (host copy)
-    int64_t hist_n = 0;          // valid samples in hist (they are the stream's samples [N - hist_n, N))
-    bool direct_ok = getenv("SDRHIP_NO_DIRECT_STREAM") == nullptr;
+    bool direct_ok = stream_knobs().direct;
     // [tail | new] up to this many samples is read in place over PCIe (tunable for experiments: SDRHIP_DIRECT_SAMPLES)
     int64_t direct_samples = getenv("SDRHIP_DIRECT_SAMPLES") ? atoll(getenv("SDRHIP_DIRECT_SAMPLES")) : kDirectSamples;
     // round 6 (tools/stream_direct_threshold_probe.py, after the in-place pushes got the largest tile): in place 11.1 / 11.7 / 12.2 Gsample/s
@@ -765,17 +755,6 @@ struct sdrhip_fm_stream {
     static constexpr int64_t kDirectSamples = 200 * 8192;
     // pushes (or piled-up batches) of at least this many samples are copied to device memory on their slot's stream before the chain runs
     int64_t stage_samples = getenv("SDRHIP_STAGE_SAMPLES") ? atoll(getenv("SDRHIP_STAGE_SAMPLES")) : 2 * 8192;
-    struct Slot {
-        PinBuf hin, hout;
-        DevBuf dout;
-        hipEvent_t ev = nullptr, ev_up = nullptr, ev_k = nullptr;
-        int64_t n_out = 0;
-        bool busy = false;
-        bool direct = false;       // the last submission ran in place: `ev` also releases the staging buffer
-    } slot[kMaxSlots];
-    int64_t pushes = 0;        // submissions so far (slot = pushes % nslots)
-    int cur() const { return (int)(pushes % nslots); }
-    int staged = 0;            // samples copied into the current slot's staging buffer, not yet submitted
     int coalesce = 0;          // submit once this many samples are staged (0: every push)
     int adaptive = 0;          // > 0: submit when the next slot is free, else keep staging up to this many samples
     int capacity() const
@@ -783,49 +762,10 @@ struct sdrhip_fm_stream {
         int c = coalesce > max_block ? coalesce : max_block;
         return adaptive > c ? adaptive : c;
     }
-    // is slot si's last submission still running on the GPU?
-    bool in_flight(int si) const { return slot[si].busy && hipEventQuery(slot[si].ev) == hipErrorNotReady; }
-    std::vector<float> fifo;
-    size_t head = 0;
-
-    ~sdrhip_fm_stream()
-    {
-        for (hipStream_t st : {up, compute[0], compute[1], compute[2], compute[3], down})
-            if (st) (void)hipStreamSynchronize(st);
-        for (auto& sl : slot)
-            for (hipEvent_t e : {sl.ev, sl.ev_up, sl.ev_k})
-                if (e) (void)hipEventDestroy(e);
-        for (hipStream_t st : {up, compute[0], compute[1], compute[2], compute[3], down})
-            if (st) (void)hipStreamDestroy(st);
-    }
-    int ready() const { return (int)((fifo.size() - head) / (size_t)block_out); }
-    // harvest, oldest first, every in-flight submission the GPU has finished (never waits)
-    int harvest_done()
-    {
-        for (int64_t k = pushes - (nslots - 1); k < pushes; k++) {
-            if (k < 0) continue;
-            const int si = (int)(k % nslots);
-            if (!slot[si].busy) continue;
-            if (hipEventQuery(slot[si].ev) != hipSuccess) break;     // still running (an error surfaces in the blocking harvest)
-            int rc = harvest(si);
-            if (rc != SDRHIP_OK) return rc;
-        }
-        return SDRHIP_OK;
-    }
-    uint8_t* staged_base(Slot& sl) const { return (uint8_t*)sl.hin.p + 2 * head_cap; }    // where staged sample 0 lives
-    int harvest(int si)
-    {
-        Slot& sl = slot[si];
-        if (!sl.busy) return SDRHIP_OK;
-        SDRHIP_CHECK_HIP(hipEventSynchronize(sl.ev));
-        if (head > 0 && head == fifo.size()) { fifo.clear(); head = 0; }
-        else if (head > (1u << 20) && head * 2 > fifo.size()) { fifo.erase(fifo.begin(), fifo.begin() + head); head = 0; }
-        const size_t old = fifo.size();
-        fifo.resize(old + (size_t)sl.n_out);
-        memcpy(fifo.data() + old, sl.hout.p, (size_t)sl.n_out * sizeof(float));
-        sl.busy = false;
-        return SDRHIP_OK;
-    }
+    int ready() const { return (int)(eng.pending() / (size_t)block_out); }
+    // u8 IQ samples (2 bytes); head room = the carried tail, a multiple of 8 samples.  Declared last: destroyed first, so its
+    // streams are idle before the workspaces are freed.
+    HostStream eng;
 };
 
 extern "C" {
@@ -841,41 +781,26 @@ int sdrhip_fm_stream_create(sdrhip_fm_stream** out, sdrhip_fm_chain* chain, int 
     st->max_block = max_block_samples;
     st->block_out = block_size_out;
     // the carried tail never exceeds the receptive field of one audio output (+ the 8-sample alignment of its start)
-    st->head_cap = (sdrhip_fm_chain_max_halo(chain) + 8 + 15) / 8 * 8;
-    st->hist.resize((size_t)(2 * st->head_cap));
+    const int64_t head_cap = (sdrhip_fm_chain_max_halo(chain) + 8 + 15) / 8 * 8;
     // four slots when even the largest push runs in place (see the struct), else two
-    {
-        const char* env = getenv("SDRHIP_STREAM_SLOTS");
-        int want = (st->direct_ok && st->head_cap + (int64_t)max_block_samples <= st->direct_samples) ? sdrhip_fm_stream::kMaxSlots : 2;
-        if (env && atoi(env) >= 2 && atoi(env) <= sdrhip_fm_stream::kMaxSlots) want = atoi(env);
-        st->nslots = want;
+    const int slots = (st->direct_ok && head_cap + (int64_t)max_block_samples <= st->direct_samples) ? HostStream::kMaxSlots : 2;
+    if (st->eng.init(slots, 2, head_cap, "sdrhip_fm_stream_create") != SDRHIP_OK) {
+        delete st;
+        return SDRHIP_ERR_HIP;
     }
     // adaptive submission by default for operators that run in place (sdrhip_fm_stream_set_adaptive; SDRHIP_STREAM_ADAPTIVE=0
     // switches the default off, =n caps it at n source blocks): up to what is still read in place over PCIe
-    if (st->nslots == sdrhip_fm_stream::kMaxSlots) {
-        const char* env = getenv("SDRHIP_STREAM_ADAPTIVE");
+    if (st->eng.nslots == HostStream::kMaxSlots) {
+        const std::optional<int64_t>& env = stream_knobs().adaptive;
         const int64_t unit = chain->block > 0 ? chain->block : 8;
-        int64_t cap = (st->direct_samples - st->head_cap) / unit;
+        int64_t cap = (st->direct_samples - head_cap) / unit;
         // ... but no more than 64 source blocks' worth (or two of the caller's largest pushes): the one-stream route is within 10 % of its full rate
         // with batches of that size (32: 13-15, 64: 18-21, 199: 20-22 Gsample/s), and what piles up beyond only adds to the push-to-audio lag
         const int64_t enough = std::max<int64_t>((64 * (int64_t)8192 + unit - 1) / unit, 2 * (((int64_t)max_block_samples + unit - 1) / unit));
         if (cap > enough) cap = enough;
-        if (env && atoll(env) < cap) cap = atoll(env);
+        if (env && *env < cap) cap = *env;
         cap *= unit;
         if (cap >= 2 * (int64_t)max_block_samples && cap <= (1 << 30)) st->adaptive = (int)cap;
-    }
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < st->nslots; i++)
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&st->compute[i], hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&st->up, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&st->down, hipStreamNonBlocking);
-    for (auto& sl : st->slot)
-        for (hipEvent_t* ev : {&sl.ev, &sl.ev_up, &sl.ev_k})
-            if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        set_error("sdrhip_fm_stream_create: %s", hipGetErrorString(e));
-        delete st;
-        return SDRHIP_ERR_HIP;
     }
     *out = st;
     return SDRHIP_OK;
@@ -890,42 +815,29 @@ void sdrhip_fm_stream_destroy(sdrhip_fm_stream* st) { delete st; }
 static int stream_submit(sdrhip_fm_stream* st)
 {
     sdrhip_fm_chain* c = st->c;
-    const int n = st->staged;
+    HostStream& e = st->eng;
+    const int n = e.staged;
     if (n == 0) return SDRHIP_OK;
-    const int si = st->cur();
-    sdrhip_fm_stream::Slot& sl = st->slot[si];
+    const int si = e.cur();
     int rc;
     // outputs whose receptive field is complete once these samples are in
     const int64_t N1 = st->N + n;
     int64_t q_new = sdrhip_fm_chain_ready(c, N1);
     if (q_new < st->q_done) q_new = st->q_done;
     // the tail starts at the first sample the next pending output needs, rounded down to a multiple of 8 samples
-    // (16-byte aligned tiles for the LDS-tiled decimator)
+    // (16-byte aligned tiles for the LDS-tiled decimator; tail and head_cap are multiples of 8 samples)
     int64_t keep_from = c->start(st->q_done) & ~(int64_t)7;
     if (keep_from > st->N) keep_from = st->N & ~(int64_t)7;
     const int64_t tail = st->N - keep_from;
-    if (tail > st->hist_n || tail > st->head_cap) {
-        set_error("sdrhip_fm_stream: carried tail of %lld samples exceeds the history (%lld)", (long long)tail, (long long)st->hist_n);
-        return SDRHIP_ERR_STATE;
-    }
-    uint8_t* first = st->staged_base(sl) - 2 * tail;               // 16-byte aligned: tail and head_cap are multiples of 8 samples
-    if (tail > 0) memcpy(first, st->hist.data() + 2 * (st->hist_n - tail), (size_t)(2 * tail));
-    // history for the next submission: the last head_cap samples of [tail | staged] (the tail alone may not reach back far
-    // enough, the staged samples alone may be fewer than head_cap)
-    {
-        const int64_t have = tail + n;
-        const int64_t keep = have < st->head_cap ? have : st->head_cap;
-        memmove(st->hist.data(), first + 2 * (have - keep), (size_t)(2 * keep));
-        st->hist_n = keep;
-    }
+    const uint8_t* first = e.carry(keep_from, st->N, n, "sdrhip_fm_stream");
+    if (first == nullptr) return SDRHIP_ERR_STATE;
 
     const int64_t n_out = q_new - st->q_done;
     const bool direct = st->direct_ok && tail + n <= st->direct_samples;
-    sl.n_out = 0;
-    // In-place pushes alternate between two compute streams (and workspaces): a push of one source block is a few small
+    // In-place pushes alternate between the slots' compute streams (and workspaces): a push of one source block is a few small
     // kernels, i.e. latency, and nothing push i+1 computes depends on what push i left on the device (the carried tail
-    // comes from the host-side history) -- so two consecutive pushes overlap on the GPU.
-    hipStream_t cs = direct ? st->compute[si] : st->compute[0];
+    // comes from the host-side history) -- so consecutive pushes overlap on the GPU.
+    hipStream_t cs = direct ? e.compute[si] : e.compute[0];
     DevBuf& wsb_buf = direct ? st->ws[si] : st->ws[0];
     if (n_out > 0) {
         const size_t wsb = sdrhip_fm_chain_workspace_bytes(c, tail + n);
@@ -934,71 +846,24 @@ static int stream_submit(sdrhip_fm_stream* st)
             SDRHIP_CHECK_HIP(hipStreamSynchronize(cs));
         }
         if ((rc = wsb_buf.ensure(wsb)) != SDRHIP_OK) return rc;
-        if ((rc = sl.hout.ensure((size_t)n_out * 4)) != SDRHIP_OK) return rc;
     }
-    if (direct) {
-        // zero-copy: the kernels read the pinned staging buffer and write the pinned result buffer themselves
-        if (n_out > 0) {
-            if (tail + n >= st->stage_samples) {
-                // ONE pass over the link into device memory on the slot's own compute stream, then the chain on device memory (round 6):
-                // read in place, the one-kernel chain fetches every sample ~1.95 times over PCIe (each tile re-reads its overlap),
-                // and the link is what such a push costs -- 8 ... 64 blocks per push 10-11 -> 19-24 Gsample/s.  No second stream, no
-                // event: the copy and the kernels of a slot are ordered by its stream.
-                DevBuf& dbuf = st->din[si];
-                if ((rc = dbuf.ensure((size_t)(tail + n) * 2 + 64)) != SDRHIP_OK) return rc;
-                SDRHIP_CHECK_HIP(hipMemcpyAsync(dbuf.p, first, (size_t)(tail + n) * 2, hipMemcpyHostToDevice, cs));
-                rc = sdrhip_fm_chain_run(c, (void*)cs, (const uint8_t*)dbuf.p, keep_from, tail + n, (float*)sl.hout.dev, st->q_done, q_new, wsb_buf.p, wsb_buf.cap);
-            } else {
-                // a lone source block (a paced real-time source: the GPU is idle when it arrives): the kernel reads the pinned buffer itself
-                c->input_over_link = true;
-                rc = sdrhip_fm_chain_run(c, (void*)cs, (const uint8_t*)sl.hin.dev_ptr(first), keep_from, tail + n,
-                                         (float*)sl.hout.dev, st->q_done, q_new, wsb_buf.p, wsb_buf.cap);
-                c->input_over_link = false;
-            }
-            if (rc != SDRHIP_OK) return rc;
-            sl.n_out = n_out;
-            sl.busy = true;
-        }
-        // ONE event per push: the results are in pinned memory and the staging buffer is free again when the kernels are done
-        SDRHIP_CHECK_HIP(hipEventRecord(sl.ev, cs));
-        sl.direct = true;
-    } else {
-        DevBuf& dbuf = st->din[si];
-        if ((rc = dbuf.ensure((size_t)(tail + n) * 2 + 64)) != SDRHIP_OK) return rc;
-        // slot si's device buffer was last read by the chain run of submission i-2, harvested before this slot was reopened
-        SDRHIP_CHECK_HIP(hipMemcpyAsync(dbuf.p, first, (size_t)(tail + n) * 2, hipMemcpyHostToDevice, st->up));
-        SDRHIP_CHECK_HIP(hipEventRecord(sl.ev_up, st->up));
-        sl.direct = false;
-        if (n_out > 0) {
-            SDRHIP_CHECK_HIP(hipStreamWaitEvent(st->compute[0], sl.ev_up, 0));
-            if ((rc = sl.dout.ensure((size_t)n_out * 4)) != SDRHIP_OK) return rc;
-            if ((rc = sdrhip_fm_chain_run(c, (void*)st->compute[0], (const uint8_t*)dbuf.p, keep_from, tail + n, (float*)sl.dout.p,
-                                          st->q_done, q_new, st->ws[0].p, st->ws[0].cap)) != SDRHIP_OK) return rc;
-            SDRHIP_CHECK_HIP(hipEventRecord(sl.ev_k, st->compute[0]));
-            SDRHIP_CHECK_HIP(hipStreamWaitEvent(st->down, sl.ev_k, 0));
-            SDRHIP_CHECK_HIP(hipMemcpyAsync(sl.hout.p, sl.dout.p, (size_t)n_out * 4, hipMemcpyDeviceToHost, st->down));
-            SDRHIP_CHECK_HIP(hipEventRecord(sl.ev, st->down));
-            sl.n_out = n_out;
-            sl.busy = true;
-        }
-    }
+    // From stage_samples up, ONE pass over the link into device memory on the slot's own compute stream, then the chain on device
+    // memory (round 6): read in place, the one-kernel chain fetches every sample ~1.95 times over PCIe (each tile re-reads its
+    // overlap), and the link is what such a push costs -- 8 ... 64 blocks per push 10-11 -> 19-24 Gsample/s.  A lone source block
+    // (a paced real-time source: the GPU is idle when it arrives) is read in place by the kernel itself.
+    const HostStream::Route route = !direct ? HostStream::kCopyEngines
+                                  : tail + n >= st->stage_samples ? HostStream::kSlotStream : HostStream::kInPlace;
+    rc = e.submit(route, cs, first, (size_t)(tail + n) * 2, n_out, [&](hipStream_t s, const void* d_in, void* d_out) {
+        c->input_over_link = route == HostStream::kInPlace;
+        const int r = sdrhip_fm_chain_run(c, (void*)s, (const uint8_t*)d_in, keep_from, tail + n, (float*)d_out, st->q_done, q_new,
+                                          wsb_buf.p, wsb_buf.cap);
+        c->input_over_link = false;
+        return r;
+    });
+    if (rc != SDRHIP_OK) return rc;
     st->q_done = q_new;
     st->N = N1;
-    st->pushes++;
-    st->staged = 0;
-    return st->harvest(st->cur());      // the oldest submission: its slot is the next to be filled
-}
-
-// make the current slot's staging buffer writable (its previous upload / in-place read and its download are over)
-static int stream_open_slot(sdrhip_fm_stream* st)
-{
-    sdrhip_fm_stream::Slot& sl = st->slot[st->cur()];
-    int rc;
-    if (st->staged == 0) {
-        if ((rc = st->harvest(st->cur())) != SDRHIP_OK) return rc;
-        SDRHIP_CHECK_HIP(hipEventSynchronize(sl.direct ? sl.ev : sl.ev_up));
-    }
-    return sl.hin.ensure((size_t)(st->head_cap + st->capacity()) * 2);
+    return SDRHIP_OK;
 }
 
 extern "C" {
@@ -1006,10 +871,10 @@ extern "C" {
 int sdrhip_fm_stream_set_coalesce(sdrhip_fm_stream* st, int samples)
 {
     SDRHIP_REQUIRE(st != nullptr && samples >= 0, "sdrhip_fm_stream_set_coalesce");
-    SDRHIP_REQUIRE(st->staged == 0, "sdrhip_fm_stream_set_coalesce: samples are staged (flush first)");
+    SDRHIP_REQUIRE(st->eng.staged == 0, "sdrhip_fm_stream_set_coalesce: samples are staged (flush first)");
     SDRHIP_REQUIRE(st->c->block == 0 || samples % st->c->block == 0, "sdrhip_fm_stream_set_coalesce: whole source blocks only");
-    for (hipStream_t s : {st->up, st->compute[0], st->compute[1], st->compute[2], st->compute[3], st->down})
-        if (s) SDRHIP_CHECK_HIP(hipStreamSynchronize(s));   // staging buffers may be reallocated
+    int rc = st->eng.sync();   // staging buffers may be reallocated
+    if (rc != SDRHIP_OK) return rc;
     st->coalesce = samples;
     return SDRHIP_OK;
 }
@@ -1017,11 +882,11 @@ int sdrhip_fm_stream_set_coalesce(sdrhip_fm_stream* st, int samples)
 int sdrhip_fm_stream_set_adaptive(sdrhip_fm_stream* st, int max_samples)
 {
     SDRHIP_REQUIRE(st != nullptr && max_samples >= 0, "sdrhip_fm_stream_set_adaptive");
-    SDRHIP_REQUIRE(st->staged == 0, "sdrhip_fm_stream_set_adaptive: samples are staged (flush first)");
+    SDRHIP_REQUIRE(st->eng.staged == 0, "sdrhip_fm_stream_set_adaptive: samples are staged (flush first)");
     SDRHIP_REQUIRE(st->c->block == 0 || max_samples % st->c->block == 0, "sdrhip_fm_stream_set_adaptive: whole source blocks only");
     SDRHIP_REQUIRE(max_samples == 0 || max_samples >= 2 * st->max_block, "sdrhip_fm_stream_set_adaptive: room for at least two pushes");
-    for (hipStream_t s : {st->up, st->compute[0], st->compute[1], st->compute[2], st->compute[3], st->down})
-        if (s) SDRHIP_CHECK_HIP(hipStreamSynchronize(s));   // staging buffers may be reallocated
+    int rc = st->eng.sync();   // staging buffers may be reallocated
+    if (rc != SDRHIP_OK) return rc;
     st->adaptive = max_samples;
     return SDRHIP_OK;
 }
@@ -1029,10 +894,11 @@ int sdrhip_fm_stream_set_adaptive(sdrhip_fm_stream* st, int max_samples)
 uint8_t* sdrhip_fm_stream_input_buffer(sdrhip_fm_stream* st)
 {
     if (st == nullptr) { set_error("sdrhip_fm_stream_input_buffer: null stream"); return nullptr; }
+    HostStream& e = st->eng;
     // the caller may write up to max_block samples: make room for all of them behind what is already staged
-    if (st->staged + st->max_block > st->capacity() && stream_submit(st) != SDRHIP_OK) return nullptr;
-    if (stream_open_slot(st) != SDRHIP_OK) return nullptr;
-    return st->staged_base(st->slot[st->cur()]) + (size_t)st->staged * 2;
+    if (e.staged + st->max_block > st->capacity() && stream_submit(st) != SDRHIP_OK) return nullptr;
+    if (e.open_slot((size_t)st->capacity() * 2, (size_t)e.staged * 2) != SDRHIP_OK) return nullptr;
+    return e.write_pos();
 }
 
 int sdrhip_fm_stream_push(sdrhip_fm_stream* st, const uint8_t* iq, int n)
@@ -1040,24 +906,25 @@ int sdrhip_fm_stream_push(sdrhip_fm_stream* st, const uint8_t* iq, int n)
     SDRHIP_REQUIRE(st != nullptr && iq != nullptr && n > 0 && n <= st->max_block, "sdrhip_fm_stream_push");
     SDRHIP_REQUIRE(st->c->block == 0 || n % st->c->block == 0,
                    "sdrhip_fm_stream_push: the chain reproduces the seams of `block`-sample source buffers (fm.hs:17,24)");
+    HostStream& e = st->eng;
     int rc;
-    if (st->staged + n > st->capacity() && (rc = stream_submit(st)) != SDRHIP_OK) return rc;
-    if ((rc = stream_open_slot(st)) != SDRHIP_OK) return rc;
-    uint8_t* dst = st->staged_base(st->slot[st->cur()]) + (size_t)st->staged * 2;
+    if (e.staged + n > st->capacity() && (rc = stream_submit(st)) != SDRHIP_OK) return rc;
+    if ((rc = e.open_slot((size_t)st->capacity() * 2, (size_t)e.staged * 2)) != SDRHIP_OK) return rc;
+    uint8_t* dst = e.write_pos();
     if (iq != dst) st->copier.copy(dst, iq, (size_t)n * 2);   // else: the caller filled our staging buffer in place
-    st->staged += n;
-    bool submit = st->staged >= st->coalesce;
+    e.staged += n;
+    bool submit = e.staged >= st->coalesce;
     if (st->adaptive > 0 && st->coalesce == 0 && submit) {     // an explicit set_coalesce takes precedence: fixed batches
         // a GPU that keeps up gets every push at once (lowest latency); one that is still busy with the slot this submission
         // would move on to lets the pushes pile up in the staging buffer and takes them as ONE launch when it frees up
-        const bool room = st->staged + st->max_block <= st->capacity();
-        submit = !room || !st->in_flight((st->cur() + 1) % st->nslots);
+        const bool room = e.staged + st->max_block <= st->capacity();
+        submit = !room || !e.next_in_flight();
     }
     if (submit) {
         if ((rc = stream_submit(st)) != SDRHIP_OK) return rc;
         // a push that went out also collects whatever the GPU has finished meanwhile: a source slower than the GPU gets the
         // audio of push i at push i + 1 instead of i + nslots - 1 (staged pushes skip the query)
-        if ((rc = st->harvest_done()) != SDRHIP_OK) return rc;
+        if ((rc = e.harvest_done()) != SDRHIP_OK) return rc;
     }
     return st->ready();
 }
@@ -1065,7 +932,7 @@ int sdrhip_fm_stream_push(sdrhip_fm_stream* st, const uint8_t* iq, int n)
 int sdrhip_fm_stream_poll(sdrhip_fm_stream* st)
 {
     SDRHIP_REQUIRE(st != nullptr, "sdrhip_fm_stream_poll");
-    int rc = st->harvest_done();
+    int rc = st->eng.harvest_done();
     if (rc != SDRHIP_OK) return rc;
     return st->ready();
 }
@@ -1074,10 +941,7 @@ int sdrhip_fm_stream_flush(sdrhip_fm_stream* st)
 {
     SDRHIP_REQUIRE(st != nullptr, "sdrhip_fm_stream_flush");
     int rc;
-    if ((rc = stream_submit(st)) != SDRHIP_OK) return rc;
-    const int first = st->cur();        // oldest first: the audio goes into the fifo in push order
-    for (int k = 0; k < st->nslots; k++)
-        if ((rc = st->harvest((first + k) % st->nslots)) != SDRHIP_OK) return rc;
+    if ((rc = stream_submit(st)) != SDRHIP_OK || (rc = st->eng.flush()) != SDRHIP_OK) return rc;
     return st->ready();
 }
 
@@ -1101,13 +965,13 @@ size_t sdrhip_fm_stream_state_bytes(sdrhip_fm_stream* st)
     if (st == nullptr) return 0;
     // exact: drains the operator exactly as sdrhip_fm_stream_save will (0 = the drain failed, sdrhip_last_error)
     if (sdrhip_fm_stream_flush(st) < 0) return 0;
-    return sizeof(StreamStateHeader) + (size_t)(2 * st->hist_n) + (st->fifo.size() - st->head) * sizeof(float);
+    return sizeof(StreamStateHeader) + st->eng.state_bytes(st->eng.hist_n, (int64_t)st->eng.pending());
 }
 
 int sdrhip_fm_stream_save(sdrhip_fm_stream* st, void* buf, size_t capacity, size_t* used)
 {
     SDRHIP_REQUIRE(st != nullptr && buf != nullptr && used != nullptr, "sdrhip_fm_stream_save");
-    int rc = sdrhip_fm_stream_flush(st);             // submits what is staged, drains both slots into the fifo
+    int rc = sdrhip_fm_stream_flush(st);             // submits what is staged, drains every slot into the fifo
     if (rc < 0) return rc;
     StreamStateHeader h;
     memset(&h, 0, sizeof h);
@@ -1115,23 +979,19 @@ int sdrhip_fm_stream_save(sdrhip_fm_stream* st, void* buf, size_t capacity, size
     h.version = 1;
     h.N = st->N;
     h.q_done = st->q_done;
-    h.head_cap = st->head_cap;
-    h.hist_n = st->hist_n;
-    h.pending = (int64_t)(st->fifo.size() - st->head);
+    h.head_cap = st->eng.head_cap;
+    h.hist_n = st->eng.hist_n;
+    h.pending = (int64_t)st->eng.pending();
     h.block_out = st->block_out;
     h.chain_block = st->c->block;
     h.chain_halo = sdrhip_fm_chain_max_halo(st->c);
-    const size_t need = sizeof h + (size_t)(2 * h.hist_n) + (size_t)h.pending * sizeof(float);
+    const size_t need = sizeof h + st->eng.state_bytes(h.hist_n, h.pending);
     if (capacity < need) {
         set_error("sdrhip_fm_stream_save: %zu bytes needed, %zu given", need, capacity);
         return SDRHIP_ERR_ARG;
     }
-    unsigned char* p = (unsigned char*)buf;
-    memcpy(p, &h, sizeof h);
-    p += sizeof h;
-    memcpy(p, st->hist.data(), (size_t)(2 * h.hist_n));
-    p += 2 * h.hist_n;
-    if (h.pending > 0) memcpy(p, st->fifo.data() + st->head, (size_t)h.pending * sizeof(float));
+    memcpy(buf, &h, sizeof h);
+    st->eng.save((unsigned char*)buf + sizeof h);
     *used = need;
     return SDRHIP_OK;
 }
@@ -1139,25 +999,20 @@ int sdrhip_fm_stream_save(sdrhip_fm_stream* st, void* buf, size_t capacity, size
 int sdrhip_fm_stream_restore(sdrhip_fm_stream* st, const void* buf, size_t bytes)
 {
     SDRHIP_REQUIRE(st != nullptr && buf != nullptr && bytes >= sizeof(StreamStateHeader), "sdrhip_fm_stream_restore");
-    SDRHIP_REQUIRE(st->N == 0 && st->staged == 0 && st->pushes == 0, "sdrhip_fm_stream_restore: only into a stream that has not been pushed to");
+    SDRHIP_REQUIRE(st->N == 0 && st->eng.staged == 0 && st->eng.pushes == 0,
+                   "sdrhip_fm_stream_restore: only into a stream that has not been pushed to");
     StreamStateHeader h;
     memcpy(&h, buf, sizeof h);
     SDRHIP_REQUIRE(h.magic == kStateMagic && h.version == 1, "sdrhip_fm_stream_restore: not a stream state");
-    SDRHIP_REQUIRE(h.block_out == st->block_out && h.chain_block == st->c->block && h.head_cap == st->head_cap &&
+    SDRHIP_REQUIRE(h.block_out == st->block_out && h.chain_block == st->c->block && h.head_cap == st->eng.head_cap &&
                        h.chain_halo == sdrhip_fm_chain_max_halo(st->c),
                    "sdrhip_fm_stream_restore: the state belongs to a stream of another geometry (chain taps / block sizes)");
     SDRHIP_REQUIRE(h.hist_n >= 0 && h.hist_n <= h.head_cap && h.pending >= 0 && h.N >= h.hist_n && h.q_done >= 0,
                    "sdrhip_fm_stream_restore: inconsistent state");
-    SDRHIP_REQUIRE(bytes >= sizeof h + (size_t)(2 * h.hist_n) + (size_t)h.pending * sizeof(float), "sdrhip_fm_stream_restore: truncated state");
-    const unsigned char* p = (const unsigned char*)buf + sizeof h;
-    memcpy(st->hist.data(), p, (size_t)(2 * h.hist_n));
-    p += 2 * h.hist_n;
-    st->hist_n = h.hist_n;
+    SDRHIP_REQUIRE(bytes >= sizeof h + st->eng.state_bytes(h.hist_n, h.pending), "sdrhip_fm_stream_restore: truncated state");
+    st->eng.restore((const unsigned char*)buf + sizeof h, h.hist_n, h.pending);
     st->N = h.N;
     st->q_done = h.q_done;
-    st->fifo.resize((size_t)h.pending);
-    st->head = 0;
-    if (h.pending > 0) memcpy(st->fifo.data(), p, (size_t)h.pending * sizeof(float));
     return st->ready();
 }
 
@@ -1166,8 +1021,7 @@ int sdrhip_fm_stream_pop(sdrhip_fm_stream* st, float* out, int capacity)
     SDRHIP_REQUIRE(st != nullptr && out != nullptr, "sdrhip_fm_stream_pop");
     if (st->ready() <= 0) return 0;
     SDRHIP_REQUIRE(capacity >= st->block_out, "sdrhip_fm_stream_pop: capacity smaller than the block");
-    memcpy(out, st->fifo.data() + st->head, (size_t)st->block_out * sizeof(float));
-    st->head += (size_t)st->block_out;
+    st->eng.take((size_t)st->block_out, out);
     return st->block_out;
 }
 

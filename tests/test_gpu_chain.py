@@ -1,5 +1,7 @@
 """GPU parity: the whole FM receiver (examples/fm/fm.hs:34-41) as one device-resident
 chain vs the restated Pipes, single launch and sharded with a right halo."""
+import struct
+
 import numpy as np
 import pytest
 
@@ -585,33 +587,54 @@ def test_chain_run_as_hipgraph(hip, oracle):
             ch.enable_timing(False)
 
 
-def test_fm_stream_crosses_the_in_place_threshold(hip, oracle):
-    """sdrhip_fm_stream: pushes of 1 block (the kernel reads the pinned buffer in place), 7, 16 and 199 blocks (one pass over the link on
-    the slot's own stream, then the one-kernel chain on device memory: the limit is 200 blocks including the carried tail), 200 and 230
-    blocks (three-stream copy path, stage kernels) in one stream, against one device-resident run."""
-    pattern = [1, 1, 7, 200, 1, 16, 1, 199, 230, 7, 1, 2, 200, 1]
-    nblk = sum(pattern) * 3
-    total = nblk * B
+# A stream whose largest push (8 blocks) runs in place: four slots, adaptive submission by default (piles of up to 64 blocks).
+_IN_PLACE_PUSHES = ([3, 8, 1, 5, 8, 2, 8, 1], 13)      # 468 blocks per phase: two batches of 210 blocks and a remainder
+_THRESHOLD_PHASES = {
+    "large_pushes": [(None, [1, 1, 7, 200, 1, 16, 1, 199, 230, 7, 1, 2, 200, 1], 3)],
+    "coalesce_above": [(("coalesce", 210),) + _IN_PLACE_PUSHES],
+    "adaptive_above": [(("adaptive", 256),) + _IN_PLACE_PUSHES],
+    "adaptive_off": [(("adaptive", 0),) + _IN_PLACE_PUSHES],
+    "switched": [(("coalesce", 210),) + _IN_PLACE_PUSHES, (("coalesce", 0),) + _IN_PLACE_PUSHES,
+                 (("adaptive", 256),) + _IN_PLACE_PUSHES, (("adaptive", 0),) + _IN_PLACE_PUSHES,
+                 (("coalesce", 205),) + _IN_PLACE_PUSHES],
+}
+
+
+@pytest.mark.parametrize("phases", sorted(_THRESHOLD_PHASES))
+def test_fm_stream_crosses_the_in_place_threshold(hip, oracle, phases):
+    """sdrhip_fm_stream across the 200-block bound (carried tail included) between the slot-stream copy and the three-stream
+    copy path, against one device-resident run.  large_pushes: pushes of 1 block (the kernel reads the pinned buffer in place),
+    7, 16 and 199 blocks (one pass over the link on the slot's own stream, then the one-kernel chain on device memory), 200 and
+    230 blocks (three-stream copy path, stage kernels) in one stream of two slots.  The others push 1 to 8 blocks into a stream
+    whose largest push runs in place -- four slots, adaptive by default -- in phases that each end with a flush: set_coalesce
+    batches of 203-210 blocks take the copy engines with four slots, set_adaptive piles of up to 256 blocks cross the bound
+    depending on timing, set_adaptive(0) sends every push alone, and `switched` changes the setting between flushes in both
+    directions across the bound."""
+    plan = _THRESHOLD_PHASES[phases]
+    total = sum(sum(pattern) * reps for _, pattern, reps in plan) * B
     u8 = S.iq_u8_fm(total)
     chain = _chain(hip)
     _, q1, _ = chain.plan(0, total, total)
     full = _run(hip, chain, to_dev(u8), 0, total, 0, q1)
-    st = hip.FmStream(chain, 230 * B, B)
+    st = hip.FmStream(chain, (230 if phases == "large_pushes" else 8) * B, B)
     got, pos = [], 0
-    for rep in range(3):
-        for k, n in enumerate(pattern):
-            chunk = u8[2 * pos * B: 2 * (pos + n) * B]
-            if (k + rep) % 2:
-                view = st.input_buffer(n * B)
-                view[: chunk.size] = chunk
-                got += st.push_inplace(view[: chunk.size])
-            else:
-                got += st.push(chunk)
-            pos += n
-    got += st.flush()
+    for setting, pattern, reps in plan:
+        if setting is not None:
+            getattr(st, "set_" + setting[0])(setting[1] * B)
+        for rep in range(reps):
+            for k, n in enumerate(pattern):
+                chunk = u8[2 * pos * B: 2 * (pos + n) * B]
+                if (k + rep) % 2:
+                    view = st.input_buffer(n * B)
+                    view[: chunk.size] = chunk
+                    got += st.push_inplace(view[: chunk.size])
+                else:
+                    got += st.push(chunk)
+                pos += n
+        got += st.flush()
     got = np.concatenate(got)
     assert got.size == q1 // B * B
-    assert_bit_equal(got, full[: got.size], "mixed in-place / copied pushes vs resident")
+    assert_bit_equal(got, full[: got.size], f"{phases}: mixed in-place / copied pushes vs resident")
 
 
 @pytest.mark.parametrize("blocks_per_push", [1, 5])
@@ -635,6 +658,12 @@ def test_fm_stream_save_and_restore(hip, oracle, blocks_per_push):
         got += first.push(u8[2 * i * B: 2 * (i + blocks_per_push) * B])
     state = first.save()
     assert len(state) < 64 * 1024 + 4 * 2048 * 8, "the state is the position, ~4k samples of history and the unpopped audio"
+    # the layout: StreamStateHeader (64 bytes), the history (u8 IQ samples), the audio not yet popped
+    assert struct.calcsize("<IIqqqqqiiq") == 64
+    magic, version, n, q_done, head_cap, hist_n, pending, block_out, chain_block, _ = struct.unpack_from("<IIqqqqqiiq", state)
+    assert (magic, version, n, q_done, block_out, chain_block) == (0x53444d46, 1, cut * B, chain.ready(cut * B), 2048, B)
+    assert 0 < hist_n <= head_cap and pending == q_done - 2048 * len(got)
+    assert len(state) == 64 + 2 * hist_n + 4 * pending
     del first
     chain2 = _chain(hip)
     second = hip.FmStream(chain2, 8 * B, 2048)

@@ -1,6 +1,8 @@
 """GPU parity, layer (3): the host-block Pipe operators (firFilter / firDecimator /
 firResampler / fmDemod) against the restated reference Pipes, including ragged block
 sizes and the reference's assert on too-short blocks."""
+import struct
+
 import numpy as np
 import pytest
 
@@ -458,6 +460,14 @@ def test_pipes_save_and_restore(hip, oracle):
             for b in blocks[:cut]:
                 got += first.push(b)
             state = first.save()
+            # the layout: PipeStateHeader (112 bytes), the history (input elements), the output not yet popped, the block lengths
+            magic, version, kind, _, _, _, _, _, _, _, _, n_blocks, e_prev, m_done, head_cap, hist_n, pending = \
+                struct.unpack_from("<II10i5q", state)
+            assert (magic, version) == (0x50504453, 1) and 0 <= hist_n <= head_cap
+            assert kind == ["firFilter", "firDecimator", "firResampler", "fmDemod", "dcBlockingFilter"].index(name)
+            assert len(state) == struct.calcsize("<II10i5q6f") + 4 * width * hist_n + 4 * pending + 4 * n_blocks
+            if name.startswith("fir"):          # (the map pipes keep no position: one output block per input block)
+                assert e_prev == sum(sizes[:cut]) and pending == m_done * width - sum(g.size for g in got)
             del first
             second = make()
             got += second.restore(state, max_block=max(sizes))
