@@ -374,12 +374,21 @@ long long sdrhip_debug_decimate_real16_launches(void);
 void sdrhip_debug_set_systolic(int mode);
 long long sdrhip_debug_systolic_launches(void);
 void sdrhip_debug_systolic_plan(int count, int *nstrips, int *nwhole);
+/* sdrhip_debug_systolic_plain_launches: systolic launches on cfloat input that took plain loads (the mid-size range that the Infinity
+ * Cache serves) instead of non-temporal ones; sdrhip_debug_decimator_crossfix_launches: seam fix-ups of the complex AVX-order
+ * decimator that ran as a launch of their own after the main kernel (not inside it).  Both process-wide, for tests that assert
+ * which route a launch size took. */
+long long sdrhip_debug_systolic_plain_launches(void);
+long long sdrhip_debug_decimator_crossfix_launches(void);
 /* fmDemod inside the resampler's tile loader for large batches (>= 2^18 resampler outputs per run): the demodulated stream
  * never makes its round trip through HBM (12 B per decimated sample less traffic); the per-stage timing then books the pair
  * under `resample` (and reports 0 for `fm_demod`).  Same bits.  ON by default since round 4 (SDRHIP_FUSE_DEMOD=0 turns it off):
  * the pair takes 0.269 ms against 0.159 + 0.089 for the two stage kernels -- the arithmetic is the same -- but the chip runs at its
  * power cap and 0.54 GB less traffic per pass leaves the decimator 4 % more clock: the whole pass gains 1.0 %. */
 int sdrhip_fm_chain_set_demod_fusion(sdrhip_fm_chain *c, int enable);
+/* resampler launches that took fmDemod into their tile loader, process-wide (the per-stage timing books fmDemod under `resample`
+ * whenever the fusion is on, also when a launch too small for the fused form ran a stand-alone fmDemod first: this tells the two apart) */
+long long sdrhip_debug_fused_demod_launches(void);
 /* Per-stage timing with HIP events recorded around each stage's kernels on the stream they are
  * launched on; stages {decimate(+seam fix-up), fmDemod, resample, filter(+gain), fused tail (the three in one kernel),
  * whole chain in one kernel (sdrhip_fm_chain_set_small_chain)}.

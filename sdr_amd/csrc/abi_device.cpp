@@ -21,6 +21,8 @@ constexpr int kSmallSeamedLaunch = 32768;
 // resampler launches of at least this many outputs take fmDemod into their tile loader (below, the two edge launches it adds
 // cost more than the round trip of y through HBM it saves)
 constexpr int kFusedDemodMinOutputs = 1 << 18;
+static std::atomic<long long> g_fused_demod_launches{0};
+long long fused_demod_launch_count() { return g_fused_demod_launches.load(); }
 static std::atomic<int> g_small_launch{getenv("SDRHIP_SMALL_LAUNCH") ? atoi(getenv("SDRHIP_SMALL_LAUNCH")) : kSmallSeamedLaunch};
 int small_launch_outputs() { return g_small_launch.load(std::memory_order_relaxed); }
 
@@ -50,11 +52,16 @@ void dropin_fail(int code, const char* fmt, ...)
     abort();
 }
 
+// Tap arrays are zero-padded to a multiple of 64 floats on the device: kernels that walk whole 64-float tap rows (the systolic
+// decimator's 64-tap instantiation on the example's 52 taps reads rows 6-7 of them) then stay inside the allocation and read zeros.
+constexpr size_t kUploadPadFloats = 64;
 int upload_floats(float** d, const std::vector<float>& h)
 {
     *d = nullptr;
-    size_t bytes = (h.size() ? h.size() : 1) * sizeof(float);
+    const size_t n = (h.size() + kUploadPadFloats - 1) / kUploadPadFloats * kUploadPadFloats;
+    const size_t bytes = (n ? n : kUploadPadFloats) * sizeof(float);
     SDRHIP_CHECK_HIP(hipMalloc((void**)d, bytes));
+    SDRHIP_CHECK_HIP(hipMemset(*d, 0, bytes));
     if (!h.empty()) SDRHIP_CHECK_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
     return SDRHIP_OK;
 }
@@ -381,6 +388,7 @@ int resamp_run_demod(const ResampDesc* r, hipStream_t s, const float* d_iq, bool
         if (!small && r->lanes == 8 && g.count >= kFusedDemodMinOutputs &&
             launch_resample_3_10_fast(s, g, t, r->increments.data(), r->d_groups, r->d_plain, d_in, d_out, d_iq, iq_has_prev, y_count)) {
             if (demod_fused) *demod_fused = true;
+            g_fused_demod_launches.fetch_add(1, std::memory_order_relaxed);
             SDRHIP_CHECK_HIP(hipGetLastError());
             return SDRHIP_OK;
         }

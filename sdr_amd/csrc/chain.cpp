@@ -585,6 +585,9 @@ long long sdrhip_debug_resample_cycle_launches(void) { return resample_cycle_lau
 long long sdrhip_debug_decimate_real16_launches(void) { return decimate_real16_launch_count(); }
 void sdrhip_debug_set_systolic(int on) { set_systolic(on); }
 long long sdrhip_debug_systolic_launches(void) { return systolic_launch_count(); }
+long long sdrhip_debug_systolic_plain_launches(void) { return systolic_plain_launch_count(); }
+long long sdrhip_debug_decimator_crossfix_launches(void) { return decimator_crossfix_launch_count(); }
+long long sdrhip_debug_fused_demod_launches(void) { return fused_demod_launch_count(); }
 void sdrhip_debug_systolic_plan(int count, int* nstrips, int* nwhole) { systolic_plan(count, nstrips, nwhole); }
 
 int sdrhip_fm_chain_set_demod_fusion(sdrhip_fm_chain* c, int enable)

@@ -207,6 +207,9 @@ bool launch_decimate_c4_systolic(hipStream_t s, const Geom& g, const float* d_ta
 void systolic_plan(int count, int* nstrips, int* nwhole);   // host arithmetic of the strip cut (CPU-testable)
 void set_systolic(int mode);        // 0 = the tile kernel everywhere, 1 = the systolic kernel wherever its shape fits, 2 (default) = by launch size
 long long systolic_launch_count();  // diagnostics
+long long systolic_plain_launch_count();  // diagnostics: launches with plain (not non-temporal) cfloat loads
+long long decimator_crossfix_launch_count();  // diagnostics: seam fix-ups of launch_decimate_c4_fast run as a launch of their own
+long long fused_demod_launch_count();  // abi_device.cpp, diagnostics: resampler launches with fmDemod in their tile loader
 // kernels_fast_orders.hip: the same tiled decimator for the SSE "RC" and the "RC2" summation orders (CO_L2, CO_X4, CO_X2)
 bool launch_decimate_c_orders_fast(hipStream_t s, const Geom& g, ComplexOrder order, const float* d_plain_taps, int P,
                                    const float* d_cross_taps, const void* d_in, bool in_is_u8, float* d_out);

@@ -411,7 +411,11 @@ __global__ void __launch_bounds__(NT, 6) k_resample3_fast(const float* __restric
         const int m0 = dm.yseam > 0 ? (int)((dm.y_abs0 + base) % dm.yseam) : 0;
         // first pair: starts at the even (16-byte aligned) sample at or below the tile's predecessor sample base - 1
         const int dd = 1 + (int)(((reinterpret_cast<uintptr_t>(in) >> 3) + (uint64_t)(base - 1)) & 1);     // tile input 0 is sample dd of the pair stream
-        const bool interior = av64 >= SPAN + 12 && base >= 4;
+        // the interior loader reads R rounds of 256 pairs from sample base - dd (dd <= 2) whatever the tile's own span: with a short
+        // filter (NLOOP = 16: SPAN = 2503) SPAN + 12 alone would let it read past the end of the decimator's output
+        constexpr int kPairLoad = 2 * 256 * R;
+        constexpr int kInteriorMin = SPAN + 12 > kPairLoad ? SPAN + 12 : kPairLoad;
+        const bool interior = av64 >= kInteriorMin && base >= 4;
         __shared__ __attribute__((aligned(16))) float atbl[kAtanRows * kAtanRowFloats];
         if (interior) {
             atan_table_fill(atbl, threadIdx.x);

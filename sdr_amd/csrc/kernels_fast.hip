@@ -26,6 +26,9 @@
 
 namespace sdrhip {
 
+static std::atomic<long long> g_decimator_crossfix_launches{0};
+long long decimator_crossfix_launch_count() { return g_decimator_crossfix_launches.load(); }
+
 bool launch_decimate_c4_fast(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps,
                              const void* d_in, bool in_is_u8, float* d_out, bool last_tap_zero)
 {
@@ -104,6 +107,7 @@ bool launch_decimate_c4_fast(hipStream_t s, const Geom& g, const float* d_plain_
             } else if (P == 52) { if (in_is_u8) FIX(true, 52); else FIX(false, 52); }
             else { if (in_is_u8) FIX(true, 128); else FIX(false, 128); }
 #undef FIX
+            g_decimator_crossfix_launches.fetch_add(1, std::memory_order_relaxed);
         }
     }
     return true;

@@ -308,6 +308,7 @@ std::atomic<int>& systolic_flag()
     return f;
 }
 std::atomic<long long> g_systolic_launches{0};
+std::atomic<long long> g_systolic_plain_launches{0};
 
 }  // namespace
 
@@ -325,6 +326,7 @@ void systolic_plan(int count, int* nstrips, int* nwhole) { systolic_plan_for(cou
 
 void set_systolic(int mode) { systolic_flag().store(mode); }
 long long systolic_launch_count() { return g_systolic_launches.load(); }
+long long systolic_plain_launch_count() { return g_systolic_plain_launches.load(); }
 
 // The SIMD ("One") outputs of a decimate-by-8, 128-tap, AVX-order launch.  False = not this kernel's shape or too small to be
 // worth it (the tile kernel computes its Cross outputs in place for launch-bound sizes); the caller then takes the tile kernel.
@@ -404,6 +406,7 @@ bool launch_decimate_c4_systolic(hipStream_t s, const Geom& g, const float* d_ta
     else SYS(false, 0, true);
 #undef SYS
     g_systolic_launches.fetch_add(1, std::memory_order_relaxed);
+    if (plain) g_systolic_plain_launches.fetch_add(1, std::memory_order_relaxed);
     return true;
 }
 

@@ -236,6 +236,19 @@ def test_systolic_strip_plan_covers_every_launch_exactly(L):
             assert 240 * t + 239 > count - 1 or 1920 * t + 2048 > avail, (count, nw)    # the first guarded strip is really ragged
 
 
+def test_route_counters_are_declared_exported_and_bound(L):
+    """The route counters the GPU tests read to prove which kernel a launch size took (tests/test_gpu_bench_size.py): declared in
+    sdr_hip.h, exported, and bound with a 64-bit result."""
+    names = ["sdrhip_debug_systolic_launches", "sdrhip_debug_systolic_plain_launches", "sdrhip_debug_decimator_crossfix_launches",
+             "sdrhip_debug_small_chain_launches", "sdrhip_debug_fused_demod_launches"]
+    declared = declared_functions()
+    for n in names:
+        assert n in declared, f"{n} is not declared in sdr_hip.h"
+        f = getattr(L.lib, n)
+        assert f.restype is C.c_longlong, f"{n} is not bound with a long long result in sdr_amd/lib.py"
+        assert f() >= 0, n
+
+
 def test_halo_staging_size():
     """The staging size of the batched halo exchange (sdrhip_fm_chain_halo_exchange_batch)."""
     import sdr_amd.lib as L

@@ -139,8 +139,9 @@ def test_random_launch_geometry_equals_the_tile_kernel(hip):
 def test_the_example_52_tap_filter_on_the_64_tap_instantiation(hip, oracle):
     """Round 6: the reference example's own RF decimation filter (51 taps -> 52, examples/fm/Coeffs.hs as data) takes the systolic kernel's
     64-tap instantiation on u8 input (12 taps of padding skipped; strips of 248 outputs, 6 Cross outputs per boundary): against the tile
-    kernel on random launch geometries -- seams 0 / 8192 / odd multiples of 8, launches inside and past the in-launch fix-up's range -- and
-    against the oracle's decimateAVXRC on one whole-stream launch."""
+    kernel on random launch geometries -- seams 0 / 8192 / odd multiples of 8, launches of up to 8 * 61 440 outputs, all inside the in-launch
+    fix-up's range (2^23 outputs; launches past it, with the fix-up as a launch of its own: tests/test_gpu_bench_size.py) -- and against the
+    oracle's decimateAVXRC on one whole-stream launch."""
     import os
     scale = max(1, int(os.environ.get("SDRHIP_SWEEP_SCALE", "1")))
     rng = np.random.default_rng(5206 + int(os.environ.get("SDRHIP_SWEEP_SEED", "0")))
