@@ -9,6 +9,11 @@
 //   inOff(m) = ceil(m*D2/I2)) -> q audio outputs (window [q, q+L3)).
 // Seams: all four Pipes of fm.hs run with blockSizeOut = `block` and the source
 // delivers `block`-sample buffers, so each stage's input blocks are `block` long.
+//
+// One run (chain_run_on): derive the stage ranges of [q0, q1) once (plan_run), check the receptive field once, pick ONE route --
+// the one-kernel chain, decimator + fused tail, or the stage kernels -- and launch it.  Whether a fused kernel applies is asked
+// of its predicate (kernels.hpp: fm_tail_shape_ok when the chain is created, fm_chain_small_fits / fm_tail_fused_fits per run)
+// together with the mode and size rule, before anything is launched or timed; the launchers launch unconditionally.
 #include <stdlib.h>
 #include <string.h>
 
@@ -24,8 +29,13 @@
 
 using namespace sdrhip;
 
-static const int kFusedTailAutoOutputs = 768;   // fused tail in auto mode: runs of at most this many audio outputs
-static const int kStages = 6;  // decimate(+seam fix-up), fmDemod, resample, filter, fused tail (fmDemod+resample+filter+gain in one kernel), whole chain in one kernel
+// fused tail in auto mode: runs of at most this many audio outputs, i.e. up to two source blocks (measured per push, in place: fused
+// 27.3 / 29.1 / 36.6 us for 1 / 2 / 4 blocks, the stage kernels on their one-launch routes 30.0 / 30.7 / 32.6 -- the single workgroup
+// of a one-tile run is serial)
+static const int kFusedTailAutoOutputs = 768;
+// the stages of the per-stage timing, in the order of sdrhip_fm_chain_read_timing's ms_sum[] (FmChain.STAGES in lib.py): decimate
+// (+ seam fix-up), fmDemod, resample, filter, fused tail (fmDemod + resample + filter + gain in one kernel), whole chain in one kernel
+enum Stage { kDecimate, kFmDemod, kResample, kFilter, kFusedTail, kFusedChain, kStages };
 // the whole chain as ONE kernel (kernels_small.hip) in auto mode: runs of at most this many audio outputs (~7.3 M input samples);
 // measured on MI355X (tools/shard_pass_probe.py): see DESIGN.md 5 "one-kernel chain"
 static const int64_t kSmallChainAutoOutputs = 159 * 1728;   // round 5 (tools/launch_sweep.py): the crossover with the stage kernels sits at ~900
@@ -62,25 +72,19 @@ struct sdrhip_fm_chain {
     // 1.005-1.011 against 1.017-1.019 ms, alternating in one process: the pair itself is slower, 0.269 against 0.159 + 0.089 ms, but
     // 0.54 GB less traffic per pass leaves the power-capped decimator 4 % more clock)
     bool fuse_demod = getenv("SDRHIP_FUSE_DEMOD") ? atoi(getenv("SDRHIP_FUSE_DEMOD")) != 0 : true;
-    bool tail_shape_ok(int64_t n_out) const
-    {
-        // auto: runs of up to two source blocks (measured per push, in place: fused 27.3 / 29.1 / 36.6 us for 1 / 2 / 4 blocks,
-        // the stage kernels on their one-launch routes 30.0 / 30.7 / 32.6 -- the single workgroup of a one-tile run is serial)
-        if (fused_tail == 0 || (fused_tail == 2 && n_out > kFusedTailAutoOutputs)) return false;
-        return !resamp.cplx && resamp.lanes == 8 && !audio.cplx && audio.sym && audio.lanes == 8 && audio.factor == 1;
-    }
     // The whole chain as one kernel for launch-bound runs (kernels_small.hip): 0 = never, 1 = whenever the configuration is the
     // one it is written for, 2 = auto (runs of at most small_chain_max audio outputs): sdrhip_fm_chain_set_small_chain,
     // SDRHIP_SMALL_CHAIN=0/1/2, SDRHIP_SMALL_CHAIN_MAX=<outputs>, SDRHIP_SMALL_CHAIN_TILE=<audio outputs per workgroup, 0 = by size>.
     int small_chain = getenv("SDRHIP_SMALL_CHAIN") ? atoi(getenv("SDRHIP_SMALL_CHAIN")) : 2;
     int64_t small_chain_max = getenv("SDRHIP_SMALL_CHAIN_MAX") ? atoll(getenv("SDRHIP_SMALL_CHAIN_MAX")) : kSmallChainAutoOutputs;
     int small_chain_tile = getenv("SDRHIP_SMALL_CHAIN_TILE") ? atoi(getenv("SDRHIP_SMALL_CHAIN_TILE")) : 0;
-    bool input_over_link = false;   // set by the host-block operator around its in-place pushes: the input is pinned HOST memory
-    bool small_chain_ok(int64_t n_out) const
+    // does a mode (0 / 1 / 2 = auto: up to auto_max audio outputs) want a run of n_out outputs?
+    static bool mode_takes(int mode, int64_t n_out, int64_t auto_max) { return mode != 0 && (mode != 2 || n_out <= auto_max); }
+    // set when the chain is created: resampler and audio filter have the shape both fused kernels are written for (AVX orders)
+    bool fm_tail = false;
+    FmTailTables tail_tables() const      // their device tables (after ensure_device)
     {
-        if (small_chain == 0 || (small_chain == 2 && n_out > small_chain_max)) return false;
-        if (!(decim.factor == 8 && decim.Lp == 128 && decim.corder == CO_L4 && !decim.h_scaled.empty())) return false;
-        return !resamp.cplx && resamp.lanes == 8 && !audio.cplx && audio.sym && audio.lanes == 8 && audio.factor == 1;
+        return {resamp.d_groups, resamp.row_stride, resamp.d_plain, resamp.ntaps, resamp.Lp, audio.d_taps, audio.d_cross, gain, block};
     }
     // Two runs in flight (sdrhip_fm_chain_set_overlap, round 4): consecutive runs alternate between two internal streams
     // ("lanes") and the two halves of the workspace, so the memory-heavy tail kernels of run k execute beside the power-bound
@@ -104,12 +108,12 @@ struct sdrhip_fm_chain {
 
     // optional per-stage timing with HIP events on the stream each kernel is launched on
     bool timing = false;
-    struct Span { int stage; hipEvent_t b, e; };
+    struct Span { Stage stage; hipEvent_t b, e; };
     std::vector<hipEvent_t> ev_pool;     // all timing events ever created
     size_t ev_used = 0;
     std::vector<Span> spans;             // recorded since the last read
     int runs = 0;
-    int new_event(hipEvent_t* ev)
+    int record_event(hipEvent_t* ev, hipStream_t s)
     {
         if (ev_used == ev_pool.size()) {
             hipEvent_t e;
@@ -117,6 +121,20 @@ struct sdrhip_fm_chain {
             ev_pool.push_back(e);
         }
         *ev = ev_pool[ev_used++];
+        SDRHIP_CHECK_HIP(hipEventRecord(*ev, s));
+        return SDRHIP_OK;
+    }
+    // launch() between the two events of a span of `stage` on stream s (timing off: launch() alone)
+    template <class F>
+    int timed(Stage stage, hipStream_t s, F&& launch)
+    {
+        Span sp{stage, nullptr, nullptr};
+        int rc;
+        if (timing && (rc = record_event(&sp.b, s)) != SDRHIP_OK) return rc;
+        if ((rc = launch()) != SDRHIP_OK) return rc;
+        if (!timing) return SDRHIP_OK;
+        if ((rc = record_event(&sp.e, s)) != SDRHIP_OK) return rc;
+        spans.push_back(sp);
         return SDRHIP_OK;
     }
     ~sdrhip_fm_chain()
@@ -197,6 +215,10 @@ int sdrhip_fm_chain_create(sdrhip_fm_chain** c, int order, int decim_factor, con
     if (rc != SDRHIP_OK) { delete ch; return rc; }
     ch->gain = gain;
     ch->block = block;
+    const ResampDesc& r = ch->resamp;
+    const FirDesc& a = ch->audio;
+    ch->fm_tail = !r.cplx && r.lanes == 8 && !a.cplx && a.sym && a.lanes == 8 && a.factor == 1 &&
+                  fm_tail_shape_ok(r.num_groups, r.nloop, r.I, r.D, r.increments.data(), r.Lp, r.ntaps, a.ntaps_kernel);
     *c = ch;
     return SDRHIP_OK;
 }
@@ -291,28 +313,135 @@ size_t sdrhip_fm_chain_workspace_bytes(const sdrhip_fm_chain* c, int64_t n_in)
     if (!c || n_in < 0) return 0;
     int64_t nk = n_in / c->decim.factor + 4;
     int64_t nm = nk * c->resamp.I / c->resamp.D + 4;
-    // + the overlap each of the (up to 16) sub-batches recomputes and its alignment padding
+    // unfused first stage: the converted input (+ 16 filter lengths with their alignment padding: what round 4's sub-batches recomputed;
+    // no run needs it any more, but the size callers allocate stays what it was)
     const size_t conv = c->fused_first_stage() ? 0 : align_up((size_t)(n_in + 16) * 8, 256) + 16 * align_up((size_t)(c->decim.Lp + 16) * 8, 256);
     const size_t one = conv + align_up((size_t)nk * 8, 256) + align_up((size_t)nk * 4, 256) + align_up((size_t)nm * 4, 256) + 256 + 16 * (64 << 10);
     return c->overlap ? 2 * align_up(one, 256) : one;      // two runs in flight: one half per lane
 }
 
 namespace {
-struct SubRange {
-    int64_t q0, q1, m0, m1, ky0, ky1, kd0, kd1;
-    size_t off_x, off_d, off_y, off_z;   // converted input (unfused first stage only), decimated, demodulated, resampled
-    int64_t xa, xb;                      // samples [xa, xb) of the stream are converted into off_x
+// The stage ranges of one run, back to front from the audio outputs [q0, q1), and where the stage routes keep them
+struct RunPlan {
+    int64_t m1;                          // resampler outputs z[q0, m1)
+    int64_t ky0, ky1;                    // demod outputs
+    int64_t kd0, kd1;                    // decimator outputs (fmDemod looks one back)
+    int64_t n_lo, n_hi;                  // the input samples the run reads
+    int64_t xa = 0, xb = 0;              // unfused first stage only: samples [xa, xb) of the stream are converted to the workspace's start
+    size_t off_d = 0, off_y, off_z;      // decimated, demodulated, resampled
+    size_t ws_need;                      // bytes of workspace the stage routes use
 };
 }  // namespace
 
-static int chain_run_on(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq, int64_t s0, int64_t n_in,
-                        float* d_audio, int64_t q0, int64_t q1, void* d_workspace, size_t workspace_bytes);
-
-int sdrhip_fm_chain_run(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq, int64_t s0, int64_t n_in,
-                        float* d_audio, int64_t q0, int64_t q1, void* d_workspace, size_t workspace_bytes)
+static RunPlan plan_run(const sdrhip_fm_chain* c, int64_t s0, int64_t q0, int64_t q1)
 {
-    SDRHIP_REQUIRE(c != nullptr, "sdrhip_fm_chain_run");
-    if (!c->overlap) return chain_run_on(c, stream, d_in_iq, s0, n_in, d_audio, q0, q1, d_workspace, workspace_bytes);
+    RunPlan r;
+    r.m1 = q1 + c->audio.Lp - 1;
+    r.ky0 = c->resamp.in_offset(q0);
+    r.ky1 = c->resamp.in_offset(r.m1 - 1) + c->y_reach();
+    r.kd0 = r.ky0 > 0 ? r.ky0 - 1 : 0;
+    r.kd1 = r.ky1;
+    r.n_lo = r.kd0 * c->decim.factor;
+    r.n_hi = (r.kd1 - 1) * c->decim.factor + c->decim.Lp;
+    if (!c->fused_first_stage()) {
+        r.xa = s0 + ((r.n_lo - s0) & ~(int64_t)7);                   // 16-byte aligned in the u8 stream
+        r.xb = r.n_hi;
+        r.off_d = align_up((size_t)(r.xb - r.xa) * 8, 256);
+    }
+    r.off_y = r.off_d + align_up((size_t)(r.kd1 - r.kd0) * 8, 256);
+    r.off_z = r.off_y + align_up((size_t)(r.ky1 - r.ky0) * 4, 256);
+    r.ws_need = r.off_z + align_up((size_t)(r.m1 - q0) * 4, 256);
+    return r;
+}
+
+// the end of every route: the first failure, or what the launches left in HIP's error state
+static int launched(int rc)
+{
+    if (rc != SDRHIP_OK) return rc;
+    SDRHIP_CHECK_HIP(hipGetLastError());
+    return SDRHIP_OK;
+}
+
+// input_over_link: d_in_iq is pinned HOST memory (the host-block operator's in-place pushes): the one-kernel chain takes its largest tile
+static int chain_run_on(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq, int64_t s0, int64_t n_in, float* d_audio,
+                        int64_t q0, int64_t q1, void* d_workspace, size_t workspace_bytes, bool input_over_link)
+{
+    SDRHIP_REQUIRE(q1 >= q0 && q0 >= 0 && s0 >= 0 && n_in >= 0, "sdrhip_fm_chain_run");
+    if (q1 == q0) return SDRHIP_OK;
+    SDRHIP_REQUIRE(d_in_iq && d_audio && d_workspace, "sdrhip_fm_chain_run");
+    hipStream_t s = (hipStream_t)stream;
+
+    const RunPlan r = plan_run(c, s0, q0, q1);
+    if (r.n_lo < s0 || r.n_hi > s0 + n_in) {
+        set_error("sdrhip_fm_chain_run: outputs [%lld,%lld) need samples [%lld,%lld) but d_in holds [%lld,%lld)",
+                  (long long)q0, (long long)q1, (long long)r.n_lo, (long long)r.n_hi, (long long)s0, (long long)(s0 + n_in));
+        return SDRHIP_ERR_ARG;
+    }
+    // the route: the first of the two fused kernels that is wanted (mode and size) and fits, else the stage kernels
+    const FirDesc& dec = c->decim;
+    const bool small = c->fm_tail && c->mode_takes(c->small_chain, q1 - q0, c->small_chain_max) &&
+                       fm_chain_small_fits(dec.factor, dec.Lp, dec.corder, !dec.h_scaled.empty(), c->block, d_in_iq, s0);
+    const bool tail = !small && c->fm_tail && c->mode_takes(c->fused_tail, q1 - q0, kFusedTailAutoOutputs) &&
+                      fm_tail_fused_fits(c->resamp.Lp, c->block);
+    if (!small && r.ws_need > workspace_bytes) {       // the one-kernel chain sends nothing through the workspace
+        set_error("sdrhip_fm_chain_run: workspace too small (%zu < %zu)", workspace_bytes, r.ws_need);
+        return SDRHIP_ERR_ARG;
+    }
+    int rc;
+    if (small || tail)
+        if ((rc = c->resamp.ensure_device()) != SDRHIP_OK || (rc = c->audio.ensure_device()) != SDRHIP_OK) return rc;
+    if (c->timing) c->runs++;
+
+    if (small) {      // launch-bound run: the whole chain in ONE kernel
+        if ((rc = dec.ensure_device()) != SDRHIP_OK) return rc;
+        return launched(c->timed(kFusedChain, s, [&] {
+            launch_fm_chain_small(s, d_in_iq, s0, n_in, d_audio, q0, q1, dec.d_scaled, dec.last_tap_is_padding(), c->tail_tables(),
+                                  c->small_chain_tile != 0 ? c->small_chain_tile : (input_over_link ? -1 : 0));
+            return SDRHIP_OK;
+        }));
+    }
+
+    char* ws = (char*)d_workspace;
+    float* d_d = (float*)(ws + r.off_d);
+    float* d_y = (float*)(ws + r.off_y);
+    float* d_z = (float*)(ws + r.off_z);
+    // K1+K2: u8 -> cfloat -> decimate (convert.c:37-50 fused into decimate.c:105-113)
+    rc = c->timed(kDecimate, s, [&] {
+        if (c->fused_first_stage()) return fir_run(&dec, s, d_in_iq, true, s0, d_d, r.kd0, r.kd1, c->block);
+        launch_convert_u8(s, d_in_iq + 2 * (r.xa - s0), (float*)ws, 2 * (r.xb - r.xa));
+        return fir_run(&dec, s, ws, false, r.xa, d_d, r.kd0, r.kd1, c->block);
+    });
+    if (rc != SDRHIP_OK) return rc;
+    const float* d_iq = d_d + 2 * (r.ky0 - r.kd0);      // the decimator output whose phase step is y[ky0]
+    if (tail)
+        return launched(c->timed(kFusedTail, s, [&] {
+            launch_fm_tail_fused(s, d_d, r.kd0, r.kd1, r.ky0, r.ky1, d_audio, q0, q1, c->tail_tables());
+            return SDRHIP_OK;
+        }));
+    if (c->fuse_demod) {
+        // K3+K4: fmDemod inside the resampler's tile loader on large batches (y never reaches HBM), a stand-alone fmDemod launch first otherwise
+        rc = c->timed(kResample, s, [&] {
+            return resamp_run_demod(&c->resamp, s, d_iq, r.ky0 > r.kd0, r.ky1 - r.ky0, d_y, r.ky0, d_z, q0, r.m1, c->block, c->block, nullptr);
+        });
+    } else {
+        // K3: fmDemod; at stream start the carried sample is 0 (Demod.hs:41)
+        rc = c->timed(kFmDemod, s, [&] {
+            launch_fm_demod_fast(s, d_iq, d_y, r.ky1 - r.ky0, r.ky0 > r.kd0, 0.0f, 0.0f);
+            return SDRHIP_OK;
+        });
+        // K4: polyphase resample
+        if (rc == SDRHIP_OK) rc = c->timed(kResample, s, [&] { return resamp_run(&c->resamp, s, d_y, r.ky0, d_z, q0, r.m1, c->block, c->block); });
+    }
+    // K5: symmetric audio filter (+ fm.hs:40 `P.map (VG.map (* 0.2))` as the kernel's epilogue: a separate f32 multiply of the rounded output)
+    if (rc == SDRHIP_OK) rc = c->timed(kFilter, s, [&] { return fir_run(&c->audio, s, d_z, false, q0, d_audio, q0, q1, c->block, c->gain); });
+    return launched(rc);
+}
+
+// One run in the chain's current mode; sdrhip_fm_chain_run and the host-block operator's submissions
+static int chain_run(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq, int64_t s0, int64_t n_in, float* d_audio, int64_t q0,
+                     int64_t q1, void* d_workspace, size_t workspace_bytes, bool input_over_link)
+{
+    if (!c->overlap) return chain_run_on(c, stream, d_in_iq, s0, n_in, d_audio, q0, q1, d_workspace, workspace_bytes, input_over_link);
     // two runs in flight: this run goes to lane j, after everything queued on the caller's stream so far (its input's
     // producer); the caller's stream is then made to wait for the PREVIOUS run (lane 1 - j), not for this one
     hipStream_t s = (hipStream_t)stream;
@@ -322,7 +451,8 @@ int sdrhip_fm_chain_run(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq
     SDRHIP_CHECK_HIP(hipEventRecord(c->ev_in[j], s));
     SDRHIP_CHECK_HIP(hipStreamWaitEvent(c->lane[j], c->ev_in[j], 0));
     const size_t half = (workspace_bytes / 2) & ~(size_t)255;
-    rc = chain_run_on(c, (void*)c->lane[j], d_in_iq, s0, n_in, d_audio, q0, q1, d_workspace ? (char*)d_workspace + (size_t)j * half : nullptr, half);
+    rc = chain_run_on(c, (void*)c->lane[j], d_in_iq, s0, n_in, d_audio, q0, q1, d_workspace ? (char*)d_workspace + (size_t)j * half : nullptr, half,
+                      input_over_link);
     // (also when the run failed half way: kernels it did enqueue on the lane may still be reading the input and writing the
     // audio and the workspace half, and a later run or join must be ordered behind them)
     const hipError_t erec = hipEventRecord(c->ev_out[j], c->lane[j]);
@@ -331,6 +461,13 @@ int sdrhip_fm_chain_run(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq
     SDRHIP_CHECK_HIP(erec);
     if (c->lane_busy[1 - j]) SDRHIP_CHECK_HIP(hipStreamWaitEvent(s, c->ev_out[1 - j], 0));
     return SDRHIP_OK;
+}
+
+int sdrhip_fm_chain_run(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq, int64_t s0, int64_t n_in,
+                        float* d_audio, int64_t q0, int64_t q1, void* d_workspace, size_t workspace_bytes)
+{
+    SDRHIP_REQUIRE(c != nullptr, "sdrhip_fm_chain_run");
+    return chain_run(c, stream, d_in_iq, s0, n_in, d_audio, q0, q1, d_workspace, workspace_bytes, false);
 }
 
 int sdrhip_fm_chain_join(sdrhip_fm_chain* c, void* stream)
@@ -354,164 +491,6 @@ int sdrhip_fm_chain_set_overlap(sdrhip_fm_chain* c, int on)
             c->lane_busy[j] = false;
         }
     c->overlap = on;
-    return SDRHIP_OK;
-}
-
-static int chain_run_on(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq, int64_t s0, int64_t n_in,
-                        float* d_audio, int64_t q0, int64_t q1, void* d_workspace, size_t workspace_bytes)
-{
-    SDRHIP_REQUIRE(c != nullptr, "sdrhip_fm_chain_run");
-    SDRHIP_REQUIRE(q1 >= q0 && q0 >= 0 && s0 >= 0 && n_in >= 0, "sdrhip_fm_chain_run");
-    if (q1 == q0) return SDRHIP_OK;
-    SDRHIP_REQUIRE(d_in_iq && d_audio && d_workspace, "sdrhip_fm_chain_run");
-    hipStream_t s = (hipStream_t)stream;
-
-    const int64_t nq = q1 - q0;
-    if (c->small_chain_ok(nq)) {
-        // launch-bound run: the whole chain in ONE kernel, nothing through the workspace
-        const int64_t kd0 = c->resamp.in_offset(q0) > 0 ? c->resamp.in_offset(q0) - 1 : 0;
-        const int64_t kd1 = c->resamp.in_offset(q1 + c->audio.Lp - 2) + c->y_reach();
-        const int64_t n_lo = kd0 * c->decim.factor, n_hi = (kd1 - 1) * c->decim.factor + c->decim.Lp;
-        if (n_lo < s0 || n_hi > s0 + n_in) {
-            set_error("sdrhip_fm_chain_run: outputs [%lld,%lld) need samples [%lld,%lld) but d_in holds [%lld,%lld)",
-                      (long long)q0, (long long)q1, (long long)n_lo, (long long)n_hi, (long long)s0, (long long)(s0 + n_in));
-            return SDRHIP_ERR_ARG;
-        }
-        int rc2;
-        if ((rc2 = c->decim.ensure_device()) != SDRHIP_OK || (rc2 = c->resamp.ensure_device()) != SDRHIP_OK ||
-            (rc2 = c->audio.ensure_device()) != SDRHIP_OK) return rc2;
-        hipEvent_t b = nullptr, e = nullptr;
-        if (c->timing) {
-            if ((rc2 = c->new_event(&b)) != SDRHIP_OK) return rc2;
-            SDRHIP_CHECK_HIP(hipEventRecord(b, s));
-        }
-        const bool last_zero = (int)c->decim.h_plain.size() == c->decim.Lp && c->decim.h_plain[c->decim.Lp - 1] == 0.0f;
-        const bool took = launch_fm_chain_small(s, d_in_iq, s0, n_in, d_audio, q0, q1, c->decim.factor, c->decim.Lp, c->decim.d_scaled, last_zero,
-                                                c->resamp.d_groups, c->resamp.row_stride, c->resamp.nloop, c->resamp.increments.data(),
-                                                c->resamp.num_groups, c->resamp.I, c->resamp.D, c->resamp.Lp, c->resamp.d_plain, c->resamp.ntaps,
-                                                c->audio.d_taps, c->audio.ntaps_kernel, c->audio.d_cross, c->gain, c->block,
-                                                c->small_chain_tile != 0 ? c->small_chain_tile : (c->input_over_link ? -1 : 0));
-        if (took) {
-            if (c->timing) {
-                if ((rc2 = c->new_event(&e)) != SDRHIP_OK) return rc2;
-                SDRHIP_CHECK_HIP(hipEventRecord(e, s));
-                c->spans.push_back({5, b, e});
-                c->runs++;
-            }
-            SDRHIP_CHECK_HIP(hipGetLastError());
-            return SDRHIP_OK;
-        }
-        if (c->timing && c->ev_used > 0) c->ev_used--;      // not this configuration after all: the stage kernels below
-    }
-
-    // the stages' ranges, back to front
-    SubRange r;
-    size_t off = 0;
-    {
-        r.q0 = q0;
-        r.q1 = q1;
-        r.m0 = r.q0;
-        r.m1 = r.q1 + c->audio.Lp - 1;                                                   // resampler outputs z[m0,m1)
-        r.ky0 = c->resamp.in_offset(r.m0);
-        r.ky1 = c->resamp.in_offset(r.m1 - 1) + c->y_reach();                           // demod outputs
-        r.kd0 = r.ky0 > 0 ? r.ky0 - 1 : 0;                                               // decimator outputs
-        r.kd1 = r.ky1;
-        r.off_x = off;
-        r.xa = r.xb = 0;
-        if (!c->fused_first_stage()) {
-            const int64_t a = r.kd0 * c->decim.factor;
-            r.xa = s0 + ((a - s0) & ~(int64_t)7);                   // 16-byte aligned in the u8 stream
-            r.xb = (r.kd1 - 1) * c->decim.factor + c->decim.Lp;
-            off += align_up((size_t)(r.xb - r.xa) * 8, 256);
-        }
-        r.off_d = off;
-        r.off_y = r.off_d + align_up((size_t)(r.kd1 - r.kd0) * 8, 256);
-        r.off_z = r.off_y + align_up((size_t)(r.ky1 - r.ky0) * 4, 256);
-        off = r.off_z + align_up((size_t)(r.m1 - r.m0) * 4, 256);
-    }
-    const int64_t n_lo = r.kd0 * c->decim.factor, n_hi = (r.kd1 - 1) * c->decim.factor + c->decim.Lp;
-    if (n_lo < s0 || n_hi > s0 + n_in) {
-        set_error("sdrhip_fm_chain_run: outputs [%lld,%lld) need samples [%lld,%lld) but d_in holds [%lld,%lld)",
-                  (long long)q0, (long long)q1, (long long)n_lo, (long long)n_hi, (long long)s0, (long long)(s0 + n_in));
-        return SDRHIP_ERR_ARG;
-    }
-    if (off > workspace_bytes) {
-        set_error("sdrhip_fm_chain_run: workspace too small (%zu < %zu)", workspace_bytes, off);
-        return SDRHIP_ERR_ARG;
-    }
-    char* ws = (char*)d_workspace;
-    int rc;
-    hipStream_t st = s;
-    auto begin_span = [&](int stage, hipStream_t on, hipEvent_t* b) -> int {
-        if (!c->timing) return SDRHIP_OK;
-        int r2 = c->new_event(b);
-        if (r2 != SDRHIP_OK) return r2;
-        (void)stage;
-        SDRHIP_CHECK_HIP(hipEventRecord(*b, on));
-        return SDRHIP_OK;
-    };
-    auto end_span = [&](int stage, hipStream_t on, hipEvent_t b) -> int {
-        if (!c->timing) return SDRHIP_OK;
-        hipEvent_t e;
-        int r2 = c->new_event(&e);
-        if (r2 != SDRHIP_OK) return r2;
-        SDRHIP_CHECK_HIP(hipEventRecord(e, on));
-        c->spans.push_back({stage, b, e});
-        return SDRHIP_OK;
-    };
-    if (c->timing) c->runs++;
-
-    float* d_d = (float*)(ws + r.off_d);
-    float* d_y = (float*)(ws + r.off_y);
-    float* d_z = (float*)(ws + r.off_z);
-    hipEvent_t b = nullptr;
-    // K1+K2 on the caller's stream: u8 -> cfloat -> decimate (convert.c:37-50 fused into decimate.c:105-113)
-    if ((rc = begin_span(0, s, &b)) != SDRHIP_OK) return rc;
-    if (c->fused_first_stage()) {
-        if ((rc = fir_run(&c->decim, s, d_in_iq, true, s0, d_d, r.kd0, r.kd1, c->block)) != SDRHIP_OK) return rc;
-    } else {
-        float* d_x = (float*)(ws + r.off_x);
-        launch_convert_u8(s, d_in_iq + 2 * (r.xa - s0), d_x, 2 * (r.xb - r.xa));
-        if ((rc = fir_run(&c->decim, s, d_x, false, r.xa, d_d, r.kd0, r.kd1, c->block)) != SDRHIP_OK) return rc;
-    }
-    if ((rc = end_span(0, s, b)) != SDRHIP_OK) return rc;
-    if (c->tail_shape_ok(r.q1 - r.q0)) {
-        if ((rc = c->resamp.ensure_device()) != SDRHIP_OK || (rc = c->audio.ensure_device()) != SDRHIP_OK) return rc;
-        if ((rc = begin_span(4, st, &b)) != SDRHIP_OK) return rc;
-        const bool took = launch_fm_tail_fused(st, d_d, r.kd0, r.kd1, r.ky0, r.ky1, d_audio + (r.q0 - q0), r.q0, r.q1, c->resamp.d_groups,
-                                               c->resamp.row_stride, c->resamp.nloop, c->resamp.increments.data(), c->resamp.num_groups,
-                                               c->resamp.I, c->resamp.D, c->resamp.Lp, c->resamp.d_plain, c->resamp.ntaps, c->audio.d_taps,
-                                               c->audio.ntaps_kernel, c->audio.d_cross, c->gain, c->block);
-        if (took) {
-            if ((rc = end_span(4, st, b)) != SDRHIP_OK) return rc;
-            SDRHIP_CHECK_HIP(hipGetLastError());
-            return SDRHIP_OK;
-        }
-        if (c->timing && c->ev_used > 0) c->ev_used--;      // the span's begin event goes back to the pool
-    }
-    if (c->fuse_demod) {
-        // K3+K4: fmDemod inside the resampler's tile loader on large batches (y never reaches HBM), a stand-alone fmDemod
-        // launch first otherwise; timed as the resample stage
-        if ((rc = begin_span(2, st, &b)) != SDRHIP_OK) return rc;
-        if ((rc = resamp_run_demod(&c->resamp, st, d_d + 2 * (r.ky0 - r.kd0), r.ky0 > r.kd0, r.ky1 - r.ky0, d_y, r.ky0, d_z, r.m0, r.m1,
-                                   c->block, c->block, nullptr)) != SDRHIP_OK) return rc;
-        if ((rc = end_span(2, st, b)) != SDRHIP_OK) return rc;
-    } else {
-        // K3: fmDemod; at stream start the carried sample is 0 (Demod.hs:41)
-        if ((rc = begin_span(1, st, &b)) != SDRHIP_OK) return rc;
-        launch_fm_demod_fast(st, d_d + 2 * (r.ky0 - r.kd0), d_y, r.ky1 - r.ky0, r.ky0 > r.kd0, 0.0f, 0.0f);
-        if ((rc = end_span(1, st, b)) != SDRHIP_OK) return rc;
-        // K4: polyphase resample
-        if ((rc = begin_span(2, st, &b)) != SDRHIP_OK) return rc;
-        if ((rc = resamp_run(&c->resamp, st, d_y, r.ky0, d_z, r.m0, r.m1, c->block, c->block)) != SDRHIP_OK) return rc;
-        if ((rc = end_span(2, st, b)) != SDRHIP_OK) return rc;
-    }
-    // K5: symmetric audio filter (+ fm.hs:40 `P.map (VG.map (* 0.2))` as the kernel's epilogue: a separate
-    // f32 multiply of the rounded output)
-    if ((rc = begin_span(3, st, &b)) != SDRHIP_OK) return rc;
-    if ((rc = fir_run(&c->audio, st, d_z, false, r.m0, d_audio + (r.q0 - q0), r.q0, r.q1, c->block, c->gain)) != SDRHIP_OK) return rc;
-    if ((rc = end_span(3, st, b)) != SDRHIP_OK) return rc;
-    SDRHIP_CHECK_HIP(hipGetLastError());
     return SDRHIP_OK;
 }
 
@@ -857,11 +836,8 @@ static int stream_submit(sdrhip_fm_stream* st)
     const HostStream::Route route = !direct ? HostStream::kCopyEngines
                                   : tail + n >= st->stage_samples ? HostStream::kSlotStream : HostStream::kInPlace;
     rc = e.submit(route, cs, first, (size_t)(tail + n) * 2, n_out, [&](hipStream_t s, const void* d_in, void* d_out) {
-        c->input_over_link = route == HostStream::kInPlace;
-        const int r = sdrhip_fm_chain_run(c, (void*)s, (const uint8_t*)d_in, keep_from, tail + n, (float*)d_out, st->q_done, q_new,
-                                          wsb_buf.p, wsb_buf.cap);
-        c->input_over_link = false;
-        return r;
+        return chain_run(c, (void*)s, (const uint8_t*)d_in, keep_from, tail + n, (float*)d_out, st->q_done, q_new, wsb_buf.p, wsb_buf.cap,
+                         route == HostStream::kInPlace);
     });
     if (rc != SDRHIP_OK) return rc;
     st->q_done = q_new;

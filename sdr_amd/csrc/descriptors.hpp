@@ -29,6 +29,8 @@ struct FirDesc {
     std::vector<float> h_scaled;
     std::vector<float> h_plain;        // Lp plain taps (sym: c ++ reverse c)
     std::vector<float> h_kernel;       // what d_taps holds
+    // tap Lp-1 is the zero the constructor padded the filter with (lets the u8 kernels skip its MACs)
+    bool last_tap_is_padding() const { return (int)h_plain.size() == Lp && h_plain[Lp - 1] == 0.0f; }
     int ensure_device() const;
     ~FirDesc();
 };

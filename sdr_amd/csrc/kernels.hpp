@@ -177,20 +177,32 @@ bool launch_resample3c_fast(hipStream_t s, const Geom& g, ComplexOrder order, co
 bool launch_resample_3_10_fast(hipStream_t s, const Geom& g, const ResampTable& t, const int* increments,
                                const float* d_groups, const float* d_plain_taps, const float* d_in, float* d_out,
                                const float* d_iq = nullptr, bool iq_has_prev = false, int64_t y_count = 0, int lanes = 8);
-// kernels_tail.hip: fmDemod -> 3/10 resampler -> symmetric filter (* gain) as one kernel (y and z never leave LDS); false = the
-// configuration is not the FM chain's tail (3 groups of 64, increments {4,3,3}, 64 half-taps, buffers longer than a tile)
+// ---- the two fused kernels of the FM chain.  chain.cpp ASKS whether one applies (the predicates below) before it launches or
+// times anything; the launchers launch unconditionally.
+// The low-rate tail's device tables as both kernels take them (chain.cpp fills them in one place)
+struct FmTailTables {
+    const float* d_groups; int row_stride;          // resampler: 3 group rows (group g = outputs m = 3c + g), the floats between them
+    const float* d_rplain; int ntaps, rLp;          // its plain taps, their unpadded count, numCoeffsR
+    const float* d_fhalf; const float* d_fplain;    // audio filter: 64 half-taps, 128 plain taps
+    float gain;
+    int64_t seam;                                   // block size of every Pipe (0 = contiguous stream)
+};
+// kernels_tail.hip: the tail both kernels are written for -- 3/10 resampler, 64-float groups, increments {4,3,3}, 64 half-taps.
+// Depends on the taps alone: evaluated once, when the chain is created.
+bool fm_tail_shape_ok(int ngroups, int nloop, int I, int D, const int* increments, int rLp, int ntaps, int nhalf);
+// kernels_tail.hip: fmDemod -> 3/10 resampler -> symmetric filter (* gain) as one kernel (y and z never leave LDS).
+// fits (given fm_tail_shape_ok): a buffer of the reference's Pipes is longer than a tile
 constexpr int kTailTileOutputs = 2046;   // audio outputs one workgroup of the fused tail kernel produces
-bool launch_fm_tail_fused(hipStream_t s, const float* d_d, int64_t kd0, int64_t kd1, int64_t ky0, int64_t ky1, float* d_audio,
-                          int64_t q0, int64_t q1, const float* d_groups, int row_stride, int nloop, const int* increments,
-                          int ngroups, int I, int D, int rLp, const float* d_rplain, int ntaps, const float* d_fhalf, int nhalf,
-                          const float* d_fplain, float gain, int64_t seam);
+bool fm_tail_fused_fits(int rLp, int64_t seam);
+void launch_fm_tail_fused(hipStream_t s, const float* d_d, int64_t kd0, int64_t kd1, int64_t ky0, int64_t ky1, float* d_audio,
+                          int64_t q0, int64_t q1, const FmTailTables& t);
 // kernels_small.hip: the WHOLE chain (u8 IQ -> /8 decimator -> fmDemod -> 3/10 resampler -> symmetric filter * gain) as one
 // kernel for launch-bound runs; d_in holds samples [s0, s0 + n_in).  tile_outputs: audio outputs per workgroup (0 = chosen
-// from the size of the run).  false = the configuration is not the FM chain's, nothing launched
-bool launch_fm_chain_small(hipStream_t s, const uint8_t* d_in, int64_t s0, int64_t n_in, float* d_audio, int64_t q0, int64_t q1,
-                           int dD, int dP, const float* d_dscaled, bool last_tap_zero, const float* d_groups, int row_stride, int nloop,
-                           const int* increments, int ngroups, int I, int D, int rLp, const float* d_rplain, int ntaps,
-                           const float* d_fhalf, int nhalf, const float* d_fplain, float gain, int64_t seam, int tile_outputs);
+// from the size of the run, < 0 = the largest).  fits (given fm_tail_shape_ok): /8 decimator with 128 padded taps in the AVX
+// order and exactly pre-scaled taps, seam block of at least 192, 16-byte aligned d_in, s0 a multiple of 8
+bool fm_chain_small_fits(int dD, int dP, ComplexOrder order, bool scaled_taps, int64_t seam, const void* d_in, int64_t s0);
+void launch_fm_chain_small(hipStream_t s, const uint8_t* d_in, int64_t s0, int64_t n_in, float* d_audio, int64_t q0, int64_t q1,
+                           const float* d_dscaled, bool last_tap_zero, const FmTailTables& t, int tile_outputs);
 long long fm_chain_small_launch_count();   // diagnostics: launches of the one-kernel chain so far
 // abi_device.cpp: the short-seamed-launch scale v (sdrhip_set_small_launch_outputs)
 int small_launch_outputs();

@@ -23,6 +23,9 @@
 //   phase 4  audio[q] = gain * sym_fir(z[q .. q+127]), one per thread (pair-add first, 8 lane partials + tree) -> HBM
 // Seams (Cross outputs of every stage) are decided per output with the predicates of the fix-up kernels, exactly as
 // kernels_tail.hip does.  Results are bit-identical to the stage kernels' (tests/test_gpu_chain.py).
+//
+// Host side: fm_chain_small_fits (first stage, seam, input alignment; the tail's shape is kernels_tail.hip's fm_tail_shape_ok) says
+// whether it applies: chain.cpp asks first, launch_fm_chain_small (FmTailTables in) launches unconditionally.
 #include "decimate_tile.hpp"
 #include "demod.hpp"
 #include "kernels.hpp"
@@ -475,19 +478,19 @@ int fm_chain_small_tile_outputs(int64_t n_out)
     return (int)a;
 }
 
-bool launch_fm_chain_small(hipStream_t s, const uint8_t* d_in, int64_t s0, int64_t n_in, float* d_audio, int64_t q0, int64_t q1,
-                           int dD, int dP, const float* d_dscaled, bool last_tap_zero, const float* d_groups, int row_stride, int nloop,
-                           const int* increments, int ngroups, int I, int D, int rLp, const float* d_rplain, int ntaps,
-                           const float* d_fhalf, int nhalf, const float* d_fplain, float gain, int64_t seam, int tile_outputs)
+bool fm_chain_small_fits(int dD, int dP, ComplexOrder order, bool scaled_taps, int64_t seam, const void* d_in, int64_t s0)
 {
-    // specialised for the FM chain of BASELINE configs[2] / [4]: /8 decimator with 128 (padded) taps in the AVX order, 3/10
-    // resampler with 64-float groups, 64 half-tap symmetric filter
-    if (!(dD == 8 && dP == 128 && d_dscaled != nullptr)) return false;
-    if (!(ngroups == 3 && nloop == SM_NL && I == 3 && D == 10 && increments[0] == 4 && increments[1] == 3 && increments[2] == 3)) return false;
-    if (!(nhalf == SM_LF / 2 && d_fhalf != nullptr && rLp <= 3 * SM_NL && ntaps <= rLp)) return false;
+    // specialised for the FM chain of BASELINE configs[2] / [4]: /8 decimator with 128 (padded) taps in the AVX order, on the tail
+    // of fm_tail_shape_ok (kernels_tail.hip)
+    static_assert(SM_NL == 64 && SM_LF == 128, "the tail of fm_tail_shape_ok");
+    if (!(dD == 8 && dP == 128 && order == CO_L4 && scaled_taps)) return false;
     if (seam != 0 && (seam < 192 || seam > (1 << 26))) return false;       // 32-bit seam arithmetic; a stage's window meets one boundary at most
-    if ((reinterpret_cast<uintptr_t>(d_in) & 15) != 0 || (s0 & 7) != 0) return false;   // 16-byte aligned tile loads
-    if (q1 <= q0) return true;
+    return (reinterpret_cast<uintptr_t>(d_in) & 15) == 0 && (s0 & 7) == 0;   // 16-byte aligned tile loads
+}
+
+void launch_fm_chain_small(hipStream_t s, const uint8_t* d_in, int64_t s0, int64_t n_in, float* d_audio, int64_t q0, int64_t q1,
+                           const float* d_dscaled, bool last_tap_zero, const FmTailTables& t, int tile_outputs)
+{
     // tile_outputs < 0: the largest tile -- for input that is read over PCIe (the host-block operators' in-place pushes): a tile's
     // ~4000-sample overlap is READ once per tile, and on the link that traffic, not the number of workgroups, is what a push costs
     // (round 6, tools/stream_tile_probe.py: 16 blocks per push 22.1 -> 14.6 us with 159 instead of 96 outputs per tile)
@@ -497,7 +500,7 @@ bool launch_fm_chain_small(hipStream_t s, const uint8_t* d_in, int64_t s0, int64
     if (A > SM_A_MAX) A = SM_A_MAX;
     SmallParams p;
     p.s0 = s0; p.n_in = n_in; p.q0 = q0; p.q1 = q1; p.A = A;
-    p.row_stride = row_stride; p.ntaps = ntaps; p.rLp = rLp; p.gain = gain; p.seam = seam;
+    p.row_stride = t.row_stride; p.ntaps = t.ntaps; p.rLp = t.rLp; p.gain = t.gain; p.seam = t.seam;
     const int64_t qa0 = (q0 / 3) * 3;
     const int64_t tiles = (q1 - qa0 + A - 1) / A;
     static std::atomic<bool> attr_set[2][64];
@@ -508,12 +511,11 @@ bool launch_fm_chain_small(hipStream_t s, const uint8_t* d_in, int64_t s0, int64
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SmT::LDS_BYTES);
             if (dev >= 0 && dev < 64) attr_set[which][dev] = true;
         }
-        hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(SM_NT), SmT::LDS_BYTES, s, d_in, d_audio, d_dscaled, d_groups, d_rplain, d_fplain, p);
+        hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(SM_NT), SmT::LDS_BYTES, s, d_in, d_audio, d_dscaled, t.d_groups, t.d_rplain, t.d_fplain, p);
     };
     if (last_tap_zero) launch(k_fm_chain_small<1>, 1);
     else launch(k_fm_chain_small<0>, 0);
     g_small_launches++;
-    return true;
 }
 
 }  // namespace sdrhip

@@ -16,6 +16,9 @@
 // per output inside the kernel (the same predicates as the fix-up kernels of kernels_chain.hip): a lane whose output is a
 // Cross one recomputes it sequentially from the same LDS tile.  ~0.8 % of z and 1.5 % of audio outputs, clustered, so few
 // waves diverge.
+//
+// Host side: fm_tail_shape_ok (the tail this kernel and kernels_small.hip are written for, from the taps alone) and fm_tail_fused_fits
+// (the seam against the tile) say whether it applies: chain.cpp asks first, launch_fm_tail_fused (FmTailTables in) launches unconditionally.
 #include "demod.hpp"
 #include "kernels.hpp"
 
@@ -241,24 +244,27 @@ __global__ void __launch_bounds__(TAIL_NT, 4) k_fm_tail(const float* __restrict_
 
 }  // namespace
 
-bool launch_fm_tail_fused(hipStream_t s, const float* d_d, int64_t kd0, int64_t kd1, int64_t ky0, int64_t ky1, float* d_audio,
-                          int64_t q0, int64_t q1, const float* d_groups, int row_stride, int nloop, const int* increments,
-                          int ngroups, int I, int D, int rLp, const float* d_rplain, int ntaps, const float* d_fhalf, int nhalf,
-                          const float* d_fplain, float gain, int64_t seam)
+bool fm_tail_shape_ok(int ngroups, int nloop, int I, int D, const int* increments, int rLp, int ntaps, int nhalf)
 {
-    // specialised for the FM chain's tail: 3/10 resampler with 64-float groups, 64 half-tap symmetric filter, AVX orders
-    if (!(ngroups == 3 && nloop == TAIL_NL && I == 3 && D == 10 && increments[0] == 4 && increments[1] == 3 && increments[2] == 3)) return false;
-    if (!(nhalf == TAIL_LF / 2 && rLp <= 3 * TAIL_NL && ntaps <= rLp)) return false;
+    return ngroups == 3 && nloop == TAIL_NL && I == 3 && D == 10 && increments[0] == 4 && increments[1] == 3 && increments[2] == 3 &&
+           nhalf == TAIL_LF / 2 && rLp <= 3 * TAIL_NL && ntaps <= rLp;
+}
+
+bool fm_tail_fused_fits(int rLp, int64_t seam)
+{
     // a tile must span less than one buffer of the reference's Pipes (one boundary per tile at most, 32-bit seam arithmetic)
-    if (seam != 0 && (seam * 3 < 10 * (int64_t)TAIL_NZ + rLp || seam < TAIL_A + 4 + TAIL_LF || seam > (1 << 28))) return false;
-    if (q1 <= q0) return true;
+    return seam == 0 || !(seam * 3 < 10 * (int64_t)TAIL_NZ + rLp || seam < TAIL_A + 4 + TAIL_LF || seam > (1 << 28));
+}
+
+void launch_fm_tail_fused(hipStream_t s, const float* d_d, int64_t kd0, int64_t kd1, int64_t ky0, int64_t ky1, float* d_audio,
+                          int64_t q0, int64_t q1, const FmTailTables& t)
+{
     TailParams p;
     p.kd0 = kd0; p.kd1 = kd1; p.ky0 = ky0; p.ky1 = ky1; p.q0 = q0; p.q1 = q1;
-    p.row_stride = row_stride; p.ntaps = ntaps; p.rLp = rLp; p.gain = gain; p.seam = seam;
+    p.row_stride = t.row_stride; p.ntaps = t.ntaps; p.rLp = t.rLp; p.gain = t.gain; p.seam = t.seam;
     const int64_t qa0 = (q0 / 3) * 3;
     const int64_t tiles = (q1 - qa0 + TAIL_A - 1) / TAIL_A;
-    hipLaunchKernelGGL(k_fm_tail, dim3((unsigned)tiles), dim3(TAIL_NT), 0, s, d_d, d_audio, d_groups, d_rplain, d_fhalf, d_fplain, p);
-    return true;
+    hipLaunchKernelGGL(k_fm_tail, dim3((unsigned)tiles), dim3(TAIL_NT), 0, s, d_d, d_audio, t.d_groups, t.d_rplain, t.d_fhalf, t.d_fplain, p);
 }
 
 }  // namespace sdrhip

@@ -256,3 +256,29 @@ def test_halo_staging_size():
     ch = L.FmChain(8, S.taps_decim127(), 3, 10, S.taps_resamp191(), S.taps_audio_half64(), 0.2, 8192)
     h = ch.halo_samples()
     assert ch.halo_staging_bytes(1) == 4 * h and ch.halo_staging_bytes(16) == 64 * h and ch.halo_staging_bytes(0) == 0
+
+
+# sdrhip_fm_chain_workspace_bytes at n_in = 0, 8192, 2^20, 2^29 with two runs in flight off / on.  The numbers were read once from the
+# library as it stood before chain.cpp's run function was reorganised; callers size their allocations by them.
+WORKSPACE_SIZES = (0, 8192, 1 << 20, 1 << 29)
+WORKSPACE_BYTES = {
+    # u8 input straight into the decimator (the fused first stage): the bench taps and the reference example's own 52 / 31 / 32
+    "bench": ([1049600, 1062912, 2779648, 886886400], [2099200, 2125824, 5559296, 1773772800]),
+    "example": ([1049600, 1062912, 2779648, 886886400], [2099200, 2125824, 5559296, 1773772800]),
+    # decimation 5 has no fused instantiation: the u8 IQ is converted into the workspace first (the unfused first stage)
+    "bench_decimate_by_5": ([1070336, 1157120, 12226816, 5713376512], [2140672, 2314240, 24453632, 11426753024]),
+}
+
+
+@pytest.mark.parametrize("config", sorted(WORKSPACE_BYTES))
+def test_chain_workspace_bytes_are_pinned(L, config):
+    if config == "example":
+        hd, hr, ha = S.taps_example_rf_decim(), S.taps_example_audio_resampler(), S.taps_example_audio_filter_half()
+    else:
+        hd, hr, ha = S.taps_decim127(), S.taps_resamp191(), S.taps_audio_half64()
+    chain = L.FmChain(5 if config.endswith("by_5") else 8, hd, 3, 10, hr, ha, 0.2, 8192)
+    for overlap in (0, 1):
+        chain.set_overlap(overlap)
+        got = [int(chain.workspace_bytes(n)) for n in WORKSPACE_SIZES]
+        assert got == WORKSPACE_BYTES[config][overlap], (config, overlap)
+    assert int(chain.workspace_bytes(-1)) == 0

@@ -34,8 +34,8 @@ SKIP = 256                           # a window not at 0 starts with fmDemod's c
 FIX_INSIDE_MAX = 1 << 23             # kFixInsideMaxOutputs, sdr_amd/csrc/kernels_systolic.hip:342
 PLAIN_MIN, PLAIN_MAX = 1000 * 1024, 4400 * 1024   # kPlainLoadMinOutputs / kPlainLoadMaxOutputs, kernels_systolic.hip:340-341
 SYSTOLIC_MIN = 64 * 240 * 4          # the systolic launcher's minimum count, kernels_systolic.hip:353
-SMALL_CHAIN_MAX = 159 * 1728         # kSmallChainAutoOutputs, sdr_amd/csrc/chain.cpp:31
-FUSED_TAIL_MAX = 768                 # kFusedTailAutoOutputs, chain.cpp:27
+SMALL_CHAIN_MAX = 159 * 1728         # kSmallChainAutoOutputs, sdr_amd/csrc/chain.cpp:41
+FUSED_TAIL_MAX = 768                 # kFusedTailAutoOutputs, chain.cpp:35
 FUSED_DEMOD_MIN = 1 << 18            # kFusedDemodMinOutputs, sdr_amd/csrc/abi_device.cpp:23 (resampler outputs of one launch)
 
 

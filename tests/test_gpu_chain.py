@@ -552,6 +552,47 @@ def test_small_chain_on_eight_shards_of_2_to_the_20(hip, oracle):
     assert_bit_equal(full[: exp.size], exp, "single stream vs restated pipes")
 
 
+def _timed(chain, run):
+    """run() with per-stage timing on -> (its result, stage -> ms, runs); a stage that did not run reads 0"""
+    chain.enable_timing(True)
+    try:
+        out = run()
+        torch.cuda.synchronize()
+        stage_ms, runs = chain.read_timing()
+    finally:
+        chain.enable_timing(False)
+    return out, stage_ms, runs
+
+
+@pytest.mark.parametrize("block,forced", [(160, "small_chain"), (1000, "fused_tail")])
+def test_forced_fused_route_that_does_not_fit_runs_the_stage_kernels_with_timing_on(hip, block, forced):
+    """A fused kernel forced on (mode 1) on a chain it does not fit falls through to the next route, and the per-stage timing books
+    what ran: nothing under the kernel that did not run, and the event pool is left fit for a second timed run.
+    Seam block 160: below the one-kernel chain's 192, and below one tile of the fused tail, which auto mode asks for on the
+    600-output range.  Seam block 1000: below the fused tail's 2046 + 4 + 128."""
+    total = 16 * B
+    d = to_dev(S.iq_u8_fm(total))
+    ch = _chain(hip, block=block)
+    for a, b in [(0, 600), (100, 2000)]:
+        ch.set_small_chain(0)
+        ch.set_fused_tail(0)
+        ref = _run(hip, ch, d, 0, total, a, b)
+        if forced == "small_chain":
+            ch.set_small_chain(1)
+            ch.set_fused_tail(2)
+        else:
+            ch.set_fused_tail(1)
+        n0 = hip.lib.sdrhip_debug_small_chain_launches()
+        for attempt in (1, 2):                                  # the second round: the first left the recorder consistent
+            got, ms, runs = _timed(ch, lambda: _run(hip, ch, d, 0, total, a, b))
+            what = f"forced {forced} on seam block {block}, outputs [{a},{b}), timed run {attempt}: {ms}"
+            assert runs == 1, what
+            assert ms["fused_chain"] == 0 and ms["fused_tail"] == 0, what
+            assert ms["decimate"] > 0 and ms["resample"] > 0 and ms["filter"] > 0, what
+            assert_bit_equal(got, ref, what)
+        assert hip.lib.sdrhip_debug_small_chain_launches() == n0, "the one-kernel chain must not launch on a seam it does not fit"
+
+
 def test_chain_run_as_hipgraph(hip, oracle):
     """sdrhip_fm_chain_graph_*: one run with fixed arguments captured into a hipGraph replays to the same audio, for as many
     launches as wanted and after the input changes under it."""

@@ -2,7 +2,7 @@
 the shape of benchmarks/Benchmarks.hs:79-134): the full FM chain and BASELINE configs[1]'s cfloat decimator at
 B in {1, 8, 64, 128, 512, 2048, 8192, 65536} blocks per launch.  For every size: the route the library picks on its own
 (`auto`: one-kernel chain / decimator + fused tail / stage kernels; systolic or tile decimator) and every other route forced, so
-that the thresholds that decide the routing (chain.cpp kSmallChainAutoOutputs, tail_shape_ok's 768 outputs, abi_device.cpp
+that the thresholds that decide the routing (chain.cpp kSmallChainAutoOutputs, kFusedTailAutoOutputs, abi_device.cpp
 kSmallSeamedLaunch, the systolic kernel's minimum) can be seen to sit at the crossovers.
 
     python tools/launch_sweep.py            (a table + one JSON line; bench.py embeds sweep() as `launch_size_sweep`)"""
