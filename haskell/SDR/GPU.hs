@@ -35,7 +35,9 @@ module SDR.GPU (
     gpuDecimatorC, gpuResamplerR, gpuFilterSymR, gpuFilterR,
     firDecimatorGpu, firResamplerGpu, firFilterGpu, fmDemodGpu, dcBlockingFilterGpu,
     interleavedIQUnsignedByteToFloatGpu,
-    GpuFmChain, gpuFmChain, fmReceiverGpu
+    GpuFmChain, gpuFmChain, fmReceiverGpu,
+    -- * The waterfall pipe as one operator (raw IQ -> windowed FFT magnitudes)
+    GpuSpectrum, SpectrumWindow (..), gpuSpectrumU8, spectrumRowsGpu
     ) where
 
 import           Control.Exception             (throwIO)
@@ -59,11 +61,13 @@ data SdrFilter
 data SdrPipe
 data SdrChain
 data SdrStream
+data SdrSpectrum
 
 newtype GpuDecimator = GpuDecimator (Ptr SdrDecimator)
 newtype GpuResampler = GpuResampler (Ptr SdrResampler)
 newtype GpuFilter    = GpuFilter    (Ptr SdrFilter)
 newtype GpuFmChain   = GpuFmChain   (Ptr SdrChain)
+data    GpuSpectrum  = GpuSpectrum  (Ptr SdrSpectrum) Int
 
 -- The imports are `safe`: the calls block on the device and must not stall the RTS.
 foreign import ccall safe "sdrhip_last_error"          c_last_error        :: IO CString
@@ -110,6 +114,15 @@ foreign import ccall safe "sdrhip_decimator_one"    c_decimator_one    :: Ptr Sd
 foreign import ccall safe "sdrhip_decimator_cross"  c_decimator_cross  :: Ptr SdrDecimator -> CInt -> Ptr CFloat -> CInt -> Ptr CFloat -> CInt -> Ptr CFloat -> IO CInt
 foreign import ccall safe "sdrhip_resampler_one"    c_resampler_one    :: Ptr SdrResampler -> CInt -> CInt -> Ptr CFloat -> CInt -> Ptr CFloat -> IO CInt
 foreign import ccall safe "sdrhip_resampler_cross"  c_resampler_cross  :: Ptr SdrResampler -> CInt -> CInt -> Ptr CFloat -> CInt -> Ptr CFloat -> CInt -> Ptr CFloat -> IO CInt
+-- the spectrum operator (include/sdr_hip.h, sdrhip_spectrum_*): interleavedIQUnsigned256ToFloat -> halfBandUp x window -> fftw ->
+-- magnitude x scale, rows of Float
+foreign import ccall safe "sdrhip_spectrum_create"     c_spectrum_create     :: Ptr (Ptr SdrSpectrum) -> CInt -> CInt -> CInt -> Ptr CDouble -> CInt -> CDouble -> IO CInt
+foreign import ccall safe "sdrhip_spectrum_destroy"    c_spectrum_destroy    :: Ptr SdrSpectrum -> IO ()
+foreign import ccall safe "sdrhip_spectrum_size"       c_spectrum_size       :: Ptr SdrSpectrum -> IO CInt
+foreign import ccall safe "sdrhip_spectrum_window"     c_spectrum_window     :: Ptr SdrSpectrum -> Ptr CDouble -> IO CInt
+foreign import ccall safe "sdrhip_spectrum_run"        c_spectrum_run        :: Ptr SdrSpectrum -> Ptr () -> Int64 -> Int64 -> CInt -> Ptr CFloat -> IO CInt
+foreign import ccall safe "sdrhip_spectrum_run_device" c_spectrum_run_device :: Ptr SdrSpectrum -> Ptr () -> Ptr () -> Int64 -> Int64 -> CInt -> Ptr CFloat -> IO CInt
+foreign import ccall safe "sdrhip_spectrum_set_route"  c_spectrum_set_route  :: Ptr SdrSpectrum -> CInt -> IO CInt
 
 -- | SDRHIP_ORDER_AVX: reproduce the variant 'SDR.CPUID.featureSelect' picks on any AVX host.
 orderAVX :: CInt
@@ -344,3 +357,24 @@ fmReceiverGpu (GpuFmChain c) maxBlock blockSizeOut = do
                 _  <- withForeignPtr fp $ \o -> c_stream_pop st o (fromIntegral blockSizeOut) >>= check
                 return $ VS.unsafeCast $ VS.unsafeFromForeignPtr0 fp blockSizeOut
             yield out
+
+-- | The windows of SDR.FilterDesign ('hanning', 'hamming', 'blackman'), computed by the library with the same formulas.
+data SpectrumWindow = NoWindow | Hanning | Hamming | Blackman deriving (Eq, Enum)
+
+-- | A spectrum operator on RTL-SDR bytes: @gpuSpectrumU8 n window halfBandShift scale@.
+gpuSpectrumU8 :: Int -> SpectrumWindow -> Bool -> Double -> IO GpuSpectrum
+gpuSpectrumU8 n window shift scale = alloca $ \pp -> do
+    void $ check =<< c_spectrum_create pp (fromIntegral n) 0 (fromIntegral (fromEnum window)) nullPtr (if shift then 1 else 0) (realToFrac scale)
+    p <- peek pp
+    return (GpuSpectrum p n)
+
+-- | Every whole row of a block of interleaved IQ bytes, @hop@ samples apart, as one vector of @rows * n@ magnitudes: what
+--   @interleavedIQUnsigned256ToFloat >-> halfBandUp * window >-> fftw >-> magnitude@ hands to SDR.Plot's waterfall.
+spectrumRowsGpu :: GpuSpectrum -> Int -> VS.Vector CUChar -> IO (VS.Vector Float)
+spectrumRowsGpu (GpuSpectrum p n) hop bytes = do
+    let samples = VS.length bytes `quot` 2
+        rows    = if samples < n then 0 else (samples - n) `quot` hop + 1
+    out <- VSM.new (rows * n)
+    when (rows > 0) $ VS.unsafeWith bytes $ \pin -> VSM.unsafeWith out $ \pout ->
+        void $ check =<< c_spectrum_run p (castPtr pin) (fromIntegral samples) (fromIntegral hop) (fromIntegral rows) (castPtr pout)
+    VS.unsafeFreeze out

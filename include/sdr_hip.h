@@ -510,6 +510,39 @@ int sdrhip_fft_run(sdrhip_fft *f, const double *in, double *out);
 /* DEVICE vectors, asynchronous on `stream` */
 int sdrhip_fft_run_device(sdrhip_fft *f, void *stream, const double *d_in, double *d_out);
 
+/* The spectrum operator: the reference's waterfall pipe, interleavedIQUnsigned256ToFloat (Util.hs:92-98) -> halfBandUp
+ * (Util.hs:264-271) x hanning / hamming / blackman (FilterDesign.hs:39-60) -> fftw (FFT.hs:44-76) -> magnitude and a scale, from raw
+ * IQ in device memory to plot-ready float32 rows.  With x[j] the converted sample, all arithmetic in double:
+ *     x'[j] = x[j] * (half_band_shift ? (-1)^j : 1) * w[j];  X = forward DFT of x' (unnormalised, sign exp(-2 pi i jk/n));
+ *     out[k] = (float)(scale * |X[k]|),  |X| = sqrt(re^2 + im^2): cf32 input must stay well inside double's range (|x| < 1e150).
+ * The windows are computed on the host in double with the reference's formulas (denominator n - 1, so n >= 2).  Tolerance
+ * contract, like sdrhip_fft: every bin within 1e-11 of the row's largest bin plus one float32 unit in the last place.
+ * Routes: power-of-two n from 64 to 8192 (8192 included: its 128 KiB of LDS fit one workgroup) run as ONE kernel, raw IQ in,
+ * magnitudes out, the transform resident in LDS; every other n takes pre-kernel -> hipFFT -> post-kernel through a bounded scratch
+ * buffer.  `auto` picks per n the route that measured faster.  Without libhipfft, create succeeds and the one-kernel
+ * sizes run; a run on the hipFFT route returns the error sdrhip_fft_create gives.  One object serves one caller at a time. */
+typedef struct sdrhip_spectrum sdrhip_spectrum;
+#define SDRHIP_IQ_U8   0   /* interleaved unsigned bytes, (v - 128) / 128   (Util.hs:92-98)  */
+#define SDRHIP_IQ_CF32 1   /* interleaved float32 re, im (e.g. a decimator's output)          */
+#define SDRHIP_WINDOW_NONE 0
+#define SDRHIP_WINDOW_HANNING 1    /* FilterDesign.hs:39-44 */
+#define SDRHIP_WINDOW_HAMMING 2    /* :47-52 */
+#define SDRHIP_WINDOW_BLACKMAN 3   /* :55-60 */
+#define SDRHIP_WINDOW_CUSTOM 4     /* n doubles from the caller */
+int  sdrhip_spectrum_create(sdrhip_spectrum **s, int n, int input_format, int window, const double *custom_window,
+                            int half_band_shift, double scale);
+void sdrhip_spectrum_destroy(sdrhip_spectrum *s);
+int  sdrhip_spectrum_size(const sdrhip_spectrum *s);
+int  sdrhip_spectrum_window(const sdrhip_spectrum *s, double *out /* n */);   /* the window in use */
+/* row r = samples [r*hop, r*hop + n) of d_in; needs hop >= 1 and (rows-1)*hop + n <= n_samples, else SDRHIP_ERR_ARG.
+ * d_out: rows x n float32, bin order of FFTW (with half_band_shift: DC in bin n/2).  Asynchronous on `stream`. */
+int  sdrhip_spectrum_run_device(sdrhip_spectrum *s, void *stream, const void *d_in, int64_t n_samples, int64_t hop,
+                                int rows, float *d_out);
+/* HOST vectors, synchronous (like sdrhip_fft_run) */
+int  sdrhip_spectrum_run(sdrhip_spectrum *s, const void *in, int64_t n_samples, int64_t hop, int rows, float *out);
+int  sdrhip_spectrum_set_route(sdrhip_spectrum *s, int route);   /* 0 = auto, 1 = the one-kernel route, 2 = hipFFT route */
+long long sdrhip_debug_spectrum_fused_launches(void);            /* process-wide, for tests that assert the route */
+
 /* ------------------------------------------------------------------------ */
 /* (3) Pipe operators on host blocks                                        */
 /* ------------------------------------------------------------------------ */

@@ -168,6 +168,16 @@ lib.sdrhip_fft_size.argtypes = [_vp]
 lib.sdrhip_fft_bins.argtypes = [_vp]
 lib.sdrhip_fft_run.argtypes = [_vp, _f64p, _f64p]
 lib.sdrhip_fft_run_device.argtypes = [_vp, _vp, _vp, _vp]
+lib.sdrhip_spectrum_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, _f64p, C.c_int, C.c_double]
+lib.sdrhip_spectrum_destroy.argtypes = [_vp]
+lib.sdrhip_spectrum_destroy.restype = None
+lib.sdrhip_spectrum_size.argtypes = [_vp]
+lib.sdrhip_spectrum_window.argtypes = [_vp, _f64p]
+lib.sdrhip_spectrum_run_device.argtypes = [_vp, _vp, _vp, _i64, _i64, C.c_int, _vp]
+lib.sdrhip_spectrum_run.argtypes = [_vp, _vp, _i64, _i64, C.c_int, _vp]
+lib.sdrhip_spectrum_set_route.argtypes = [_vp, C.c_int]
+lib.sdrhip_debug_spectrum_fused_launches.argtypes = []
+lib.sdrhip_debug_spectrum_fused_launches.restype = C.c_longlong
 lib.sdrhip_filter_one.argtypes = [_vp, C.c_int, _f32p, _f32p]
 lib.sdrhip_filter_cross.argtypes = [_vp, C.c_int, _f32p, C.c_int, _f32p, C.c_int, _f32p]
 lib.sdrhip_decimator_one.argtypes = [_vp, C.c_int, _f32p, _f32p]
@@ -524,6 +534,64 @@ class Fft(_Handle):
         out = np.empty((self.batch, self.bins), np.complex128)
         check(lib.sdrhip_fft_run(self.h, a.ctypes.data_as(_f64p), out.ctypes.data_as(_f64p)), "sdrhip_fft_run")
         return out if self.batch > 1 else out[0]
+
+
+IQ_U8, IQ_CF32 = 0, 1
+WINDOW_NONE, WINDOW_HANNING, WINDOW_HAMMING, WINDOW_BLACKMAN, WINDOW_CUSTOM = 0, 1, 2, 3, 4
+SPECTRUM_ROUTE_AUTO, SPECTRUM_ROUTE_FUSED, SPECTRUM_ROUTE_HIPFFT = 0, 1, 2
+
+
+class Spectrum(_Handle):
+    """The reference's waterfall pipe as one operator: raw IQ (u8 or interleaved float32) x halfBandUp x window -> DFT ->
+    scale * |X| as float32 rows (sdr_hip.h, sdrhip_spectrum_*).  Row r covers samples [r*hop, r*hop + n)."""
+    _destroy = lib.sdrhip_spectrum_destroy
+
+    def __init__(self, n, input_format=IQ_U8, window=WINDOW_NONE, half_band_shift=False, scale=1.0, custom_window=None):
+        super().__init__()
+        import numpy as np
+        cw = None
+        if custom_window is not None:
+            cw = np.ascontiguousarray(custom_window, dtype=np.float64)
+            if cw.size != n:
+                raise SdrHipError(f"a custom window of {cw.size} values for n = {n}")
+        check(lib.sdrhip_spectrum_create(C.byref(self.h), n, input_format, window, cw.ctypes.data_as(_f64p) if cw is not None else None,
+                                         int(bool(half_band_shift)), float(scale)), "sdrhip_spectrum_create")
+        self.n, self.input_format = n, input_format
+
+    def window(self):
+        import numpy as np
+        w = np.empty(self.n, np.float64)
+        check(lib.sdrhip_spectrum_window(self.h, w.ctypes.data_as(_f64p)), "sdrhip_spectrum_window")
+        return w
+
+    def set_route(self, route):
+        check(lib.sdrhip_spectrum_set_route(self.h, int(route)), "sdrhip_spectrum_set_route")
+
+    def rows_of(self, n_samples, hop):
+        """Whole rows a buffer of n_samples holds at this hop."""
+        return 0 if n_samples < self.n else (n_samples - self.n) // hop + 1
+
+    def run_device(self, d_in, n_samples, d_out, hop=None, rows=None, stream=None):
+        """d_in, d_out: device addresses; d_out takes rows x n float32."""
+        hop = self.n if hop is None else int(hop)
+        rows = self.rows_of(n_samples, hop) if rows is None else int(rows)
+        check(lib.sdrhip_spectrum_run_device(self.h, stream, d_in, n_samples, hop, rows, d_out), "sdrhip_spectrum_run_device")
+        return rows
+
+    def run(self, iq, hop=None, rows=None):
+        """iq: a host array of interleaved samples (uint8 or float32, by input_format) -> rows x n float32."""
+        import numpy as np
+        a = np.ascontiguousarray(iq, dtype=np.uint8 if self.input_format == IQ_U8 else np.float32).reshape(-1)
+        n_samples = a.size // 2
+        hop = self.n if hop is None else int(hop)
+        rows = self.rows_of(n_samples, hop) if rows is None else int(rows)
+        out = np.empty((max(rows, 0), self.n), np.float32)
+        check(lib.sdrhip_spectrum_run(self.h, a.ctypes.data, n_samples, hop, rows, out.ctypes.data), "sdrhip_spectrum_run")
+        return out
+
+
+def spectrum_fused_launches():
+    return int(lib.sdrhip_debug_spectrum_fused_launches())
 
 
 TRANSPORT_RCCL, TRANSPORT_PEER_COPY = 1, 2
