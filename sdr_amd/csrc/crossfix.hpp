@@ -1,114 +1,17 @@
-// crossfix.hpp -- generic "Cross" (seam) fix-up kernels shared by the tiled kernels (internal header).
+// crossfix.hpp -- the LDS-staged "Cross" (seam) fix-up of real data, shared by the tiled kernels (internal header).
 //
 // The tiled kernels compute every output in the SIMD ("One") order; the few outputs whose window straddles a
 // seam of the reference's input buffers are then rewritten in the sequential order the reference's Haskell
-// fallbacks use (FilterInternal.hs:397-423).  These versions take any D / Lp / I and read global memory
-// directly; the hot configurations have LDS-staged specialisations next to their kernels.
+// fallbacks use (FilterInternal.hs:397-423).  Every launcher describes its seams once (seam_span, kernels.hpp), picks a
+// fix-up by a short tier table of its own over that description, and launches it: the generic one-thread-per-straddler
+// kernels (any D / Lp / I, global reads) are compiled once, in kernels_crossfix.hip, behind launch_fir_crossfix /
+// launch_resample_crossfix; the LDS-staged bodies stay in headers -- here and in decimate_tile.hpp -- because they are also
+// the fix-up workgroups inside other kernels, and the filters' own stay next to their kernels.
 #pragma once
 #include "kernels.hpp"
 
 namespace sdrhip {
 namespace {
-
-// Cross outputs of a complex filter / decimator: sequential over the Lp plain taps
-// (filterCrossHighLevel with Mult (Complex a) a, FilterInternal.hs:397-408, Util.hs:87-88).
-template <bool U8 = false>
-__global__ void __launch_bounds__(256) k_fir_cplx_crossfix(Geom g, const float* __restrict__ xtaps,
-                                                            const void* __restrict__ in, float* __restrict__ out,
-                                                            int64_t first_seam, int nseams, int per_seam)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nseams * per_seam) return;
-    const int si = t / per_seam, ci = t - si * per_seam;
-    const int64_t edge = (first_seam + si) * g.seamBI;
-    const int64_t m = (edge + g.D - 1) / g.D - 1 - ci;
-    if (m < g.k_begin || m >= g.k_begin + g.count) return;
-    const int64_t v = m * g.D;
-    if (!(v < edge && v + g.Lp > edge)) return;
-    float re = 0.0f, im = 0.0f;
-    if constexpr (U8) {   // interleaved u8 IQ: convert.c's (u - 128) / 128 on the way in (exact)
-        const uchar2* x = reinterpret_cast<const uchar2*>(in) + (v - g.in_base);
-        for (int j = 0; j < g.Lp; j++) {
-            const uchar2 u = x[j];
-            re = re + (((float)u.x - 128.0f) * (1.0f / 128.0f)) * xtaps[j];
-            im = im + (((float)u.y - 128.0f) * (1.0f / 128.0f)) * xtaps[j];
-        }
-    } else {
-        const float2* x = reinterpret_cast<const float2*>(in) + (v - g.in_base);
-        for (int j = 0; j < g.Lp; j++) {
-            const float2 s = x[j];
-            re = re + s.x * xtaps[j];
-            im = im + s.y * xtaps[j];
-        }
-    }
-    *reinterpret_cast<float2*>(out + 2 * (m - g.k_begin)) = make_float2(re, im);
-}
-
-// Cross outputs of a real FIR / decimator: sequential over the Lp plain taps
-// (filterCrossHighLevel / decimateCrossHighLevel, FilterInternal.hs:397-408).
-__global__ void __launch_bounds__(256) k_fir_real_crossfix(Geom g, const float* __restrict__ xtaps,
-                                                            const float* __restrict__ in, float* __restrict__ out,
-                                                            int64_t first_seam, int nseams, int per_seam, float gain,
-                                                            int apply_gain)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nseams * per_seam) return;
-    const int si = t / per_seam, ci = t - si * per_seam;
-    const int64_t edge = (first_seam + si) * g.seamBI;
-    const int64_t m = (edge + g.D - 1) / g.D - 1 - ci;
-    if (m < g.k_begin || m >= g.k_begin + g.count) return;
-    const int64_t v = m * g.D;
-    if (!(v < edge && v + g.Lp > edge)) return;
-    const float* x = in + (v - g.in_base);
-    float r = 0.0f;
-    for (int j = 0; j < g.Lp; j++) r = r + x[j] * xtaps[j];
-    if (apply_gain) r = r * gain;
-    out[m - g.k_begin] = r;
-}
-
-// Cross outputs of a resampler, real or complex data (resampleCrossHighLevel, FilterInternal.hs:410-423):
-// taps = stride I (drop filterOffset coeffs) over the UNPADDED taps, sequential.
-template <bool CPLX>
-__global__ void __launch_bounds__(256) k_resample_crossfix(Geom g, const float* __restrict__ plain, int ntaps,
-                                                            const float* __restrict__ in, float* __restrict__ out,
-                                                            int64_t first_seam, int nseams, int per_seam)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nseams * per_seam) return;
-    const int si = t / per_seam, ci = t - si * per_seam;
-    const int64_t edge = (first_seam + si) * g.seamBI;           // upsampled units
-    const int64_t m = (edge + g.D - 1) / g.D - 1 - ci;
-    if (m < g.k_begin || m >= g.k_begin + g.count) return;
-    const int64_t v = m * g.D;
-    if (!(v < edge && v + g.Lp > edge)) return;
-    if (!seam_has_crossover(edge, g.I, g.D, g.Lp)) return;       // the Pipe goes straight to the next buffer here
-    if (late_output_is_one(m, edge, g.I, g.D, g.outB)) return;   // first output of an output block, first input beyond the seam
-    const int64_t pos = (v + g.I - 1) / g.I;                     // inOff(m)
-    const int fo = (int)(pos * g.I - v);
-    if constexpr (CPLX) {
-        const float2* x = reinterpret_cast<const float2*>(in) + (pos - g.in_base);
-        float re = 0.0f, im = 0.0f;
-        for (int l = 0, j = fo; j < ntaps; l++, j += g.I) {
-            const float2 sv = x[l];
-            re = re + sv.x * plain[j];
-            im = im + sv.y * plain[j];
-        }
-        *reinterpret_cast<float2*>(out + 2 * (m - g.k_begin)) = make_float2(re, im);
-    } else {
-        const float* x = in + (pos - g.in_base);
-        float r = 0.0f;
-        for (int l = 0, j = fo; j < ntaps; l++, j += g.I) r = r + x[l] * plain[j];
-        out[m - g.k_begin] = r;
-    }
-}
-
-// seams (multiples of seamBI) strictly inside the launch's window range
-inline void seam_range(const Geom& g, int64_t& first, int64_t& last)
-{
-    const int64_t v_lo = g.k_begin * g.D, v_hi = (g.k_begin + g.count - 1) * g.D + g.Lp;
-    first = v_lo / g.seamBI + 1;
-    last = (v_hi - 1) / g.seamBI;
-}
 
 // Cross outputs of the real resampler (resampleCrossHighLevel, FilterInternal.hs:410-423):
 // taps = stride I (drop filterOffset coeffs) over the UNPADDED taps, sequential -- and with I = 1 the Cross outputs of a real
@@ -192,6 +95,16 @@ __global__ void __launch_bounds__(256) k_resample_real_crossfix(Geom g, const fl
                                                                  int apply_gain = 0)
 {
     resample_real_crossfix_wg<PER, UNI, LPG>((int)blockIdx.x, g, plain, ntaps, in, out, first_seam, nseams, in_avail, gain, apply_gain);
+}
+
+// one tier of a launcher's table: PER slots per seam, a union of UNI inputs, a group of LPG lanes per seam
+template <int PER, int UNI, int LPG>
+inline void launch_real_crossfix_lds(hipStream_t s, const Geom& g, const SeamSpan& sp, const float* plain, int ntaps, const float* in,
+                                     float* out, int64_t in_avail, float gain = 1.0f, bool apply_gain = false)
+{
+    constexpr int SPW = 256 / LPG;
+    hipLaunchKernelGGL((k_resample_real_crossfix<PER, UNI, LPG>), dim3((sp.nseams + SPW - 1) / SPW), dim3(256), 0, s, g, plain, ntaps, in, out,
+                       sp.first, sp.nseams, in_avail, gain, apply_gain ? 1 : 0);
 }
 
 }  // namespace

@@ -70,6 +70,40 @@ __host__ __device__ inline bool is_cross(const Geom& g, int64_t m)
     return seam_has_crossover(edge, g.I, g.D, g.Lp);
 }
 
+// The seams of one launch, as every tiled launcher's fix-up sees them: the multiples of seamBI strictly inside the launch's
+// window range [k_begin D, (k_end - 1) D + Lp) are first * seamBI ... (first + nseams - 1) * seamBI, and the straddlers of a
+// seam are among the last `per` outputs whose window starts before it.  nseams = 0: a contiguous stream, or no seam inside.
+struct SeamSpan {
+    int64_t first;
+    int nseams;
+    int per;           // candidate slots per seam: ceil((Lp - 1) / D)
+};
+inline SeamSpan seam_span(const Geom& g)
+{
+    SeamSpan sp = {0, 0, (g.Lp - 1 + g.D - 1) / g.D};
+    if (g.seamBI <= 0 || g.count <= 0) return sp;
+    const int64_t v_lo = g.k_begin * g.D, v_hi = (g.k_begin + g.count - 1) * g.D + g.Lp;
+    sp.first = v_lo / g.seamBI + 1;                      // first boundary strictly above v_lo
+    const int64_t last = (v_hi - 1) / g.seamBI;          // last boundary strictly below v_hi
+    if (last >= sp.first) sp.nseams = (int)(last - sp.first + 1);
+    return sp;
+}
+// Inputs (from d_in[0]) the caller of a launch guarantees: the first input of its last output and the `reach` inputs that output
+// walks (a filter / decimator: Lp; a resampler: the nloop floats of a group row).  The LDS-staged fix-ups clamp their loads to it.
+inline int64_t seam_in_avail(const Geom& g, int reach)
+{
+    const int64_t last_m = g.k_begin + g.count - 1;
+    return (last_m * g.D + g.I - 1) / g.I - g.in_base + reach;
+}
+// kernels_crossfix.hip: the generic fix-up kernels (one thread per candidate slot, any D / Lp / I, global reads), compiled once.
+// Filter / decimator seams: real or complex data (complex: cfloat or interleaved u8 IQ input), sequential over the g.Lp taps of
+// d_cross_taps; gain for real data only.  Nothing is launched when sp.nseams == 0.
+void launch_fir_crossfix(hipStream_t s, const Geom& g, const SeamSpan& sp, bool cplx, bool in_is_u8, const float* d_cross_taps,
+                         const void* d_in, float* d_out, float gain = 1.0f, bool apply_gain = false);
+// Resampler seams, real or complex data: stride I over the `ntaps` UNPADDED taps.
+void launch_resample_crossfix(hipStream_t s, const Geom& g, const SeamSpan& sp, bool cplx, const float* d_plain_taps, int ntaps,
+                              const float* d_in, float* d_out);
+
 // Real data ------------------------------------------------------------------
 // taps: `ntaps` floats (multiple of lanes).  sym: taps are the HALF filter.
 // cross_taps: Lp floats used by the sequential "Cross" outputs (may be null when seamBI == 0).
@@ -111,6 +145,31 @@ void launch_resample_real(hipStream_t s, const Geom& g, int lanes, const ResampT
                           const float* d_plain_taps, const float* d_in, float* d_out);
 void launch_resample_cplx(hipStream_t s, const Geom& g, ComplexOrder order, const ResampTable& t,
                           const float* d_groups, const float* d_plain_taps, const float* d_in, float* d_out);
+
+// The cut of a polyphase launch for the kernels that compute whole cycles (group 0 .. ngroups - 1 per thread): `lead` outputs
+// before the first group-0 output, `ncycles` whole cycles, `tail` outputs after them; the first cycle starts `skip` inputs
+// behind t.pos0.  pre[]: ResampTable::pre (prefix from group0); increments: per group, from group 0.
+struct CycleSplit {
+    int lead, ncycles, tail;
+    int done;          // outputs in front of the tail
+    int64_t skip;
+};
+inline CycleSplit cycle_split(int ngroups, int group0, int count, const int* pre, const int* increments)
+{
+    CycleSplit c = {};
+    c.lead = (ngroups - group0) % ngroups;
+    if (c.lead > count) c.lead = count;
+    c.ncycles = (count - c.lead) / ngroups;
+    c.done = c.lead + ngroups * c.ncycles;
+    c.tail = count - c.done;
+    c.skip = c.lead > 0 ? pre[c.lead - 1] + increments[(group0 + c.lead - 1) % ngroups] : 0;
+    return c;
+}
+// kernels_generic.hip: the lead-in and tail outputs of such a launch by the generic kernels, every output as One (the caller
+// fixes its seams up afterwards); lanes for real data, corder for complex.
+void launch_resample_lead_tail(hipStream_t s, const Geom& g, const CycleSplit& c, bool cplx, int lanes, ComplexOrder corder,
+                               const ResampTable& t, const int* increments, const float* d_groups, const float* d_plain_taps,
+                               const float* d_in, float* d_out);
 
 // Element-wise ----------------------------------------------------------------
 void launch_convert_u8(hipStream_t s, const uint8_t* d_in, float* d_out, int64_t n);

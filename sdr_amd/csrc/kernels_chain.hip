@@ -697,25 +697,12 @@ bool launch_fir_real8_fast(hipStream_t s, const Geom& g, bool sym, const float* 
     else
         hipLaunchKernelGGL((k_fir_real8_fast<false, R, NT, 4>), dim3(tiles), dim3(NT), lds_bytes, s, d_in, x0, g.count, d_taps, nk, d_out,
                            gain, apply_gain ? 1 : 0, aligned);
-    if (g.seamBI != 0) {
-        int64_t first, last;
-        seam_range(g, first, last);
-        if (last >= first) {
-            const int nseams = (int)(last - first + 1);
-            if (full == 128)
-                hipLaunchKernelGGL((k_filter_real_crossfix_lds<128>), dim3(nseams), dim3(128), 0, s, g, d_cross_taps, d_in, d_out,
-                                   first, gain, apply_gain ? 1 : 0);
-            else if (full == 64)
-                hipLaunchKernelGGL((k_filter_real_crossfix_lds<64>), dim3(nseams), dim3(64), 0, s, g, d_cross_taps, d_in, d_out,
-                                   first, gain, apply_gain ? 1 : 0);
-            else {
-                const int per = full - 1;
-                const int64_t total = (int64_t)nseams * per;
-                hipLaunchKernelGGL(k_fir_real_crossfix, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, g, d_cross_taps, d_in,
-                                   d_out, first, nseams, per, gain, apply_gain ? 1 : 0);
-            }
-        }
-    }
+    const SeamSpan sp = seam_span(g);
+    const int ga = apply_gain ? 1 : 0;
+    if (sp.nseams <= 0) return true;
+    if (full == 128) hipLaunchKernelGGL((k_filter_real_crossfix_lds<128>), dim3(sp.nseams), dim3(128), 0, s, g, d_cross_taps, d_in, d_out, sp.first, gain, ga);
+    else if (full == 64) hipLaunchKernelGGL((k_filter_real_crossfix_lds<64>), dim3(sp.nseams), dim3(64), 0, s, g, d_cross_taps, d_in, d_out, sp.first, gain, ga);
+    else launch_fir_crossfix(s, g, sp, false, false, d_cross_taps, d_in, d_out, gain, apply_gain);
     return true;
 }
 
@@ -729,17 +716,7 @@ bool launch_filter_cplx4_fast(hipStream_t s, const Geom& g, const float* d_dup_t
     const int tiles = (g.count + NT * R - 1) / (NT * R);
     const size_t lds_bytes = ((size_t)(NT * R + P - 1) + 16) * sizeof(float2);
     hipLaunchKernelGGL((k_filter_cplx4_fast<R, NT>), dim3(tiles), dim3(NT), lds_bytes, s, d_in, x0, g.count, d_dup_taps, P, d_out);
-    if (g.seamBI != 0) {
-        int64_t first, last;
-        seam_range(g, first, last);
-        if (last >= first) {
-            const int nseams = (int)(last - first + 1);
-            const int per = P - 1;
-            const int64_t total = (int64_t)nseams * per;
-            hipLaunchKernelGGL(k_fir_cplx_crossfix<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, g, d_cross_taps, d_in, d_out,
-                               first, nseams, per);
-        }
-    }
+    launch_fir_crossfix(s, g, seam_span(g), true, false, d_cross_taps, d_in, d_out);
     return true;
 }
 
@@ -765,19 +742,14 @@ bool launch_resample_3_10_fast(hipStream_t s, const Geom& g, const ResampTable& 
     if (g.seamBI != 0 && d_plain_taps == nullptr) return false;
     if (g.count <= 0) return false;
     constexpr int NT = 256;
-    // outputs before the first group-0 output and after the last whole cycle go to the generic kernel
-    int lead = (3 - t.group0) % 3;
-    if (lead > g.count) lead = g.count;
-    const int ncycles = (g.count - lead) / 3;
-    const int tail = g.count - lead - 3 * ncycles;
-    if (d_iq != nullptr) {
-        // the tail's windows must lie inside the last kEdge inputs
-        const int64_t tail_pos = t.pos0 + (lead > 0 ? t.pre[lead - 1] + increments[(t.group0 + lead - 1) % 3] : 0) + (int64_t)ncycles * 10;
-        if (tail_pos < y_count - kEdge + 16 || ncycles < 1) return false;
-    }
+    // outputs before the first group-0 output and after the last whole cycle go to the stragglers' kernel
+    const CycleSplit cs = cycle_split(3, t.group0, g.count, t.pre, increments);
+    const int lead = cs.lead, ncycles = cs.ncycles, tail = cs.tail;
+    const int64_t pos = t.pos0 + cs.skip;                           // the first group-0 output, relative to d_in
+    const int64_t tail_pos0 = pos + (int64_t)ncycles * 10;          // the tail's cycle
+    // fused fmDemod: the tail's windows must lie inside the last kEdge inputs
+    if (d_iq != nullptr && (tail_pos0 < y_count - kEdge + 16 || ncycles < 1)) return false;
     if (ncycles > 0) {
-        // position of the first group-0 output relative to d_in
-        int64_t pos = t.pos0 + (lead > 0 ? t.pre[lead - 1] + increments[(t.group0 + lead - 1) % 3] : 0);
         const int64_t avail_total = (int64_t)(ncycles - 1) * 10 + 7 + t.nloop;
         const int blocks = (ncycles + NT - 1) / NT;
         DemodSide dm = {};
@@ -807,32 +779,27 @@ bool launch_resample_3_10_fast(hipStream_t s, const Geom& g, const ResampTable& 
                                d_groups, t.row_stride, d_out + lead, dm);
     }
     // (after the tile kernel: with fmDemod fused its first and last workgroup write the y the lead-in / tail outputs read)
-    {
-        int64_t first = 0, last = -1;
-        if (g.seamBI != 0) seam_range(g, first, last);
-        const int nseams = last >= first ? (int)(last - first + 1) : 0;
-        if (nseams > 0 || lead > 0 || tail > 0) {
-            Stragglers sg = {};
-            sg.lead = lead;
-            sg.tail = tail;
-            sg.lead_group0 = t.group0;
-            for (int i = 0; i < lead && i < 2; i++) sg.lead_pos[i] = t.pos0 + t.pre[i];
-            sg.tail_pos0 = t.pos0 + (lead > 0 ? t.pre[lead - 1] + increments[(t.group0 + lead - 1) % 3] : 0) + (int64_t)ncycles * 10;
-            sg.done = lead + 3 * ncycles;
-            sg.nloop = t.nloop;
-            sg.row_stride = t.row_stride;
-            // Lp <= 192, D = 10: <= 20 straddlers per seam, 3.33 inputs apart, each reading <= 64 inputs
-            constexpr int PER = 20, UNI = 64 + (PER * 10 + 2) / 3 + 4;
-            const int64_t last_m = g.k_begin + g.count - 1;
-            const int64_t in_avail = (last_m * g.D + g.I - 1) / g.I - g.in_base + t.nloop;          // inputs the caller guarantees
-            const dim3 grid((nseams + 7) / 8 + ((lead > 0 || tail > 0) ? 1 : 0));
-            if (lanes == 8)
-                hipLaunchKernelGGL((k_resample3_stragglers<PER, UNI, 8>), grid, dim3(256), 0, s, g, sg, d_groups, d_plain_taps, t.ntaps_plain, d_in, d_out,
-                                   first, nseams, in_avail);
-            else
-                hipLaunchKernelGGL((k_resample3_stragglers<PER, UNI, 4>), grid, dim3(256), 0, s, g, sg, d_groups, d_plain_taps, t.ntaps_plain, d_in, d_out,
-                                   first, nseams, in_avail);
-        }
+    const SeamSpan sp = seam_span(g);
+    if (sp.nseams > 0 || lead > 0 || tail > 0) {
+        Stragglers sg = {};
+        sg.lead = lead;
+        sg.tail = tail;
+        sg.lead_group0 = t.group0;
+        for (int i = 0; i < lead && i < 2; i++) sg.lead_pos[i] = t.pos0 + t.pre[i];
+        sg.tail_pos0 = tail_pos0;
+        sg.done = cs.done;
+        sg.nloop = t.nloop;
+        sg.row_stride = t.row_stride;
+        // Lp <= 192, D = 10: <= 20 straddlers per seam, 3.33 inputs apart, each reading <= 64 inputs
+        constexpr int PER = 20, UNI = 64 + (PER * 10 + 2) / 3 + 4;
+        const int64_t in_avail = seam_in_avail(g, t.nloop);
+        const dim3 grid((sp.nseams + 7) / 8 + ((lead > 0 || tail > 0) ? 1 : 0));
+        if (lanes == 8)
+            hipLaunchKernelGGL((k_resample3_stragglers<PER, UNI, 8>), grid, dim3(256), 0, s, g, sg, d_groups, d_plain_taps, t.ntaps_plain, d_in, d_out,
+                               sp.first, sp.nseams, in_avail);
+        else
+            hipLaunchKernelGGL((k_resample3_stragglers<PER, UNI, 4>), grid, dim3(256), 0, s, g, sg, d_groups, d_plain_taps, t.ntaps_plain, d_in, d_out,
+                               sp.first, sp.nseams, in_avail);
     }
     return true;
 }

@@ -162,20 +162,10 @@ bool launch_resample3c_fast(hipStream_t s, const Geom& g, ComplexOrder order, co
     if (g.count <= 0) return false;
     constexpr int NT = 256;
     // outputs before the first group-0 output and after the last whole cycle go to the generic kernel
-    int lead = (3 - t.group0) % 3;
-    if (lead > g.count) lead = g.count;
-    const int ncycles = (g.count - lead) / 3;
-    const int tail = g.count - lead - 3 * ncycles;
-    Geom gs = g;
-    gs.seamBI = 0;      // every output as One first; seams are fixed up below
-    const int64_t skip = lead > 0 ? t.pre[lead - 1] + increments[(t.group0 + lead - 1) % 3] : 0;
-    if (lead > 0) {
-        Geom gl = gs;
-        gl.count = lead;
-        launch_resample_cplx(s, gl, order, t, d_groups, d_plain_taps, d_in, d_out);
-    }
+    const CycleSplit cs = cycle_split(3, t.group0, g.count, t.pre, increments);
+    const int lead = cs.lead, ncycles = cs.ncycles;
     if (ncycles > 0) {
-        const int64_t pos = t.pos0 + skip;
+        const int64_t pos = t.pos0 + cs.skip;
         const int64_t avail_total = (int64_t)(ncycles - 1) * 10 + 7 + t.nloop;
         const int blocks = (ncycles + NT - 1) / NT;
         if (order == CO_X4)
@@ -185,28 +175,8 @@ bool launch_resample3c_fast(hipStream_t s, const Geom& g, ComplexOrder order, co
             hipLaunchKernelGGL((k_resample3c_fast<64, 4, NT>), dim3(blocks), dim3(NT), 0, s, d_in, pos, ncycles, avail_total, d_groups, t.row_stride,
                                d_out + 2 * lead);
     }
-    if (tail > 0) {
-        const int done = lead + 3 * ncycles;
-        Geom gt = gs;
-        gt.k_begin = g.k_begin + done;
-        gt.count = tail;
-        ResampTable tt = t;
-        tt.group0 = 0;
-        tt.pos0 = t.pos0 + skip + (int64_t)ncycles * 10;
-        tt.pre[0] = 0; tt.pre[1] = 4; tt.pre[2] = 7;
-        launch_resample_cplx(s, gt, order, tt, d_groups, d_plain_taps, d_in, d_out + 2 * done);
-    }
-    if (g.seamBI != 0) {
-        int64_t first, last;
-        seam_range(g, first, last);
-        if (last >= first) {
-            const int nseams = (int)(last - first + 1);
-            const int per = (g.Lp - 1 + g.D - 1) / g.D;
-            const int64_t total = (int64_t)nseams * per;
-            hipLaunchKernelGGL(k_resample_crossfix<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, g, d_plain_taps, t.ntaps_plain, d_in,
-                               d_out, first, nseams, per);
-        }
-    }
+    launch_resample_lead_tail(s, g, cs, true, 0, order, t, increments, d_groups, d_plain_taps, d_in, d_out);
+    launch_resample_crossfix(s, g, seam_span(g), true, d_plain_taps, t.ntaps_plain, d_in, d_out);
     return true;
 }
 

@@ -9,7 +9,7 @@
 // floats of padding after every 16 (thread stride 20 dwords: 16 consecutive lanes cover all 64 banks once), and because a
 // step is as long as a thread's chunk the padding sits at the same place in every step.  Tiles are staged with 16-byte
 // global loads (4-byte aligned: the stream API hands over any float offset).  Seams: every output in the SIMD order first,
-// then the generic sequential fix-up of crossfix.hpp.
+// then the sequential fix-up of crossfix.hpp / kernels_crossfix.hip.
 #include <atomic>
 #include <type_traits>
 
@@ -346,39 +346,20 @@ bool launch_decimate_real16_fast(hipStream_t s, const Geom& g, int lanes, const 
 #undef DRS
 #undef DR
     if (!took) return false;
-    if (g.seamBI != 0) {
-        int64_t first, last;
-        seam_range(g, first, last);
-        if (last >= first) {
-            const int nseams = (int)(last - first + 1);
-            const int per = (g.Lp - 1 + g.D - 1) / g.D;
-            // LDS-staged fix-up (the resamplers' kernel with interpolation 1: one group of 32 / 64 lanes per seam, the straddlers'
-            // union of inputs and the taps in LDS) where a seam's straddlers fit, the generic one (global reads) beyond
-            const int64_t last_m = g.k_begin + g.count - 1;
-            const int64_t in_avail = last_m * g.D - g.in_base + g.Lp;                                // inputs the caller guarantees
-            const int ga = apply_gain ? 1 : 0;
-            auto uni = [&](int PER) { return g.Lp + PER * g.D + 4; };
-            if (per <= 16 && uni(16) <= 416)
-                hipLaunchKernelGGL((k_resample_real_crossfix<16, 416, 32>), dim3((nseams + 7) / 8), dim3(256), 0, s, g, d_cross_taps, ncross, d_in, d_out,
-                                   first, nseams, in_avail, gain, ga);
-            else if (per <= 32 && uni(32) <= 416)
-                hipLaunchKernelGGL((k_resample_real_crossfix<32, 416, 32>), dim3((nseams + 7) / 8), dim3(256), 0, s, g, d_cross_taps, ncross, d_in, d_out,
-                                   first, nseams, in_avail, gain, ga);
-            else if (per <= 64 && uni(64) <= 1152)
-                hipLaunchKernelGGL((k_resample_real_crossfix<64, 1152, 64>), dim3((nseams + 3) / 4), dim3(256), 0, s, g, d_cross_taps, ncross, d_in, d_out,
-                                   first, nseams, in_avail, gain, ga);
-            else if (ncross != g.Lp) {
-                // a resampler with interpolation 1 whose seams do not fit the LDS kernel: its own generic fix-up (unpadded taps)
-                const int64_t total = (int64_t)nseams * per;
-                hipLaunchKernelGGL(k_resample_crossfix<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, g, d_cross_taps, ncross, d_in, d_out,
-                                   first, nseams, per);
-            } else {
-                const int64_t total = (int64_t)nseams * per;
-                hipLaunchKernelGGL(k_fir_real_crossfix, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, g, d_cross_taps, d_in, d_out, first, nseams,
-                                   per, gain, ga);
-            }
-        }
-    }
+    // LDS-staged fix-up (the resamplers' kernel with interpolation 1: one group of 32 / 64 lanes per seam, the straddlers' union of
+    // inputs and the taps in LDS) where a seam's straddlers fit, the generic one (global reads) beyond -- for a resampler with
+    // interpolation 1 (ncross != Lp) the resamplers' own, over the unpadded taps
+    const SeamSpan sp = seam_span(g);
+    const int64_t in_avail = seam_in_avail(g, g.Lp);
+    auto uni = [&](int PER) { return g.Lp + PER * g.D + 4; };
+#define LDS(PER, UNI, LPG) launch_real_crossfix_lds<PER, UNI, LPG>(s, g, sp, d_cross_taps, ncross, d_in, d_out, in_avail, gain, apply_gain)
+    if (sp.nseams <= 0) return true;
+    if (sp.per <= 16 && uni(16) <= 416) LDS(16, 416, 32);
+    else if (sp.per <= 32 && uni(32) <= 416) LDS(32, 416, 32);
+    else if (sp.per <= 64 && uni(64) <= 1152) LDS(64, 1152, 64);
+    else if (ncross != g.Lp) launch_resample_crossfix(s, g, sp, false, d_cross_taps, ncross, d_in, d_out);
+    else launch_fir_crossfix(s, g, sp, false, false, d_cross_taps, d_in, d_out, gain, apply_gain);
+#undef LDS
     return true;
 }
 

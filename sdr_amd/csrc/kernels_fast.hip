@@ -85,30 +85,18 @@ bool launch_decimate_c4_fast(hipStream_t s, const Geom& g, const float* d_plain_
         else launch_c4<8, 128, 2, 256, false>(s, g, d_plain_taps, d_in, d_out, inl, &inlined);
     }
 
-    if (g.seamBI != 0 && !inlined) {
-        // seams whose straddling outputs may fall in [k_begin, k_end)
-        int64_t v_lo = g.k_begin * g.D, v_hi = (g.k_begin + g.count - 1) * g.D + g.Lp;
-        int64_t first = v_lo / g.seamBI + 1;          // first boundary strictly above v_lo
-        int64_t last = (v_hi - 1) / g.seamBI;         // last boundary strictly below v_hi
-        if (last >= first) {
-            int nseams = (int)(last - first + 1);
-            constexpr int PER = 16, SPW = 16;          // 16 candidate slots per seam (ceil((128-1)/8))
-            dim3 grid((nseams + SPW - 1) / SPW), block(PER * SPW);
-#define FIX(U, LPV) hipLaunchKernelGGL((k_decimate_c_crossfix<U, 8, LPV, PER, SPW>), grid, block, 0, s, g, d_cross_taps, d_in, d_out, first, nseams)
-            if (g.D != 8 || P > 128) {   // the generic one-thread-per-straddler kernel (crossfix.hpp)
-                const int per = (g.Lp - 1 + g.D - 1) / g.D;
-                const int64_t total = (int64_t)nseams * per;
-                const dim3 ggrid((unsigned)((total + 255) / 256));
-                if (in_is_u8) hipLaunchKernelGGL(k_fir_cplx_crossfix<true>, ggrid, dim3(256), 0, s, g, d_cross_taps, d_in, d_out, first, nseams, per);
-                else hipLaunchKernelGGL(k_fir_cplx_crossfix<false>, ggrid, dim3(256), 0, s, g, d_cross_taps, d_in, d_out, first, nseams, per);
-            } else if (guarded) {
-                if (in_is_u8) hipLaunchKernelGGL((k_decimate_c_crossfix<true, 8, 128, PER, SPW, true>), grid, block, 0, s, g, d_cross_taps, d_in, d_out, first, nseams);
-                else hipLaunchKernelGGL((k_decimate_c_crossfix<false, 8, 128, PER, SPW, true>), grid, block, 0, s, g, d_cross_taps, d_in, d_out, first, nseams);
-            } else if (P == 52) { if (in_is_u8) FIX(true, 52); else FIX(false, 52); }
-            else { if (in_is_u8) FIX(true, 128); else FIX(false, 128); }
+    const SeamSpan sp = seam_span(g);
+    if (sp.nseams > 0 && !inlined) {
+        constexpr int PER = 16, SPW = 16;              // 16 candidate slots per seam (ceil((128-1)/8)), 16 seams per workgroup
+        const dim3 grid((sp.nseams + SPW - 1) / SPW), block(PER * SPW);
+#define FIX(LPV, RTV) do { if (in_is_u8) hipLaunchKernelGGL((k_decimate_c_crossfix<true, 8, LPV, PER, SPW, RTV>), grid, block, 0, s, g, d_cross_taps, d_in, d_out, sp.first, sp.nseams); \
+                           else hipLaunchKernelGGL((k_decimate_c_crossfix<false, 8, LPV, PER, SPW, RTV>), grid, block, 0, s, g, d_cross_taps, d_in, d_out, sp.first, sp.nseams); } while (0)
+        if (g.D != 8 || P > 128) launch_fir_crossfix(s, g, sp, true, in_is_u8, d_cross_taps, d_in, d_out);    // generic
+        else if (guarded) FIX(128, true);              // any length up to 128: run-time tap count
+        else if (P == 52) FIX(52, false);
+        else FIX(128, false);
 #undef FIX
-            g_decimator_crossfix_launches.fetch_add(1, std::memory_order_relaxed);
-        }
+        g_decimator_crossfix_launches.fetch_add(1, std::memory_order_relaxed);
     }
     return true;
 }

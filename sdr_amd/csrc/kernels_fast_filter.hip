@@ -69,16 +69,10 @@ bool launch_filter_c4_tile(hipStream_t s, const Geom& g, const float* d_plain_ta
     if ((reinterpret_cast<uintptr_t>(d_out) & 15) != 0) return false;
     if (P == 128) launch_c4<1, 128, 4, 256, false>(s, g, d_plain_taps, d_in, d_out);
     else launch_c4<1, 64, 4, 256, false>(s, g, d_plain_taps, d_in, d_out);
-    if (g.seamBI != 0) {
-        // Cross outputs: sequential order over the plain taps (filterCrossHighLevel, FilterInternal.hs:404-408)
-        const int64_t v_lo = g.k_begin, v_hi = g.k_begin + g.count - 1 + g.Lp;
-        const int64_t first = v_lo / g.seamBI + 1, last = (v_hi - 1) / g.seamBI;
-        if (last >= first) {
-            const int nseams = (int)(last - first + 1);
-            if (P == 128) hipLaunchKernelGGL((k_filter_cplx_crossfix_lds<128>), dim3(nseams), dim3(128), 0, s, g, d_cross_taps, d_in, d_out, first);
-            else hipLaunchKernelGGL((k_filter_cplx_crossfix_lds<64>), dim3(nseams), dim3(64), 0, s, g, d_cross_taps, d_in, d_out, first);
-        }
-    }
+    // Cross outputs: sequential order over the plain taps (filterCrossHighLevel, FilterInternal.hs:404-408)
+    const SeamSpan sp = seam_span(g);
+    if (sp.nseams > 0 && P == 128) hipLaunchKernelGGL((k_filter_cplx_crossfix_lds<128>), dim3(sp.nseams), dim3(128), 0, s, g, d_cross_taps, d_in, d_out, sp.first);
+    else if (sp.nseams > 0) hipLaunchKernelGGL((k_filter_cplx_crossfix_lds<64>), dim3(sp.nseams), dim3(64), 0, s, g, d_cross_taps, d_in, d_out, sp.first);
     return true;
 }
 

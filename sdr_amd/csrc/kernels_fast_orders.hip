@@ -65,19 +65,8 @@ bool launch_decimate_c_orders_fast(hipStream_t s, const Geom& g, ComplexOrder or
         default: return false;
     }
     if (!took) return false;
-    if (g.seamBI != 0) {
-        // Cross outputs: sequential order over the plain taps, the same for every SIMD order (FilterInternal.hs:397-402)
-        const int64_t v_lo = g.k_begin * g.D, v_hi = (g.k_begin + g.count - 1) * g.D + g.Lp;
-        const int64_t first = v_lo / g.seamBI + 1, last = (v_hi - 1) / g.seamBI;
-        if (last >= first) {
-            const int nseams = (int)(last - first + 1);
-            const int per = (g.Lp - 1 + g.D - 1) / g.D;
-            const int64_t total = (int64_t)nseams * per;
-            const dim3 grid((unsigned)((total + 255) / 256));
-            if (in_is_u8) hipLaunchKernelGGL(k_fir_cplx_crossfix<true>, grid, dim3(256), 0, s, g, d_cross_taps, d_in, d_out, first, nseams, per);
-            else hipLaunchKernelGGL(k_fir_cplx_crossfix<false>, grid, dim3(256), 0, s, g, d_cross_taps, d_in, d_out, first, nseams, per);
-        }
-    }
+    // Cross outputs: sequential order over the plain taps, the same for every SIMD order (FilterInternal.hs:397-402)
+    launch_fir_crossfix(s, g, seam_span(g), true, in_is_u8, d_cross_taps, d_in, d_out);
     return true;
 }
 

@@ -317,6 +317,35 @@ void launch_resample_cplx(hipStream_t s, const Geom& g, ComplexOrder order, cons
     else hipLaunchKernelGGL((k_resample_cplx<CO_X4>), grid, block, 0, s, g, t, d_groups, d_plain_taps, d_in, d_out);
 }
 
+// What a whole-cycle kernel leaves of its launch (CycleSplit, kernels.hpp): the lead-in outputs as the launch's own table has
+// them, the tail outputs as a launch that starts at group 0 behind the last whole cycle.
+void launch_resample_lead_tail(hipStream_t s, const Geom& g, const CycleSplit& c, bool cplx, int lanes, ComplexOrder corder,
+                               const ResampTable& t, const int* increments, const float* d_groups, const float* d_plain_taps,
+                               const float* d_in, float* d_out)
+{
+    Geom gs = g;
+    gs.seamBI = 0;          // every output as One; the caller fixes its seams up afterwards
+    const int es = cplx ? 2 : 1;
+    if (c.lead > 0) {
+        Geom gl = gs;
+        gl.count = c.lead;
+        if (cplx) launch_resample_cplx(s, gl, corder, t, d_groups, d_plain_taps, d_in, d_out);
+        else launch_resample_real(s, gl, lanes, t, d_groups, d_plain_taps, d_in, d_out);
+    }
+    if (c.tail > 0) {
+        Geom gt = gs;
+        gt.k_begin = g.k_begin + c.done;
+        gt.count = c.tail;
+        ResampTable tt = t;
+        tt.group0 = 0;
+        int period = 0;
+        for (int q = 0; q < t.ngroups; q++) { tt.pre[q] = period; period += increments[q]; }      // the un-rotated prefix
+        tt.pos0 = t.pos0 + c.skip + (int64_t)c.ncycles * period;
+        if (cplx) launch_resample_cplx(s, gt, corder, tt, d_groups, d_plain_taps, d_in, d_out + es * c.done);
+        else launch_resample_real(s, gt, lanes, tt, d_groups, d_plain_taps, d_in, d_out + es * c.done);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // element-wise
 // ---------------------------------------------------------------------------

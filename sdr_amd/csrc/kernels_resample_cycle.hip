@@ -13,7 +13,7 @@
 // (stride D dwords) bank-conflict free; even ones stay on the split kernel (3/10 has its own).  Tiles are staged with
 // aligned 16-byte loads from the 16-byte boundary below the tile's first input; the thread windows start `shift` floats
 // into the LDS copy.  Lead / tail outputs (before the first group-0 output, after the last whole cycle) go to the generic
-// kernel, Cross outputs to the generic fix-up kernel of crossfix.hpp.
+// kernel, Cross outputs to the fix-ups of crossfix.hpp / kernels_crossfix.hip.
 //
 // Measured (tools/resamp_cycle_ab.py, 2^24 inputs, 8192-sample seams; lane-split kernel -> this one, G inputs/s):
 // 2/3 191 taps AVX 132 -> 235, 5/7 216 -> 406, 3/5 235 -> 344, 4/5 150 taps 219 -> 375, 6/7 700 taps 79 -> 148,
@@ -238,7 +238,6 @@ bool launch_resample_cycle_fast(hipStream_t s, const Geom& g, int lanes, const R
         if (!(corder == CO_X4 || corder == CO_X2)) return false;          // the "RC2" orders of resampleAVXRC / resampleSSERC
         lanes = corder == CO_X4 ? 8 : 4;
     }
-    const int es = cplx ? 2 : 1;
     if (t.force_seq || t.ext != nullptr || g.seamBI < 0 || g.count < 4096) return false;
     if (!(lanes == 8 || lanes == 4) || t.ngroups != g.I || t.nloop < 8 || t.nloop % lanes != 0 || t.nloop > 1024) return false;
     if (g.seamBI != 0 && d_plain_taps == nullptr) return false;
@@ -252,13 +251,10 @@ bool launch_resample_cycle_fast(hipStream_t s, const Geom& g, int lanes, const R
         }
     }
     // outputs before the first group-0 output and after the last whole cycle go to the generic kernel
-    int lead = (I - t.group0) % I;
-    if (lead > g.count) lead = g.count;
-    const int ncycles = (g.count - lead) / I;
-    const int tail = g.count - lead - I * ncycles;
+    const CycleSplit cs = cycle_split(I, t.group0, g.count, t.pre, increments);
+    const int lead = cs.lead, ncycles = cs.ncycles;
     if (ncycles < 1) return false;
-    const int64_t skip = lead > 0 ? t.pre[lead - 1] + increments[(t.group0 + lead - 1) % I] : 0;
-    const int64_t pos = t.pos0 + skip;
+    const int64_t pos = t.pos0 + cs.skip;
     bool took = false;
 #define CYC(IV, DV) if (I == IV && D == DV) took = lanes == 8 ? launch_cycle<IV, DV, 8, false>(s, d_in, pos, ncycles, t.nloop, d_groups, t.row_stride, d_out + lead) \
                                                               : launch_cycle<IV, DV, 4, false>(s, d_in, pos, ncycles, t.nloop, d_groups, t.row_stride, d_out + lead)
@@ -269,55 +265,18 @@ bool launch_resample_cycle_fast(hipStream_t s, const Geom& g, int lanes, const R
 #undef CYC
 #undef CYCC
     if (!took) return false;
-    Geom gs = g;
-    gs.seamBI = 0;          // every output as One first; seams are fixed up below
-    if (lead > 0) {
-        Geom gl = gs;
-        gl.count = lead;
-        if (cplx) launch_resample_cplx(s, gl, corder, t, d_groups, d_plain_taps, d_in, d_out);
-        else launch_resample_real(s, gl, lanes, t, d_groups, d_plain_taps, d_in, d_out);
-    }
-    if (tail > 0) {
-        const int done = lead + I * ncycles;
-        Geom gt = gs;
-        gt.k_begin = g.k_begin + done;
-        gt.count = tail;
-        ResampTable tt = t;
-        tt.group0 = 0;
-        tt.pos0 = pos + (int64_t)ncycles * D;
-        int acc = 0;
-        for (int q = 0; q < I; q++) { tt.pre[q] = acc; acc += increments[q]; }
-        if (cplx) launch_resample_cplx(s, gt, corder, tt, d_groups, d_plain_taps, d_in, d_out + es * done);
-        else launch_resample_real(s, gt, lanes, tt, d_groups, d_plain_taps, d_in, d_out + done);
-    }
-    if (g.seamBI != 0) {
-        int64_t first, last;
-        seam_range(g, first, last);
-        if (last >= first) {
-            const int nseams = (int)(last - first + 1);
-            const int per = (g.Lp - 1 + g.D - 1) / g.D;
-            // LDS-staged fix-up (one group of 32 / 64 lanes per seam: the straddlers' union of inputs and the taps in LDS)
-            // where the seam's straddlers fit, the generic one (global reads) beyond
-            const int64_t last_m = g.k_begin + g.count - 1;
-            const int64_t in_avail = (last_m * g.D + g.I - 1) / g.I - g.in_base + t.nloop;          // inputs the caller guarantees
-            auto uni = [&](int PER) { return t.nloop + (PER * g.D + g.I - 1) / g.I + 4; };
-            if (cplx) {
-                const int64_t total = (int64_t)nseams * per;
-                hipLaunchKernelGGL(k_resample_crossfix<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, g, d_plain_taps, t.ntaps_plain, d_in,
-                                   d_out, first, nseams, per);
-            } else if (per <= 32 && uni(32) <= 192)
-                hipLaunchKernelGGL((k_resample_real_crossfix<32, 192, 32>), dim3((nseams + 7) / 8), dim3(256), 0, s, g, d_plain_taps, t.ntaps_plain, d_in,
-                                   d_out, first, nseams, in_avail);
-            else if (per <= 64 && uni(64) <= 384)
-                hipLaunchKernelGGL((k_resample_real_crossfix<64, 384, 64>), dim3((nseams + 3) / 4), dim3(256), 0, s, g, d_plain_taps, t.ntaps_plain, d_in,
-                                   d_out, first, nseams, in_avail);
-            else {
-                const int64_t total = (int64_t)nseams * per;
-                hipLaunchKernelGGL(k_resample_crossfix<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, g, d_plain_taps, t.ntaps_plain, d_in,
-                                   d_out, first, nseams, per);
-            }
-        }
-    }
+    launch_resample_lead_tail(s, g, cs, cplx, lanes, corder, t, increments, d_groups, d_plain_taps, d_in, d_out);
+    // LDS-staged fix-up (one group of 32 / 64 lanes per seam: the straddlers' union of inputs and the taps in LDS) where the
+    // seam's straddlers fit, the generic one (global reads) beyond and for complex data
+    const SeamSpan sp = seam_span(g);
+    const int64_t in_avail = seam_in_avail(g, t.nloop);
+    auto uni = [&](int PER) { return t.nloop + (PER * g.D + g.I - 1) / g.I + 4; };
+#define LDS(PER, UNI, LPG) launch_real_crossfix_lds<PER, UNI, LPG>(s, g, sp, d_plain_taps, t.ntaps_plain, d_in, d_out, in_avail)
+    if (sp.nseams <= 0) return true;
+    if (!cplx && sp.per <= 32 && uni(32) <= 192) LDS(32, 192, 32);
+    else if (!cplx && sp.per <= 64 && uni(64) <= 384) LDS(64, 384, 64);
+    else launch_resample_crossfix(s, g, sp, cplx, d_plain_taps, t.ntaps_plain, d_in, d_out);
+#undef LDS
     return true;
 }
 

@@ -15,7 +15,7 @@
 // A resampler is NC = numGroups interleaved decimators: outputs i = n*NC + c share tap row (group0 + c) % NC and start
 // at pos0 + n*period + pre[c] (Filter.hs:613-641, resample.c:70-87), so a wave stays on one row for a whole run of n.
 // One workgroup stages the input span of NN cycles once, computes its NN*NC outputs, and stores them coalesced from LDS.
-// Seam straddlers ("Cross" outputs) are rewritten afterwards by the generic kernels of crossfix.hpp.
+// Seam straddlers ("Cross" outputs) are rewritten afterwards by the generic kernels of kernels_crossfix.hip.
 #include <stdlib.h>
 
 #include <atomic>
@@ -380,21 +380,7 @@ bool launch_fir_split(hipStream_t s, const Geom& g, bool cplx, int lanes, Comple
     a.apply_gain = apply_gain ? 1 : 0;
     if (!(cplx ? dispatch<true>(s, a, o, sym) : dispatch<false>(s, a, o, sym))) return false;
     g_split_launches++;
-    if (g.seamBI != 0) {
-        int64_t first, last;
-        seam_range(g, first, last);
-        if (last >= first) {
-            const int nseams = (int)(last - first + 1);
-            const int per = (g.Lp - 1 + g.D - 1) / g.D;
-            const int64_t total = (int64_t)nseams * per;
-            const dim3 grid((unsigned)((total + 255) / 256));
-            if (cplx)
-                hipLaunchKernelGGL(k_fir_cplx_crossfix<false>, grid, dim3(256), 0, s, g, d_cross_taps, d_in, d_out, first, nseams, per);
-            else
-                hipLaunchKernelGGL(k_fir_real_crossfix, grid, dim3(256), 0, s, g, d_cross_taps, d_in, d_out, first, nseams, per, gain,
-                                   apply_gain ? 1 : 0);
-        }
-    }
+    launch_fir_crossfix(s, g, seam_span(g), cplx, false, d_cross_taps, d_in, d_out, gain, apply_gain);
     return true;
 }
 
@@ -427,22 +413,7 @@ bool launch_resample_split(hipStream_t s, const Geom& g, bool cplx, int lanes, C
     a.apply_gain = 0;
     if (!(cplx ? dispatch<true>(s, a, o, false) : dispatch<false>(s, a, o, false))) return false;
     g_split_launches++;
-    if (g.seamBI != 0) {
-        int64_t first, lastb;
-        seam_range(g, first, lastb);
-        if (lastb >= first) {
-            const int nseams = (int)(lastb - first + 1);
-            const int per = (g.Lp - 1 + g.D - 1) / g.D;
-            const int64_t total = (int64_t)nseams * per;
-            const dim3 grid((unsigned)((total + 255) / 256));
-            if (cplx)
-                hipLaunchKernelGGL(k_resample_crossfix<true>, grid, dim3(256), 0, s, g, d_plain_taps, t.ntaps_plain, d_in, d_out, first,
-                                   nseams, per);
-            else
-                hipLaunchKernelGGL(k_resample_crossfix<false>, grid, dim3(256), 0, s, g, d_plain_taps, t.ntaps_plain, d_in, d_out, first,
-                                   nseams, per);
-        }
-    }
+    launch_resample_crossfix(s, g, seam_span(g), cplx, d_plain_taps, t.ntaps_plain, d_in, d_out);
     return true;
 }
 

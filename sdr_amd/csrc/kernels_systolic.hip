@@ -370,19 +370,18 @@ bool launch_decimate_c4_systolic(hipStream_t s, const Geom& g, const float* d_ta
     // instructions cost the same wherever they run, plus what they disturb: 1.5-4 % SLOWER inside at 2^27 ... 2^29 samples
     // (profiles/r06/k2_fix_inside_ab_sizes.txt) -- those launches keep the second launch.
     if (mode == 2 && g.count <= kFixInsideMaxOutputs && seams_done && g.seamBI > 0 && g.seamBI % 8 == 0 && g.seamBI / 8 >= 256 && g.seamBI / 8 < (1 << 30) && d_cross_taps != nullptr) {
-        const int64_t v_lo = g.k_begin * g.D, v_hi = (g.k_begin + g.count - 1) * g.D + g.Lp;
-        const int64_t first = v_lo / g.seamBI + 1, last = (v_hi - 1) / g.seamBI;
-        if (last >= first && last - first + 1 < (int64_t)1 << 30) {
+        const SeamSpan sp = seam_span(g);          // (at most 2^26 samples here and seams of at least 2048: a few thousand of them)
+        if (sp.nseams > 0) {
             fx.g = g;
             fx.xtaps = d_cross_taps;
-            fx.first_seam = first;
-            fx.nseams = (int)(last - first + 1);
+            fx.first_seam = sp.first;
+            fx.nseams = sp.nseams;
             fx.nfix_groups = ((fx.nseams + kFixSpw - 1) / kFixSpw + 63) / 64;
             fx.period_g = (groups + fx.nfix_groups) / fx.nfix_groups;
             fx.seamK = (int)(g.seamBI / 8);
             fx.k0mod = (int)(g.k_begin % fx.seamK);
             fix = fx.period_g >= 2;
-        } else if (last < first) {
+        } else {
             *seams_done = true;          // no boundary inside the launch: nothing to fix up
         }
     }
