@@ -266,6 +266,29 @@ int sdrhip_dc_blocker_run(void *stream, const float *d_in, float *d_out, int64_t
                           float last_output, float *d_final, void *d_workspace, size_t workspace_bytes,
                           int run_in);
 
+/* agc (hs_sources/SDR/Util.hs:325-342; Pipe agcPipe, Util.hs:344-348) on device memory, interleaved complex samples.
+ * Per sample (re, im), everything in f32, no FMA:
+ *     c_re = re * state;  c_im = im * state                  -- the output sample
+ *     m    = magnitude(c_re, c_im)
+ *     state' = state + mu * (reference - m)
+ * with GHC base's Data.Complex.magnitude at Float:
+ *     k = max(exponent c_re, exponent c_im)                  -- exponent 0 = 0, else frexp's (denormals normalised)
+ *     m = ldexpf(sqrtf(a*a + b*b), k),  a = ldexpf(c_re, -k), b = ldexpf(c_im, -k)      -- correctly rounded sqrt
+ * which is not sqrtf(re*re + im*im): the two differ where a square under- or overflows.  Bit-identical to the
+ * sequential loop for finite inputs whose trajectory stays finite (once the state is NaN its payload is unspecified).
+ * d_final receives the final state (one float); n == 0 writes `state` there.  d_workspace may be NULL (sequential
+ * walk); when given it starts with the three uint32 statistics of sdrhip_dc_blocker_run and a fourth word, the chunks
+ * the launch speculated on (0 = sequential walk).  run_in = samples each chunk runs in before its first output
+ * (0 = default, about 128 / mu: the contraction rate is mu * |x|); blocks shorter than two run-ins take the
+ * sequential walk.  The result never depends on run_in.  Not in-place. */
+size_t sdrhip_agc_workspace_bytes(int64_t n);       /* enough for any run_in */
+int sdrhip_agc_run(void *stream, const float *d_in_iq, float *d_out_iq, int64_t n /* complex samples */,
+                   float mu, float reference, float state, float *d_final /* 1 float: final state */,
+                   void *d_workspace, size_t workspace_bytes, int run_in);
+/* Diagnostics: the plan sdrhip_agc_run follows for these arguments when it has a workspace.  Returns the number of
+ * chunks (0 = sequential walk); *chunk and *run_in_used (either may be NULL) receive the chunk length and the run-in. */
+int sdrhip_debug_agc_plan(int64_t n, float mu, int run_in, int64_t *chunk, int64_t *run_in_used);
+
 /* ---- the record seam on HOST vectors (hs_sources/SDR/Filter.hs:116-144) ---- */
 /* The closures a Haskell constructor puts into the reference's own Filter / Decimator / Resampler records, so that
  * the reference's UNCHANGED Pipes (firFilter / firDecimator / firResampler, Filter.hs:532-727) drive the device:
@@ -553,6 +576,9 @@ int sdrhip_pipe_fir_decimator(sdrhip_pipe **p, const sdrhip_decimator *d, int bl
 int sdrhip_pipe_fir_resampler(sdrhip_pipe **p, const sdrhip_resampler *r, int block_size_out);    /* firResampler */
 int sdrhip_pipe_fm_demod(sdrhip_pipe **p);                                                         /* fmDemod      */
 int sdrhip_pipe_dc_blocker(sdrhip_pipe **p);                                     /* dcBlockingFilter, Filter.hs:730-739 */
+/* complex blocks in, complex blocks out at the length they came in; the state starts at 1 and is carried across blocks on the
+ * device (sdrhip_agc_run).  save / restore carry the state; mu and reference are the constructor's, not part of it. */
+int sdrhip_pipe_agc(sdrhip_pipe **p, float mu, float reference);                 /* agcPipe, Util.hs:344-348 */
 /* Feed one upstream block (n elements: floats, or complex pairs for complex
  * stages).  Returns the number of complete output blocks now ready (>= 0) or a
  * negative error.  A block shorter than numCoeffs is the reference's

@@ -659,4 +659,29 @@ int sdrhip_dc_blocker_run(void* stream, const float* d_in, float* d_out, int64_t
     return SDRHIP_OK;
 }
 
+size_t sdrhip_agc_workspace_bytes(int64_t n) { return agc_workspace_bytes(n); }
+
+int sdrhip_agc_run(void* stream, const float* d_in_iq, float* d_out_iq, int64_t n, float mu, float reference, float state,
+                   float* d_final, void* d_workspace, size_t workspace_bytes, int run_in)
+{
+    SDRHIP_REQUIRE(n >= 0 && d_final != nullptr && run_in >= 0, "sdrhip_agc_run");
+    if (n > 0) {
+        SDRHIP_REQUIRE(d_in_iq != nullptr && d_out_iq != nullptr && d_in_iq != d_out_iq, "sdrhip_agc_run: in-place is not supported");
+        SDRHIP_REQUIRE(d_workspace == nullptr || workspace_bytes >= agc_workspace_bytes(n),
+                       "sdrhip_agc_run: workspace smaller than sdrhip_agc_workspace_bytes(n)");
+    }
+    launch_agc((hipStream_t)stream, n, mu, reference, state, d_in_iq, d_out_iq, d_final, n > 0 ? d_workspace : nullptr, run_in);
+    SDRHIP_CHECK_HIP(hipGetLastError());
+    return SDRHIP_OK;
+}
+
+int sdrhip_debug_agc_plan(int64_t n, float mu, int run_in, int64_t* chunk, int64_t* run_in_used)
+{
+    SDRHIP_REQUIRE(n >= 0 && run_in >= 0, "sdrhip_debug_agc_plan");
+    const AgcPlan p = agc_plan(n, mu, run_in);
+    if (chunk) *chunk = p.C;
+    if (run_in_used) *run_in_used = p.W;
+    return p.nchunks;
+}
+
 }  // extern "C"

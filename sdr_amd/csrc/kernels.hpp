@@ -187,6 +187,16 @@ void launch_fm_demod(hipStream_t s, const float* d_in_iq, float* d_out, int64_t 
 size_t dc_blocker_workspace_bytes(int64_t num);
 void launch_dc_blocker(hipStream_t s, int64_t num, float last_sample, float last_output, const float* d_in,
                        float* d_out, float* d_final, void* d_ws, int run_in, const float* d_state = nullptr);
+// agc, Util.hs:325-342 (kernels_agc.hip: the same speculate / repair / settle scheme on interleaved complex samples,
+// bit-exact with the sequential walk).  d_final receives the final state (one float); d_ws as for dcBlocker, with a fourth
+// statistics word {chunks of the launch, 0 = the sequential walk}; run_in <= 0 selects the default, a function of mu.
+// d_state, when given, holds the starting state on the device and overrides `state` (it may alias d_final).  num == 0
+// hands the state on to d_final.
+struct AgcPlan { int64_t C, W; int nchunks; };   // chunk length, run-in, chunks (0 = the sequential walk)
+AgcPlan agc_plan(int64_t num, float mu, int run_in);
+size_t agc_workspace_bytes(int64_t num);         // enough for any run_in
+void launch_agc(hipStream_t s, int64_t num, float mu, float reference, float state, const float* d_in, float* d_out,
+                float* d_final, void* d_ws, int run_in, const float* d_state = nullptr);
 
 // Lane-split tiled kernels (kernels_split.hip): every SIMD order of the filter / decimator / resampler families,
 // any factor and tap count that fits a tile.  Plain taps (sym: the half taps).  false = not applicable.

@@ -28,7 +28,7 @@
 
 using namespace sdrhip;
 
-enum PipeKind { PK_FILTER, PK_DECIMATOR, PK_RESAMPLER, PK_DEMOD, PK_DCBLOCK };
+enum PipeKind { PK_FILTER, PK_DECIMATOR, PK_RESAMPLER, PK_DEMOD, PK_DCBLOCK, PK_AGC };
 
 struct sdrhip_pipe {
     PipeKind kind;
@@ -74,8 +74,10 @@ struct sdrhip_pipe {
     int lent = 0;              // elements behind the staged ones the caller may have filled through sdrhip_pipe_input_buffer
 
     std::deque<int> demod_blocks;      // fmDemod / dcBlockingFilter: output block lengths (one per input block)
-    DevBuf dc_state, dc_ws;            // dcBlockingFilter: {lastSample, lastOutput} carried on the device
-    bool is_map() const { return kind == PK_DEMOD || kind == PK_DCBLOCK; }
+    DevBuf dc_state, dc_ws;            // dcBlockingFilter: {lastSample, lastOutput} carried on the device; agcPipe: {state}
+    float agc_mu = 0.0f, agc_ref = 0.0f;
+    bool is_map() const { return kind == PK_DEMOD || kind == PK_DCBLOCK || kind == PK_AGC; }
+    bool has_dev_state() const { return (kind == PK_DCBLOCK || kind == PK_AGC) && dc_state.p; }
 
     int esz_in() const { return cplx_in ? 2 : 1; }
     int esz_out() const { return cplx_out ? 2 : 1; }
@@ -113,8 +115,9 @@ static int ready_blocks(const sdrhip_pipe* p)
     if (p->is_map()) {
         // complete blocks = those whose floats have all been harvested
         size_t have = p->eng.pending(), n = 0;
-        for (int len : p->demod_blocks) {
-            if (have < (size_t)len) break;
+        for (int blk : p->demod_blocks) {
+            const size_t len = (size_t)blk * p->esz_out();
+            if (have < len) break;
             have -= len;
             n++;
         }
@@ -297,7 +300,22 @@ int sdrhip_pipe_dc_blocker(sdrhip_pipe** pp)
     return SDRHIP_OK;
 }
 
-// ---- map stages (fmDemod, dcBlockingFilter): one output vector per input vector --------------------------------------
+int sdrhip_pipe_agc(sdrhip_pipe** pp, float mu, float reference)
+{
+    SDRHIP_REQUIRE(pp != nullptr, "sdrhip_pipe_agc");
+    int rc = pipe_new(pp, PK_AGC, nullptr, nullptr, 0, true, true, 1, 1, 1);
+    if (rc != SDRHIP_OK) return rc;
+    sdrhip_pipe* p = *pp;
+    p->agc_mu = mu;
+    p->agc_ref = reference;
+    if ((rc = p->dc_state.ensure(16)) != SDRHIP_OK) { delete p; *pp = nullptr; return rc; }
+    const float init[4] = {1.0f, 0.0f, 0.0f, 0.0f};                           // pMapAccum (agc mu reference) 1, Util.hs:348
+    hipError_t e = hipMemcpy(p->dc_state.p, init, 16, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { set_error("sdrhip_pipe_agc: %s", hipGetErrorString(e)); delete p; *pp = nullptr; return SDRHIP_ERR_HIP; }
+    return SDRHIP_OK;
+}
+
+// ---- map stages (fmDemod, dcBlockingFilter, agcPipe): one output vector per input vector ------------------------------
 // Blocks are staged one behind the other in the slot's pinned buffer and go out as ONE run over all of them -- the carry of a
 // block is its predecessor's last sample (fmDemod, Demod.hs:41,46) / the filter's running pair kept on the device
 // (dcBlockingFilter, Filter.hs:730-739), which is exactly what a run over the concatenation computes; the block lengths are
@@ -309,7 +327,8 @@ static int map_submit(sdrhip_pipe* p)
     const int n = e.staged;
     if (n == 0) return SDRHIP_OK;
     const size_t ein = (size_t)p->esz_in() * 4;
-    // (dcBlockingFilter never in place: its lanes re-read their run-in and a short block is one lane's dependent loads)
+    // (dcBlockingFilter and agcPipe never in place: their lanes re-read their run-in and a short block is one lane's dependent
+    // loads)
     const bool direct = p->direct_ok && p->kind == PK_DEMOD && (size_t)n * ein <= sdrhip_pipe::kDirectBytes;
     const float* h = (const float*)e.staged_base();
     return e.submit(direct ? HostStream::kInPlace : HostStream::kCopyEngines, e.compute[0], h, (size_t)n * ein,
@@ -318,6 +337,12 @@ static int map_submit(sdrhip_pipe* p)
             launch_fm_demod_fast(s, (const float*)d_in, (float*)d_out, n, false, p->last_re, p->last_im);
             p->last_re = h[2 * (size_t)(n - 1)];
             p->last_im = h[2 * (size_t)(n - 1) + 1];
+        } else if (p->kind == PK_AGC) {
+            if (agc_workspace_bytes(n) > p->dc_ws.cap) SDRHIP_CHECK_HIP(hipStreamSynchronize(s));            // growing frees the old buffer
+            int rc = p->dc_ws.ensure(agc_workspace_bytes(n));
+            if (rc != SDRHIP_OK) return rc;
+            launch_agc(s, n, p->agc_mu, p->agc_ref, 1.0f, (const float*)d_in, (float*)d_out, (float*)p->dc_state.p, p->dc_ws.p, 0,
+                       (const float*)p->dc_state.p);
         } else {
             if (dc_blocker_workspace_bytes(n) > p->dc_ws.cap) SDRHIP_CHECK_HIP(hipStreamSynchronize(s));     // growing frees the old buffer
             int rc = p->dc_ws.ensure(dc_blocker_workspace_bytes(n));
@@ -429,7 +454,7 @@ int sdrhip_pipe_pop(sdrhip_pipe* p, float* out, int capacity)
 
 // ---- checkpoint / resume (as sdrhip_fm_stream_save / _restore, chain.cpp) -------------------------------------------
 // Between two pushes a Pipe's state is its position (elements consumed, outputs produced), the last head_cap input elements,
-// the carried fmDemod sample / dcBlocker pair, and the output not yet popped: what the reference keeps in the Pipe's closure
+// the carried fmDemod sample / dcBlocker pair / agc state, and the output not yet popped: what the reference keeps in the Pipe's closure
 // (Filter.hs:536-727: overlap remainder, resampler (group, offset); Demod.hs:41,46; Filter.hs:730-739).
 namespace {
 struct PipeStateHeader {
@@ -469,7 +494,7 @@ int sdrhip_pipe_save(sdrhip_pipe* p, void* buf, size_t capacity, size_t* used)
     h.E_prev = p->E_prev; h.m_done = p->m_done; h.head_cap = p->eng.head_cap; h.hist_n = p->eng.hist_n;
     h.pending = (int64_t)p->eng.pending();
     h.last_re = p->last_re; h.last_im = p->last_im;
-    if (p->kind == PK_DCBLOCK && p->dc_state.p) {
+    if (p->has_dev_state()) {
         SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));
         SDRHIP_CHECK_HIP(hipMemcpy(h.dc, p->dc_state.p, 16, hipMemcpyDeviceToHost));
     }
@@ -520,7 +545,7 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
     p->last_im = h.last_im;
     p->demod_blocks.clear();
     for (int i = 0; i < h.n_blocks; i++) { int32_t v; memcpy(&v, in, sizeof v); in += sizeof v; p->demod_blocks.push_back(v); }
-    if (p->kind == PK_DCBLOCK && p->dc_state.p) {
+    if (p->has_dev_state()) {
         SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));       // the create call's memset
         SDRHIP_CHECK_HIP(hipMemcpy(p->dc_state.p, h.dc, 16, hipMemcpyHostToDevice));
     }

@@ -205,6 +205,10 @@ lib.sdrhip_debug_tiled_launches.restype = C.c_longlong
 lib.sdrhip_dc_blocker_workspace_bytes.argtypes = [C.c_int64]
 lib.sdrhip_dc_blocker_workspace_bytes.restype = C.c_size_t
 lib.sdrhip_dc_blocker_run.argtypes = [_vp, _vp, _vp, C.c_int64, C.c_float, C.c_float, _vp, _vp, C.c_size_t, C.c_int]
+lib.sdrhip_agc_workspace_bytes.argtypes = [C.c_int64]
+lib.sdrhip_agc_workspace_bytes.restype = C.c_size_t
+lib.sdrhip_agc_run.argtypes = [_vp, _vp, _vp, C.c_int64, C.c_float, C.c_float, C.c_float, _vp, _vp, C.c_size_t, C.c_int]
+lib.sdrhip_debug_agc_plan.argtypes = [C.c_int64, C.c_float, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]
 
 lib.sdrhip_fm_stream_create.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int]
 lib.sdrhip_fm_stream_destroy.argtypes = [_vp]
@@ -223,6 +227,7 @@ lib.sdrhip_pipe_fir_decimator.argtypes = [C.POINTER(_vp), _vp, C.c_int]
 lib.sdrhip_pipe_fir_resampler.argtypes = [C.POINTER(_vp), _vp, C.c_int]
 lib.sdrhip_pipe_fm_demod.argtypes = [C.POINTER(_vp)]
 lib.sdrhip_pipe_dc_blocker.argtypes = [C.POINTER(_vp)]
+lib.sdrhip_pipe_agc.argtypes = [C.POINTER(_vp), C.c_float, C.c_float]
 lib.sdrhip_pipe_set_coalesce.argtypes = [_vp, C.c_int]
 lib.sdrhip_pipe_set_adaptive.argtypes = [_vp, C.c_int]
 lib.sdrhip_pipe_input_buffer.argtypes = [_vp, C.c_int]
@@ -356,6 +361,51 @@ class DropIn:
         fs, fo = C.c_float(), C.c_float()
         lib.dcBlocker(x.size, C.c_float(last_sample), C.c_float(last_output), C.byref(fs), C.byref(fo), _fp(x), _fp(out))
         return out, fs.value, fo.value
+
+
+def agc_plan(n, mu, run_in=0):
+    """sdrhip_debug_agc_plan: (chunks, chunk length, run-in) of an agc run over n samples; chunks == 0: the sequential walk."""
+    c, w = _i64(), _i64()
+    chunks = check(lib.sdrhip_debug_agc_plan(n, mu, run_in, C.byref(c), C.byref(w)), "sdrhip_debug_agc_plan")
+    return chunks, c.value, w.value
+
+
+def agc(x, mu, reference, state=1.0, run_in=0):
+    """agc (Util.hs:325-342) -> (out, final_state).  x: a device tensor (complex64, or float32 interleaved; `out` is then a
+    device tensor of the same type and shape) or a host array (complex64 or float32 interleaved; `out` is a numpy array)."""
+    if hasattr(x, "data_ptr"):
+        import torch
+        n = x.numel() if x.is_complex() else x.numel() // 2
+        d_in = x.contiguous()
+        d_out = torch.empty_like(d_in)
+        fin = torch.empty(1, dtype=torch.float32, device=d_in.device)
+        wsb = lib.sdrhip_agc_workspace_bytes(n)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=d_in.device)
+        check(lib.sdrhip_agc_run(torch.cuda.current_stream().cuda_stream, d_in.data_ptr(), d_out.data_ptr(), n, mu, reference, state,
+                                 fin.data_ptr(), ws.data_ptr(), wsb, run_in), "sdrhip_agc_run")
+        return d_out, float(fin.item())
+    a = np.ascontiguousarray(x)
+    cplx = np.iscomplexobj(a)
+    a = np.ascontiguousarray(a, dtype=np.complex64 if cplx else np.float32)
+    n = a.size if cplx else a.size // 2
+    out = np.empty_like(a)
+    fin = np.empty(1, np.float32)
+    wsb = lib.sdrhip_agc_workspace_bytes(n)
+    bufs = [_vp(), _vp(), _vp(), _vp()]
+    try:
+        for b, size in zip(bufs, (max(8 * n, 8), max(8 * n, 8), 4, wsb)):
+            check(lib.sdrhip_malloc(C.byref(b), size), "sdrhip_malloc")
+        d_in, d_out, d_fin, d_ws = bufs
+        check(lib.sdrhip_memcpy_h2d(d_in, a.ctypes.data, 8 * n, None), "sdrhip_memcpy_h2d")
+        check(lib.sdrhip_agc_run(None, d_in, d_out, n, mu, reference, state, d_fin, d_ws, wsb, run_in), "sdrhip_agc_run")
+        check(lib.sdrhip_memcpy_d2h(out.ctypes.data, d_out, 8 * n, None), "sdrhip_memcpy_d2h")
+        check(lib.sdrhip_memcpy_d2h(fin.ctypes.data, d_fin, 4, None), "sdrhip_memcpy_d2h")
+        check(lib.sdrhip_stream_sync(None), "sdrhip_stream_sync")
+    finally:
+        for b in bufs:
+            if b:
+                lib.sdrhip_free(b)
+    return out, float(fin[0])
 
 
 # ---- descriptors ----------------------------------------------------------------------
@@ -735,15 +785,16 @@ class FmStream(_Handle):
 
 
 class Pipe(_Handle):
-    """firFilter / firDecimator / firResampler / fmDemod on host blocks (Filter.hs:532-727, Demod.hs:40-46)."""
+    """firFilter / firDecimator / firResampler / fmDemod / dcBlockingFilter / agcPipe on host blocks (Filter.hs:532-739,
+    Demod.hs:40-46, Util.hs:344-348)."""
     _destroy = lib.sdrhip_pipe_destroy
 
-    def __init__(self, kind, desc=None, block_size_out=8192):
+    def __init__(self, kind, desc=None, block_size_out=8192, mu=None, reference=None):
         super().__init__()
         self.desc = desc  # keep the descriptor alive
         self.block_size_out = block_size_out
-        self.complex_in = bool(getattr(desc, "complex", False)) or kind == "fm_demod"
-        self.complex_out = bool(getattr(desc, "complex", False))
+        self.complex_in = bool(getattr(desc, "complex", False)) or kind in ("fm_demod", "agc")
+        self.complex_out = bool(getattr(desc, "complex", False)) or kind == "agc"
         if kind == "filter":
             check(lib.sdrhip_pipe_fir_filter(C.byref(self.h), desc.h, block_size_out), "sdrhip_pipe_fir_filter")
         elif kind == "decimator":
@@ -754,6 +805,10 @@ class Pipe(_Handle):
             check(lib.sdrhip_pipe_fm_demod(C.byref(self.h)), "sdrhip_pipe_fm_demod")
         elif kind == "dc_blocker":
             check(lib.sdrhip_pipe_dc_blocker(C.byref(self.h)), "sdrhip_pipe_dc_blocker")
+        elif kind == "agc":
+            if mu is None or reference is None:
+                raise ValueError("Pipe('agc') needs mu and reference")
+            check(lib.sdrhip_pipe_agc(C.byref(self.h), mu, reference), "sdrhip_pipe_agc")
         else:
             raise ValueError(kind)
         self.kind = kind
@@ -835,6 +890,11 @@ def fmDemod():
 def dcBlockingFilter():
     """Filter.hs:730-739."""
     return Pipe("dc_blocker")
+
+
+def agcPipe(mu, reference):
+    """Util.hs:344-348: interleaved float32 complex blocks in and out, the state starts at 1."""
+    return Pipe("agc", mu=mu, reference=reference)
 
 
 def interleavedIQUnsignedByteToFloat(u8):
