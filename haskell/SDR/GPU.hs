@@ -123,6 +123,9 @@ foreign import ccall safe "sdrhip_spectrum_window"     c_spectrum_window     :: 
 foreign import ccall safe "sdrhip_spectrum_run"        c_spectrum_run        :: Ptr SdrSpectrum -> Ptr () -> Int64 -> Int64 -> CInt -> Ptr CFloat -> IO CInt
 foreign import ccall safe "sdrhip_spectrum_run_device" c_spectrum_run_device :: Ptr SdrSpectrum -> Ptr () -> Ptr () -> Int64 -> Int64 -> CInt -> Ptr CFloat -> IO CInt
 foreign import ccall safe "sdrhip_spectrum_set_route"  c_spectrum_set_route  :: Ptr SdrSpectrum -> CInt -> IO CInt
+-- the rows reduced on the device (mean power / mean magnitude / max hold over `group` rows, linear or dB): samples, hop, rows_out, group,
+-- reduce, unit, floor_db
+foreign import ccall safe "sdrhip_spectrum_reduce_run" c_spectrum_reduce_run :: Ptr SdrSpectrum -> Ptr () -> Int64 -> Int64 -> CInt -> CInt -> CInt -> CInt -> CDouble -> Ptr CFloat -> IO CInt
 
 -- | SDRHIP_ORDER_AVX: reproduce the variant 'SDR.CPUID.featureSelect' picks on any AVX host.
 orderAVX :: CInt

@@ -566,6 +566,35 @@ int  sdrhip_spectrum_run(sdrhip_spectrum *s, const void *in, int64_t n_samples, 
 int  sdrhip_spectrum_set_route(sdrhip_spectrum *s, int route);   /* 0 = auto, 1 = the one-kernel route, 2 = hipFFT route */
 long long sdrhip_debug_spectrum_fused_launches(void);            /* process-wide, for tests that assert the route */
 
+/* The operator's rows reduced on the device: output row R is made of the `group` consecutive input rows R*group .. R*group + group - 1
+ * (input row r = samples [r*hop, r*hop + n), as above), which never reach memory.  With m_r[k] = scale * |X_r[k]|, exactly the double
+ * sdrhip_spectrum_run_device rounds to float32, all arithmetic in double, no FMA:
+ *     MEAN_POWER v = (sum of m^2) / group;  MEAN_MAGNITUDE v = (sum of m) / group;  MAX_MAGNITUDE v = max m;
+ *     LINEAR out = (float)v;  DB out = (float)max(floor_db, c log10 v), c = 10 for MEAN_POWER and 20 otherwise (v = 0 gives floor_db).
+ * SUMMATION ORDER (part of the definition): the group is cut into chunks of 32 consecutive input rows (the last may be shorter); each
+ * chunk is summed in ascending row order starting from 0.0; the chunk sums are then added in ascending order starting from 0.0.
+ * Needs rows_out >= 1, group >= 1, hop >= 1, (rows_out*group - 1)*hop + n <= n_samples, rows_out*group within int, reduce and unit
+ * in range and a finite floor_db; otherwise SDRHIP_ERR_ARG, no launch, nothing written.  Asynchronous on `stream`.
+ * On the one-kernel route an output row's bits depend on its own (group-1)*hop + n samples, group, reduce and unit alone: not on
+ * rows_out, its place in the batch, the split mode or the grid; between the two routes the tolerance contract holds.  Groups of more
+ * than 32 rows, and the hipFFT route, go through a bounded scratch buffer of the object (doubles per output bin, not per input row).
+ * Split: with few output rows and a long group the chunks of a group are spread over the chip and added up by a second kernel, in
+ * the order above (the same bits); `auto` does so when the output rows alone would leave compute units idle. */
+#define SDRHIP_REDUCE_MEAN_POWER     0   /* Welch: mean over the group of m^2 */
+#define SDRHIP_REDUCE_MEAN_MAGNITUDE 1   /* mean over the group of m          */
+#define SDRHIP_REDUCE_MAX_MAGNITUDE  2   /* max hold: max over the group of m */
+#define SDRHIP_UNIT_LINEAR 0
+#define SDRHIP_UNIT_DB     1             /* 10 log10 v (power) / 20 log10 v (magnitudes), never below floor_db */
+int  sdrhip_spectrum_reduce_run_device(sdrhip_spectrum *s, void *stream, const void *d_in, int64_t n_samples, int64_t hop,
+                                       int rows_out, int group, int reduce, int unit, double floor_db, float *d_out /* rows_out x n */);
+/* HOST vectors, synchronous */
+int  sdrhip_spectrum_reduce_run(sdrhip_spectrum *s, const void *in, int64_t n_samples, int64_t hop, int rows_out, int group,
+                                int reduce, int unit, double floor_db, float *out);
+int  sdrhip_spectrum_set_reduce_split(sdrhip_spectrum *s, int mode);   /* 0 = auto, 1 = never, 2 = always (groups of more than 32 rows) */
+/* process-wide: reduce calls that spread a group over workgroups.  Every reduce call on the one-kernel route also counts once in
+ * sdrhip_debug_spectrum_fused_launches. */
+long long sdrhip_debug_spectrum_reduce_split_launches(void);
+
 /* ------------------------------------------------------------------------ */
 /* (3) Pipe operators on host blocks                                        */
 /* ------------------------------------------------------------------------ */

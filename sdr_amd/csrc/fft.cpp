@@ -174,6 +174,7 @@ int sdrhip_fft_run(sdrhip_fft* f, const double* in, double* out)
 namespace {
 
 std::atomic<long long> g_spectrum_fused_launches{0};
+std::atomic<long long> g_spectrum_reduce_split_launches{0};
 
 constexpr size_t SPECTRUM_SCRATCH_BYTES = (size_t)64 << 20;      // the hipFFT route's intermediate: at most this, or one row
 
@@ -186,13 +187,14 @@ struct SpectrumPlan {
 
 struct sdrhip_spectrum {
     int n = 0, format = 0, shift = 0, route = 0;
+    int reduce_split = 0;                  // 0 = auto, 1 = never, 2 = always
     double scale = 1.0;
     std::vector<double> window;
     DevBuf d_window, d_twiddle;
     bool uploaded = false;
     ScratchCtx* ctx = nullptr;             // leased on first need (host entry point, hipFFT route), held until destroy
-    hipStream_t last_stream = nullptr;     // the stream of the last hipFFT-route run: drained before the scratch goes back
-    bool ran_hipfft = false;
+    hipStream_t last_stream = nullptr;     // the stream of the last run that used ctx->work: drained before the scratch goes back
+    bool ran_hipfft = false;               // ... and whether there was one (the hipFFT route, or a reduction through layers)
     std::vector<SpectrumPlan> plans;       // one per batch size in use: the chunk, and the last chunk of a run
     bool fused_size() const { return spectrum_fused_size(n); }
     bool takes_fused() const { return route == 1 || (route == 0 && fused_size()); }
@@ -261,6 +263,18 @@ int spectrum_plan(sdrhip_spectrum* s, int batch, hipfftHandle* out)
     return SDRHIP_OK;
 }
 
+// ctx->work for a run on `stream`, at least `bytes` large.  There is one such buffer: a run on another stream waits for the last one.
+int spectrum_take_work(sdrhip_spectrum* s, hipStream_t stream, size_t bytes)
+{
+    int rc;
+    if ((rc = spectrum_lease(s)) != SDRHIP_OK) return rc;
+    if (s->ran_hipfft && s->last_stream != stream) SDRHIP_CHECK_HIP(hipStreamSynchronize(s->last_stream));
+    if ((rc = s->ctx->work.ensure(bytes)) != SDRHIP_OK) return rc;
+    s->last_stream = stream;
+    s->ran_hipfft = true;
+    return SDRHIP_OK;
+}
+
 int spectrum_run_hipfft(sdrhip_spectrum* s, hipStream_t stream, const SpectrumArgs& a, float* d_out)
 {
     HipFft* h = hipfft();
@@ -274,11 +288,8 @@ int spectrum_run_hipfft(sdrhip_spectrum* s, hipStream_t stream, const SpectrumAr
     int64_t chunk = (int64_t)(SPECTRUM_SCRATCH_BYTES / row_bytes);
     if (chunk < 1) chunk = 1;
     if (chunk > a.rows) chunk = a.rows;
-    if (s->ran_hipfft && s->last_stream != stream) SDRHIP_CHECK_HIP(hipStreamSynchronize(s->last_stream));   // one scratch: runs take turns
-    if ((rc = s->ctx->work.ensure((size_t)chunk * row_bytes)) != SDRHIP_OK) return rc;
+    if ((rc = spectrum_take_work(s, stream, (size_t)chunk * row_bytes)) != SDRHIP_OK) return rc;
     double2* work = static_cast<double2*>(s->ctx->work.p);
-    s->last_stream = stream;
-    s->ran_hipfft = true;
     for (int64_t row0 = 0; row0 < a.rows; row0 += chunk) {
         const int64_t nrows = a.rows - row0 < chunk ? a.rows - row0 : chunk;
         hipfftHandle plan;
@@ -289,6 +300,116 @@ int spectrum_run_hipfft(sdrhip_spectrum* s, hipStream_t stream, const SpectrumAr
         SDRHIP_CHECK_HIP(launch_spectrum_magnitude(stream, work, nrows * s->n, s->scale, d_out + row0 * s->n));
     }
     return SDRHIP_OK;
+}
+
+// ---- the reducing form -----------------------------------------------------------------------------------------------------------
+// Work items a layered launch is spread over when it splits: 4 per CU of a 256-CU chip.  A guess, like the rule that `auto` splits
+// when the output tiles alone are fewer than the CUs: tools/spectrum_reduce_bench.py is there to set both.
+constexpr int64_t SPECTRUM_SPLIT_ITEMS = 1024;
+constexpr int64_t SPECTRUM_CHIP_CUS = 256;
+
+int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// the input `rows` output rows further on (a.rows is set by the caller)
+SpectrumArgs spectrum_args_from(const sdrhip_spectrum* s, const SpectrumArgs& a, int64_t rows, int group)
+{
+    SpectrumArgs b = a;
+    b.in = static_cast<const unsigned char*>(a.in) + (size_t)(rows * group * a.hop) * s->sample_bytes();
+    return b;
+}
+
+// One-kernel route.  A group of one chunk leaves the kernel as floats.  A longer one goes through layers of chunk sums in ctx->work
+// and the finalise kernel, in slices of output rows and of chunks that keep the scratch inside SPECTRUM_SCRATCH_BYTES: rows are
+// independent of each other and the total is carried from slice to slice in the defined order, so the slicing changes no bit.
+int spectrum_reduce_fused(sdrhip_spectrum* s, hipStream_t stream, const SpectrumArgs& a, int rows_out, const SpectrumReduce& f, float* d_out)
+{
+    const int n = s->n;
+    if (f.group <= SPECTRUM_REDUCE_CHUNK) {
+        SDRHIP_CHECK_HIP(launch_spectrum_fused_reduce(stream, a, f, 0, 1, 1, nullptr, d_out));
+        g_spectrum_fused_launches.fetch_add(1);
+        return SDRHIP_OK;
+    }
+    const int rows_per_tile = n >= 2048 ? 1 : 2048 / n;
+    const int nchunks = (int)ceil_div(f.group, SPECTRUM_REDUCE_CHUNK);
+    const size_t row_bytes = (size_t)n * sizeof(double);
+    // a sixteenth of the scratch for the carried totals of a row slice (whole tiles, at least one row), the rest for its layers
+    int64_t rows_slice = (int64_t)(SPECTRUM_SCRATCH_BYTES / 16 / row_bytes);
+    if (rows_slice > rows_per_tile) rows_slice -= rows_slice % rows_per_tile;
+    if (rows_slice < 1) rows_slice = 1;
+    if (rows_slice > rows_out) rows_slice = rows_out;
+    int64_t layers_slice = (int64_t)(SPECTRUM_SCRATCH_BYTES / (rows_slice * row_bytes)) - 1;
+    if (layers_slice < 1) layers_slice = 1;
+    if (layers_slice > nchunks) layers_slice = nchunks;
+    const int64_t tiles_all = ceil_div(rows_out, rows_per_tile);
+    const bool split = s->reduce_split == 2 || (s->reduce_split == 0 && tiles_all < SPECTRUM_CHIP_CUS);
+    int rc;
+    if ((rc = spectrum_take_work(s, stream, (size_t)rows_slice * row_bytes * (size_t)(1 + layers_slice))) != SDRHIP_OK) return rc;
+    double* total = static_cast<double*>(s->ctx->work.p);
+    double* partial = total + rows_slice * n;
+    for (int64_t r0 = 0; r0 < rows_out; r0 += rows_slice) {
+        SpectrumArgs b = spectrum_args_from(s, a, r0, f.group);
+        b.rows = rows_out - r0 < rows_slice ? rows_out - r0 : rows_slice;
+        const int64_t tiles = ceil_div(b.rows, rows_per_tile);
+        for (int c0 = 0; c0 < nchunks; c0 += (int)layers_slice) {
+            const int c1 = c0 + layers_slice < nchunks ? c0 + (int)layers_slice : nchunks;
+            int per_item = c1 - c0;                     // not split: a tile's chunks stay with one workgroup
+            if (split) per_item = (int)ceil_div(c1 - c0, ceil_div(SPECTRUM_SPLIT_ITEMS, tiles));
+            SDRHIP_CHECK_HIP(launch_spectrum_fused_reduce(stream, b, f, c0, c1, per_item, partial, nullptr));
+            SDRHIP_CHECK_HIP(launch_spectrum_reduce_finalise(stream, partial, c1 - c0, b.rows * n, total, c0 == 0, c1 == nchunks, f, d_out + r0 * n));
+        }
+    }
+    g_spectrum_fused_launches.fetch_add(1);
+    if (split) g_spectrum_reduce_split_launches.fetch_add(1);
+    return SDRHIP_OK;
+}
+
+// hipFFT route: half the scratch for the state of a slice of output rows (two doubles per bin), half for the batches of its input rows
+int spectrum_reduce_hipfft(sdrhip_spectrum* s, hipStream_t stream, const SpectrumArgs& a, int rows_out, const SpectrumReduce& f, float* d_out)
+{
+    HipFft* h = hipfft();
+    if (!h->handle) {
+        set_error("sdrhip_spectrum_reduce_run_device: hipFFT is not available (%s)", h->why.c_str());
+        return SDRHIP_ERR_STATE;
+    }
+    const int n = s->n;
+    const size_t state_row = 2 * (size_t)n * sizeof(double), work_row = (size_t)n * sizeof(double2);
+    int64_t rows_slice = (int64_t)(SPECTRUM_SCRATCH_BYTES / 2 / state_row);
+    if (rows_slice < 1) rows_slice = 1;
+    if (rows_slice > rows_out) rows_slice = rows_out;
+    int64_t batch = (int64_t)(SPECTRUM_SCRATCH_BYTES / 2 / work_row);
+    if (batch < 1) batch = 1;
+    if (batch > rows_slice * f.group) batch = rows_slice * f.group;
+    int rc;
+    if ((rc = spectrum_take_work(s, stream, (size_t)rows_slice * state_row + (size_t)batch * work_row)) != SDRHIP_OK) return rc;
+    double* chunk = static_cast<double*>(s->ctx->work.p);
+    double* total = chunk + rows_slice * n;
+    double2* work = reinterpret_cast<double2*>(total + rows_slice * n);
+    for (int64_t r0 = 0; r0 < rows_out; r0 += rows_slice) {
+        const int64_t nr = rows_out - r0 < rows_slice ? rows_out - r0 : rows_slice;
+        const int64_t in_rows = nr * f.group;
+        for (int64_t b0 = 0; b0 < in_rows; b0 += batch) {
+            const int64_t nrows = in_rows - b0 < batch ? in_rows - b0 : batch;
+            hipfftHandle plan;
+            if ((rc = spectrum_plan(s, (int)nrows, &plan)) != SDRHIP_OK) return rc;
+            SDRHIP_CHECK_HIP(launch_spectrum_prepare(stream, a, r0 * f.group + b0, nrows, work));
+            SDRHIP_CHECK_FFT(h->SetStream(plan, stream));
+            SDRHIP_CHECK_FFT(h->ExecZ2Z(plan, reinterpret_cast<hipfftDoubleComplex*>(work), reinterpret_cast<hipfftDoubleComplex*>(work), HIPFFT_FORWARD));
+            SDRHIP_CHECK_HIP(launch_spectrum_accumulate(stream, work, b0, nrows, n, s->scale, f, chunk, total, d_out + r0 * n));
+        }
+    }
+    return SDRHIP_OK;
+}
+
+// what both reduce entry points require of their arguments
+bool spectrum_reduce_args_ok(const sdrhip_spectrum* s, int64_t n_samples, int64_t hop, int rows_out, int group, int reduce, int unit, double floor_db)
+{
+    if (rows_out < 1 || group < 1 || hop < 1 || n_samples < s->n) return false;
+    if ((int64_t)rows_out * group > 2147483647LL) return false;
+    const int64_t rows = (int64_t)rows_out * group;
+    if (rows > 1 && hop > (n_samples - s->n) / (rows - 1)) return false;      // (rows - 1) hop + n <= n_samples, without overflow
+    if (reduce < SDRHIP_REDUCE_MEAN_POWER || reduce > SDRHIP_REDUCE_MAX_MAGNITUDE) return false;
+    if (unit != SDRHIP_UNIT_LINEAR && unit != SDRHIP_UNIT_DB) return false;
+    return std::isfinite(floor_db);
 }
 
 }  // namespace
@@ -386,6 +507,70 @@ int sdrhip_spectrum_run(sdrhip_spectrum* s, const void* in, int64_t n_samples, i
     memcpy(c->hin.p, in, in_bytes);
     SDRHIP_CHECK_HIP(hipMemcpyAsync(c->in.p, c->hin.p, in_bytes, hipMemcpyHostToDevice, c->stream));
     if ((rc = sdrhip_spectrum_run_device(s, c->stream, c->in.p, n_samples, hop, rows, static_cast<float*>(c->out.p))) != SDRHIP_OK) return rc;
+    SDRHIP_CHECK_HIP(hipMemcpyAsync(c->hout.p, c->out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    SDRHIP_CHECK_HIP(hipStreamSynchronize(c->stream));
+    memcpy(out, c->hout.p, out_bytes);
+    return SDRHIP_OK;
+}
+
+}  // extern "C"
+
+// ---- the reducing form: mean power / mean magnitude / max hold over `group` consecutive rows, on the device ---------------------------
+extern "C" {
+
+int sdrhip_spectrum_set_reduce_split(sdrhip_spectrum* s, int mode)
+{
+    SDRHIP_REQUIRE(s != nullptr && mode >= 0 && mode <= 2, "sdrhip_spectrum_set_reduce_split");
+    s->reduce_split = mode;
+    return SDRHIP_OK;
+}
+
+long long sdrhip_debug_spectrum_reduce_split_launches(void) { return g_spectrum_reduce_split_launches.load(); }
+
+int sdrhip_spectrum_reduce_run_device(sdrhip_spectrum* s, void* stream, const void* d_in, int64_t n_samples, int64_t hop, int rows_out, int group,
+                                      int reduce, int unit, double floor_db, float* d_out)
+{
+    SDRHIP_REQUIRE(s != nullptr && d_in != nullptr && d_out != nullptr, "sdrhip_spectrum_reduce_run_device");
+    SDRHIP_REQUIRE(spectrum_reduce_args_ok(s, n_samples, hop, rows_out, group, reduce, unit, floor_db), "sdrhip_spectrum_reduce_run_device");
+    int rc;
+    if ((rc = spectrum_upload(s)) != SDRHIP_OK) return rc;
+    SpectrumArgs a;
+    a.in = d_in;
+    a.format = s->format;
+    a.hop = hop;
+    a.rows = rows_out;
+    a.n = s->n;
+    a.shift = s->shift;
+    a.scale = s->scale;
+    a.window = static_cast<const double*>(s->d_window.p);
+    a.twiddle = static_cast<const double2*>(s->d_twiddle.p);
+    SpectrumReduce f;
+    f.group = group;
+    f.reduce = reduce;
+    f.unit = unit;
+    f.floor_db = floor_db;
+    if (!s->takes_fused()) return spectrum_reduce_hipfft(s, (hipStream_t)stream, a, rows_out, f, d_out);
+    return spectrum_reduce_fused(s, (hipStream_t)stream, a, rows_out, f, d_out);
+}
+
+int sdrhip_spectrum_reduce_run(sdrhip_spectrum* s, const void* in, int64_t n_samples, int64_t hop, int rows_out, int group, int reduce, int unit,
+                               double floor_db, float* out)
+{
+    SDRHIP_REQUIRE(s != nullptr && in != nullptr && out != nullptr, "sdrhip_spectrum_reduce_run");
+    SDRHIP_REQUIRE(spectrum_reduce_args_ok(s, n_samples, hop, rows_out, group, reduce, unit, floor_db), "sdrhip_spectrum_reduce_run");
+    int rc;
+    if ((rc = spectrum_lease(s)) != SDRHIP_OK) return rc;
+    ScratchCtx* c = s->ctx;
+    const size_t in_bytes = (size_t)n_samples * s->sample_bytes(), out_bytes = (size_t)rows_out * s->n * sizeof(float);
+    if ((rc = c->in.ensure(in_bytes)) != SDRHIP_OK) return rc;
+    if ((rc = c->out.ensure(out_bytes)) != SDRHIP_OK) return rc;
+    if ((rc = c->hin.ensure(in_bytes)) != SDRHIP_OK) return rc;
+    if ((rc = c->hout.ensure(out_bytes)) != SDRHIP_OK) return rc;
+    memcpy(c->hin.p, in, in_bytes);
+    SDRHIP_CHECK_HIP(hipMemcpyAsync(c->in.p, c->hin.p, in_bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = sdrhip_spectrum_reduce_run_device(s, c->stream, c->in.p, n_samples, hop, rows_out, group, reduce, unit, floor_db,
+                                                static_cast<float*>(c->out.p))) != SDRHIP_OK)
+        return rc;
     SDRHIP_CHECK_HIP(hipMemcpyAsync(c->hout.p, c->out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
     SDRHIP_CHECK_HIP(hipStreamSynchronize(c->stream));
     memcpy(out, c->hout.p, out_bytes);

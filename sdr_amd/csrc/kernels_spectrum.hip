@@ -30,6 +30,12 @@
 //
 // HIPFFT ROUTE (every other n, or on request): spectrum_prepare writes the converted, signed, windowed rows as complex doubles,
 // hipFFT transforms them in place, spectrum_magnitude takes scale * |X| to float32.
+//
+// REDUCING FORM (sdrhip_spectrum_reduce_*: mean power, mean magnitude or max hold over `group` consecutive rows, linear or dB):
+// spectrum_fused_reduce runs the passes above once per input row and keeps the last pass's magnitudes in registers, so the full-rate
+// rows never reach memory; with few output rows and a long group the split form spreads a group's 32-row chunks over workgroups and
+// spectrum_reduce_finalise adds them up.  The hipFFT route adds each batch into two doubles of state per output bin
+// (spectrum_accumulate).  All three follow the summation order the header defines; the first two give the same bits.
 #include "spectrum.hpp"
 
 namespace sdrhip {
@@ -78,7 +84,104 @@ __device__ __forceinline__ void radix4(double2 (&u)[4])
     u[3] = csub(b, dr);
 }
 
-__device__ __forceinline__ float magnitude(double2 v, double scale) { return (float)(scale * sqrt(v.x * v.x + v.y * v.y)); }
+// m = scale * |v|: the double every output of the operator is made from
+__device__ __forceinline__ double magnitude_d(double2 v, double scale) { return scale * sqrt(v.x * v.x + v.y * v.y); }
+__device__ __forceinline__ float magnitude(double2 v, double scale) { return (float)magnitude_d(v, scale); }
+
+// ---- the passes of one tile, shared by spectrum_fused and spectrum_fused_reduce ---------------------------------------------------
+// pass p = 1: global memory -> LDS.  Butterfly g = tid + b T of the tile is butterfly i of the tile's slot rl; slot rl of the tile
+// that starts at slot0 transforms input row (slot0 + rl) * row_mul + row_add, and loads zeros when slot0 + rl >= slots.
+template <int T, int FMT>
+__device__ __forceinline__ void pass_first(double2* s, const void* __restrict__ in, int64_t hop, int64_t slot0, int64_t slots, int64_t row_mul,
+                                           int64_t row_add, int lg, int shift, const double* __restrict__ window, bool wide)
+{
+    const int q = 1 << (lg - 2), lgq = lg - 2, tid = threadIdx.x;
+#pragma unroll
+    for (int b = 0; b < 2; b++) {
+        const int g = tid + b * T, rl = g >> lgq, i = g & (q - 1);
+        const int64_t slot = slot0 + rl;
+        double2 u[4];
+        if (slot < slots) {
+            const int64_t row = slot * row_mul + row_add;
+            const double sign = (shift && (i & 1)) ? -1.0 : 1.0;      // q is even: the parity of i + r q is that of i
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int j = i + r * q;
+                const double2 x = load_sample<FMT>(in, row * hop + j, wide);
+                const double w = sign * window[j];
+                u[r] = make_double2(x.x * w, x.y * w);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; r++) u[r] = make_double2(0.0, 0.0);
+        }
+        radix4(u);
+        double2* dst = s + (rl << lg) + 4 * i;
+#pragma unroll
+        for (int r = 0; r < 4; r++) dst[r] = u[r];
+    }
+    __syncthreads();
+}
+
+// radix-4 passes p = 4, 16, ... that stay in LDS: LDS -> registers, barrier, registers -> LDS
+template <int T>
+__device__ __forceinline__ void passes_mid(double2* s, const double2* __restrict__ twiddle, int lg)
+{
+    const int q = 1 << (lg - 2), lgq = lg - 2, tid = threadIdx.x;
+    const int passes4 = lg >> 1;
+    const int mid_end = (lg & 1) ? passes4 : passes4 - 1;
+#pragma unroll 1
+    for (int ps = 1; ps < mid_end; ps++) {
+        const int lgp = 2 * ps, p = 1 << lgp;
+        double2 u[2][4];
+        int rl[2], i[2];
+#pragma unroll
+        for (int b = 0; b < 2; b++) {
+            const int g = tid + b * T;
+            rl[b] = g >> lgq;
+            i[b] = g & (q - 1);
+            const double2* src = s + (rl[b] << lg) + i[b];
+#pragma unroll
+            for (int r = 0; r < 4; r++) u[b][r] = src[r * q];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int b = 0; b < 2; b++) {
+            const int k = i[b] & (p - 1);
+            const int tw = k << (lgq - lgp);             // k n / (4 p)
+            u[b][1] = cmul(u[b][1], twiddle[tw]);
+            u[b][2] = cmul(u[b][2], twiddle[2 * tw]);
+            u[b][3] = cmul(u[b][3], twiddle[3 * tw]);
+            radix4(u[b]);
+            double2* dst = s + (rl[b] << lg) + ((i[b] - k) << 2) + k;
+#pragma unroll
+            for (int r = 0; r < 4; r++) dst[r << lgp] = u[b][r];
+        }
+        __syncthreads();
+    }
+}
+
+// log2 n even: butterfly i of slot rl in the last radix-4 pass p = n / 4.  k = i: u[r] is bin i + r n/4.
+__device__ __forceinline__ void last_radix4(const double2* s, const double2* __restrict__ twiddle, int lg, int rl, int i, double2 (&u)[4])
+{
+    const int q = 1 << (lg - 2);
+    const double2* src = s + (rl << lg) + i;
+    u[0] = src[0];
+    u[1] = cmul(src[q], twiddle[i]);
+    u[2] = cmul(src[2 * q], twiddle[2 * i]);
+    u[3] = cmul(src[3 * q], twiddle[3 * i]);
+    radix4(u);
+}
+
+// log2 n odd: butterfly i of slot rl in the radix-2 pass p = n / 2: bins i (lo) and i + n/2 (hi).
+__device__ __forceinline__ void last_radix2(const double2* s, const double2* __restrict__ twiddle, int lg, int rl, int i, double2& lo, double2& hi)
+{
+    const int h = 1 << (lg - 1);
+    const double2* src = s + (rl << lg) + i;
+    const double2 u0 = src[0], u1 = cmul(src[h], twiddle[i]);
+    lo = cadd(u0, u1);
+    hi = csub(u0, u1);
+}
 
 template <int T, int FMT>
 __global__ __launch_bounds__(T) void spectrum_fused(const void* __restrict__ in, int64_t hop, int64_t rows, int lg, int shift, double scale,
@@ -90,106 +193,244 @@ __global__ __launch_bounds__(T) void spectrum_fused(const void* __restrict__ in,
     const int n = 1 << lg, q = n >> 2, lgq = lg - 2;
     const int rows_per_tile = E >> lg;
     const int64_t ntiles = (rows + rows_per_tile - 1) / rows_per_tile;
-    const int passes4 = lg >> 1;
     const bool odd = (lg & 1) != 0;
     const int tid = threadIdx.x;
 
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t row0 = tile * rows_per_tile;
+        pass_first<T, FMT>(s, in, hop, row0, rows, 1, 0, lg, shift, window, wide);
+        passes_mid<T>(s, twiddle, lg);
 
-        // pass p = 1: global memory -> LDS.  Butterfly g = tid + b T of the tile is butterfly i of the tile's row rl.
-#pragma unroll
-        for (int b = 0; b < 2; b++) {
-            const int g = tid + b * T, rl = g >> lgq, i = g & (q - 1);
-            const int64_t row = row0 + rl;
-            double2 u[4];
-            if (row < rows) {
-                const double sign = (shift && (i & 1)) ? -1.0 : 1.0;      // q is even: the parity of i + r q is that of i
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int j = i + r * q;
-                    const double2 x = load_sample<FMT>(in, row * hop + j, wide);
-                    const double w = sign * window[j];
-                    u[r] = make_double2(x.x * w, x.y * w);
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; r++) u[r] = make_double2(0.0, 0.0);
-            }
-            radix4(u);
-            double2* dst = s + (rl << lg) + 4 * i;
-#pragma unroll
-            for (int r = 0; r < 4; r++) dst[r] = u[r];
-        }
-        __syncthreads();
-
-        // radix-4 passes p = 4, 16, ... that stay in LDS: LDS -> registers, barrier, registers -> LDS
-        const int mid_end = odd ? passes4 : passes4 - 1;
-#pragma unroll 1
-        for (int ps = 1; ps < mid_end; ps++) {
-            const int lgp = 2 * ps, p = 1 << lgp;
-            double2 u[2][4];
-            int rl[2], i[2];
-#pragma unroll
-            for (int b = 0; b < 2; b++) {
-                const int g = tid + b * T;
-                rl[b] = g >> lgq;
-                i[b] = g & (q - 1);
-                const double2* src = s + (rl[b] << lg) + i[b];
-#pragma unroll
-                for (int r = 0; r < 4; r++) u[b][r] = src[r * q];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int b = 0; b < 2; b++) {
-                const int k = i[b] & (p - 1);
-                const int tw = k << (lgq - lgp);             // k n / (4 p)
-                u[b][1] = cmul(u[b][1], twiddle[tw]);
-                u[b][2] = cmul(u[b][2], twiddle[2 * tw]);
-                u[b][3] = cmul(u[b][3], twiddle[3 * tw]);
-                radix4(u[b]);
-                double2* dst = s + (rl[b] << lg) + ((i[b] - k) << 2) + k;
-#pragma unroll
-                for (int r = 0; r < 4; r++) dst[r << lgp] = u[b][r];
-            }
-            __syncthreads();
-        }
-
-        // log2 n even: the last radix-4 pass p = n / 4, LDS -> global memory.  k = i: butterfly i holds bins i + r n/4.
+        // log2 n even: the last radix-4 pass, LDS -> global memory
         if (!odd) {
 #pragma unroll 1
             for (int b = 0; b < 2; b++) {
                 const int g = tid + b * T, rl = g >> lgq, i = g & (q - 1);
                 if (row0 + rl >= rows) continue;
-                const double2* src = s + (rl << lg) + i;
                 double2 u[4];
-                u[0] = src[0];
-                u[1] = cmul(src[q], twiddle[i]);
-                u[2] = cmul(src[2 * q], twiddle[2 * i]);
-                u[3] = cmul(src[3 * q], twiddle[3 * i]);
-                radix4(u);
+                last_radix4(s, twiddle, lg, rl, i, u);
                 float* o = out + (row0 + rl) * n + i;
 #pragma unroll
                 for (int r = 0; r < 4; r++) o[r * q] = magnitude(u[r], scale);
             }
         }
 
-        // log2 n odd: the radix-2 pass p = n / 2, LDS -> global memory.  Butterfly i holds bins i and i + n/2.
+        // log2 n odd: the radix-2 pass, LDS -> global memory
         if (odd) {
             const int h = n >> 1;
 #pragma unroll 1
             for (int b = 0; b < 4; b++) {
                 const int g = tid + b * T, rl = g >> (lg - 1), i = g & (h - 1);
-                const double2* src = s + (rl << lg) + i;
-                const double2 u0 = src[0], u1 = cmul(src[h], twiddle[i]);
+                double2 lo, hi;
+                last_radix2(s, twiddle, lg, rl, i, lo, hi);
                 if (row0 + rl < rows) {
                     float* o = out + (row0 + rl) * n + i;
-                    o[0] = magnitude(cadd(u0, u1), scale);
-                    o[h] = magnitude(csub(u0, u1), scale);
+                    o[0] = magnitude(lo, scale);
+                    o[h] = magnitude(hi, scale);
                 }
             }
         }
         __syncthreads();        // the next tile's first pass overwrites what this tile's last pass reads
+    }
+}
+
+// ---- the reducing form (sdrhip_spectrum_reduce_*) -------------------------------------------------------------------------------
+// one value into an accumulator / a chunk's accumulator into the total / the total into the output float
+__device__ __forceinline__ double reduce_add(double acc, double m, int reduce)
+{
+    if (reduce == 2) return m > acc ? m : acc;
+    return acc + (reduce == 0 ? m * m : m);
+}
+__device__ __forceinline__ double reduce_fold(double total, double acc, int reduce)
+{
+    if (reduce == 2) return acc > total ? acc : total;
+    return total + acc;
+}
+__device__ __forceinline__ float reduce_finish(double v, const SpectrumReduce& f)
+{
+    if (f.reduce != 2) v = v / (double)f.group;
+    if (f.unit == 1) {
+        const double d = (f.reduce == 0 ? 10.0 : 20.0) * log10(v);
+        v = d > f.floor_db ? d : f.floor_db;         // log10(0) = -inf: the floor
+    }
+    return (float)v;
+}
+
+// element e (0 .. 7) of a thread's accumulators: which slot of the tile and which bin the last pass hands this thread
+template <int T>
+__device__ __forceinline__ void owned_bin(int tid, int lg, int e, int& rl, int& bin)
+{
+    if (lg & 1) {
+        const int h = 1 << (lg - 1), g = tid + (e >> 1) * T;
+        rl = g >> (lg - 1);
+        bin = (g & (h - 1)) + (e & 1) * h;
+    } else {
+        const int q = 1 << (lg - 2), g = tid + (e >> 2) * T;
+        rl = g >> (lg - 2);
+        bin = (g & (q - 1)) + (e & 3) * q;
+    }
+}
+
+// Tile slot rl belongs to OUTPUT row tile * rows_per_tile + rl; the workgroup runs that slot's input rows one after the other through
+// the same passes as spectrum_fused and keeps what the last pass produces in registers: 8 doubles per thread (2 butterflies x 4 bins,
+// or 4 x 2 when log2 n is odd).  The group is cut into chunks of SPECTRUM_REDUCE_CHUNK rows, each summed from 0.0 in ascending order.
+// LAYERS = false (a group of one chunk): one work item per tile; the chunk's sums are the totals (0.0 + x = x) and leave as n floats.
+// LAYERS = true: a work item is (tile, `per_item` consecutive chunks of [chunk0, chunk1)); every chunk's sums go out as doubles, layer
+// (chunk - chunk0) of `partial`, and spectrum_reduce_finalise adds the layers in ascending order from 0.0.  How the chunks are dealt
+// out to work items (all of a tile's to one, or spread over the chip: the split) therefore cannot change a bit.  A second set of 8
+// doubles for the running total does not fit beside the transform at T = 1024 (128 VGPRs: 8 spilled), which is why groups of more
+// than one chunk always go through the layers.
+template <int T, int FMT, bool LAYERS>
+__global__ __launch_bounds__(T) void spectrum_fused_reduce(const void* __restrict__ in, int64_t hop, int64_t rows_out, int lg, int shift, double scale,
+                                                           const double* __restrict__ window, const double2* __restrict__ twiddle, bool wide,
+                                                           SpectrumReduce f, int chunk0, int chunk1, int per_item, double* __restrict__ partial,
+                                                           float* __restrict__ out)
+{
+    constexpr int E = 8 * T;
+    __shared__ double2 s[E];
+    const int n = 1 << lg;
+    const int rows_per_tile = E >> lg;
+    const int64_t ntiles = (rows_out + rows_per_tile - 1) / rows_per_tile;
+    const bool odd = (lg & 1) != 0;
+    const int tid = threadIdx.x;
+    const int per_tile = LAYERS ? (chunk1 - chunk0 + per_item - 1) / per_item : 1;      // work items of one tile
+    const int64_t items = ntiles * per_tile;
+
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t tile = item / per_tile, row0 = tile * rows_per_tile;
+        const int c0 = LAYERS ? chunk0 + (int)(item - tile * per_tile) * per_item : chunk0;
+        const int c1 = LAYERS ? (c0 + per_item < chunk1 ? c0 + per_item : chunk1) : chunk1;
+        double acc[8];
+#pragma unroll
+        for (int e = 0; e < 8; e++) acc[e] = 0.0;
+        const int j0 = c0 * SPECTRUM_REDUCE_CHUNK;
+        const int j1 = (int64_t)c1 * SPECTRUM_REDUCE_CHUNK < f.group ? c1 * SPECTRUM_REDUCE_CHUNK : f.group;
+#pragma unroll 1
+        for (int j = j0; j < j1; j++) {
+            {
+                const double* w = window;
+                const double2* tw = twiddle;
+                asm volatile("" : "+s"(w), "+s"(tw));
+                pass_first<T, FMT>(s, in, hop, row0, rows_out, f.group, j, lg, shift, w, wide);
+                passes_mid<T>(s, tw, lg);
+                // One butterfly at a time, like spectrum_fused (two in flight cost 30 VGPRs more, and T = 1024 has 128).  The loops are
+                // real loops, so the accumulators rotate instead of being indexed: every turn works on the first elements and moves
+                // them to the back, and after the last turn each one is in its own place again.
+                if (!odd) {
+#pragma unroll 1
+                    for (int b = 0; b < 2; b++) {
+                        const int g = tid + b * T;
+                        double2 u[4];
+                        last_radix4(s, tw, lg, g >> (lg - 2), g & ((n >> 2) - 1), u);
+                        double v[4];
+#pragma unroll
+                        for (int r = 0; r < 4; r++) v[r] = reduce_add(acc[r], magnitude_d(u[r], scale), f.reduce);
+#pragma unroll
+                        for (int r = 0; r < 4; r++) {
+                            acc[r] = acc[r + 4];
+                            acc[r + 4] = v[r];
+                        }
+                    }
+                } else {
+#pragma unroll 1
+                    for (int b = 0; b < 4; b++) {
+                        const int g = tid + b * T;
+                        double2 lo, hi;
+                        last_radix2(s, tw, lg, g >> (lg - 1), g & ((n >> 1) - 1), lo, hi);
+                        const double v0 = reduce_add(acc[0], magnitude_d(lo, scale), f.reduce);
+                        const double v1 = reduce_add(acc[1], magnitude_d(hi, scale), f.reduce);
+#pragma unroll
+                        for (int e = 0; e < 6; e++) acc[e] = acc[e + 2];
+                        acc[6] = v0;
+                        acc[7] = v1;
+                    }
+                }
+                __syncthreads();        // the next row's first pass overwrites what this row's last pass reads
+            }
+            // a chunk that ends with this row goes out
+            // (the thread index behind an empty asm: what is computed from it for these rare steps stays here, instead of being
+            // hoisted out of every loop into registers the transform needs)
+            if (LAYERS && (((j + 1) & (SPECTRUM_REDUCE_CHUNK - 1)) == 0 || j + 1 == j1)) {
+                int t = tid;
+                asm volatile("" : "+v"(t));
+                double* layer = partial + (int64_t)(j / SPECTRUM_REDUCE_CHUNK - chunk0) * rows_out * n;
+#pragma unroll 1
+                for (int e = 0; e < 8; e++) {       // a real loop: the sums rotate past element 0
+                    int rl, bin;
+                    owned_bin<T>(t, lg, e, rl, bin);
+                    if (row0 + rl < rows_out) layer[(row0 + rl) * n + bin] = acc[0];
+#pragma unroll
+                    for (int x = 0; x < 7; x++) acc[x] = acc[x + 1];
+                }
+#pragma unroll
+                for (int e = 0; e < 8; e++) acc[e] = 0.0;
+            }
+        }
+        if (!LAYERS) {
+            // the sums go through LDS (free since the last row's barrier) in output order: the finishing loop, with its division and
+            // log10, then holds one value at a time and writes whole runs of consecutive floats
+            double* sd = reinterpret_cast<double*>(s);
+            int t = tid;
+            asm volatile("" : "+v"(t));
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+                int rl, bin;
+                owned_bin<T>(t, lg, e, rl, bin);
+                sd[(rl << lg) + bin] = acc[e];
+            }
+            __syncthreads();
+            const int64_t left = (rows_out - row0) * n;        // floats of `out` from this tile's first row on
+#pragma unroll 1
+            for (int x = t; x < E && x < left; x += T) out[row0 * n + x] = reduce_finish(sd[x], f);
+            __syncthreads();        // the next item's first pass overwrites what this loop reads
+        }
+    }
+}
+
+// the layers' second kernel: per output bin, the layers of `partial` in ascending order onto the carried total (0.0 before the
+// first slice of a group); the last slice applies mean / dB and writes the float
+__global__ __launch_bounds__(256) void spectrum_reduce_finalise(const double* __restrict__ partial, int layers, int64_t count, double* __restrict__ total,
+                                                                 int first, int last, SpectrumReduce f, float* __restrict__ out)
+{
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < count; k += (int64_t)gridDim.x * 256) {
+        double t = first ? 0.0 : total[k];
+        for (int l = 0; l < layers; l++) t = reduce_fold(t, partial[(int64_t)l * count + k], f.reduce);
+        if (last) out[k] = reduce_finish(t, f);
+        else total[k] = t;
+    }
+}
+
+// hipFFT route: input rows [b0, b0 + nrows) of a slice (transformed, in `work`) into the two doubles of state every output bin has,
+// the running chunk sum and the total, in the defined order; the row that completes a group writes the output float
+__global__ __launch_bounds__(256) void spectrum_accumulate(const double2* __restrict__ work, int64_t b0, int64_t nrows, int n, double scale,
+                                                            SpectrumReduce f, double* __restrict__ chunk, double* __restrict__ total,
+                                                            float* __restrict__ out)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    const int64_t r_first = b0 / f.group, r_last = (b0 + nrows - 1) / f.group;
+    for (int64_t R = r_first + blockIdx.y; R <= r_last; R += gridDim.y) {
+        const int64_t lo = R * f.group > b0 ? R * f.group : b0;
+        const int64_t hi = (R + 1) * f.group < b0 + nrows ? (R + 1) * f.group : b0 + nrows;
+        int64_t j = lo - R * f.group;
+        double c = 0.0, t = 0.0;
+        if (j != 0) {
+            c = chunk[R * n + k];
+            t = total[R * n + k];
+        }
+        for (int64_t r = lo; r < hi; r++, j++) {
+            if (j != 0 && j % SPECTRUM_REDUCE_CHUNK == 0) {
+                t = reduce_fold(t, c, f.reduce);
+                c = 0.0;
+            }
+            c = reduce_add(c, magnitude_d(work[(r - b0) * n + k], scale), f.reduce);
+        }
+        if (j == f.group) {
+            out[R * n + k] = reduce_finish(reduce_fold(t, c, f.reduce), f);
+        } else {
+            chunk[R * n + k] = c;
+            total[R * n + k] = t;
+        }
     }
 }
 
@@ -227,7 +468,61 @@ hipError_t launch_fused(hipStream_t stream, const SpectrumArgs& a, int lg, float
     return hipGetLastError();
 }
 
+template <int T>
+hipError_t launch_fused_reduce(hipStream_t stream, const SpectrumArgs& a, const SpectrumReduce& f, int lg, int chunk0, int chunk1, int per_item,
+                               double* partial, float* out)
+{
+    const int rows_per_tile = (8 * T) >> lg;
+    const int64_t ntiles = (a.rows + rows_per_tile - 1) / rows_per_tile;
+    const int64_t items = partial ? ntiles * ((chunk1 - chunk0 + per_item - 1) / per_item) : ntiles;
+    const int64_t resident = 2048;
+    const unsigned grid = (unsigned)(items < resident ? items : resident);
+    const bool wide = wide_loads(a);
+#define SDRHIP_REDUCE_LAUNCH(FMT, LAYERS)                                                                                                     \
+    spectrum_fused_reduce<T, FMT, LAYERS><<<grid, T, 0, stream>>>(a.in, a.hop, a.rows, lg, a.shift, a.scale, a.window, a.twiddle, wide, f, chunk0, \
+                                                                 chunk1, per_item, partial, out)
+    if (a.format == 0) {
+        if (partial) SDRHIP_REDUCE_LAUNCH(0, true);
+        else SDRHIP_REDUCE_LAUNCH(0, false);
+    } else {
+        if (partial) SDRHIP_REDUCE_LAUNCH(1, true);
+        else SDRHIP_REDUCE_LAUNCH(1, false);
+    }
+#undef SDRHIP_REDUCE_LAUNCH
+    return hipGetLastError();
+}
+
 }  // namespace
+
+hipError_t launch_spectrum_fused_reduce(hipStream_t stream, const SpectrumArgs& a, const SpectrumReduce& f, int chunk0, int chunk1, int per_item,
+                                        double* partial, float* out)
+{
+    if (!spectrum_fused_size(a.n) || a.rows < 1 || f.group < 1 || chunk0 < 0 || chunk1 <= chunk0 || per_item < 1) return hipErrorInvalidValue;
+    if ((int64_t)(chunk1 - 1) * SPECTRUM_REDUCE_CHUNK >= f.group) return hipErrorInvalidValue;      // the last chunk holds a row
+    if (!partial && (chunk0 != 0 || f.group > SPECTRUM_REDUCE_CHUNK)) return hipErrorInvalidValue;   // straight to `out`: one chunk
+    int lg = 0;
+    while ((1 << lg) < a.n) lg++;
+    if (a.n == 8192) return launch_fused_reduce<1024>(stream, a, f, lg, chunk0, chunk1, per_item, partial, out);
+    if (a.n == 4096) return launch_fused_reduce<512>(stream, a, f, lg, chunk0, chunk1, per_item, partial, out);
+    return launch_fused_reduce<256>(stream, a, f, lg, chunk0, chunk1, per_item, partial, out);
+}
+
+hipError_t launch_spectrum_reduce_finalise(hipStream_t stream, const double* partial, int layers, int64_t count, double* total, bool first, bool last,
+                                           const SpectrumReduce& f, float* out)
+{
+    const int64_t blocks = (count + 255) / 256;
+    spectrum_reduce_finalise<<<(unsigned)(blocks < 16384 ? blocks : 16384), 256, 0, stream>>>(partial, layers, count, total, first, last, f, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_spectrum_accumulate(hipStream_t stream, const double2* work, int64_t b0, int64_t nrows, int n, double scale, const SpectrumReduce& f,
+                                      double* chunk, double* total, float* out)
+{
+    const int64_t touched = (b0 + nrows - 1) / f.group - b0 / f.group + 1;
+    const dim3 grid((unsigned)((n + 255) / 256), (unsigned)(touched < 4096 ? touched : 4096));
+    spectrum_accumulate<<<grid, 256, 0, stream>>>(work, b0, nrows, n, scale, f, chunk, total, out);
+    return hipGetLastError();
+}
 
 hipError_t launch_spectrum_fused(hipStream_t stream, const SpectrumArgs& a, float* out)
 {

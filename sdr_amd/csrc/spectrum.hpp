@@ -18,6 +18,18 @@ struct SpectrumArgs {
     const double2* twiddle; // exp(-2 pi i m / n), m in [0, n), device (one-kernel route only)
 };
 
+// what the reducing form adds (sdrhip_spectrum_reduce_run_device): SpectrumArgs::rows then counts OUTPUT rows, each made of `group`
+// consecutive input rows
+struct SpectrumReduce {
+    int group;
+    int reduce;             // SDRHIP_REDUCE_*
+    int unit;               // SDRHIP_UNIT_*
+    double floor_db;
+};
+
+// rows per chunk of the defined summation order (include/sdr_hip.h): part of the definition, not a tuning knob
+constexpr int SPECTRUM_REDUCE_CHUNK = 32;
+
 // sizes the one-kernel route serves: powers of two from 64 to 8192
 inline bool spectrum_fused_size(int n) { return n >= 64 && n <= 8192 && (n & (n - 1)) == 0; }
 
@@ -26,5 +38,18 @@ hipError_t launch_spectrum_fused(hipStream_t stream, const SpectrumArgs& a, floa
 // hipFFT route, rows [row0, row0 + nrows): raw IQ -> complex doubles, and complex doubles -> float32 magnitudes
 hipError_t launch_spectrum_prepare(hipStream_t stream, const SpectrumArgs& a, int64_t row0, int64_t nrows, double2* work);
 hipError_t launch_spectrum_magnitude(hipStream_t stream, const double2* work, int64_t count, double scale, float* out);
+
+// the reducing form of the one-kernel route over chunks [chunk0, chunk1) of every group.  partial == nullptr (a group of one chunk
+// only: chunk0 = 0, chunk1 = 1): one launch writes `out`.  Otherwise work items of `per_item` chunks each write every chunk's sums to
+// layer (chunk - chunk0) of `partial` (layers of rows x n doubles) for launch_spectrum_reduce_finalise, and `out` is not touched.
+hipError_t launch_spectrum_fused_reduce(hipStream_t stream, const SpectrumArgs& a, const SpectrumReduce& f, int chunk0, int chunk1, int per_item,
+                                        double* partial, float* out);
+// `layers` layers of `count` doubles, in ascending order, onto `total` (taken as 0.0 when `first`); `last` writes `out` instead
+hipError_t launch_spectrum_reduce_finalise(hipStream_t stream, const double* partial, int layers, int64_t count, double* total, bool first, bool last,
+                                           const SpectrumReduce& f, float* out);
+// hipFFT route: transformed input rows [b0, b0 + nrows) (numbered from the first row of out's first output row) into chunk / total
+// (output rows x n doubles each); a group's last row writes its output row
+hipError_t launch_spectrum_accumulate(hipStream_t stream, const double2* work, int64_t b0, int64_t nrows, int n, double scale, const SpectrumReduce& f,
+                                      double* chunk, double* total, float* out);
 
 }  // namespace sdrhip

@@ -178,6 +178,11 @@ lib.sdrhip_spectrum_run.argtypes = [_vp, _vp, _i64, _i64, C.c_int, _vp]
 lib.sdrhip_spectrum_set_route.argtypes = [_vp, C.c_int]
 lib.sdrhip_debug_spectrum_fused_launches.argtypes = []
 lib.sdrhip_debug_spectrum_fused_launches.restype = C.c_longlong
+lib.sdrhip_spectrum_reduce_run_device.argtypes = [_vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _vp]
+lib.sdrhip_spectrum_reduce_run.argtypes = [_vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _vp]
+lib.sdrhip_spectrum_set_reduce_split.argtypes = [_vp, C.c_int]
+lib.sdrhip_debug_spectrum_reduce_split_launches.argtypes = []
+lib.sdrhip_debug_spectrum_reduce_split_launches.restype = C.c_longlong
 lib.sdrhip_filter_one.argtypes = [_vp, C.c_int, _f32p, _f32p]
 lib.sdrhip_filter_cross.argtypes = [_vp, C.c_int, _f32p, C.c_int, _f32p, C.c_int, _f32p]
 lib.sdrhip_decimator_one.argtypes = [_vp, C.c_int, _f32p, _f32p]
@@ -589,6 +594,9 @@ class Fft(_Handle):
 IQ_U8, IQ_CF32 = 0, 1
 WINDOW_NONE, WINDOW_HANNING, WINDOW_HAMMING, WINDOW_BLACKMAN, WINDOW_CUSTOM = 0, 1, 2, 3, 4
 SPECTRUM_ROUTE_AUTO, SPECTRUM_ROUTE_FUSED, SPECTRUM_ROUTE_HIPFFT = 0, 1, 2
+REDUCE_MEAN_POWER, REDUCE_MEAN_MAGNITUDE, REDUCE_MAX_MAGNITUDE = 0, 1, 2
+UNIT_LINEAR, UNIT_DB = 0, 1
+REDUCE_SPLIT_AUTO, REDUCE_SPLIT_NEVER, REDUCE_SPLIT_ALWAYS = 0, 1, 2
 
 
 class Spectrum(_Handle):
@@ -639,9 +647,38 @@ class Spectrum(_Handle):
         check(lib.sdrhip_spectrum_run(self.h, a.ctypes.data, n_samples, hop, rows, out.ctypes.data), "sdrhip_spectrum_run")
         return out
 
+    def set_reduce_split(self, mode):
+        check(lib.sdrhip_spectrum_set_reduce_split(self.h, int(mode)), "sdrhip_spectrum_set_reduce_split")
+
+    def reduce_device(self, d_in, n_samples, d_out, group, reduce=REDUCE_MEAN_POWER, unit=UNIT_LINEAR, floor_db=-200.0, hop=None, rows_out=None,
+                      stream=None):
+        """d_in, d_out: device addresses; d_out takes rows_out x n float32, output row R reducing input rows R*group .. R*group+group-1
+        (mean power, mean magnitude or max; linear or dB, never below floor_db).  -> rows_out."""
+        hop = self.n if hop is None else int(hop)
+        rows_out = self.rows_of(n_samples, hop) // int(group) if rows_out is None else int(rows_out)
+        check(lib.sdrhip_spectrum_reduce_run_device(self.h, stream, d_in, n_samples, hop, rows_out, int(group), int(reduce), int(unit),
+                                                    float(floor_db), d_out), "sdrhip_spectrum_reduce_run_device")
+        return rows_out
+
+    def reduce(self, iq, group, reduce=REDUCE_MEAN_POWER, unit=UNIT_LINEAR, floor_db=-200.0, hop=None, rows_out=None):
+        """iq: a host array of interleaved samples -> rows_out x n float32 (see reduce_device)."""
+        import numpy as np
+        a = np.ascontiguousarray(iq, dtype=np.uint8 if self.input_format == IQ_U8 else np.float32).reshape(-1)
+        n_samples = a.size // 2
+        hop = self.n if hop is None else int(hop)
+        rows_out = self.rows_of(n_samples, hop) // int(group) if rows_out is None else int(rows_out)
+        out = np.empty((max(rows_out, 0), self.n), np.float32)
+        check(lib.sdrhip_spectrum_reduce_run(self.h, a.ctypes.data, n_samples, hop, rows_out, int(group), int(reduce), int(unit), float(floor_db),
+                                             out.ctypes.data), "sdrhip_spectrum_reduce_run")
+        return out
+
 
 def spectrum_fused_launches():
     return int(lib.sdrhip_debug_spectrum_fused_launches())
+
+
+def spectrum_reduce_split_launches():
+    return int(lib.sdrhip_debug_spectrum_reduce_split_launches())
 
 
 TRANSPORT_RCCL, TRANSPORT_PEER_COPY = 1, 2
