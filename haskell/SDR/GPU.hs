@@ -35,6 +35,8 @@ module SDR.GPU (
     gpuDecimatorC, gpuResamplerR, gpuFilterSymR, gpuFilterR,
     firDecimatorGpu, firResamplerGpu, firFilterGpu, fmDemodGpu, dcBlockingFilterGpu,
     interleavedIQUnsignedByteToFloatGpu,
+    -- * The tuner: an oscillator mixed into the complex decimator (P.map (VG.zipWith (*) osc) >-> firDecimator)
+    GpuTuner, gpuTuner, gpuTunerShift, tunerShiftTable, tunerGpu,
     GpuFmChain, gpuFmChain, fmReceiverGpu,
     -- * The waterfall pipe as one operator (raw IQ -> windowed FFT magnitudes)
     GpuSpectrum, SpectrumWindow (..), gpuSpectrumU8, spectrumRowsGpu
@@ -59,6 +61,7 @@ data SdrDecimator
 data SdrResampler
 data SdrFilter
 data SdrPipe
+data SdrTuner
 data SdrChain
 data SdrStream
 data SdrSpectrum
@@ -66,6 +69,7 @@ data SdrSpectrum
 newtype GpuDecimator = GpuDecimator (Ptr SdrDecimator)
 newtype GpuResampler = GpuResampler (Ptr SdrResampler)
 newtype GpuFilter    = GpuFilter    (Ptr SdrFilter)
+newtype GpuTuner     = GpuTuner     (Ptr SdrTuner)
 newtype GpuFmChain   = GpuFmChain   (Ptr SdrChain)
 data    GpuSpectrum  = GpuSpectrum  (Ptr SdrSpectrum) Int
 
@@ -114,6 +118,19 @@ foreign import ccall safe "sdrhip_decimator_one"    c_decimator_one    :: Ptr Sd
 foreign import ccall safe "sdrhip_decimator_cross"  c_decimator_cross  :: Ptr SdrDecimator -> CInt -> Ptr CFloat -> CInt -> Ptr CFloat -> CInt -> Ptr CFloat -> IO CInt
 foreign import ccall safe "sdrhip_resampler_one"    c_resampler_one    :: Ptr SdrResampler -> CInt -> CInt -> Ptr CFloat -> CInt -> Ptr CFloat -> IO CInt
 foreign import ccall safe "sdrhip_resampler_cross"  c_resampler_cross  :: Ptr SdrResampler -> CInt -> CInt -> Ptr CFloat -> CInt -> Ptr CFloat -> CInt -> Ptr CFloat -> IO CInt
+-- the tuner (include/sdr_hip.h, sdrhip_tuner_*): osc[n mod period] * x[n] (Data.Complex's (*) at Float) in front of the complex
+-- decimator, n = the absolute stream index; device-pointer runs, the shift tables (host code) and the host-block Pipe
+foreign import ccall safe "sdrhip_tuner_create"      c_tuner_create      :: Ptr (Ptr SdrTuner) -> CInt -> CInt -> Ptr CFloat -> CInt -> Ptr CFloat -> CInt -> IO CInt
+foreign import ccall safe "sdrhip_tuner_destroy"     c_tuner_destroy     :: Ptr SdrTuner -> IO ()
+foreign import ccall safe "sdrhip_tuner_num_coeffs"  c_tuner_num_coeffs  :: Ptr SdrTuner -> IO CInt
+foreign import ccall safe "sdrhip_tuner_factor"      c_tuner_factor      :: Ptr SdrTuner -> IO CInt
+foreign import ccall safe "sdrhip_tuner_period"      c_tuner_period      :: Ptr SdrTuner -> IO CInt
+foreign import ccall safe "sdrhip_tuner_run"         c_tuner_run         :: Ptr SdrTuner -> Ptr () -> Ptr CFloat -> Int64 -> Ptr CFloat -> Int64 -> Int64 -> Int64 -> IO CInt
+foreign import ccall safe "sdrhip_tuner_run_u8"      c_tuner_run_u8      :: Ptr SdrTuner -> Ptr () -> Ptr CUChar -> Int64 -> Ptr CFloat -> Int64 -> Int64 -> Int64 -> IO CInt
+foreign import ccall safe "sdrhip_tuner_set_route"   c_tuner_set_route   :: Ptr SdrTuner -> CInt -> IO CInt
+foreign import ccall safe "sdrhip_tuner_shift_table" c_tuner_shift_table :: Int64 -> Int64 -> Ptr CFloat -> IO CInt
+foreign import ccall safe "sdrhip_debug_tuner_fused_launches" c_tuner_fused_launches :: IO CLLong
+foreign import ccall safe "sdrhip_pipe_tuner"        c_pipe_tuner        :: Ptr (Ptr SdrPipe) -> Ptr SdrTuner -> CInt -> IO CInt
 -- the spectrum operator (include/sdr_hip.h, sdrhip_spectrum_*): interleavedIQUnsigned256ToFloat -> halfBandUp x window -> fftw ->
 -- magnitude x scale, rows of Float
 foreign import ccall safe "sdrhip_spectrum_create"     c_spectrum_create     :: Ptr (Ptr SdrSpectrum) -> CInt -> CInt -> CInt -> Ptr CDouble -> CInt -> CDouble -> IO CInt
@@ -275,6 +292,31 @@ mkPipe create = alloca $ \pp -> create pp >>= check >> peek pp
 firDecimatorGpu :: GpuDecimator -> Int -> Pipe (VS.Vector (Complex Float)) (VS.Vector (Complex Float)) IO ()
 firDecimatorGpu (GpuDecimator d) blockSizeOut = do
     pipe <- lift $ mkPipe $ \pp -> c_pipe_decimator pp d (fromIntegral blockSizeOut)
+    runPipe 2 2 pipe blockSizeOut
+
+-- | @exp (2 pi i ((num n) mod den) / den)@, n < den, with exact quarter turns: @tunerShiftTable 1 4@ is 'quarterBandUp' 4 and
+--   @tunerShiftTable 1 2@ is 'halfBandUp' 2 (Util.hs:263-285).  Host code, no device.
+tunerShiftTable :: Int -> Int -> IO (VS.Vector (Complex Float))
+tunerShiftTable num den = do
+    fp <- mallocForeignPtrArray (2 * den) :: IO (ForeignPtr CFloat)
+    _  <- withForeignPtr fp $ \o -> c_tuner_shift_table (fromIntegral num) (fromIntegral den) o >>= check
+    return $ VS.unsafeCast $ VS.unsafeFromForeignPtr0 fp (2 * den)
+
+-- | A tuner: 'fastDecimatorC' taps behind one period of a complex oscillator (1 .. 65536 entries).
+gpuTuner :: Int -> [Float] -> VS.Vector (Complex Float) -> IO GpuTuner
+gpuTuner factor coeffs osc = alloca $ \pp -> do
+    _ <- withCoeffs coeffs $ \p n -> VS.unsafeWith (VS.unsafeCast osc) $ \po ->
+             c_tuner_create pp orderAVX (fromIntegral factor) p n po (fromIntegral (VS.length osc)) >>= check
+    GpuTuner <$> peek pp
+
+-- | @gpuTunerShift factor coeffs num den@: shift the band up by num / den of the sampling frequency, then decimate.
+gpuTunerShift :: Int -> [Float] -> Int -> Int -> IO GpuTuner
+gpuTunerShift factor coeffs num den = tunerShiftTable num den >>= gpuTuner factor coeffs
+
+-- | @P.map (VG.zipWith (*) osc) >-> firDecimator deci blockSizeOut@ with the oscillator indexed by the stream position.
+tunerGpu :: GpuTuner -> Int -> Pipe (VS.Vector (Complex Float)) (VS.Vector (Complex Float)) IO ()
+tunerGpu (GpuTuner t) blockSizeOut = do
+    pipe <- lift $ mkPipe $ \pp -> c_pipe_tuner pp t (fromIntegral blockSizeOut)
     runPipe 2 2 pipe blockSizeOut
 
 firResamplerGpu :: GpuResampler -> Int -> Pipe (VS.Vector Float) (VS.Vector Float) IO ()

@@ -219,6 +219,57 @@ int sdrhip_decimator_run(const sdrhip_decimator *d, void *stream, const float *d
 int sdrhip_decimator_run_u8(const sdrhip_decimator *d, void *stream, const uint8_t *d_in_iq, int64_t in_base,
                             float *d_out, int64_t k_begin, int64_t k_end, int64_t seam_block);
 
+/* ---- Tuner: a periodic complex oscillator mixed into the complex decimator -------- */
+/* `P.map (VG.zipWith (*) osc) >-> firDecimator deci n` as ONE device operator: move a part of the band to 0 Hz, then low-pass and
+ * decimate there (oscillators: quarterBandUp / halfBandUp, Util.hs:263-285; the product: Data.Complex's (*) at Float).  With n the
+ * ABSOLUTE stream index of an input sample and N = period:
+ *     x[n] = the input sample (u8 IQ: (u - 128) * (1/128) as convert.c; cfloat: as given)
+ *     o[n] = osc[n mod N]
+ *     m[n] = (x.re*o.re - x.im*o.im,  x.re*o.im + x.im*o.re)         f32, every product and every sum rounded, no FMA
+ *     y[k] = what sdrhip_decimator_run computes on m                  same order, same One / Cross rule
+ * The result equals, bit for bit, sdrhip_decimator_run applied to a buffer that already holds m, for every order, seam_block,
+ * in_base and cut into launches.  The mix is computed in full for every entry (no shortcut for 0 or +-1: the sign of a zero
+ * would change).  The oscillator phase depends on the absolute index alone, not on seam_block: N need not divide the block size.
+ * Inputs and table must be finite (NaN payloads are out of contract).  The (*) parity is argued from GHC base's formula
+ * (Data.Complex: (x:+y) * (x':+y') = (x*x'-y*y') :+ (x*y'+y*x')), no GHC ran.
+ * The taps are prepared exactly as sdrhip_decimator_create(order, data_complex = 1, ...) prepares them; osc_iq = period (re, im)
+ * float32 pairs, copied; period 1 .. 65536.  A descriptor is immutable after create (but for set_route) and may be shared by
+ * host threads; it belongs to the device of its first run. */
+typedef struct sdrhip_tuner sdrhip_tuner;
+int sdrhip_tuner_create(sdrhip_tuner **t, int order, int factor, const float *coeffs, int ncoeffs, const float *osc_iq,
+                        int period);
+int sdrhip_tuner_num_coeffs(const sdrhip_tuner *t);              /* numCoeffsD */
+int sdrhip_tuner_factor(const sdrhip_tuner *t);
+int sdrhip_tuner_period(const sdrhip_tuner *t);
+void sdrhip_tuner_destroy(sdrhip_tuner *t);
+/* Ranges and guaranteed inputs as sdrhip_decimator_run: d_in[0] is stream sample in_base, the caller guarantees inputs
+ * [k_begin*factor, (k_end-1)*factor + numCoeffsD); k_begin >= 0.  SDRHIP_ERR_ARG before any device work for a null handle or a
+ * seam_block shorter than the filter.  Asynchronous on `stream`. */
+int sdrhip_tuner_run(const sdrhip_tuner *t, void *stream, const float *d_in, int64_t in_base, float *d_out,
+                     int64_t k_begin, int64_t k_end, int64_t seam_block);
+int sdrhip_tuner_run_u8(const sdrhip_tuner *t, void *stream, const uint8_t *d_in_iq, int64_t in_base, float *d_out,
+                        int64_t k_begin, int64_t k_end, int64_t seam_block);
+/* Routes (same bits).  1 = fused: one tile kernel whose loader converts, fetches the oscillator entry and mixes on the way into
+ * LDS, so m never reaches memory -- AVX order, factor 4 / 8 / 16, up to 128 prepared taps, seam_block >= 0, a 16-byte aligned
+ * first window; a launch outside that returns SDRHIP_ERR_ARG.  2 = two-pass: a mix kernel writes m into a bounded
+ * scratch buffer chunk by chunk and the stock decimator runs on it (every order and factor).  0 = auto (default): fused wherever
+ * it applies, else two-pass. */
+int sdrhip_tuner_set_route(sdrhip_tuner *t, int route);
+long long sdrhip_debug_tuner_fused_launches(void);   /* process-wide: launches of the fused tile kernel (tests assert the route) */
+/* test knob: samples one chunk of the two-pass route mixes at a time (<= 0: the default, 2^22); returns the previous value */
+int64_t sdrhip_debug_set_tuner_chunk(int64_t samples);
+/* osc[n] = exp(2 pi i ((num n) mod den) / den), n = 0 .. den - 1, as den (re, im) float32 pairs.  Pure host code, no device.
+ * (1, 4) is quarterBandUp and (1, 2) is halfBandUp, bit for bit, zeros +0; a negative num shifts down.  1 <= den < 2^31.
+ * The reduction, so that the table can be reproduced elsewhere (integers exact, `pi` = the double 3.141592653589793):
+ *     r = (num n) mod den in [0, den);  q = floor(4 r / den) the quarter turn, f = 4 r - q den in [0, den)
+ *     f = 0:        (c, s) = (1, 0)
+ *     2 f = den:    c = s = (float)cos(pi * 0.25)                                  an odd eighth: |re| == |im|
+ *     2 f < den:    phi = pi * ((double)f / (double)(2 den));        c = (float)cos(phi), s = (float)sin(phi)
+ *     2 f > den:    phi = pi * ((double)(den - f) / (double)(2 den)); c = (float)sin(phi), s = (float)cos(phi)
+ *     q = 0: (c, s);  q = 1: (0 - s, c);  q = 2: (0 - c, 0 - s);  q = 3: (s, 0 - c)     0 - x in float32: -x, and +0 for x = 0
+ * cos / sin are the double-precision library functions of an angle in (0, pi/4), rounded once to float32. */
+int sdrhip_tuner_shift_table(int64_t num, int64_t den, float *osc_iq /* den pairs */);
+
 /* ---- Resampler (Filter.hs:137-144; constructors :408-502) ---------------- */
 typedef struct sdrhip_resampler sdrhip_resampler;
 int sdrhip_resampler_create(sdrhip_resampler **r, int order, int data_complex, int interpolation,
@@ -608,6 +659,11 @@ int sdrhip_pipe_dc_blocker(sdrhip_pipe **p);                                    
 /* complex blocks in, complex blocks out at the length they came in; the state starts at 1 and is carried across blocks on the
  * device (sdrhip_agc_run).  save / restore carry the state; mu and reference are the constructor's, not part of it. */
 int sdrhip_pipe_agc(sdrhip_pipe **p, float mu, float reference);                 /* agcPipe, Util.hs:344-348 */
+/* `P.map (VG.zipWith (*) osc) >-> firDecimator deci n` with osc indexed by the stream position: cfloat blocks in, blocks of exactly
+ * block_size_out decimated samples out.  Push, pop, coalesce, adaptive, input_buffer, save and restore behave as for
+ * sdrhip_pipe_fir_decimator; the stream position that selects the oscillator phase is part of the saved state (the table and
+ * the taps are the descriptor's, not part of it).  The tuner must outlive the pipe. */
+int sdrhip_pipe_tuner(sdrhip_pipe **p, const sdrhip_tuner *t, int block_size_out);
 /* Feed one upstream block (n elements: floats, or complex pairs for complex
  * stages).  Returns the number of complete output blocks now ready (>= 0) or a
  * negative error.  A block shorter than numCoeffs is the reference's

@@ -82,8 +82,28 @@ int resamp_run_demod(const ResampDesc* r, hipStream_t s, const float* d_iq, bool
                      int64_t in_base, float* d_out, int64_t k_begin, int64_t k_end, int64_t seam_block, int64_t out_block,
                      bool* demod_fused);
 
+// The tuner (include/sdr_hip.h): a complex decimator's prepared taps plus the oscillator table.  Immutable after create except for
+// the route and the scratch lanes of the two-pass route, so host threads may share one.
+struct TunerScratch;
+struct TunerDesc {
+    FirDesc fir;                       // as sdrhip_decimator_create(order, data_complex = 1, ...) prepares it
+    int period = 0;
+    std::vector<float> h_osc;          // period (re, im) pairs
+    mutable float* d_osc = nullptr;
+    mutable int route = 0;             // 0 = auto, 1 = fused, 2 = two-pass
+    TunerScratch* scratch = nullptr;   // tuner.cpp
+    int ensure_device() const;
+    TunerDesc();
+    ~TunerDesc();
+    TunerDesc(const TunerDesc&) = delete;
+    TunerDesc& operator=(const TunerDesc&) = delete;
+};
+int tuner_run(const TunerDesc* t, hipStream_t s, const void* d_in, bool in_u8, int64_t in_base, float* d_out, int64_t k_begin,
+              int64_t k_end, int64_t seam_block);
+
 }  // namespace sdrhip
 
 struct sdrhip_filter : sdrhip::FirDesc {};
 struct sdrhip_decimator : sdrhip::FirDesc {};
 struct sdrhip_resampler : sdrhip::ResampDesc {};
+struct sdrhip_tuner : sdrhip::TunerDesc {};

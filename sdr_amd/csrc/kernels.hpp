@@ -295,4 +295,14 @@ long long fused_demod_launch_count();  // abi_device.cpp, diagnostics: resampler
 bool launch_decimate_c_orders_fast(hipStream_t s, const Geom& g, ComplexOrder order, const float* d_plain_taps, int P,
                                    const float* d_cross_taps, const void* d_in, bool in_is_u8, float* d_out);
 
+// kernels_tuner.hip: the tuner = multiplication by a periodic complex oscillator (d_osc: `period` (re, im) pairs, indexed by the
+// ABSOLUTE stream index mod period) in front of the complex decimator.  Fused route: the tiled decimator with the mix in its loader,
+// AVX "RC" order, decimation 4 / 8 / 16, up to 128 prepared taps (d_plain_taps, never pre-scaled), 16-byte aligned tile starts;
+// Cross outputs in the tile kernel for short launches, else by a fix-up launch over seam_span(g).  false = not this shape, nothing launched.
+bool launch_tuner_fused(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in,
+                        bool in_is_u8, float* d_out, const float* d_osc, int period);
+// two-pass route, first pass: d_out[i] = mixed sample i of d_in (cfloat or u8 IQ), i < n < 2^31; ph0 = phase of sample 0
+void launch_tuner_mix(hipStream_t s, const void* d_in, bool in_is_u8, float* d_out, int64_t n, const float* d_osc, int period, int ph0);
+long long tuner_fused_launch_count();   // diagnostics: launches of the fused tile kernel
+
 }  // namespace sdrhip

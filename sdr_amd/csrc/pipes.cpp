@@ -28,12 +28,13 @@
 
 using namespace sdrhip;
 
-enum PipeKind { PK_FILTER, PK_DECIMATOR, PK_RESAMPLER, PK_DEMOD, PK_DCBLOCK, PK_AGC };
+enum PipeKind { PK_FILTER, PK_DECIMATOR, PK_RESAMPLER, PK_DEMOD, PK_DCBLOCK, PK_AGC, PK_TUNER };
 
 struct sdrhip_pipe {
     PipeKind kind;
     const FirDesc* fir = nullptr;
     const ResampDesc* rs = nullptr;
+    const TunerDesc* tuner = nullptr;  // PK_TUNER: the decimator behind the oscillator mix (fir = &tuner->fir)
     int block_out = 0;
     bool cplx_in = false, cplx_out = false;
     int I = 1, D = 1, Lp = 1;
@@ -165,6 +166,12 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
                       (m_end - m_done) * p->esz_out(), [&](hipStream_t s, const void* d_in, void* d_out) {
         const float* din = (const float*)d_in;
         float* dout = (float*)d_out;
+        // filter / decimator, or the tuner's mix + decimator: in_base is the absolute stream position of din[0], which is what
+        // selects the oscillator phase
+        auto fir_run = [&](const FirDesc* f, hipStream_t st, const float* in, bool, int64_t base, float* out, int64_t k0, int64_t k1, int64_t seam) {
+            if (p->kind == PK_TUNER) return tuner_run(p->tuner, st, in, false, base, out, k0, k1, seam);
+            return sdrhip::fir_run(f, st, in, false, base, out, k0, k1, seam);
+        };
         if (uniform_seam > 0) {
             if (p->kind == PK_RESAMPLER) return resamp_run(p->rs, s, din, in_base, dout, m_done, m_end, uniform_seam, p->block_out);
             return fir_run(p->fir, s, din, false, in_base, dout, m_done, m_end, uniform_seam);
@@ -272,6 +279,14 @@ int sdrhip_pipe_fir_decimator(sdrhip_pipe** pp, const sdrhip_decimator* d, int b
 {
     SDRHIP_REQUIRE(pp && d && block_size_out > 0, "sdrhip_pipe_fir_decimator");
     return pipe_new(pp, PK_DECIMATOR, d, nullptr, block_size_out, d->cplx, d->cplx, 1, d->factor, d->Lp);
+}
+
+int sdrhip_pipe_tuner(sdrhip_pipe** pp, const sdrhip_tuner* t, int block_size_out)
+{
+    SDRHIP_REQUIRE(pp && t && block_size_out > 0, "sdrhip_pipe_tuner");
+    int rc = pipe_new(pp, PK_TUNER, &t->fir, nullptr, block_size_out, true, true, 1, t->fir.factor, t->fir.Lp);
+    if (rc == SDRHIP_OK) (*pp)->tuner = t;
+    return rc;
 }
 
 int sdrhip_pipe_fir_resampler(sdrhip_pipe** pp, const sdrhip_resampler* r, int block_size_out)
@@ -523,7 +538,7 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
                    "sdrhip_pipe_restore: the state belongs to a pipe of another kind or geometry");
     SDRHIP_REQUIRE(h.hist_n >= 0 && h.hist_n <= h.head_cap && h.pending >= 0 && h.n_blocks >= 0 && h.E_prev >= h.hist_n && h.m_done >= 0,
                    "sdrhip_pipe_restore: inconsistent state");
-    if (p->kind == PK_FILTER || p->kind == PK_DECIMATOR || p->kind == PK_RESAMPLER) {
+    if (p->kind == PK_FILTER || p->kind == PK_DECIMATOR || p->kind == PK_RESAMPLER || p->kind == PK_TUNER) {
         // the next pending output must start inside what the pipe has seen, every output computable from those elements must be
         // done at most once, and the history must reach back to its first input (3 elements of alignment slack, fir_submit):
         // otherwise the kernels would be sent in front of the staging buffer

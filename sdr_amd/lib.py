@@ -92,6 +92,21 @@ lib.sdrhip_decimator_destroy.restype = None
 lib.sdrhip_decimator_run.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64]
 lib.sdrhip_decimator_run_u8.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64]
 
+lib.sdrhip_tuner_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int, _f32p, C.c_int, _f32p, C.c_int]
+lib.sdrhip_tuner_num_coeffs.argtypes = [_vp]
+lib.sdrhip_tuner_factor.argtypes = [_vp]
+lib.sdrhip_tuner_period.argtypes = [_vp]
+lib.sdrhip_tuner_destroy.argtypes = [_vp]
+lib.sdrhip_tuner_destroy.restype = None
+lib.sdrhip_tuner_run.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64]
+lib.sdrhip_tuner_run_u8.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64]
+lib.sdrhip_tuner_set_route.argtypes = [_vp, C.c_int]
+lib.sdrhip_tuner_shift_table.argtypes = [_i64, _i64, _f32p]
+lib.sdrhip_debug_tuner_fused_launches.argtypes = []
+lib.sdrhip_debug_tuner_fused_launches.restype = C.c_longlong
+lib.sdrhip_debug_set_tuner_chunk.argtypes = [_i64]
+lib.sdrhip_debug_set_tuner_chunk.restype = _i64
+
 lib.sdrhip_resampler_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.c_int]
 lib.sdrhip_resampler_num_coeffs.argtypes = [_vp]
 lib.sdrhip_resampler_num_groups.argtypes = [_vp]
@@ -233,6 +248,7 @@ lib.sdrhip_pipe_fir_resampler.argtypes = [C.POINTER(_vp), _vp, C.c_int]
 lib.sdrhip_pipe_fm_demod.argtypes = [C.POINTER(_vp)]
 lib.sdrhip_pipe_dc_blocker.argtypes = [C.POINTER(_vp)]
 lib.sdrhip_pipe_agc.argtypes = [C.POINTER(_vp), C.c_float, C.c_float]
+lib.sdrhip_pipe_tuner.argtypes = [C.POINTER(_vp), _vp, C.c_int]
 lib.sdrhip_pipe_set_coalesce.argtypes = [_vp, C.c_int]
 lib.sdrhip_pipe_set_adaptive.argtypes = [_vp, C.c_int]
 lib.sdrhip_pipe_input_buffer.argtypes = [_vp, C.c_int]
@@ -498,6 +514,52 @@ class Resampler(_Handle):
     def run(self, d_in, in_base, d_out, k_begin, k_end, seam_block=0, stream=None, out_block=0):
         check(lib.sdrhip_resampler_run(self.h, stream, d_in, in_base, d_out, k_begin, k_end, seam_block, out_block),
               "sdrhip_resampler_run")
+
+
+TUNER_ROUTE_AUTO, TUNER_ROUTE_FUSED, TUNER_ROUTE_TWO_PASS = 0, 1, 2
+
+
+def tuner_shift_table(num, den):
+    """sdrhip_tuner_shift_table: exp(2 pi i ((num n) mod den) / den), n < den, as interleaved float32 (re, im) pairs.
+    (1, 4) = quarterBandUp, (1, 2) = halfBandUp (Util.hs:263-285).  Host code: no device needed."""
+    out = np.empty(2 * int(den), np.float32)
+    check(lib.sdrhip_tuner_shift_table(int(num), int(den), _fp(out)), "sdrhip_tuner_shift_table")
+    return out
+
+
+def tuner_fused_launches():
+    return int(lib.sdrhip_debug_tuner_fused_launches())
+
+
+def set_tuner_chunk(samples):
+    """sdrhip_debug_set_tuner_chunk (test knob of the two-pass route): returns the previous value."""
+    return int(lib.sdrhip_debug_set_tuner_chunk(int(samples)))
+
+
+class Tuner(_Handle):
+    """`P.map (VG.zipWith (*) osc) >-> firDecimator`: a periodic complex oscillator (osc_iq: interleaved float32 pairs, indexed by the
+    absolute stream position) mixed into a complex decimator (sdr_hip.h, sdrhip_tuner_*)."""
+    _destroy = lib.sdrhip_tuner_destroy
+    complex = True
+
+    def __init__(self, factor, coeffs, osc_iq, order=ORDER_AVX):
+        super().__init__()
+        c, o = _f32(coeffs), _f32(osc_iq).reshape(-1)
+        if o.size % 2:
+            raise SdrHipError("the oscillator table is interleaved (re, im) pairs")
+        check(lib.sdrhip_tuner_create(C.byref(self.h), order, factor, _fp(c), c.size, _fp(o), o.size // 2), "sdrhip_tuner_create")
+        self.factor = factor
+        self.num_coeffs = lib.sdrhip_tuner_num_coeffs(self.h)
+        self.period = lib.sdrhip_tuner_period(self.h)
+
+    def set_route(self, route):
+        check(lib.sdrhip_tuner_set_route(self.h, int(route)), "sdrhip_tuner_set_route")
+
+    def run(self, d_in, in_base, d_out, k_begin, k_end, seam_block=0, stream=None):
+        check(lib.sdrhip_tuner_run(self.h, stream, d_in, in_base, d_out, k_begin, k_end, seam_block), "sdrhip_tuner_run")
+
+    def run_u8(self, d_in, in_base, d_out, k_begin, k_end, seam_block=0, stream=None):
+        check(lib.sdrhip_tuner_run_u8(self.h, stream, d_in, in_base, d_out, k_begin, k_end, seam_block), "sdrhip_tuner_run_u8")
 
 
 class FmChain(_Handle):
@@ -838,6 +900,8 @@ class Pipe(_Handle):
             check(lib.sdrhip_pipe_fir_decimator(C.byref(self.h), desc.h, block_size_out), "sdrhip_pipe_fir_decimator")
         elif kind == "resampler":
             check(lib.sdrhip_pipe_fir_resampler(C.byref(self.h), desc.h, block_size_out), "sdrhip_pipe_fir_resampler")
+        elif kind == "tuner":
+            check(lib.sdrhip_pipe_tuner(C.byref(self.h), desc.h, block_size_out), "sdrhip_pipe_tuner")
         elif kind == "fm_demod":
             check(lib.sdrhip_pipe_fm_demod(C.byref(self.h)), "sdrhip_pipe_fm_demod")
         elif kind == "dc_blocker":
@@ -849,6 +913,11 @@ class Pipe(_Handle):
         else:
             raise ValueError(kind)
         self.kind = kind
+
+    @staticmethod
+    def tuner(tuner, block_size_out):
+        """The tuner on host blocks: cfloat blocks in, blocks of block_size_out decimated samples out."""
+        return Pipe("tuner", tuner, block_size_out)
 
     def push(self, block):
         """block: float32 array (interleaved for complex stages).  Returns list of output blocks."""
