@@ -1,7 +1,7 @@
 /* fm_replay.c -- the FM receiver of the reference's examples/fm/fm.hs:30-41 fed from a file instead of a radio
  * ("file replay source feeding pinned buffers"), in plain C over the C ABI of libsdr_hip.so.
  *
- *     fm_replay <iq_u8_file | udp:PORT> <audio_f32_file> [blocks_per_push] [taps_prefix]
+ *     fm_replay [--shift NUM/DEN] <iq_u8_file | udp:PORT> <audio_f32_file> [blocks_per_push] [taps_prefix]
  *
  * Reads interleaved unsigned 8-bit IQ (what rtl_sdr writes, what RTLSDRStream.hs:48-67 yields) in source blocks of
  * 8192 samples, `blocks_per_push` of them at a time, straight into the stream operator's pinned staging buffer
@@ -10,6 +10,9 @@
  * instead (the reference's udpSource, NetworkStream.hs:28-35), reassembled into source blocks; a zero-length datagram
  * ends the stream.  Taps arrive as three raw f32 files (<taps_prefix>.decim.f32, .resamp.f32, .audio_half.f32; the
  * prefix defaults to the capture's path) so the example carries no filter design of its own.
+ * --shift NUM/DEN receives a station that is off the centre of the capture: the samples are multiplied by exp(2 pi i NUM n / DEN)
+ * (sdrhip_tuner_shift_table, 1 <= DEN <= 65536; sample n of the capture meets entry n mod DEN) in front of the decimator
+ * (sdrhip_fm_chain_set_tuner), which moves the station NUM / DEN of the sampling frequency BELOW the centre onto it.
  * Output is bit-identical to the reference pipeline's (tests/test_gpu_examples.py). */
 #define _POSIX_C_SOURCE 200809L
 #include <arpa/inet.h>
@@ -64,7 +67,24 @@ static void check(int rc, const char *what)
 
 int main(int argc, char **argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: fm_replay <iq_u8_file | udp:PORT> <audio_f32_file> [blocks_per_push] [taps_prefix]\n"); return 2; }
+    /* --shift NUM/DEN, anywhere on the line; what is left are the positional arguments */
+    long long shift_num = 0, shift_den = 0;
+    {
+        int w = 1;
+        for (int i = 1; i < argc; i++) {
+            if (strcmp(argv[i], "--shift") == 0) {
+                if (i + 1 >= argc || sscanf(argv[i + 1], "%lld/%lld", &shift_num, &shift_den) != 2 || shift_den < 1 || shift_den > 65536) {
+                    fprintf(stderr, "fm_replay: --shift NUM/DEN with 1 <= DEN <= 65536\n");
+                    return 2;
+                }
+                i++;
+            } else {
+                argv[w++] = argv[i];
+            }
+        }
+        argc = w;
+    }
+    if (argc < 3) { fprintf(stderr, "usage: fm_replay [--shift NUM/DEN] <iq_u8_file | udp:PORT> <audio_f32_file> [blocks_per_push] [taps_prefix]\n"); return 2; }
     const int bpp = argc > 3 ? atoi(argv[3]) : 64;
     if (bpp < 1) { fprintf(stderr, "fm_replay: blocks_per_push must be >= 1\n"); return 2; }
     int n_decim, n_resamp, n_audio;
@@ -78,6 +98,12 @@ int main(int argc, char **argv)
     sdrhip_fm_chain *chain = NULL;
     check(sdrhip_fm_chain_create(&chain, SDRHIP_ORDER_AVX, 8, decim, n_decim, 3, 10, resamp, n_resamp, audio_half, n_audio,
                                  0.2f, SOURCE_BLOCK), "sdrhip_fm_chain_create");
+    if (shift_den > 0) {
+        float *osc = (float *)malloc((size_t)shift_den * 2 * sizeof(float));
+        check(sdrhip_tuner_shift_table(shift_num, shift_den, osc), "sdrhip_tuner_shift_table");
+        check(sdrhip_fm_chain_set_tuner(chain, osc, (int)shift_den), "sdrhip_fm_chain_set_tuner");   /* copied */
+        free(osc);
+    }
     sdrhip_fm_stream *st = NULL;
     check(sdrhip_fm_stream_create(&st, chain, bpp * SOURCE_BLOCK, SOURCE_BLOCK), "sdrhip_fm_stream_create");
 

@@ -8,7 +8,9 @@
  *      with adaptive submission, with neither; popped at odd times; saved and restored half way into a fresh Pipe;
  *   2. the whole-receiver operator (sdrhip_fm_stream) with pushes of 1, 7, 64 and 4096 source blocks from caller memory (the
  *      4096-block push goes through the threaded copy) and from its own staging buffer, flush, checkpoint, restore, destroy;
- *   3. every handle destroyed, some of them while results are still pending.
+ *   3. the same operator on a TUNED chain (sdrhip_fm_chain_set_tuner): tables set, refused, replaced between streams, removed and set
+ *      again, a chain destroyed with its table never uploaded -- the table copy, the plan, the workspace sizing;
+ *   4. every handle destroyed, some of them while results are still pending.
  * Values are not checked here (tests/test_gpu_pipes.py does, against the restated Pipes); a wrong total count, an error return or
  * any sanitizer report fails the run.  Exit code 0 and "pipes_soak: ok" = clean. */
 #define _POSIX_C_SOURCE 200809L
@@ -114,6 +116,29 @@ int main(int argc, char **argv)
     lowpass(h191, 191, 1.0 / 10);
     lowpass(full128, 128, 0.3);
     memcpy(half64, full128, sizeof half64);
+    /* a tuned chain that never reaches a device: table set, removed, set, replaced; destroyed with a table set.  This leg runs
+     * first so that a host without a GPU still walks it (the first device call below ends the program there). */
+    static float osc[2 * 1000];
+    {
+        sdrhip_fm_chain *idle = NULL;
+        check(sdrhip_fm_chain_create(&idle, SDRHIP_ORDER_AVX, 8, h127, 127, 3, 10, h191, 191, half64, 64, 0.2f, BLOCK), "sdrhip_fm_chain_create");
+        const size_t plain_bytes = sdrhip_fm_chain_workspace_bytes(idle, BLOCK);
+        check(sdrhip_tuner_shift_table(1, 4, osc), "sdrhip_tuner_shift_table");
+        check(sdrhip_fm_chain_set_tuner(idle, osc, 4), "sdrhip_fm_chain_set_tuner");
+        check(sdrhip_fm_chain_set_tuner(idle, NULL, 0), "sdrhip_fm_chain_set_tuner (remove)");
+        if (sdrhip_fm_chain_tuner_period(idle) != 0 || sdrhip_fm_chain_workspace_bytes(idle, BLOCK) != plain_bytes) {
+            fprintf(stderr, "pipes_soak: a chain that lost its tuner is not the chain it was\n");
+            return 1;
+        }
+        check(sdrhip_tuner_shift_table(-3, 1000, osc), "sdrhip_tuner_shift_table");
+        check(sdrhip_fm_chain_set_tuner(idle, osc, 1000), "sdrhip_fm_chain_set_tuner");
+        if (sdrhip_fm_chain_tuner_period(idle) != 1000 || sdrhip_fm_chain_workspace_bytes(idle, BLOCK) <= plain_bytes) {
+            fprintf(stderr, "pipes_soak: a tuned chain reports the wrong period or reserves no room for the mixed samples\n");
+            return 1;
+        }
+        sdrhip_fm_chain_destroy(idle);
+        fprintf(stderr, "pipes_soak: tuned chain, host paths done\n");
+    }
     sdrhip_decimator *dec = NULL;
     sdrhip_resampler *res = NULL;
     sdrhip_filter *fil = NULL;
@@ -143,10 +168,22 @@ int main(int argc, char **argv)
     /* the whole-receiver operator */
     sdrhip_fm_chain *chain = NULL;
     check(sdrhip_fm_chain_create(&chain, SDRHIP_ORDER_AVX, 8, h127, 127, 3, 10, h191, 191, half64, 64, 0.2f, BLOCK), "sdrhip_fm_chain_create");
-    static const int bpps[4] = {1, 7, 64, 4096};
+    static const int bpps[7] = {1, 7, 64, 4096, 1, 7, 64};
     float *audio = (float *)malloc(BLOCK * sizeof(float));
-    for (int c = 0; c < 4; c++) {
+    /* the tuned legs (c >= 4): a table of another period before each, a refused one in between, the tuner removed at the end */
+    for (int c = 0; c < 7; c++) {
         const int bpp = bpps[c];
+        if (c >= 4) {
+            const int period = c == 4 ? 4 : (c == 5 ? 1000 : 7);
+            check(sdrhip_tuner_shift_table(c == 5 ? -3 : 1, period, osc), "sdrhip_tuner_shift_table");
+            if (sdrhip_fm_chain_set_tuner(chain, NULL, period) >= 0 || sdrhip_fm_chain_set_tuner(chain, osc, 65537) >= 0 ||
+                sdrhip_fm_chain_set_tuner(NULL, osc, period) >= 0) {
+                fprintf(stderr, "pipes_soak: sdrhip_fm_chain_set_tuner accepted bad arguments\n");
+                return 1;
+            }
+            check(sdrhip_fm_chain_set_tuner(chain, osc, period), "sdrhip_fm_chain_set_tuner");
+            if (sdrhip_fm_chain_tuner_period(chain) != period) { fprintf(stderr, "pipes_soak: wrong tuner period\n"); return 1; }
+        }
         sdrhip_fm_stream *st = NULL, *st2 = NULL;
         check(sdrhip_fm_stream_create(&st, chain, bpp * BLOCK, BLOCK), "sdrhip_fm_stream_create");
         check(sdrhip_fm_stream_create(&st2, chain, bpp * BLOCK, BLOCK), "sdrhip_fm_stream_create");
@@ -184,6 +221,10 @@ int main(int argc, char **argv)
         free(mine);
     }
     free(audio);
+    check(sdrhip_fm_chain_set_tuner(chain, NULL, 0), "sdrhip_fm_chain_set_tuner (remove)");
+    if (sdrhip_fm_chain_tuner_period(chain) != 0) { fprintf(stderr, "pipes_soak: the tuner is still there\n"); return 1; }
+    check(sdrhip_tuner_shift_table(1, 4, osc), "sdrhip_tuner_shift_table");
+    check(sdrhip_fm_chain_set_tuner(chain, osc, 4), "sdrhip_fm_chain_set_tuner");      /* destroyed with a table set */
     sdrhip_fm_chain_destroy(chain);
     sdrhip_decimator_destroy(dec);
     sdrhip_resampler_destroy(res);

@@ -37,7 +37,7 @@ module SDR.GPU (
     interleavedIQUnsignedByteToFloatGpu,
     -- * The tuner: an oscillator mixed into the complex decimator (P.map (VG.zipWith (*) osc) >-> firDecimator)
     GpuTuner, gpuTuner, gpuTunerShift, tunerShiftTable, tunerGpu,
-    GpuFmChain, gpuFmChain, fmReceiverGpu,
+    GpuFmChain, gpuFmChain, fmChainSetTuner, fmReceiverGpu,
     -- * The waterfall pipe as one operator (raw IQ -> windowed FFT magnitudes)
     GpuSpectrum, SpectrumWindow (..), gpuSpectrumU8, spectrumRowsGpu
     ) where
@@ -131,6 +131,8 @@ foreign import ccall safe "sdrhip_tuner_set_route"   c_tuner_set_route   :: Ptr 
 foreign import ccall safe "sdrhip_tuner_shift_table" c_tuner_shift_table :: Int64 -> Int64 -> Ptr CFloat -> IO CInt
 foreign import ccall safe "sdrhip_debug_tuner_fused_launches" c_tuner_fused_launches :: IO CLLong
 foreign import ccall safe "sdrhip_pipe_tuner"        c_pipe_tuner        :: Ptr (Ptr SdrPipe) -> Ptr SdrTuner -> CInt -> IO CInt
+-- the FM chain with a tuner: the same oscillator in front of the chain's own decimator (a null table with period 0 removes it)
+foreign import ccall safe "sdrhip_fm_chain_set_tuner" c_fm_chain_set_tuner :: Ptr SdrChain -> Ptr CFloat -> CInt -> IO CInt
 -- the spectrum operator (include/sdr_hip.h, sdrhip_spectrum_*): interleavedIQUnsigned256ToFloat -> halfBandUp x window -> fftw ->
 -- magnitude x scale, rows of Float
 foreign import ccall safe "sdrhip_spectrum_create"     c_spectrum_create     :: Ptr (Ptr SdrSpectrum) -> CInt -> CInt -> CInt -> Ptr CDouble -> CInt -> CDouble -> IO CInt
@@ -386,6 +388,11 @@ gpuFmChain decimation rfTaps interpolation decimation2 resampTaps audioHalf gain
                  (fromIntegral interpolation) (fromIntegral decimation2) p2 (fromIntegral n2)
                  p3 (fromIntegral n3) (realToFrac gain) (fromIntegral block) >>= check
         GpuFmChain <$> peek pp
+
+-- | @P.map (VG.zipWith (*) osc)@ in front of the chain's decimator, the oscillator indexed by the stream position (an empty vector
+--   removes it): @tunerShiftTable num den >>= fmChainSetTuner chain@ receives the station num / den of the sampling frequency below the centre.
+fmChainSetTuner :: GpuFmChain -> VS.Vector (Complex Float) -> IO ()
+fmChainSetTuner (GpuFmChain c) osc = void $ VS.unsafeWith (VS.unsafeCast osc) $ \po -> c_fm_chain_set_tuner c (if VS.null osc then nullPtr else po) (fromIntegral (VS.length osc)) >>= check
 
 -- | u8 IQ blocks from 'sdrStream' in, audio blocks of exactly @blockSizeOut@ floats out: same blocks,
 --   bit for bit, as the five stages it replaces.  @maxBlock@ = the largest source block (a multiple of

@@ -433,6 +433,28 @@ int sdrhip_fm_chain_set_fused_tail(sdrhip_fm_chain *c, int mode);
 int sdrhip_fm_chain_set_small_chain(sdrhip_fm_chain *c, int mode, int64_t max_outputs, int tile_outputs);
 /* launches of that kernel so far, process-wide (tests assert that this path, not the stage kernels, ran) */
 long long sdrhip_debug_small_chain_launches(void);
+
+/* The chain with a tuner: a station that is off the centre of the capture.  Puts `P.map (VG.zipWith (*) osc)` in front of the chain's
+ * decimator:  P.map convert >-> P.map (VG.zipWith (*) osc) >-> firDecimator >-> fmDemod >-> firResampler >-> firFilter >-> P.map (* gain).
+ * osc_iq = period (re, im) float32 pairs, copied (sdrhip_tuner_shift_table builds the usual ones); period 1 .. 65536; (NULL, 0)
+ * removes the tuner again.  SDRHIP_ERR_ARG before any device work for a null chain, a null table with period != 0 (or a table with
+ * period 0), a period outside 1 .. 65536 and a non-finite entry.
+ * Definition: with t = sdrhip_tuner_create(order, factor, decim_taps, ..., osc_iq, period) the chain's decimator outputs are, bit
+ * for bit, what sdrhip_tuner_run_u8(t, ..., seam_block = block) writes; fmDemod, resampler, filter and gain behind them are the
+ * chain's as it is, on every route (stage kernels, fused tail, the one-kernel chain).  The oscillator phase of a sample is its
+ * ABSOLUTE stream index mod period: it does not depend on s0, on how a stream is cut into runs, shards or pushes, or on `block`,
+ * so sdrhip_fm_chain_plan, the halo sizes and exchange, sdrhip_fm_chain_graph_*, sdrhip_fm_chain_set_overlap and sdrhip_fm_stream_*
+ * (save / restore included: same state layout) work on a tuned chain as they are.  sdrhip_fm_chain_workspace_bytes of a tuned chain
+ * also reserves 8 bytes per input sample (the mixed samples of a launch whose first window is not 16-byte aligned, or whose
+ * decimator the tuner's tile kernel does not serve); a chain whose tuner was removed reports and behaves as one that never had one.
+ * A large tuned run takes the tuner's tile kernel: the systolic decimator has no tuned form.
+ * Call with no run of this chain in flight (after sdrhip_fm_chain_join in overlap mode): the previous table's device copy is
+ * freed.  Graphs captured earlier keep what they captured -- the previous table's address included -- and must be destroyed and
+ * created again, as must the workspace be re-sized. */
+int sdrhip_fm_chain_set_tuner(sdrhip_fm_chain *c, const float *osc_iq, int period);
+int sdrhip_fm_chain_tuner_period(const sdrhip_fm_chain *c);      /* 0 = none */
+/* launches of the tuned one-kernel chain so far, process-wide (they count in sdrhip_debug_small_chain_launches too) */
+long long sdrhip_debug_small_chain_tuned_launches(void);
 /* launches of the thread-per-polyphase-cycle resampler (real I/D with an odd decimation: 2/3, 5/7, ...; any filter length),
  * process-wide (tests assert that this kernel, not the lane-split one, served those ratios) */
 long long sdrhip_debug_resample_cycle_launches(void);

@@ -10,10 +10,16 @@
 // Seams: all four Pipes of fm.hs run with blockSizeOut = `block` and the source
 // delivers `block`-sample buffers, so each stage's input blocks are `block` long.
 //
+// Tuner (sdrhip_fm_chain_set_tuner): `P.map (VG.zipWith (*) osc)` between convert and firDecimator.  The decimator outputs are then,
+// bit for bit, sdrhip_tuner_run_u8's (kernels_tuner.hip) and everything behind them is unchanged; the oscillator phase of a sample is
+// its absolute stream index mod the period, so halos, shards, pushes and saved streams need nothing new.
+//
 // One run (chain_run_on): derive the stage ranges of [q0, q1) once (plan_run), check the receptive field once, pick ONE route --
 // the one-kernel chain, decimator + fused tail, or the stage kernels -- and launch it.  Whether a fused kernel applies is asked
 // of its predicate (kernels.hpp: fm_tail_shape_ok when the chain is created, fm_chain_small_fits / fm_tail_fused_fits per run)
 // together with the mode and size rule, before anything is launched or timed; the launchers launch unconditionally.
+#include <float.h>
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -82,6 +88,20 @@ struct sdrhip_fm_chain {
     static bool mode_takes(int mode, int64_t n_out, int64_t auto_max) { return mode != 0 && (mode != 2 || n_out <= auto_max); }
     // set when the chain is created: resampler and audio filter have the shape both fused kernels are written for (AVX orders)
     bool fm_tail = false;
+    // The tuner: `period` (re, im) pairs, 0 = none.  The device copy is made by the first run after set_tuner (a chain, tuned or
+    // not, can be created and planned on a host without a GPU) and lives until the next set_tuner or the chain's end.
+    int tuner_period = 0;
+    std::vector<float> h_osc;
+    float* d_osc = nullptr;
+    bool tuner_pskip_ok = false;       // no mixed sample can overflow: the zero tap the constructor padded may be skipped (mac_window's PSKIP)
+    int ensure_osc()
+    {
+        if (tuner_period == 0 || d_osc != nullptr) return SDRHIP_OK;
+        return upload_floats(&d_osc, h_osc);
+    }
+    // the tuner's fused tile kernel (kernels_tuner.hip) serves this chain's decimator; whether it serves a LAUNCH also depends on
+    // the alignment of that launch's first window (tuner_fused_fits)
+    bool tuner_tile_shape() const { return decim.corder == CO_L4; }
     FmTailTables tail_tables() const      // their device tables (after ensure_device)
     {
         return {resamp.d_groups, resamp.row_stride, resamp.d_plain, resamp.ntaps, resamp.Lp, audio.d_taps, audio.d_cross, gain, block};
@@ -146,6 +166,7 @@ struct sdrhip_fm_chain {
             if (lane[j]) (void)hipStreamDestroy(lane[j]);
         }
         for (auto ev : ev_pool) (void)hipEventDestroy(ev);
+        if (d_osc) (void)hipFree(d_osc);
     }
 
     // reach of resampler output m in y: the One kernel walks nloop floats, the Cross
@@ -315,7 +336,9 @@ size_t sdrhip_fm_chain_workspace_bytes(const sdrhip_fm_chain* c, int64_t n_in)
     int64_t nm = nk * c->resamp.I / c->resamp.D + 4;
     // unfused first stage: the converted input (+ 16 filter lengths with their alignment padding: what round 4's sub-batches recomputed;
     // no run needs it any more, but the size callers allocate stays what it was)
-    const size_t conv = c->fused_first_stage() ? 0 : align_up((size_t)(n_in + 16) * 8, 256) + 16 * align_up((size_t)(c->decim.Lp + 16) * 8, 256);
+    // a tuned chain reserves the same region for the mixed samples whatever its first stage: a launch whose first window is not
+    // 16-byte aligned cannot take the tuner's tile kernel, and the size is asked for before any launch is known
+    const size_t conv = c->fused_first_stage() && c->tuner_period == 0 ? 0 : align_up((size_t)(n_in + 16) * 8, 256) + 16 * align_up((size_t)(c->decim.Lp + 16) * 8, 256);
     const size_t one = conv + align_up((size_t)nk * 8, 256) + align_up((size_t)nk * 4, 256) + align_up((size_t)nm * 4, 256) + 256 + 16 * (64 << 10);
     return c->overlap ? 2 * align_up(one, 256) : one;      // two runs in flight: one half per lane
 }
@@ -327,13 +350,29 @@ struct RunPlan {
     int64_t ky0, ky1;                    // demod outputs
     int64_t kd0, kd1;                    // decimator outputs (fmDemod looks one back)
     int64_t n_lo, n_hi;                  // the input samples the run reads
-    int64_t xa = 0, xb = 0;              // unfused first stage only: samples [xa, xb) of the stream are converted to the workspace's start
+    int64_t xa = 0, xb = 0;              // staged first stage only: samples [xa, xb) of the stream are converted (tuned: mixed) to the workspace's start
+    bool tuner_tile = false;             // tuned chain: the first stage is the tuner's fused tile kernel
     size_t off_d = 0, off_y, off_z;      // decimated, demodulated, resampled
     size_t ws_need;                      // bytes of workspace the stage routes use
 };
 }  // namespace
 
-static RunPlan plan_run(const sdrhip_fm_chain* c, int64_t s0, int64_t q0, int64_t q1)
+// The first stage of a tuned run as the tuner sees it: decimator outputs [kd0, kd1) from u8 IQ whose sample 0 is stream index s0
+static Geom tuner_geom(const sdrhip_fm_chain* c, int64_t s0, int64_t kd0, int64_t kd1)
+{
+    Geom g;
+    g.in_base = s0;
+    g.k_begin = kd0;
+    g.count = (int)(kd1 - kd0);
+    g.I = 1;
+    g.D = c->decim.factor;
+    g.Lp = c->decim.Lp;
+    g.seamBI = c->block;
+    return g;
+}
+
+// d_in_iq, d_workspace: only their alignment counts (a tuned run takes the tuner's tile kernel where its 16-byte loads are aligned)
+static RunPlan plan_run(const sdrhip_fm_chain* c, int64_t s0, int64_t q0, int64_t q1, const void* d_in_iq, const void* d_workspace)
 {
     RunPlan r;
     r.m1 = q1 + c->audio.Lp - 1;
@@ -343,7 +382,13 @@ static RunPlan plan_run(const sdrhip_fm_chain* c, int64_t s0, int64_t q0, int64_
     r.kd1 = r.ky1;
     r.n_lo = r.kd0 * c->decim.factor;
     r.n_hi = (r.kd1 - 1) * c->decim.factor + c->decim.Lp;
-    if (!c->fused_first_stage()) {
+    bool staged = !c->fused_first_stage();      // the first stage reads cfloat samples from the workspace's start
+    if (c->tuner_period != 0) {
+        r.tuner_tile = c->tuner_tile_shape() && r.kd1 - r.kd0 < (int64_t)0x7fffffff &&
+                       tuner_fused_fits(tuner_geom(c, s0, r.kd0, r.kd1), c->decim.Lp, true, d_in_iq, true, d_workspace, c->tuner_period);
+        staged = !r.tuner_tile;
+    }
+    if (staged) {
         r.xa = s0 + ((r.n_lo - s0) & ~(int64_t)7);                   // 16-byte aligned in the u8 stream
         r.xb = r.n_hi;
         r.off_d = align_up((size_t)(r.xb - r.xa) * 8, 256);
@@ -371,7 +416,7 @@ static int chain_run_on(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq
     SDRHIP_REQUIRE(d_in_iq && d_audio && d_workspace, "sdrhip_fm_chain_run");
     hipStream_t s = (hipStream_t)stream;
 
-    const RunPlan r = plan_run(c, s0, q0, q1);
+    const RunPlan r = plan_run(c, s0, q0, q1, d_in_iq, d_workspace);
     if (r.n_lo < s0 || r.n_hi > s0 + n_in) {
         set_error("sdrhip_fm_chain_run: outputs [%lld,%lld) need samples [%lld,%lld) but d_in holds [%lld,%lld)",
                   (long long)q0, (long long)q1, (long long)r.n_lo, (long long)r.n_hi, (long long)s0, (long long)(s0 + n_in));
@@ -379,8 +424,10 @@ static int chain_run_on(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq
     }
     // the route: the first of the two fused kernels that is wanted (mode and size) and fits, else the stage kernels
     const FirDesc& dec = c->decim;
+    const bool tuned = c->tuner_period != 0;
+    // (the tuned one-kernel chain reads the plain taps: it needs no exactly pre-scaled ones)
     const bool small = c->fm_tail && c->mode_takes(c->small_chain, q1 - q0, c->small_chain_max) &&
-                       fm_chain_small_fits(dec.factor, dec.Lp, dec.corder, !dec.h_scaled.empty(), c->block, d_in_iq, s0);
+                       fm_chain_small_fits(dec.factor, dec.Lp, dec.corder, tuned || !dec.h_scaled.empty(), c->block, d_in_iq, s0);
     const bool tail = !small && c->fm_tail && c->mode_takes(c->fused_tail, q1 - q0, kFusedTailAutoOutputs) &&
                       fm_tail_fused_fits(c->resamp.Lp, c->block);
     if (!small && r.ws_need > workspace_bytes) {       // the one-kernel chain sends nothing through the workspace
@@ -390,13 +437,24 @@ static int chain_run_on(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq
     int rc;
     if (small || tail)
         if ((rc = c->resamp.ensure_device()) != SDRHIP_OK || (rc = c->audio.ensure_device()) != SDRHIP_OK) return rc;
+    if (tuned) {
+        if (!small && !r.tuner_tile && r.xb - r.xa >= (int64_t)0x7fffffff) {
+            set_error("sdrhip_fm_chain_run: a tuned run that mixes into the workspace takes fewer than 2^31 samples");
+            return SDRHIP_ERR_ARG;
+        }
+        if ((rc = dec.ensure_device()) != SDRHIP_OK || (rc = c->ensure_osc()) != SDRHIP_OK) return rc;
+    }
     if (c->timing) c->runs++;
 
     if (small) {      // launch-bound run: the whole chain in ONE kernel
         if ((rc = dec.ensure_device()) != SDRHIP_OK) return rc;
         return launched(c->timed(kFusedChain, s, [&] {
-            launch_fm_chain_small(s, d_in_iq, s0, n_in, d_audio, q0, q1, dec.d_scaled, dec.last_tap_is_padding(), c->tail_tables(),
-                                  c->small_chain_tile != 0 ? c->small_chain_tile : (input_over_link ? -1 : 0));
+            const int tile = c->small_chain_tile != 0 ? c->small_chain_tile : (input_over_link ? -1 : 0);
+            if (tuned)
+                launch_fm_chain_small(s, d_in_iq, s0, n_in, d_audio, q0, q1, dec.d_plain, dec.last_tap_is_padding() && c->tuner_pskip_ok,
+                                      c->tail_tables(), tile, c->d_osc, c->tuner_period);
+            else
+                launch_fm_chain_small(s, d_in_iq, s0, n_in, d_audio, q0, q1, dec.d_scaled, dec.last_tap_is_padding(), c->tail_tables(), tile);
             return SDRHIP_OK;
         }));
     }
@@ -407,6 +465,20 @@ static int chain_run_on(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq
     float* d_z = (float*)(ws + r.off_z);
     // K1+K2: u8 -> cfloat -> decimate (convert.c:37-50 fused into decimate.c:105-113)
     rc = c->timed(kDecimate, s, [&] {
+        if (tuned) {
+            // the tuner's own routes on the caller's workspace and this run's stream (no leased scratch, no events: runs are captured
+            // into graphs and alternate between the overlap lanes): its tile kernel, or the mix into the workspace's start and the
+            // stock cfloat decimator on it
+            if (r.tuner_tile) {
+                if (!launch_tuner_fused(s, tuner_geom(c, s0, r.kd0, r.kd1), dec.d_plain, dec.Lp, dec.d_cross, d_in_iq, true, d_d, c->d_osc, c->tuner_period)) {
+                    set_error("sdrhip_fm_chain_run: the tuner's tile kernel refused a launch its predicate accepted");
+                    return SDRHIP_ERR_STATE;
+                }
+                return SDRHIP_OK;
+            }
+            launch_tuner_mix(s, d_in_iq + 2 * (r.xa - s0), true, (float*)ws, r.xb - r.xa, c->d_osc, c->tuner_period, (int)(r.xa % c->tuner_period));
+            return fir_run(&dec, s, ws, false, r.xa, d_d, r.kd0, r.kd1, c->block);
+        }
         if (c->fused_first_stage()) return fir_run(&dec, s, d_in_iq, true, s0, d_d, r.kd0, r.kd1, c->block);
         launch_convert_u8(s, d_in_iq + 2 * (r.xa - s0), (float*)ws, 2 * (r.xb - r.xa));
         return fir_run(&dec, s, ws, false, r.xa, d_d, r.kd0, r.kd1, c->block);
@@ -560,6 +632,7 @@ int sdrhip_fm_chain_set_small_chain(sdrhip_fm_chain* c, int mode, int64_t max_ou
 }
 
 long long sdrhip_debug_small_chain_launches(void) { return fm_chain_small_launch_count(); }
+long long sdrhip_debug_small_chain_tuned_launches(void) { return fm_chain_small_tuned_launch_count(); }
 long long sdrhip_debug_resample_cycle_launches(void) { return resample_cycle_launch_count(); }
 long long sdrhip_debug_decimate_real16_launches(void) { return decimate_real16_launch_count(); }
 void sdrhip_debug_set_systolic(int on) { set_systolic(on); }
@@ -568,6 +641,30 @@ long long sdrhip_debug_systolic_plain_launches(void) { return systolic_plain_lau
 long long sdrhip_debug_decimator_crossfix_launches(void) { return decimator_crossfix_launch_count(); }
 long long sdrhip_debug_fused_demod_launches(void) { return fused_demod_launch_count(); }
 void sdrhip_debug_systolic_plan(int count, int* nstrips, int* nwhole) { systolic_plan(count, nstrips, nwhole); }
+
+int sdrhip_fm_chain_set_tuner(sdrhip_fm_chain* c, const float* osc_iq, int period)
+{
+    SDRHIP_REQUIRE(c != nullptr, "sdrhip_fm_chain_set_tuner");
+    SDRHIP_REQUIRE(period >= 0 && period <= 65536, "sdrhip_fm_chain_set_tuner: period 1 .. 65536 (0 with a null table: no tuner)");
+    SDRHIP_REQUIRE((osc_iq == nullptr) == (period == 0), "sdrhip_fm_chain_set_tuner: a table and its period, or (NULL, 0)");
+    // |x| <= 1 for converted u8, so a mixed component is at most |re| + |im| in magnitude: while that is finite no sample overflows
+    bool no_overflow = true;
+    for (size_t i = 0; i < 2 * (size_t)period; i++) {
+        SDRHIP_REQUIRE(isfinite(osc_iq[i]), "sdrhip_fm_chain_set_tuner: non-finite table entry");
+        if (i % 2 == 1 && fabs((double)osc_iq[i - 1]) + fabs((double)osc_iq[i]) > (double)FLT_MAX) no_overflow = false;
+    }
+    // no run of this chain is in flight (the caller's side of the contract): the old table can go.  hipFree waits for the device.
+    if (c->d_osc) {
+        SDRHIP_CHECK_HIP(hipFree(c->d_osc));
+        c->d_osc = nullptr;
+    }
+    c->h_osc.assign(osc_iq, osc_iq + 2 * (size_t)period);
+    c->tuner_period = period;
+    c->tuner_pskip_ok = no_overflow;
+    return SDRHIP_OK;
+}
+
+int sdrhip_fm_chain_tuner_period(const sdrhip_fm_chain* c) { return c ? c->tuner_period : SDRHIP_ERR_ARG; }
 
 int sdrhip_fm_chain_set_demod_fusion(sdrhip_fm_chain* c, int enable)
 {

@@ -270,9 +270,15 @@ void launch_fm_tail_fused(hipStream_t s, const float* d_d, int64_t kd0, int64_t 
 // from the size of the run, < 0 = the largest).  fits (given fm_tail_shape_ok): /8 decimator with 128 padded taps in the AVX
 // order and exactly pre-scaled taps, seam block of at least 192, 16-byte aligned d_in, s0 a multiple of 8
 bool fm_chain_small_fits(int dD, int dP, ComplexOrder order, bool scaled_taps, int64_t seam, const void* d_in, int64_t s0);
+// d_osc != nullptr: the tuned kernel -- the oscillator (`period` (re, im) pairs, indexed by the absolute stream index) is mixed into
+// the converted samples in the tile loader, as kernels_tuner.hip does; d_dtaps is then the PLAIN prepared taps (the mix rounds on the
+// fully converted sample, so the 1/128 cannot move into the taps: pass scaled_taps = true to the predicate), and last_tap_zero may
+// only be set when no mixed sample can overflow
 void launch_fm_chain_small(hipStream_t s, const uint8_t* d_in, int64_t s0, int64_t n_in, float* d_audio, int64_t q0, int64_t q1,
-                           const float* d_dscaled, bool last_tap_zero, const FmTailTables& t, int tile_outputs);
-long long fm_chain_small_launch_count();   // diagnostics: launches of the one-kernel chain so far
+                           const float* d_dtaps, bool last_tap_zero, const FmTailTables& t, int tile_outputs,
+                           const float* d_osc = nullptr, int period = 0);
+long long fm_chain_small_launch_count();   // diagnostics: launches of the one-kernel chain so far (tuned ones included)
+long long fm_chain_small_tuned_launch_count();   // ... and those of the tuned kernel alone
 // abi_device.cpp: the short-seamed-launch scale v (sdrhip_set_small_launch_outputs)
 int small_launch_outputs();
 
@@ -301,6 +307,8 @@ bool launch_decimate_c_orders_fast(hipStream_t s, const Geom& g, ComplexOrder or
 // Cross outputs in the tile kernel for short launches, else by a fix-up launch over seam_span(g).  false = not this shape, nothing launched.
 bool launch_tuner_fused(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in,
                         bool in_is_u8, float* d_out, const float* d_osc, int period);
+// the conditions launch_tuner_fused checks, for callers that plan before they launch (chain.cpp); only the alignment of d_out counts
+bool tuner_fused_fits(const Geom& g, int P, bool has_cross_taps, const void* d_in, bool in_is_u8, const void* d_out, int period);
 // two-pass route, first pass: d_out[i] = mixed sample i of d_in (cfloat or u8 IQ), i < n < 2^31; ph0 = phase of sample 0
 void launch_tuner_mix(hipStream_t s, const void* d_in, bool in_is_u8, float* d_out, int64_t n, const float* d_osc, int period, int ph0);
 long long tuner_fused_launch_count();   // diagnostics: launches of the fused tile kernel

@@ -29,6 +29,7 @@
 #include "decimate_tile.hpp"
 #include "demod.hpp"
 #include "kernels.hpp"
+#include "tuner_mix.hpp"
 
 namespace sdrhip {
 
@@ -183,12 +184,17 @@ __device__ __forceinline__ float2 seq_one(const float2* __restrict__ tile, int i
 
 // dtaps: the decimator's 128 plain taps pre-scaled by 1/128 (FirDesc::d_scaled); groups: 3 rows of row_stride floats;
 // rplain: the resampler's plain taps; fplain: the audio filter's 128 plain taps (coeffs ++ reverse coeffs: its first 64 are the half-taps)
-template <int PSKIP>
+// TUNED: `P.map (VG.zipWith (*) osc)` in front of the decimator.  The loader stores tuner_mul(tuner_u8(re, im), osc[n mod period]),
+// n = the sample's absolute stream index, exactly as k_tuner_c4's does (tuner_mix.hpp), so LDS holds the SCALED mixed samples and
+// dtaps is the decimator's PLAIN prepared taps, for the One walk and for the sequential Cross outputs alike: with a mix between
+// the conversion and the taps the 1/128 cannot move into the taps (((u - 128) / 128) * o and (u - 128) * o round differently once
+// an entry is subnormal).  ph_launch = the phase of tile 0's first sample, (80 (q0 / 3) - 8) mod period: the one 64-bit modulo,
+// done by the host; from there 32-bit arithmetic (every factor is below 2^16).  Phases 1-4 are the untuned kernel's.
+template <int PSKIP, bool TUNED>
 __global__ void __launch_bounds__(SM_NT, 2) k_fm_chain_small(const uint8_t* __restrict__ in, float* __restrict__ audio,
                                                              const float* __restrict__ dtaps, const float* __restrict__ groups,
                                                              const float* __restrict__ rplain, const float* __restrict__ fplain,
-                                                             SmallParams p
-)
+                                                             SmallParams p, const float2* __restrict__ osc, int period, int ph_launch)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2* lds = reinterpret_cast<float2*>(smem_raw);
@@ -252,7 +258,17 @@ __global__ void __launch_bounds__(SM_NT, 2) k_fm_chain_small(const uint8_t* __re
         }
         if (tid < SM_LF) t_f = fplain[tid];
         else if (tid < SM_LF + 128) t_f = dtaps[tid - SM_LF];
-        st.store(lds);
+        if constexpr (TUNED) {
+            // tile b starts 80 (A / 3) samples after tile b - 1; a thread's first vector 8 tid samples into the tile.  Samples
+            // outside [s0, s0 + n_in) were read as u8 128 above: their mixed value (a zero of either sign) feeds no output of
+            // this launch either
+            const uint32_t n = (uint32_t)period;
+            const uint32_t ts = (uint32_t)(80 * (A / 3)) % n;
+            const uint32_t ph = ((uint32_t)ph_launch + (((uint32_t)blockIdx.x % n) * ts) % n + (uint32_t)(tid * 8) % n) % n;
+            tuner_store<SmT, true, SM_NT>(st.r, lds, osc, n, ph);
+        } else {
+            st.store(lds);
+        }
         if (tid < 3 * SM_NL) { gtab[tid] = t_g; rpl[tid] = t_r; }
         if (tid < SM_LF) fpl[tid] = t_f;
         else if (tid < SM_LF + 128) dtl[tid - SM_LF] = t_f;
@@ -461,11 +477,12 @@ __global__ void __launch_bounds__(SM_NT, 2) k_fm_chain_small(const uint8_t* __re
 }
 
 
-std::atomic<long long> g_small_launches{0};
+std::atomic<long long> g_small_launches{0}, g_small_tuned_launches{0};
 
 }  // namespace
 
 long long fm_chain_small_launch_count() { return g_small_launches.load(); }
+long long fm_chain_small_tuned_launch_count() { return g_small_tuned_launches.load(); }
 
 int fm_chain_small_tile_outputs(int64_t n_out)
 {
@@ -489,7 +506,7 @@ bool fm_chain_small_fits(int dD, int dP, ComplexOrder order, bool scaled_taps, i
 }
 
 void launch_fm_chain_small(hipStream_t s, const uint8_t* d_in, int64_t s0, int64_t n_in, float* d_audio, int64_t q0, int64_t q1,
-                           const float* d_dscaled, bool last_tap_zero, const FmTailTables& t, int tile_outputs)
+                           const float* d_dtaps, bool last_tap_zero, const FmTailTables& t, int tile_outputs, const float* d_osc, int period)
 {
     // tile_outputs < 0: the largest tile -- for input that is read over PCIe (the host-block operators' in-place pushes): a tile's
     // ~4000-sample overlap is READ once per tile, and on the link that traffic, not the number of workgroups, is what a push costs
@@ -503,7 +520,14 @@ void launch_fm_chain_small(hipStream_t s, const uint8_t* d_in, int64_t s0, int64
     p.row_stride = t.row_stride; p.ntaps = t.ntaps; p.rLp = t.rLp; p.gain = t.gain; p.seam = t.seam;
     const int64_t qa0 = (q0 / 3) * 3;
     const int64_t tiles = (q1 - qa0 + A - 1) / A;
-    static std::atomic<bool> attr_set[2][64];
+    static_assert(sizeof(Stage<SmT, true, SM_NT>::r) == sizeof(uint4[SM_PER]) && Stage<SmT, true, SM_NT>::NV == SM_NV, "tuner_store walks the loader's vectors");
+    // tuned: the phase of tile 0's first sample, 80 (q0 / 3) - 8 (-8 at the stream's start: d[-1], which the kernel zeroes)
+    int ph_launch = 0;
+    if (d_osc != nullptr) {
+        const int64_t first = 80 * (q0 / 3) - 8;
+        ph_launch = (int)(((first % period) + period) % period);
+    }
+    static std::atomic<bool> attr_set[4][64];
     int dev = 0;
     (void)hipGetDevice(&dev);
     auto launch = [&](auto kern, int which) {
@@ -511,10 +535,15 @@ void launch_fm_chain_small(hipStream_t s, const uint8_t* d_in, int64_t s0, int64
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SmT::LDS_BYTES);
             if (dev >= 0 && dev < 64) attr_set[which][dev] = true;
         }
-        hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(SM_NT), SmT::LDS_BYTES, s, d_in, d_audio, d_dscaled, t.d_groups, t.d_rplain, t.d_fplain, p);
+        hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(SM_NT), SmT::LDS_BYTES, s, d_in, d_audio, d_dtaps, t.d_groups, t.d_rplain, t.d_fplain, p,
+                           reinterpret_cast<const float2*>(d_osc), period, ph_launch);
     };
-    if (last_tap_zero) launch(k_fm_chain_small<1>, 1);
-    else launch(k_fm_chain_small<0>, 0);
+    if (d_osc != nullptr) {
+        if (last_tap_zero) launch(k_fm_chain_small<1, true>, 3);
+        else launch(k_fm_chain_small<0, true>, 2);
+        g_small_tuned_launches++;
+    } else if (last_tap_zero) launch(k_fm_chain_small<1, false>, 1);
+    else launch(k_fm_chain_small<0, false>, 0);
     g_small_launches++;
 }
 

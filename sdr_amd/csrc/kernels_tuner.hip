@@ -25,6 +25,7 @@
 // Two-pass route (every other order / factor, and the A/B partner): k_tuner_mix writes m to a scratch buffer, the stock
 // decimator runs on it (tuner.cpp).
 #include "decimate_tile.hpp"
+#include "tuner_mix.hpp"
 
 namespace sdrhip {
 
@@ -32,60 +33,6 @@ static std::atomic<long long> g_tuner_fused_launches{0};
 long long tuner_fused_launch_count() { return g_tuner_fused_launches.load(); }
 
 namespace {
-
-__device__ __forceinline__ float2 tuner_mul(const float2 x, const float2 o)
-{
-    return make_float2(x.x * o.x - x.y * o.y, x.x * o.y + x.y * o.x);
-}
-// convert.c: (u - 128) / 128, both steps exact in f32
-__device__ __forceinline__ float2 tuner_u8(uint32_t re, uint32_t im)
-{
-    return make_float2(((float)re - 128.0f) * (1.0f / 128.0f), ((float)im - 128.0f) * (1.0f / 128.0f));
-}
-__device__ __forceinline__ uint32_t wrap_inc(uint32_t p, uint32_t n) { return p + 1 == n ? 0u : p + 1; }
-
-// The raw vectors of Stage::load -> mixed samples in the padded LDS layout.  ph = phase of the thread's first sample.
-template <class T, bool U8, int NT>
-__device__ __forceinline__ void tuner_store(const uint4 (&r)[Stage<T, U8, NT>::PER], float2* __restrict__ lds,
-                                            const float2* __restrict__ osc, uint32_t n, uint32_t ph)
-{
-    using St = Stage<T, U8, NT>;
-    constexpr int SPV = St::SPV, NV = St::NV, PER = St::PER;
-    const uint32_t step = (uint32_t)(NT * SPV) % n;       // between a thread's consecutive vectors
-    // every oscillator load of the thread in flight before the first use (they hit L2; the raw loads are already out)
-    float2 o[PER][SPV];
-#pragma unroll
-    for (int i = 0; i < PER; i++) {
-        uint32_t p = ph;
-#pragma unroll
-        for (int k = 0; k < SPV; k++) {
-            o[i][k] = osc[p];
-            p = wrap_inc(p, n);
-        }
-        ph += step;
-        if (ph >= n) ph -= n;
-    }
-#pragma unroll
-    for (int i = 0; i < PER; i++) {
-        const int v = threadIdx.x + i * NT;
-        const int s = v * SPV;
-        if (v >= NV) continue;
-        if constexpr (!U8) {
-            const float2 m0 = tuner_mul(make_float2(__uint_as_float(r[i].x), __uint_as_float(r[i].y)), o[i][0]);
-            const float2 m1 = tuner_mul(make_float2(__uint_as_float(r[i].z), __uint_as_float(r[i].w)), o[i][1]);
-            *reinterpret_cast<float4*>(&lds[T::lds_idx(s)]) = make_float4(m0.x, m0.y, m1.x, m1.y);
-        } else {
-            const uint32_t w[4] = {r[i].x, r[i].y, r[i].z, r[i].w};
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const float2 m0 = tuner_mul(tuner_u8(w[k] & 0xff, (w[k] >> 8) & 0xff), o[i][2 * k]);
-                const float2 m1 = tuner_mul(tuner_u8((w[k] >> 16) & 0xff, w[k] >> 24), o[i][2 * k + 1]);
-                const int ss = s + 2 * k;
-                if (ss < T::SPAN + 1) *reinterpret_cast<float4*>(&lds[T::lds_idx(ss)]) = make_float4(m0.x, m0.y, m1.x, m1.y);
-            }
-        }
-    }
-}
 
 // One tile: decimate_c4_tile's general body (ragged-end loader, in-tile Cross outputs) around the mixing loader.
 template <int D, int P, int R, int NT, bool U8, int TC, bool GUARD>
@@ -247,18 +194,23 @@ void launch_tuner_c4(hipStream_t s, const Geom& g, const float* taps, const void
 
 }  // namespace
 
-bool launch_tuner_fused(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in,
-                        bool in_is_u8, float* d_out, const float* d_osc, int period)
+bool tuner_fused_fits(const Geom& g, int P, bool has_cross_taps, const void* d_in, bool in_is_u8, const void* d_out, int period)
 {
     if (g.I != 1 || g.count <= 0 || g.seamBI < 0 || g.k_begin < 0 || period < 1) return false;
     // the shapes decimate_tile.hpp serves up to 128 prepared taps: decimation 4 / 8 / 16, a multiple of 4 taps (mkDecimatorC pads to that)
     if (!((g.D == 8 || g.D == 4 || g.D == 16) && P >= 8 && P <= 128 && P % 4 == 0 && g.Lp == P && P > g.D)) return false;
-    if (g.seamBI != 0 && d_cross_taps == nullptr) return false;
+    if (g.seamBI != 0 && !has_cross_taps) return false;
     // vector loads need 16-byte aligned tile starts (tiles begin at multiples of 8 samples from x0)
     const int64_t x0 = g.k_begin * g.D - g.in_base;
     const uintptr_t base = reinterpret_cast<uintptr_t>(d_in);
     if (((base + (in_is_u8 ? 2 : 8) * (uintptr_t)x0) & 15) != 0) return false;
-    if ((reinterpret_cast<uintptr_t>(d_out) & 7) != 0) return false;
+    return (reinterpret_cast<uintptr_t>(d_out) & 7) == 0;
+}
+
+bool launch_tuner_fused(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in,
+                        bool in_is_u8, float* d_out, const float* d_osc, int period)
+{
+    if (!tuner_fused_fits(g, P, d_cross_taps != nullptr, d_in, in_is_u8, d_out, period)) return false;
     // launch-bound sizes compute their Cross outputs inside the tile kernel, as the decimator does (abi_device.cpp: the 5v row)
     const bool inl = g.seamBI > 0 && g.count <= 5 * (int64_t)small_launch_outputs();
     bool inlined = false;

@@ -145,6 +145,10 @@ lib.sdrhip_fm_chain_join.argtypes = [_vp, _vp]
 lib.sdrhip_fm_chain_set_fused_tail.argtypes = [_vp, C.c_int]
 lib.sdrhip_fm_chain_set_small_chain.argtypes = [_vp, C.c_int, _i64, C.c_int]
 lib.sdrhip_debug_small_chain_launches.restype = C.c_longlong
+lib.sdrhip_fm_chain_set_tuner.argtypes = [_vp, _f32p, C.c_int]
+lib.sdrhip_fm_chain_tuner_period.argtypes = [_vp]
+lib.sdrhip_debug_small_chain_tuned_launches.argtypes = []
+lib.sdrhip_debug_small_chain_tuned_launches.restype = C.c_longlong
 lib.sdrhip_debug_resample_cycle_launches.restype = C.c_longlong
 lib.sdrhip_debug_decimate_real16_launches.restype = C.c_longlong
 lib.sdrhip_debug_systolic_launches.restype = C.c_longlong
@@ -527,6 +531,11 @@ def tuner_shift_table(num, den):
     return out
 
 
+def small_chain_tuned_launches():
+    """Launches of the tuned one-kernel chain so far (sdrhip_debug_small_chain_tuned_launches)."""
+    return int(lib.sdrhip_debug_small_chain_tuned_launches())
+
+
 def tuner_fused_launches():
     return int(lib.sdrhip_debug_tuner_fused_launches())
 
@@ -612,6 +621,22 @@ class FmChain(_Handle):
     def set_small_chain(self, mode=2, max_outputs=0, tile_outputs=0):
         """0 = never, 1 = always, 2 = auto: the whole chain as one kernel for launch-bound runs (kernels_small.hip)."""
         check(lib.sdrhip_fm_chain_set_small_chain(self.h, int(mode), int(max_outputs), int(tile_outputs)), "sdrhip_fm_chain_set_small_chain")
+
+    def set_tuner(self, osc_iq=None):
+        """`P.map (VG.zipWith (*) osc)` in front of the chain's decimator (sdrhip_fm_chain_set_tuner): osc_iq = interleaved float32
+        (re, im) pairs, indexed by the absolute stream position mod their count (tuner_shift_table builds the usual tables);
+        None removes the tuner.  No run of the chain may be in flight; graphs and workspaces made before are made again."""
+        if osc_iq is None:
+            check(lib.sdrhip_fm_chain_set_tuner(self.h, None, 0), "sdrhip_fm_chain_set_tuner")
+            return
+        o = _f32(osc_iq).reshape(-1)
+        if o.size % 2:
+            raise SdrHipError("the oscillator table is interleaved (re, im) pairs")
+        check(lib.sdrhip_fm_chain_set_tuner(self.h, _fp(o), o.size // 2), "sdrhip_fm_chain_set_tuner")
+
+    def tuner_period(self):
+        """Entries of the tuner's table, 0 = no tuner."""
+        return check(lib.sdrhip_fm_chain_tuner_period(self.h), "sdrhip_fm_chain_tuner_period")
 
     def set_demod_fusion(self, on=True):
         """fmDemod inside the resampler's tile loader on large batches (sdrhip_fm_chain_set_demod_fusion)."""
