@@ -63,6 +63,7 @@ data SdrFilter
 data SdrPipe
 data SdrTuner
 data SdrChain
+data SdrBank
 data SdrStream
 data SdrSpectrum
 
@@ -133,6 +134,19 @@ foreign import ccall safe "sdrhip_debug_tuner_fused_launches" c_tuner_fused_laun
 foreign import ccall safe "sdrhip_pipe_tuner"        c_pipe_tuner        :: Ptr (Ptr SdrPipe) -> Ptr SdrTuner -> CInt -> IO CInt
 -- the FM chain with a tuner: the same oscillator in front of the chain's own decimator (a null table with period 0 removes it)
 foreign import ccall safe "sdrhip_fm_chain_set_tuner" c_fm_chain_set_tuner :: Ptr SdrChain -> Ptr CFloat -> CInt -> IO CInt
+-- the receiver bank (include/sdr_hip.h, sdrhip_fm_bank_*): K tuned chains of the same arguments over ONE input, one table per station;
+-- station j's outputs [q0, q1) go to audio + j * stride.  Device-pointer runs; route 0 = auto, 1 = one banked launch, 2 = station by station
+foreign import ccall safe "sdrhip_fm_bank_create"   c_fm_bank_create   :: Ptr (Ptr SdrBank) -> CInt -> CInt -> Ptr CFloat -> CInt -> CInt -> CInt -> Ptr CFloat -> CInt -> Ptr CFloat -> CInt -> CFloat -> Int64 -> CInt -> Ptr (Ptr CFloat) -> Ptr CInt -> IO CInt
+foreign import ccall safe "sdrhip_fm_bank_destroy"  c_fm_bank_destroy  :: Ptr SdrBank -> IO ()
+foreign import ccall safe "sdrhip_fm_bank_stations" c_fm_bank_stations :: Ptr SdrBank -> IO CInt
+foreign import ccall safe "sdrhip_fm_bank_period"   c_fm_bank_period   :: Ptr SdrBank -> CInt -> IO CInt
+foreign import ccall safe "sdrhip_fm_bank_plan"     c_fm_bank_plan     :: Ptr SdrBank -> Int64 -> Int64 -> Int64 -> Ptr Int64 -> Ptr Int64 -> Ptr Int64 -> IO CInt
+foreign import ccall safe "sdrhip_fm_bank_ready"    c_fm_bank_ready    :: Ptr SdrBank -> Int64 -> IO Int64
+foreign import ccall safe "sdrhip_fm_bank_max_halo" c_fm_bank_max_halo :: Ptr SdrBank -> IO Int64
+foreign import ccall safe "sdrhip_fm_bank_workspace_bytes" c_fm_bank_workspace_bytes :: Ptr SdrBank -> Int64 -> IO CSize
+foreign import ccall safe "sdrhip_fm_bank_run"      c_fm_bank_run      :: Ptr SdrBank -> Ptr () -> Ptr CUChar -> Int64 -> Int64 -> Ptr CFloat -> Int64 -> Int64 -> Int64 -> Ptr () -> CSize -> IO CInt
+foreign import ccall safe "sdrhip_fm_bank_set_route" c_fm_bank_set_route :: Ptr SdrBank -> CInt -> Int64 -> CInt -> IO CInt
+foreign import ccall safe "sdrhip_debug_fm_bank_launches" c_fm_bank_launches :: IO CLLong
 -- the spectrum operator (include/sdr_hip.h, sdrhip_spectrum_*): interleavedIQUnsigned256ToFloat -> halfBandUp x window -> fftw ->
 -- magnitude x scale, rows of Float
 foreign import ccall safe "sdrhip_spectrum_create"     c_spectrum_create     :: Ptr (Ptr SdrSpectrum) -> CInt -> CInt -> CInt -> Ptr CDouble -> CInt -> CDouble -> IO CInt

@@ -455,6 +455,60 @@ int sdrhip_fm_chain_set_tuner(sdrhip_fm_chain *c, const float *osc_iq, int perio
 int sdrhip_fm_chain_tuner_period(const sdrhip_fm_chain *c);      /* 0 = none */
 /* launches of the tuned one-kernel chain so far, process-wide (they count in sdrhip_debug_small_chain_launches too) */
 long long sdrhip_debug_small_chain_tuned_launches(void);
+
+/* The receiver bank: every station of ONE capture in one launch.  An RTL-SDR capture of 1.28 .. 2.4 Msample/s spans six to twelve
+ * broadcast channels; receiving them all with tuned chains is K chains and K runs per push, and the pushes of a live receiver (one
+ * to sixteen 8192-sample blocks) are launch-bound: K launch latencies on a chip that is nearly idle during each.  A bank is K tuned
+ * chains of the SAME arguments -- chain arguments exactly as sdrhip_fm_chain_create -- with one oscillator table per station:
+ * osc_iq[j] = periods[j] (re, im) float32 pairs, copied; 1 .. SDRHIP_FM_BANK_MAX_STATIONS stations; every period 1 .. 65536, every
+ * entry finite.  A station on the centre frequency takes the table {1, 0} and is then DEFINED as a chain tuned with that table:
+ * there is no untuned station form (the untuned chain folds 1/128 into its taps, a tuned one cannot).
+ * Definition: station j's row equals, bit for bit, what a sdrhip_fm_chain created with the same arguments and
+ * sdrhip_fm_chain_set_tuner(osc_iq[j], periods[j]) writes for the same (s0, n_in, q0, q1), on every route of the bank and for any
+ * tile_outputs.
+ * SDRHIP_ERR_ARG before any device work, nothing written: a null handle, 0 or more than 32 stations, a null table pointer, a period
+ * outside 1 .. 65536, a non-finite table entry, whatever sdrhip_fm_chain_create refuses, and (sdrhip_fm_bank_run)
+ * audio_stride < q1 - q0, a receptive field outside d_in_iq, a workspace too small for the station-by-station route.
+ * Like a chain, a bank is created, planned and sized on a host without a GPU; device copies are made by the first run.  More than
+ * 32 stations: two banks. */
+#define SDRHIP_FM_BANK_MAX_STATIONS 32
+typedef struct sdrhip_fm_bank sdrhip_fm_bank;
+int sdrhip_fm_bank_create(sdrhip_fm_bank **b, int order, int decim_factor, const float *decim_taps, int n_decim_taps,
+                          int interpolation, int decimation, const float *resamp_taps, int n_resamp_taps,
+                          const float *audio_half_taps, int n_audio_half, float gain, int64_t block,
+                          int stations, const float *const *osc_iq, const int *periods);
+void sdrhip_fm_bank_destroy(sdrhip_fm_bank *b);
+int sdrhip_fm_bank_stations(const sdrhip_fm_bank *b);
+int sdrhip_fm_bank_period(const sdrhip_fm_bank *b, int station);
+/* what the tuned chain of the same arguments reports (plan / ready / max_halo do not depend on a table; workspace_bytes is the
+ * tuned chain's figure: the station-by-station route runs the stations one after the other on ONE workspace) */
+int sdrhip_fm_bank_plan(const sdrhip_fm_bank *b, int64_t s0, int64_t s1, int64_t total_in, int64_t *q0, int64_t *q1, int64_t *halo);
+int64_t sdrhip_fm_bank_ready(const sdrhip_fm_bank *b, int64_t n_samples);
+int64_t sdrhip_fm_bank_max_halo(const sdrhip_fm_bank *b);
+size_t sdrhip_fm_bank_workspace_bytes(const sdrhip_fm_bank *b, int64_t n_in);
+/* d_in_iq[0] is stream sample s0, n_in samples are readable (as sdrhip_fm_chain_run).  Station j's audio outputs [q0, q1) go to
+ * d_audio + j * audio_stride (floats), audio_stride >= q1 - q0; floats of d_audio outside the K rows' [0, q1 - q0) are not
+ * touched.  Asynchronous on `stream`.  After the first run of a shape a run makes no allocation, no host synchronisation and no
+ * host-to-device copy: what changes from launch to launch (each station's oscillator phase at the launch's first sample, the row
+ * stride) travels in the kernel's arguments.  The banked route sends nothing through the workspace and accepts a null one; the
+ * station-by-station route needs sdrhip_fm_bank_workspace_bytes(n_in) bytes.  No overlap mode, no hipGraph helper and no
+ * host-block stream front end for a bank. */
+int sdrhip_fm_bank_run(sdrhip_fm_bank *b, void *stream, const uint8_t *d_in_iq, int64_t s0, int64_t n_in,
+                       float *d_audio, int64_t audio_stride, int64_t q0, int64_t q1, void *d_workspace, size_t workspace_bytes);
+/* Routes.  1 = the banked launch: ONE launch of the tuned one-kernel chain (sdrhip_fm_chain_set_small_chain) with a station axis in
+ * its grid; it fits exactly where that kernel serves a tuned chain -- decimation 8 with 128 padded taps, AVX order, the FM
+ * receiver's tail, block 0 or 192 .. 2^26, 16-byte aligned input, s0 a multiple of 8 -- and the grid exists (at most 65535 tiles);
+ * forced outside these conditions, sdrhip_fm_bank_run returns SDRHIP_ERR_ARG.  2 = station by station: sdrhip_fm_chain_run of the
+ * bank's own tuned chains, one after the other on the caller's stream and workspace.  0 = auto (default), a rule in two
+ * dimensions: the banked launch where it fits while a station's run is short, q1 - q0 <= 39322 (a run of 2^20 samples; fixed), AND
+ * stations * (q1 - q0) <= max_outputs (0 = the built-in bound, 32 * 39322); else station by station -- every size and alignment
+ * the banked launch refuses, and every longer run, whatever the number of stations: those are bound by arithmetic, not by launches,
+ * and from 159 * 1728 outputs on a station's own chain leaves the one-kernel route.  Both bounds are the edges of what was measured
+ * against K runs of K tuned chains (1 .. 32 stations x runs of up to 2^20 samples), not crossovers.  tile_outputs as
+ * sdrhip_fm_chain_set_small_chain (0 = chosen from the total work, stations * outputs).  Same bits on every route. */
+int sdrhip_fm_bank_set_route(sdrhip_fm_bank *b, int route, int64_t max_outputs, int tile_outputs);
+/* banked launches so far, process-wide (they do NOT count in sdrhip_debug_small_chain_launches: those are the chains') */
+long long sdrhip_debug_fm_bank_launches(void);
 /* launches of the thread-per-polyphase-cycle resampler (real I/D with an odd decimation: 2/3, 5/7, ...; any filter length),
  * process-wide (tests assert that this kernel, not the lane-split one, served those ratios) */
 long long sdrhip_debug_resample_cycle_launches(void);

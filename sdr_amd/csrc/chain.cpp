@@ -407,43 +407,70 @@ static int launched(int rc)
     return SDRHIP_OK;
 }
 
+// does the one-kernel chain (kernels_small.hip) serve a run of this chain on this input?  (the tuned one reads the plain taps: it
+// needs no exactly pre-scaled ones)
+static bool chain_small_fits(const sdrhip_fm_chain* c, const uint8_t* d_in_iq, int64_t s0)
+{
+    const FirDesc& dec = c->decim;
+    return c->fm_tail && fm_chain_small_fits(dec.factor, dec.Lp, dec.corder, c->tuner_period != 0 || !dec.h_scaled.empty(), c->block, d_in_iq, s0);
+}
+
+// does d_in hold the receptive field of the run's outputs?  (it depends on no table: the receiver bank asks once for all stations)
+static int input_holds(const char* who, const RunPlan& r, int64_t s0, int64_t n_in, int64_t q0, int64_t q1)
+{
+    if (r.n_lo >= s0 && r.n_hi <= s0 + n_in) return SDRHIP_OK;
+    set_error("%s: outputs [%lld,%lld) need samples [%lld,%lld) but d_in holds [%lld,%lld)", who, (long long)q0, (long long)q1,
+              (long long)r.n_lo, (long long)r.n_hi, (long long)s0, (long long)(s0 + n_in));
+    return SDRHIP_ERR_ARG;
+}
+
+// The route of one run of at least one output, and EVERY refusal of such a run: chain_run_on launches only after this, and the
+// receiver bank asks it for all its stations before the first one runs, so that a refused bank run has written no row.  A new
+// refusal belongs here.  who: the public call the message names.
+struct RunRoute {
+    RunPlan r;
+    bool small = false, tail = false;     // the first of the two fused kernels that is wanted (mode and size) and fits, else the stage kernels
+};
+static int chain_route(const sdrhip_fm_chain* c, const char* who, const uint8_t* d_in_iq, int64_t s0, int64_t n_in, const float* d_audio,
+                       int64_t q0, int64_t q1, const void* d_workspace, size_t workspace_bytes, RunRoute* out)
+{
+    SDRHIP_REQUIRE(d_in_iq && d_audio && d_workspace, who);
+    RunRoute& t = *out;
+    t.r = plan_run(c, s0, q0, q1, d_in_iq, d_workspace);
+    int rc;
+    if ((rc = input_holds(who, t.r, s0, n_in, q0, q1)) != SDRHIP_OK) return rc;
+    t.small = c->mode_takes(c->small_chain, q1 - q0, c->small_chain_max) && chain_small_fits(c, d_in_iq, s0);
+    t.tail = !t.small && c->fm_tail && c->mode_takes(c->fused_tail, q1 - q0, kFusedTailAutoOutputs) && fm_tail_fused_fits(c->resamp.Lp, c->block);
+    if (!t.small && t.r.ws_need > workspace_bytes) {       // the one-kernel chain sends nothing through the workspace
+        set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, t.r.ws_need);
+        return SDRHIP_ERR_ARG;
+    }
+    if (c->tuner_period != 0 && !t.small && !t.r.tuner_tile && t.r.xb - t.r.xa >= (int64_t)0x7fffffff) {
+        set_error("%s: a tuned run that mixes into the workspace takes fewer than 2^31 samples", who);
+        return SDRHIP_ERR_ARG;
+    }
+    return SDRHIP_OK;
+}
+
 // input_over_link: d_in_iq is pinned HOST memory (the host-block operator's in-place pushes): the one-kernel chain takes its largest tile
 static int chain_run_on(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq, int64_t s0, int64_t n_in, float* d_audio,
                         int64_t q0, int64_t q1, void* d_workspace, size_t workspace_bytes, bool input_over_link)
 {
     SDRHIP_REQUIRE(q1 >= q0 && q0 >= 0 && s0 >= 0 && n_in >= 0, "sdrhip_fm_chain_run");
     if (q1 == q0) return SDRHIP_OK;
-    SDRHIP_REQUIRE(d_in_iq && d_audio && d_workspace, "sdrhip_fm_chain_run");
     hipStream_t s = (hipStream_t)stream;
 
-    const RunPlan r = plan_run(c, s0, q0, q1, d_in_iq, d_workspace);
-    if (r.n_lo < s0 || r.n_hi > s0 + n_in) {
-        set_error("sdrhip_fm_chain_run: outputs [%lld,%lld) need samples [%lld,%lld) but d_in holds [%lld,%lld)",
-                  (long long)q0, (long long)q1, (long long)r.n_lo, (long long)r.n_hi, (long long)s0, (long long)(s0 + n_in));
-        return SDRHIP_ERR_ARG;
-    }
-    // the route: the first of the two fused kernels that is wanted (mode and size) and fits, else the stage kernels
+    RunRoute route;
+    int rc;
+    if ((rc = chain_route(c, "sdrhip_fm_chain_run", d_in_iq, s0, n_in, d_audio, q0, q1, d_workspace, workspace_bytes, &route)) != SDRHIP_OK) return rc;
+    const RunPlan& r = route.r;
+    const bool small = route.small, tail = route.tail;
     const FirDesc& dec = c->decim;
     const bool tuned = c->tuner_period != 0;
-    // (the tuned one-kernel chain reads the plain taps: it needs no exactly pre-scaled ones)
-    const bool small = c->fm_tail && c->mode_takes(c->small_chain, q1 - q0, c->small_chain_max) &&
-                       fm_chain_small_fits(dec.factor, dec.Lp, dec.corder, tuned || !dec.h_scaled.empty(), c->block, d_in_iq, s0);
-    const bool tail = !small && c->fm_tail && c->mode_takes(c->fused_tail, q1 - q0, kFusedTailAutoOutputs) &&
-                      fm_tail_fused_fits(c->resamp.Lp, c->block);
-    if (!small && r.ws_need > workspace_bytes) {       // the one-kernel chain sends nothing through the workspace
-        set_error("sdrhip_fm_chain_run: workspace too small (%zu < %zu)", workspace_bytes, r.ws_need);
-        return SDRHIP_ERR_ARG;
-    }
-    int rc;
     if (small || tail)
         if ((rc = c->resamp.ensure_device()) != SDRHIP_OK || (rc = c->audio.ensure_device()) != SDRHIP_OK) return rc;
-    if (tuned) {
-        if (!small && !r.tuner_tile && r.xb - r.xa >= (int64_t)0x7fffffff) {
-            set_error("sdrhip_fm_chain_run: a tuned run that mixes into the workspace takes fewer than 2^31 samples");
-            return SDRHIP_ERR_ARG;
-        }
+    if (tuned)
         if ((rc = dec.ensure_device()) != SDRHIP_OK || (rc = c->ensure_osc()) != SDRHIP_OK) return rc;
-    }
     if (c->timing) c->runs++;
 
     if (small) {      // launch-bound run: the whole chain in ONE kernel
@@ -697,6 +724,171 @@ int sdrhip_fm_chain_read_timing(sdrhip_fm_chain* c, double* ms_sum, int* runs)
     c->spans.clear();
     c->ev_used = 0;
     c->runs = 0;
+    return SDRHIP_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// The receiver bank: every station of ONE capture.  K tuned chains of the same arguments, one oscillator table each, over one
+// input.  Station j's audio row is, bit for bit, what a chain created with these arguments and sdrhip_fm_chain_set_tuner(table j)
+// writes: the bank OWNS those K chains -- they answer plan / ready / max_halo / workspace_bytes and ARE the station-by-station
+// route -- and one device copy of all the tables for the banked route, ONE launch of the one-kernel chain with a station axis in
+// its grid (kernels_small.hip): K launch-bound runs for the launch latency of one.
+//   banked route      where the tuned one-kernel chain fits (fm_chain_small_fits with tuned taps, the tail's shape, a grid that
+//                     exists); auto takes it while outputs <= kBankAutoStationOutputs and stations * outputs <= max_outputs
+//   station by station  sdrhip_fm_chain_run per station on the caller's stream and the caller's ONE workspace (the runs are ordered
+//                     on the stream); every size and alignment the banked launch refuses, and large runs, which are bound by
+//                     arithmetic and take the tuner's tile kernel as a tuned chain does
+// ---------------------------------------------------------------------------
+static_assert(SDRHIP_FM_BANK_MAX_STATIONS == kFmBankMaxStations, "the header's limit is the kernel's");
+// auto is a rule in TWO dimensions: the banked launch while a station's run, q1 - q0, is at most kBankAutoStationOutputs AND
+// stations * (q1 - q0) is at most max_outputs (built-in: kBankAutoOutputs).  Both are the edges of what was measured
+// (tools/fm_bank_bench.py, profiles/fm_bank_bench.txt: 1 .. 32 stations x runs of 1 block, 16 blocks and 2^20 samples = 39322 outputs),
+// not crossovers: inside that rectangle the banked launch is ahead of K runs of K tuned chains at every point with K > 1, its
+// far corner included (32 x 39322 outputs, 201 against 443 us), and level at K = 1.  A longer run per station goes station by
+// station whatever K is: nothing there is measured, a station is bound by arithmetic there, and beyond the chain's own
+// kSmallChainAutoOutputs its chain leaves the one-kernel route for the stage kernels, which the banked launch cannot follow.
+// (The chain's 159 * 1728 as the total, where this started, would have sent 8 stations x 2^20 samples station by station at 1.9
+// times the time.)
+static const int64_t kBankAutoStationOutputs = 39322;
+static const int64_t kBankAutoOutputs = 32 * kBankAutoStationOutputs;
+static_assert(kBankAutoStationOutputs <= kSmallChainAutoOutputs, "auto banks no run that the station's own chain would give to the stage kernels");
+
+struct sdrhip_fm_bank {
+    std::vector<sdrhip_fm_chain*> ch;       // station j as a tuned chain
+    std::vector<float> h_tables;            // every table, back to back
+    int off[SDRHIP_FM_BANK_MAX_STATIONS] = {0};      // station j's first (re, im) pair in h_tables / d_tables
+    int period[SDRHIP_FM_BANK_MAX_STATIONS] = {0};
+    float* d_tables = nullptr;              // made by the first banked run
+    int route = 0;                          // 0 = auto, 1 = banked, 2 = station by station
+    int64_t max_outputs = kBankAutoOutputs;
+    int tile = 0;
+    // the zero tap the constructor padded may be skipped only when no station's mixed samples can overflow
+    bool pskip_ok() const
+    {
+        for (const sdrhip_fm_chain* c : ch)
+            if (!c->tuner_pskip_ok) return false;
+        return true;
+    }
+    ~sdrhip_fm_bank()
+    {
+        for (sdrhip_fm_chain* c : ch) delete c;
+        if (d_tables) (void)hipFree(d_tables);
+    }
+};
+
+extern "C" {
+
+int sdrhip_fm_bank_create(sdrhip_fm_bank** b, int order, int decim_factor, const float* decim_taps, int n_decim_taps, int interpolation,
+                          int decimation, const float* resamp_taps, int n_resamp_taps, const float* audio_half_taps, int n_audio_half,
+                          float gain, int64_t block, int stations, const float* const* osc_iq, const int* periods)
+{
+    SDRHIP_REQUIRE(b != nullptr, "sdrhip_fm_bank_create");
+    *b = nullptr;
+    SDRHIP_REQUIRE(stations >= 1 && stations <= SDRHIP_FM_BANK_MAX_STATIONS, "sdrhip_fm_bank_create: 1 .. 32 stations");
+    SDRHIP_REQUIRE(osc_iq != nullptr && periods != nullptr, "sdrhip_fm_bank_create");
+    for (int j = 0; j < stations; j++) {
+        SDRHIP_REQUIRE(osc_iq[j] != nullptr, "sdrhip_fm_bank_create: every station has a table (a station on the centre: {1, 0})");
+        SDRHIP_REQUIRE(periods[j] >= 1 && periods[j] <= 65536, "sdrhip_fm_bank_create: period 1 .. 65536");
+        for (size_t i = 0; i < 2 * (size_t)periods[j]; i++)
+            SDRHIP_REQUIRE(isfinite(osc_iq[j][i]), "sdrhip_fm_bank_create: non-finite table entry");
+    }
+    sdrhip_fm_bank* bk = new sdrhip_fm_bank();
+    size_t pairs = 0;
+    for (int j = 0; j < stations; j++) {
+        sdrhip_fm_chain* c = nullptr;
+        int rc = sdrhip_fm_chain_create(&c, order, decim_factor, decim_taps, n_decim_taps, interpolation, decimation, resamp_taps, n_resamp_taps,
+                                        audio_half_taps, n_audio_half, gain, block);
+        if (rc == SDRHIP_OK) {
+            bk->ch.push_back(c);
+            rc = sdrhip_fm_chain_set_tuner(c, osc_iq[j], periods[j]);
+        }
+        if (rc != SDRHIP_OK) { delete bk; return rc; }
+        bk->off[j] = (int)pairs;
+        bk->period[j] = periods[j];
+        bk->h_tables.insert(bk->h_tables.end(), osc_iq[j], osc_iq[j] + 2 * (size_t)periods[j]);
+        pairs += (size_t)periods[j];
+    }
+    *b = bk;
+    return SDRHIP_OK;
+}
+
+void sdrhip_fm_bank_destroy(sdrhip_fm_bank* b) { delete b; }
+
+int sdrhip_fm_bank_stations(const sdrhip_fm_bank* b) { return b ? (int)b->ch.size() : SDRHIP_ERR_ARG; }
+
+int sdrhip_fm_bank_period(const sdrhip_fm_bank* b, int station)
+{
+    SDRHIP_REQUIRE(b != nullptr && station >= 0 && station < (int)b->ch.size(), "sdrhip_fm_bank_period");
+    return b->period[station];
+}
+
+int sdrhip_fm_bank_plan(const sdrhip_fm_bank* b, int64_t s0, int64_t s1, int64_t total_in, int64_t* q0, int64_t* q1, int64_t* halo)
+{
+    SDRHIP_REQUIRE(b != nullptr, "sdrhip_fm_bank_plan");
+    return sdrhip_fm_chain_plan(b->ch[0], s0, s1, total_in, q0, q1, halo);
+}
+
+int64_t sdrhip_fm_bank_ready(const sdrhip_fm_bank* b, int64_t n_samples) { return b ? sdrhip_fm_chain_ready(b->ch[0], n_samples) : -1; }
+
+int64_t sdrhip_fm_bank_max_halo(const sdrhip_fm_bank* b) { return b ? sdrhip_fm_chain_max_halo(b->ch[0]) : -1; }
+
+size_t sdrhip_fm_bank_workspace_bytes(const sdrhip_fm_bank* b, int64_t n_in) { return b ? sdrhip_fm_chain_workspace_bytes(b->ch[0], n_in) : 0; }
+
+int sdrhip_fm_bank_set_route(sdrhip_fm_bank* b, int route, int64_t max_outputs, int tile_outputs)
+{
+    SDRHIP_REQUIRE(b != nullptr && route >= 0 && route <= 2 && max_outputs >= 0 && tile_outputs >= 0, "sdrhip_fm_bank_set_route");
+    b->route = route;
+    b->max_outputs = max_outputs > 0 ? max_outputs : kBankAutoOutputs;
+    b->tile = tile_outputs;
+    return SDRHIP_OK;
+}
+
+long long sdrhip_debug_fm_bank_launches(void) { return fm_chain_small_bank_launch_count(); }
+
+int sdrhip_fm_bank_run(sdrhip_fm_bank* b, void* stream, const uint8_t* d_in_iq, int64_t s0, int64_t n_in, float* d_audio, int64_t audio_stride,
+                       int64_t q0, int64_t q1, void* d_workspace, size_t workspace_bytes)
+{
+    SDRHIP_REQUIRE(b != nullptr, "sdrhip_fm_bank_run");
+    SDRHIP_REQUIRE(q1 >= q0 && q0 >= 0 && s0 >= 0 && n_in >= 0, "sdrhip_fm_bank_run");
+    SDRHIP_REQUIRE(audio_stride >= q1 - q0, "sdrhip_fm_bank_run: a station's row holds its outputs");
+    if (q1 == q0) return SDRHIP_OK;
+    SDRHIP_REQUIRE(d_in_iq && d_audio, "sdrhip_fm_bank_run");
+    hipStream_t s = (hipStream_t)stream;
+    const int K = (int)b->ch.size();
+    sdrhip_fm_chain* c0 = b->ch[0];         // ranges, taps and tail tables are the same for every station
+
+    // the receptive field of [q0, q1) does not depend on a table: checked once, before either route launches anything
+    int rc;
+    if ((rc = input_holds("sdrhip_fm_bank_run", plan_run(c0, s0, q0, q1, d_in_iq, d_workspace), s0, n_in, q0, q1)) != SDRHIP_OK) return rc;
+    const bool fits = chain_small_fits(c0, d_in_iq, s0) && fm_chain_small_bank_fits(q0, q1, K, b->tile);
+    if (b->route == 1 && !fits) {
+        set_error("sdrhip_fm_bank_run: the banked launch does not fit this run (decimator / tail shape, seam block, input alignment, "
+                  "s0 %% 8, or more than 65535 tiles)");
+        return SDRHIP_ERR_ARG;
+    }
+    const bool banked = fits && (b->route == 1 || (b->route == 0 && (int64_t)K * (q1 - q0) <= b->max_outputs && q1 - q0 <= kBankAutoStationOutputs));
+    if (banked) {
+        const FirDesc& dec = c0->decim;
+        if ((rc = dec.ensure_device()) != SDRHIP_OK || (rc = c0->resamp.ensure_device()) != SDRHIP_OK || (rc = c0->audio.ensure_device()) != SDRHIP_OK)
+            return rc;
+        if (b->d_tables == nullptr && (rc = upload_floats(&b->d_tables, b->h_tables)) != SDRHIP_OK) return rc;
+        launch_fm_chain_small_bank(s, d_in_iq, s0, n_in, d_audio, audio_stride, q0, q1, dec.d_plain, dec.last_tap_is_padding() && b->pskip_ok(),
+                                   c0->tail_tables(), b->tile, b->d_tables, K, b->off, b->period);
+        return launched(SDRHIP_OK);
+    }
+    // station by station.  What a station's run would refuse is found for ALL stations first (chain_route, the chain's own
+    // refusals), so that a refused bank run has written no row: whether a tuned run takes the tuner's tile kernel, and with it the
+    // workspace it needs, depends on its period
+    for (int j = 0; j < K; j++) {
+        RunRoute route;
+        if ((rc = chain_route(b->ch[j], "sdrhip_fm_bank_run", d_in_iq, s0, n_in, d_audio, q0, q1, d_workspace, workspace_bytes, &route)) != SDRHIP_OK)
+            return rc;
+    }
+    for (int j = 0; j < K; j++)
+        if ((rc = sdrhip_fm_chain_run(b->ch[j], stream, d_in_iq, s0, n_in, d_audio + (int64_t)j * audio_stride, q0, q1, d_workspace, workspace_bytes)) != SDRHIP_OK)
+            return rc;
     return SDRHIP_OK;
 }
 

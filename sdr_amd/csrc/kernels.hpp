@@ -279,6 +279,17 @@ void launch_fm_chain_small(hipStream_t s, const uint8_t* d_in, int64_t s0, int64
                            const float* d_osc = nullptr, int period = 0);
 long long fm_chain_small_launch_count();   // diagnostics: launches of the one-kernel chain so far (tuned ones included)
 long long fm_chain_small_tuned_launch_count();   // ... and those of the tuned kernel alone
+// The receiver bank (sdrhip_fm_bank_run): `stations` tuned chains over ONE input in one launch of that kernel with a station axis in
+// the grid.  d_tables holds every station's oscillator table, station j's `periods[j]` (re, im) pairs from pair offsets[j] on; its
+// audio outputs [q0, q1) go to d_audio + j * audio_stride.  d_dtaps: the PLAIN prepared taps; last_tap_zero only when no mixed sample
+// of ANY station can overflow.  tile_outputs: 0 = chosen from stations * outputs.  fits: fm_chain_small_fits (scaled_taps = true) and
+// fm_chain_small_bank_fits, which says whether the grid exists (at most 65535 tiles).  Launches of it count on their own.
+constexpr int kFmBankMaxStations = 32;
+bool fm_chain_small_bank_fits(int64_t q0, int64_t q1, int stations, int tile_outputs);
+void launch_fm_chain_small_bank(hipStream_t s, const uint8_t* d_in, int64_t s0, int64_t n_in, float* d_audio, int64_t audio_stride,
+                                int64_t q0, int64_t q1, const float* d_dtaps, bool last_tap_zero, const FmTailTables& t, int tile_outputs,
+                                const float* d_tables, int stations, const int* offsets, const int* periods);
+long long fm_chain_small_bank_launch_count();
 // abi_device.cpp: the short-seamed-launch scale v (sdrhip_set_small_launch_outputs)
 int small_launch_outputs();
 

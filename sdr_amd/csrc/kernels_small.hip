@@ -31,6 +31,8 @@
 #include "kernels.hpp"
 #include "tuner_mix.hpp"
 
+#include <type_traits>
+
 namespace sdrhip {
 
 namespace {
@@ -190,12 +192,38 @@ __device__ __forceinline__ float2 seq_one(const float2* __restrict__ tile, int i
 // the conversion and the taps the 1/128 cannot move into the taps (((u - 128) / 128) * o and (u - 128) * o round differently once
 // an entry is subnormal).  ph_launch = the phase of tile 0's first sample, (80 (q0 / 3) - 8) mod period: the one 64-bit modulo,
 // done by the host; from there 32-bit arithmetic (every factor is below 2^16).  Phases 1-4 are the untuned kernel's.
-template <int PSKIP, bool TUNED>
+// BANK: the receiver bank (sdrhip_fm_bank_run), K stations of ONE input in one launch.  The grid gets a station axis: station
+// j = blockIdx.x mixes with its own table (osc + bank.off[j], bank.period[j] entries) from its own launch phase bank.ph[j] and writes
+// its own audio row, audio + j * bank.audio_stride; everything else -- the input tile, the taps, phases 1-4 -- is the tuned kernel's.
+// The per-station values travel in the kernel's arguments (392 bytes; the station index is uniform, so they are scalar loads from
+// the argument segment).  Axis order: the station is x, the FASTEST axis of the dispatch order, the tile is y: the K workgroups that
+// read one 16 KB input tile are handed out back to back, so the tile is fetched from HBM once and the other K - 1 readers find it in
+// the Infinity Cache while it is fresh there (and, from 9 stations on, stations j and j + 8 in the L2 of the XCD they share:
+// workgroups go round-robin over the 8 XCDs).  The price is the y limit of a grid: 65535 tiles per launch (fm_chain_small_bank_fits).
+struct BankStations {
+    int64_t audio_stride;                      // floats between the stations' audio rows
+    int off[kFmBankMaxStations];               // first entry of the station's table, in (re, im) pairs
+    int period[kFmBankMaxStations];
+    int ph[kFmBankMaxStations];                // (80 (q0 / 3) - 8) mod period: the host's one 64-bit modulo per station and launch
+};
+struct NoBank {};
+template <int PSKIP, bool TUNED, bool BANK = false>
 __global__ void __launch_bounds__(SM_NT, 2) k_fm_chain_small(const uint8_t* __restrict__ in, float* __restrict__ audio,
                                                              const float* __restrict__ dtaps, const float* __restrict__ groups,
                                                              const float* __restrict__ rplain, const float* __restrict__ fplain,
-                                                             SmallParams p, const float2* __restrict__ osc, int period, int ph_launch)
+                                                             SmallParams p, const float2* __restrict__ osc, int period, int ph_launch,
+                                                             typename std::conditional<BANK, BankStations, NoBank>::type bank)
 {
+    static_assert(TUNED || !BANK, "a bank is tuned chains");
+    unsigned tile = blockIdx.x;
+    if constexpr (BANK) {
+        const unsigned j = blockIdx.x;
+        tile = blockIdx.y;
+        audio += (int64_t)j * bank.audio_stride;
+        osc += bank.off[j];
+        period = bank.period[j];
+        ph_launch = bank.ph[j];
+    }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float2* lds = reinterpret_cast<float2*>(smem_raw);
     __shared__ __attribute__((aligned(16))) float gtab[3 * SM_NL];   // the three polyphase groups
@@ -205,7 +233,7 @@ __global__ void __launch_bounds__(SM_NT, 2) k_fm_chain_small(const uint8_t* __re
     const int tid = threadIdx.x;
 
     const int A = p.A;
-    const int64_t qa = (p.q0 / 3) * 3 + (int64_t)blockIdx.x * A;     // first audio output of the tile (cycle aligned)
+    const int64_t qa = (p.q0 / 3) * 3 + (int64_t)tile * A;     // first audio output of the tile (cycle aligned)
     const int64_t c0 = qa / 3;                                        // first resampler cycle
     const int64_t y0 = 10 * c0;                                       // first y of the tile = in_offset(3 c0)
     const int64_t kb = y0 - 1;                                        // decimator output of local index 0 (-1 at stream start)
@@ -264,7 +292,7 @@ __global__ void __launch_bounds__(SM_NT, 2) k_fm_chain_small(const uint8_t* __re
             // this launch either
             const uint32_t n = (uint32_t)period;
             const uint32_t ts = (uint32_t)(80 * (A / 3)) % n;
-            const uint32_t ph = ((uint32_t)ph_launch + (((uint32_t)blockIdx.x % n) * ts) % n + (uint32_t)(tid * 8) % n) % n;
+            const uint32_t ph = ((uint32_t)ph_launch + (((uint32_t)tile % n) * ts) % n + (uint32_t)(tid * 8) % n) % n;
             tuner_store<SmT, true, SM_NT>(st.r, lds, osc, n, ph);
         } else {
             st.store(lds);
@@ -477,12 +505,13 @@ __global__ void __launch_bounds__(SM_NT, 2) k_fm_chain_small(const uint8_t* __re
 }
 
 
-std::atomic<long long> g_small_launches{0}, g_small_tuned_launches{0};
+std::atomic<long long> g_small_launches{0}, g_small_tuned_launches{0}, g_small_bank_launches{0};
 
 }  // namespace
 
 long long fm_chain_small_launch_count() { return g_small_launches.load(); }
 long long fm_chain_small_tuned_launch_count() { return g_small_tuned_launches.load(); }
+long long fm_chain_small_bank_launch_count() { return g_small_bank_launches.load(); }
 
 int fm_chain_small_tile_outputs(int64_t n_out)
 {
@@ -536,7 +565,7 @@ void launch_fm_chain_small(hipStream_t s, const uint8_t* d_in, int64_t s0, int64
             if (dev >= 0 && dev < 64) attr_set[which][dev] = true;
         }
         hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(SM_NT), SmT::LDS_BYTES, s, d_in, d_audio, d_dtaps, t.d_groups, t.d_rplain, t.d_fplain, p,
-                           reinterpret_cast<const float2*>(d_osc), period, ph_launch);
+                           reinterpret_cast<const float2*>(d_osc), period, ph_launch, NoBank{});
     };
     if (d_osc != nullptr) {
         if (last_tap_zero) launch(k_fm_chain_small<1, true>, 3);
@@ -545,6 +574,59 @@ void launch_fm_chain_small(hipStream_t s, const uint8_t* d_in, int64_t s0, int64
     } else if (last_tap_zero) launch(k_fm_chain_small<1, false>, 1);
     else launch(k_fm_chain_small<0, false>, 0);
     g_small_launches++;
+}
+
+namespace {
+constexpr int64_t kBankMaxTiles = 65535;      // the y extent of a grid
+// tile size and tile count of a banked launch: the tile is chosen for the TOTAL work, stations * outputs
+int bank_tile_outputs(int64_t q0, int64_t q1, int stations, int tile_outputs)
+{
+    int A = tile_outputs > 0 ? tile_outputs : fm_chain_small_tile_outputs((int64_t)stations * (q1 - (q0 / 3) * 3));
+    A = A / 3 * 3;
+    if (A < 3) A = 3;
+    if (A > SM_A_MAX) A = SM_A_MAX;
+    return A;
+}
+int64_t bank_tiles(int64_t q0, int64_t q1, int A) { return (q1 - (q0 / 3) * 3 + A - 1) / A; }
+}  // namespace
+
+bool fm_chain_small_bank_fits(int64_t q0, int64_t q1, int stations, int tile_outputs)
+{
+    if (stations < 1 || stations > kFmBankMaxStations || q1 <= q0) return false;
+    return bank_tiles(q0, q1, bank_tile_outputs(q0, q1, stations, tile_outputs)) <= kBankMaxTiles;
+}
+
+void launch_fm_chain_small_bank(hipStream_t s, const uint8_t* d_in, int64_t s0, int64_t n_in, float* d_audio, int64_t audio_stride,
+                                int64_t q0, int64_t q1, const float* d_dtaps, bool last_tap_zero, const FmTailTables& t, int tile_outputs,
+                                const float* d_tables, int stations, const int* offsets, const int* periods)
+{
+    const int A = bank_tile_outputs(q0, q1, stations, tile_outputs);
+    SmallParams p;
+    p.s0 = s0; p.n_in = n_in; p.q0 = q0; p.q1 = q1; p.A = A;
+    p.row_stride = t.row_stride; p.ntaps = t.ntaps; p.rLp = t.rLp; p.gain = t.gain; p.seam = t.seam;
+    const int64_t tiles = bank_tiles(q0, q1, A);
+    BankStations st = {};
+    st.audio_stride = audio_stride;
+    const int64_t first = 80 * (q0 / 3) - 8;      // as launch_fm_chain_small: the phase of tile 0's first sample, per station
+    for (int j = 0; j < stations; j++) {
+        st.off[j] = offsets[j];
+        st.period[j] = periods[j];
+        st.ph[j] = (int)(((first % periods[j]) + periods[j]) % periods[j]);
+    }
+    static std::atomic<bool> attr_set[2][64];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    auto launch = [&](auto kern, int which) {
+        if (dev < 0 || dev >= 64 || !attr_set[which][dev]) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SmT::LDS_BYTES);
+            if (dev >= 0 && dev < 64) attr_set[which][dev] = true;
+        }
+        hipLaunchKernelGGL(kern, dim3((unsigned)stations, (unsigned)tiles), dim3(SM_NT), SmT::LDS_BYTES, s, d_in, d_audio, d_dtaps, t.d_groups, t.d_rplain,
+                           t.d_fplain, p, reinterpret_cast<const float2*>(d_tables), 0, 0, st);
+    };
+    if (last_tap_zero) launch(k_fm_chain_small<1, true, true>, 1);
+    else launch(k_fm_chain_small<0, true, true>, 0);
+    g_small_bank_launches++;
 }
 
 }  // namespace sdrhip

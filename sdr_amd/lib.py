@@ -149,6 +149,23 @@ lib.sdrhip_fm_chain_set_tuner.argtypes = [_vp, _f32p, C.c_int]
 lib.sdrhip_fm_chain_tuner_period.argtypes = [_vp]
 lib.sdrhip_debug_small_chain_tuned_launches.argtypes = []
 lib.sdrhip_debug_small_chain_tuned_launches.restype = C.c_longlong
+lib.sdrhip_fm_bank_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, _f32p, C.c_int, _f32p, C.c_int,
+                                      C.c_float, _i64, C.c_int, C.POINTER(_f32p), C.POINTER(C.c_int)]
+lib.sdrhip_fm_bank_destroy.argtypes = [_vp]
+lib.sdrhip_fm_bank_destroy.restype = None
+lib.sdrhip_fm_bank_stations.argtypes = [_vp]
+lib.sdrhip_fm_bank_period.argtypes = [_vp, C.c_int]
+lib.sdrhip_fm_bank_plan.argtypes = [_vp, _i64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
+lib.sdrhip_fm_bank_ready.argtypes = [_vp, _i64]
+lib.sdrhip_fm_bank_ready.restype = _i64
+lib.sdrhip_fm_bank_max_halo.argtypes = [_vp]
+lib.sdrhip_fm_bank_max_halo.restype = _i64
+lib.sdrhip_fm_bank_workspace_bytes.argtypes = [_vp, _i64]
+lib.sdrhip_fm_bank_workspace_bytes.restype = C.c_size_t
+lib.sdrhip_fm_bank_run.argtypes = [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, C.c_size_t]
+lib.sdrhip_fm_bank_set_route.argtypes = [_vp, C.c_int, _i64, C.c_int]
+lib.sdrhip_debug_fm_bank_launches.argtypes = []
+lib.sdrhip_debug_fm_bank_launches.restype = C.c_longlong
 lib.sdrhip_debug_resample_cycle_launches.restype = C.c_longlong
 lib.sdrhip_debug_decimate_real16_launches.restype = C.c_longlong
 lib.sdrhip_debug_systolic_launches.restype = C.c_longlong
@@ -655,6 +672,63 @@ class FmChain(_Handle):
 
     def run(self, d_in_u8, s0, n_in, d_audio, q0, q1, d_ws, ws_bytes, stream=None):
         check(lib.sdrhip_fm_chain_run(self.h, stream, d_in_u8, s0, n_in, d_audio, q0, q1, d_ws, ws_bytes), "sdrhip_fm_chain_run")
+
+
+def fm_bank_launches():
+    """Banked launches so far (sdrhip_debug_fm_bank_launches)."""
+    return int(lib.sdrhip_debug_fm_bank_launches())
+
+
+class FmBank(_Handle):
+    """Every station of one capture: K tuned FmChains of the same arguments over ONE input, one launch per run where the banked route
+    fits (sdr_hip.h, sdrhip_fm_bank_*).  tables: one interleaved float32 (re, im) table per station (tuner_shift_table builds the
+    usual ones; a station on the centre frequency takes [1, 0]).  Row j of a run is, bit for bit, what
+    FmChain(...).set_tuner(tables[j]) writes."""
+    _destroy = lib.sdrhip_fm_bank_destroy
+    ROUTE_AUTO, ROUTE_BANKED, ROUTE_STATIONS = 0, 1, 2
+
+    def __init__(self, decim_factor, decim_taps, interpolation, decimation, resamp_taps, audio_half_taps, tables,
+                 gain=1.0, block=8192, order=ORDER_AVX):
+        super().__init__()
+        a, b, c = _f32(decim_taps), _f32(resamp_taps), _f32(audio_half_taps)
+        ts = [_f32(t).reshape(-1) for t in tables]
+        if any(t.size % 2 for t in ts):
+            raise SdrHipError("an oscillator table is interleaved (re, im) pairs")
+        ptrs = (_f32p * max(len(ts), 1))(*[_fp(t) for t in ts])
+        periods = (C.c_int * max(len(ts), 1))(*[t.size // 2 for t in ts])
+        check(lib.sdrhip_fm_bank_create(C.byref(self.h), order, decim_factor, _fp(a), a.size, interpolation, decimation, _fp(b), b.size,
+                                        _fp(c), c.size, C.c_float(gain), block, len(ts), ptrs, periods), "sdrhip_fm_bank_create")
+
+    def stations(self):
+        return check(lib.sdrhip_fm_bank_stations(self.h), "sdrhip_fm_bank_stations")
+
+    def period(self, station):
+        return check(lib.sdrhip_fm_bank_period(self.h, int(station)), "sdrhip_fm_bank_period")
+
+    def plan(self, s0, s1, total_in=-1):
+        q0, q1, halo = _i64(), _i64(), _i64()
+        check(lib.sdrhip_fm_bank_plan(self.h, s0, s1, total_in, C.byref(q0), C.byref(q1), C.byref(halo)), "sdrhip_fm_bank_plan")
+        return q0.value, q1.value, halo.value
+
+    def ready(self, n_samples):
+        return int(lib.sdrhip_fm_bank_ready(self.h, n_samples))
+
+    def max_halo(self):
+        return int(lib.sdrhip_fm_bank_max_halo(self.h))
+
+    def workspace_bytes(self, n_in):
+        return int(lib.sdrhip_fm_bank_workspace_bytes(self.h, n_in))
+
+    def set_route(self, route=0, max_outputs=0, tile_outputs=0):
+        """0 = auto, 1 = the banked one-kernel launch (a run it does not fit is an error), 2 = station by station.  Auto is a rule
+        in two dimensions: the banked launch while a station's run is at most 39322 outputs (2^20 samples; fixed) AND stations * outputs
+        <= max_outputs (0 = built-in, 32 * 39322); longer runs go station by station whatever the number of stations.  tile_outputs
+        as FmChain.set_small_chain."""
+        check(lib.sdrhip_fm_bank_set_route(self.h, int(route), int(max_outputs), int(tile_outputs)), "sdrhip_fm_bank_set_route")
+
+    def run(self, d_in_u8, s0, n_in, d_audio, audio_stride, q0, q1, d_ws=None, ws_bytes=0, stream=None):
+        """Station j's outputs [q0, q1) -> d_audio + 4 * j * audio_stride bytes."""
+        check(lib.sdrhip_fm_bank_run(self.h, stream, d_in_u8, s0, n_in, d_audio, audio_stride, q0, q1, d_ws, ws_bytes), "sdrhip_fm_bank_run")
 
 
 class Fft(_Handle):
