@@ -187,6 +187,13 @@ int sdrhip_stream_create(void **stream);
 int sdrhip_stream_destroy(void *stream);
 int sdrhip_stream_sync(void *stream);
 
+/* Non-finite input to the FIR operators (filter, decimator, resampler: this descriptor API, the drop-in symbols and the Pipes):
+ * an output is NaN exactly where the reference's x86 kernels give NaN -- also where a zero tap, the zero padding included, meets an
+ * infinity -- but a NaN's sign and payload are unspecified (x86 generates 0xffc00000, this device 0x7fc00000, and which operand's
+ * payload a sum keeps follows the order of evaluation).  Everything else is exact: +0 and -0, subnormal results (no flush to
+ * zero), +Inf and -Inf, sums that overflow in the reference's own order.  u8 input on a descriptor with a nonzero tap below 2^-119
+ * takes the generic kernel instead of the u8-fused ones (taps / 128 would not be exact): same results, fewer samples per second. */
+
 /* ---- Filter (Filter.hs:116-120; constructors :163-261) ------------------- */
 typedef struct sdrhip_filter sdrhip_filter;
 /* fastFilter{C,SSE,AVX}{R,C}: zero-pads to the order's SIMD multiple
@@ -539,6 +546,9 @@ int sdrhip_fm_chain_set_demod_fusion(sdrhip_fm_chain *c, int enable);
 /* resampler launches that took fmDemod into their tile loader, process-wide (the per-stage timing books fmDemod under `resample`
  * whenever the fusion is on, also when a launch too small for the fused form ran a stand-alone fmDemod first: this tells the two apart) */
 long long sdrhip_debug_fused_demod_launches(void);
+/* u8 launches of a complex filter / decimator that went to the generic kernel (convert, then the plain taps), process-wide: the shapes
+ * no u8-fused tiled kernel serves, and every descriptor with a nonzero tap below 2^-119, whose taps / 128 would not be exact. */
+long long sdrhip_debug_generic_u8_launches(void);
 /* Per-stage timing with HIP events recorded around each stage's kernels on the stream they are
  * launched on; stages {decimate(+seam fix-up), fmDemod, resample, filter(+gain), fused tail (the three in one kernel),
  * whole chain in one kernel (sdrhip_fm_chain_set_small_chain)}.

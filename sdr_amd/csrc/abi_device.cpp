@@ -23,6 +23,8 @@ constexpr int kSmallSeamedLaunch = 32768;
 constexpr int kFusedDemodMinOutputs = 1 << 18;
 static std::atomic<long long> g_fused_demod_launches{0};
 long long fused_demod_launch_count() { return g_fused_demod_launches.load(); }
+static std::atomic<long long> g_generic_u8_launches{0};
+long long generic_u8_launch_count() { return g_generic_u8_launches.load(); }
 static std::atomic<int> g_small_launch{getenv("SDRHIP_SMALL_LAUNCH") ? atoi(getenv("SDRHIP_SMALL_LAUNCH")) : kSmallSeamedLaunch};
 int small_launch_outputs() { return g_small_launch.load(std::memory_order_relaxed); }
 
@@ -242,6 +244,7 @@ int fir_run(const FirDesc* d, hipStream_t s, const void* d_in, bool in_u8, int64
                                               d->sym ? d->ntaps_kernel : d->Lp, d->d_cross, (const float*)d_in, d_out, 1.0f, false)) {
             // lane-split tiled kernel took it (any factor / tap count / SIMD order)
         } else if (in_u8) {
+            g_generic_u8_launches.fetch_add(1, std::memory_order_relaxed);
             launch_fir_cplx_u8(s, g, d->corder, d->d_taps, d->ntaps_kernel, d->d_cross, (const uint8_t*)d_in, d_out);
         } else {
             launch_fir_cplx(s, g, d->corder, false, d->d_taps, d->ntaps_kernel, d->d_cross, (const float*)d_in, d_out);

@@ -667,6 +667,7 @@ long long sdrhip_debug_systolic_launches(void) { return systolic_launch_count();
 long long sdrhip_debug_systolic_plain_launches(void) { return systolic_plain_launch_count(); }
 long long sdrhip_debug_decimator_crossfix_launches(void) { return decimator_crossfix_launch_count(); }
 long long sdrhip_debug_fused_demod_launches(void) { return fused_demod_launch_count(); }
+long long sdrhip_debug_generic_u8_launches(void) { return generic_u8_launch_count(); }
 void sdrhip_debug_systolic_plan(int count, int* nstrips, int* nwhole) { systolic_plan(count, nstrips, nwhole); }
 
 int sdrhip_fm_chain_set_tuner(sdrhip_fm_chain* c, const float* osc_iq, int period)

@@ -307,6 +307,7 @@ void set_systolic(int mode);        // 0 = the tile kernel everywhere, 1 = the s
 long long systolic_launch_count();  // diagnostics
 long long systolic_plain_launch_count();  // diagnostics: launches with plain (not non-temporal) cfloat loads
 long long decimator_crossfix_launch_count();  // diagnostics: seam fix-ups of launch_decimate_c4_fast run as a launch of their own
+long long generic_u8_launch_count();  // abi_device.cpp, diagnostics: u8 launches of a complex stage that no u8-fused tiled kernel took
 long long fused_demod_launch_count();  // abi_device.cpp, diagnostics: resampler launches with fmDemod in their tile loader
 // kernels_fast_orders.hip: the same tiled decimator for the SSE "RC" and the "RC2" summation orders (CO_L2, CO_X4, CO_X2)
 bool launch_decimate_c_orders_fast(hipStream_t s, const Geom& g, ComplexOrder order, const float* d_plain_taps, int P,

@@ -172,6 +172,7 @@ lib.sdrhip_debug_systolic_launches.restype = C.c_longlong
 lib.sdrhip_debug_systolic_plain_launches.restype = C.c_longlong
 lib.sdrhip_debug_decimator_crossfix_launches.restype = C.c_longlong
 lib.sdrhip_debug_fused_demod_launches.restype = C.c_longlong
+lib.sdrhip_debug_generic_u8_launches.restype = C.c_longlong
 lib.sdrhip_debug_set_systolic.argtypes = [C.c_int]
 lib.sdrhip_debug_set_systolic.restype = None
 lib.sdrhip_debug_systolic_plan.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]

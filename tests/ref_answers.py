@@ -11,9 +11,11 @@ equality with a recorded answer is equality of the digest, so the tests assert e
     no live build       -> the recorded answers (SDRHIP_REF_REPLAY=1 forces this even where the live build exists)
     SDRHIP_REF_RECORD=PATH (live build required) -> its answers, and every call is written to PATH, merged into what the
                            committed record holds: the way to regenerate tests/golden/ref_answers.json, e.g.
-        SDRHIP_REF_RECORD=tests/golden/ref_answers.json python -m pytest tests/test_oracle_vs_ref.py tests/test_dc_blocker.py
+        SDRHIP_REF_RECORD=tests/golden/ref_answers.json python -m pytest tests/test_oracle_vs_ref.py tests/test_dc_blocker.py \
+            tests/test_oracle_value_classes.py
     and the same for the GPU tests that ask the reference (tests/test_gpu_dropin.py) on a GPU machine with oracle/_ref.
 """
+import contextlib
 import ctypes as C
 import hashlib
 import json
@@ -31,6 +33,17 @@ def bits_digest(a):
     return hashlib.blake2b(np.ascontiguousarray(a, dtype=np.float32).tobytes(), digest_size=16).hexdigest()
 
 
+NAN_BITS = 0x7FC00000
+
+
+def canonical_nan(a):
+    """`a` as float32 with every NaN replaced by the one pattern 0x7fc00000: sign and payload of a NaN are not part of any comparison
+    (tests/value_classes.py), every other bit is."""
+    a = np.array(a, dtype=np.float32, copy=True)
+    a.view(np.uint32)[np.isnan(a)] = NAN_BITS
+    return a
+
+
 def _f32_bits(v):
     return int(np.array([v], np.float32).view(np.uint32)[0])
 
@@ -42,15 +55,15 @@ def _f32_from_bits(b):
 class RecordedArray:
     """A recorded answer: its element count and the digest of its bits.  conftest.assert_bit_equal compares an array with it."""
 
-    def __init__(self, size, digest, call):
-        self.size, self.digest, self.call = size, digest, call
+    def __init__(self, size, digest, call, canon=False):
+        self.size, self.digest, self.call, self.canon = size, digest, call, canon      # canon: the digest was taken after canonical_nan
 
     def mismatch(self, a):
         """None when `a` has exactly the recorded bits, else what differs."""
         a = np.ascontiguousarray(a, dtype=np.float32).ravel()
         if a.size != self.size:
             return f"{a.size} elements against the reference build's {self.size} ({self.call})"
-        if bits_digest(a) != self.digest:
+        if bits_digest(canonical_nan(a) if self.canon else a) != self.digest:
             return f"the bits of the {a.size} elements differ from the reference build's recorded answer ({self.call})"
         return None
 
@@ -89,6 +102,8 @@ def _calls():
         "resample_legacy": lambda buf_size, interp, decim, fo, c, x: ((int(buf_size), int(interp), int(decim), int(fo), np.ascontiguousarray(c, np.float32),
                                                                        np.ascontiguousarray(x, np.float32)),
                                                                       f"resampleRR num={buf_size} {interp}/{decim} offset {fo}"),
+        "scale": lambda sym, factor, x: ((sym, _f32_bits(factor), np.ascontiguousarray(x, np.float32)), f"{sym} factor={factor!r} n={np.size(x)}"),
+        "convert_tx": lambda x: ((np.ascontiguousarray(x, np.float32),), f"convertBladeRFTransmit n={np.size(x)}"),
         "dc_blocker": lambda x, ls=0.0, lo=0.0: ((np.ascontiguousarray(x, np.float32), _f32_bits(ls), _f32_bits(lo)), f"dcBlocker n={np.size(x)}"),
     }
 
@@ -124,6 +139,13 @@ class _Live:
         getattr(self.ref.lib, sym)(C.c_int(i16.size), buf.ctypes.data_as(C.POINTER(C.c_int16)), out.ctypes.data_as(C.POINTER(C.c_float)))
         return out[:i16.size].copy()
 
+    def convert_tx(self, x):
+        """int16 answers: as float32 they are exact, so the record's digest of float32 bits serves."""
+        x = np.ascontiguousarray(x, np.float32)
+        out = np.empty(x.size, np.int16)
+        self.ref.lib.convertBladeRFTransmit(C.c_int(x.size), x.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.POINTER(C.c_int16)))
+        return out
+
     def __getattr__(self, name):
         return getattr(self.ref, name)
 
@@ -135,9 +157,11 @@ class RefAnswers:
         self.live = _Live(live) if live is not None else None
         self.record_to = record_to
         self.table = json.load(open(RECORD)) if os.path.exists(RECORD) else {}
+        self.last_key = list(self.table)[-1] if self.table else None
         if record_to and os.path.exists(record_to):
             self.table.update(json.load(open(record_to)))
         self.recorded = {}
+        self.canon = False
         for method, describe in _calls().items():
             setattr(self, method, self._method(method, describe))
 
@@ -150,10 +174,13 @@ class RefAnswers:
                 if entry is None:
                     pytest.fail(f"no recorded answer of the reference build for {method} {what}: regenerate tests/golden/ref_answers.json "
                                 "where oracle/_ref exists (tests/ref_answers.py)")
-                return _join(method, RecordedArray(entry["n"], entry["b2"], f"{method} {what}"), entry)
+                assert bool(entry.get("canon", False)) == self.canon, f"{method} {what}: recorded with canon = {entry.get('canon', False)}"
+                return _join(method, RecordedArray(entry["n"], entry["b2"], f"{method} {what}", self.canon), entry)
             answer = getattr(self.live, method)(*args, **kw)
             arr, extras = _split(method, answer)
-            new = {"n": int(np.size(arr)), "b2": bits_digest(arr), "call": f"{method} {what}", **extras}
+            new = {"n": int(np.size(arr)), "b2": bits_digest(canonical_nan(arr) if self.canon else arr), "call": f"{method} {what}", **extras}
+            if self.canon:
+                new["canon"] = True
             if entry is not None and not self.record_to:
                 assert {k: entry.get(k) for k in new if k != "call"} == {k: v for k, v in new.items() if k != "call"}, \
                     f"tests/golden/ref_answers.json disagrees with the reference build on {method} {what}: regenerate it"
@@ -162,11 +189,25 @@ class RefAnswers:
             return answer
         return call
 
+    @contextlib.contextmanager
+    def canonical(self):
+        """Calls made inside compare and record their answers with NaNs made canonical (canonical_nan); their entries carry
+        "canon": true, and RecordedArray.mismatch then treats the array it is given the same way."""
+        prev, self.canon = self.canon, True
+        try:
+            yield self
+        finally:
+            self.canon = prev
+
     def close(self):
         if self.record_to and self.recorded:
             self.table.update(self.recorded)
+            keys = sorted(self.table)
+            if self.last_key in self.table:              # the record's last line stays last (it alone has no comma): regenerating adds lines only
+                keys.remove(self.last_key)
+                keys.append(self.last_key)
             with open(self.record_to, "w") as f:         # one answer per line
-                f.write("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(v, sort_keys=True)}" for k, v in sorted(self.table.items())) + "\n}\n")
+                f.write("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(self.table[k], sort_keys=True)}" for k in keys) + "\n}\n")
 
 
 def open_ref():
