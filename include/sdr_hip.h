@@ -365,6 +365,9 @@ int sdrhip_decimator_cross(const sdrhip_decimator *d, int num, const float *last
 int sdrhip_resampler_one(const sdrhip_resampler *r, int group, int num, const float *in, int n_in, float *out);
 int sdrhip_resampler_cross(const sdrhip_resampler *r, int filter_offset, int num, const float *last, int n_last,
                            const float *next, int n_next, float *out);
+/* Calls of the six above whose buffers were over 512 KiB and went through the copy engine into device buffers instead of being read
+ * and written in place from pinned memory; process-wide, for tests that assert which branch a buffer size took. */
+long long sdrhip_debug_record_copied_calls(void);
 
 /* ---- the FM receiver chain (examples/fm/fm.hs:34-41) ----------------------- */
 /* u8 IQ -> [convert] -> decimator -> fmDemod -> resampler -> symmetric filter

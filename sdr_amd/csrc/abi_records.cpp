@@ -11,6 +11,7 @@
 // use (scratch_pool.hpp), so the closures of several pipelines do not queue behind one another.
 #include <string.h>
 
+#include <atomic>
 
 #include "descriptors.hpp"
 #include "scratch_pool.hpp"
@@ -21,6 +22,7 @@ namespace {
 
 using RecScratch = ScratchCtx;          // leased per call (scratch_pool.hpp): concurrent callers do not queue
 constexpr size_t kRecDirectBytes = 512 << 10;
+std::atomic<long long> g_copied_calls{0};   // diagnostics: calls that took the copying branch of stage()
 
 // stage `bytes` of host input (already assembled in sc.hin) and give back the device-visible input / output pointers
 int stage(RecScratch& sc, size_t in_bytes, size_t out_bytes, const float** d_in, float** d_out, bool* direct)
@@ -33,6 +35,7 @@ int stage(RecScratch& sc, size_t in_bytes, size_t out_bytes, const float** d_in,
         *d_out = (float*)sc.hout.dev;
         return SDRHIP_OK;
     }
+    g_copied_calls.fetch_add(1, std::memory_order_relaxed);
     if ((rc = sc.in.ensure(in_bytes + 64)) != SDRHIP_OK) return rc;
     if ((rc = sc.out.ensure(out_bytes + 64)) != SDRHIP_OK) return rc;
     SDRHIP_CHECK_HIP(hipMemcpyAsync(sc.in.p, sc.hin.p, in_bytes, hipMemcpyHostToDevice, sc.stream));
@@ -190,5 +193,7 @@ int sdrhip_resampler_cross(const sdrhip_resampler* r, int filter_offset, int num
     if ((rc = finish(sc, direct, out, ob)) != SDRHIP_OK) return rc;
     return r->filter_offset(m0 + num);
 }
+
+long long sdrhip_debug_record_copied_calls(void) { return g_copied_calls.load(); }
 
 }  // extern "C"

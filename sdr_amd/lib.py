@@ -226,6 +226,8 @@ lib.sdrhip_decimator_one.argtypes = [_vp, C.c_int, _f32p, _f32p]
 lib.sdrhip_decimator_cross.argtypes = [_vp, C.c_int, _f32p, C.c_int, _f32p, C.c_int, _f32p]
 lib.sdrhip_resampler_one.argtypes = [_vp, C.c_int, C.c_int, _f32p, C.c_int, _f32p]
 lib.sdrhip_resampler_cross.argtypes = [_vp, C.c_int, C.c_int, _f32p, C.c_int, _f32p, C.c_int, _f32p]
+lib.sdrhip_debug_record_copied_calls.argtypes = []
+lib.sdrhip_debug_record_copied_calls.restype = C.c_longlong
 # ---- measurement utilities (include/sdr_hip_bench.h): libsdr_hip_bench.so, a library of its own beside the product (round 6); bench.py and
 # tools/ reach them as lib.sdrhip_bench_* like everything else, so the names are attached to `lib` here
 BENCH_LIB_PATH = os.path.join(HERE, "lib", "libsdr_hip_bench.so")
