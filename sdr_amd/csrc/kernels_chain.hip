@@ -11,9 +11,12 @@
 //
 // Arithmetic contract as in kernels_generic.hip (-ffp-contract=off, lane orders of the
 // AVX variants: resampleAVXRR resample.c:70-87, filterAVXSymmetricRR filter.c:60-68).
+#include <type_traits>
+
 #include "kernels.hpp"
 #include "crossfix.hpp"
 #include "demod.hpp"
+#include "first_mac.hpp"
 
 namespace sdrhip {
 
@@ -149,8 +152,10 @@ __global__ void __launch_bounds__(NT) k_fir_real8_fast(const float* __restrict__
     // The taps are fetched ONE STEP AHEAD (a scalar-load wait is a full lgkmcnt(0) drain: with the load issued a whole step
     // of arithmetic earlier it finds the data there); the loop stays rolled.
     f8v cnext = *reinterpret_cast<const f8v*>(taps);
-#pragma unroll 1
-    for (int j = 0; j < nk / 8; j++) {
+    // one step of eight taps; FIRST (step 0, peeled out of the rolled loop): the additions that start the partials are +0 + product,
+    // one fma each (first_mac.hpp)
+    auto step = [&](const int j, auto first) {
+        constexpr bool FIRST = decltype(first)::value;
         const f8v c8 = cnext;
         const float* fp = win + 8 * j;
         float fw[12], bw[12];
@@ -182,11 +187,16 @@ __global__ void __launch_bounds__(NT) k_fir_real8_fast(const float* __restrict__
 #pragma unroll
             for (int r = 0; r < R; r++) {
                 // k = 8j+kk: front w[r+k] = fw[r+kk]; back w[r+2n-1-k] = bw[r + 7 - kk]; lane k & (L-1) = kk & (L-1)
-                if constexpr (SYM) acc[r][kk % L] = acc[r][kk % L] + c8[kk] * (fw[r + kk] + bw[r + 7 - kk]);
-                else acc[r][kk % L] = acc[r][kk % L] + c8[kk] * fw[r + kk];
+                float x = fw[r + kk];
+                if constexpr (SYM) x = fw[r + kk] + bw[r + 7 - kk];
+                if (FIRST && kk < L) acc[r][kk % L] = first_mac(c8[kk], x);
+                else acc[r][kk % L] = acc[r][kk % L] + c8[kk] * x;
             }
         }
-    }
+    };
+    step(0, std::true_type{});
+#pragma unroll 1
+    for (int j = 1; j < nk / 8; j++) step(j, std::false_type{});
     const int o = out0 + threadIdx.x * R;
 #pragma unroll
     for (int r = 0; r < R; r++) {
@@ -553,21 +563,24 @@ __global__ void __launch_bounds__(NT, 6) k_resample3_fast(const float* __restric
             float acc[8];
             {
                 if (PRE[g] % 2 == 0) {
+                    // the first trip of each pair of partials is +0 + product: one packed fma (first_mac.hpp)
                     f2 A[4];
 #pragma unroll
-                    for (int p = 0; p < 4; p++) A[p] = f2{0.0f, 0.0f};
+                    for (int j = 0; j < 8; j += 2) A[j / 2] = first_mac(W2[(PRE[g] + j) / 2], f2{c[j], c[j + 1]});
 #pragma unroll
-                    for (int j = 0; j < NLOOP; j += 2) A[(j % 8) / 2] = A[(j % 8) / 2] + W2[(PRE[g] + j) / 2] * f2{c[j], c[j + 1]};
+                    for (int j = 8; j < NLOOP; j += 2) A[(j % 8) / 2] = A[(j % 8) / 2] + W2[(PRE[g] + j) / 2] * f2{c[j], c[j + 1]};
 #pragma unroll
                     for (int p = 0; p < 4; p++) { acc[2 * p] = A[p].x; acc[2 * p + 1] = A[p].y; }
                 } else {
                     // B[p] = (partial 2p + 1, partial 2p + 2 mod 8): B[3] = (partial 7, partial 0)
+                    // B[0..2]'s first trips and tap 0 are +0 + product: one fma each (first_mac.hpp).  B[3]'s first trip is not: its high
+                    // half already holds tap 0's product
                     f2 B[4];
+                    B[3] = f2{0.0f, first_mac(c[0], W2[PRE[g] / 2].y)};                    // tap 0: sample PRE is the high half of its pair
 #pragma unroll
-                    for (int p = 0; p < 4; p++) B[p] = f2{0.0f, 0.0f};
-                    B[3].y = 0.0f + c[0] * W2[PRE[g] / 2].y;                               // tap 0: sample PRE is the high half of its pair
+                    for (int j = 1; j < 7; j += 2) B[(j - 1) / 2] = first_mac(W2[(PRE[g] + j) / 2], f2{c[j], c[j + 1]});
 #pragma unroll
-                    for (int j = 1; j + 1 < NLOOP; j += 2) B[((j % 8) - 1) / 2] = B[((j % 8) - 1) / 2] + W2[(PRE[g] + j) / 2] * f2{c[j], c[j + 1]};
+                    for (int j = 7; j + 1 < NLOOP; j += 2) B[((j % 8) - 1) / 2] = B[((j % 8) - 1) / 2] + W2[(PRE[g] + j) / 2] * f2{c[j], c[j + 1]};
                     B[3].x = B[3].x + c[NLOOP - 1] * W2[(PRE[g] + NLOOP - 1) / 2].x;       // tap NLOOP - 1: the low half of the last pair
                     acc[0] = B[3].y; acc[7] = B[3].x;
 #pragma unroll

@@ -35,6 +35,7 @@
 #include <utility>
 
 #include "kernels.hpp"
+#include "first_mac.hpp"
 #include "decimate_tile.hpp"      // decimate_c_crossfix_wg: the seam fix-up's workgroup body (round 6: interleaved into this kernel's launch)
 
 namespace sdrhip {
@@ -215,10 +216,12 @@ __device__ __forceinline__ void systolic_strip(const void* __restrict__ in, int6
                     if (t > 0 && c == 0 && r < 4) acc[i][k] = f2{dpp_shr1(acc[i][k].x), dpp_shr1(acc[i][k].y)};
                     continue;
                 }
-                const f2 p = S[8 * c + r] * tc[b][r];
                 if (b == 0 && r < 4) {
-                    acc[i][k] = f2{0.f, 0.f} + p;                  // the first addition of the partial: +0 + product
-                } else if (t > 0 && c == 0 && r < 4) {
+                    acc[i][k] = first_mac(S[8 * c + r], tc[b][r]);  // the first addition of the partial, +0 + product: one fma (first_mac.hpp)
+                    continue;
+                }
+                const f2 p = S[8 * c + r] * tc[b][r];
+                if (t > 0 && c == 0 && r < 4) {
                     acc[i][k] = f2{dpp_shr1(acc[i][k].x) + p.x, dpp_shr1(acc[i][k].y) + p.y};   // the group enters the stage one lane up
                 } else {
                     acc[i][k] = acc[i][k] + p;
