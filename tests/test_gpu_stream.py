@@ -7,6 +7,7 @@ import pytest
 from conftest import assert_bit_equal
 from oracle import pipes_model as PM
 import signals as S
+import stream_slice_cases as SC
 from gpu_util import to_dev, dev_empty_f32, ptr, to_host
 
 pytestmark = pytest.mark.gpu
@@ -19,15 +20,25 @@ def _split(x, width, block):
     return [x[i * block * width:(i + 1) * block * width] for i in range(n // block)]
 
 
-def _run_ranges(desc, d_in, in_total, out_width, K, seam, cuts, u8=False, out_block=0):
-    """Run [0,K) as several launches cut at `cuts`, each with its own in_base/slice of the input."""
+def _run_ranges(desc, d_in, in_total, out_width, K, seam, cuts, u8=False, out_block=0, sliced=False):
+    """Run [0,K) as several launches cut at `cuts`.  sliced: each launch with its own in_base and its own slice of the input -- a
+    buffer that holds only the inputs the header guarantees for that launch, between guard bands (NaN floats / the stream's bytes
+    with the top bit flipped: stream_slice_cases.upload_slice); otherwise every launch reads the whole resident stream, in_base 0."""
     out = dev_empty_f32(K * out_width)
     edges = [0] + list(cuts) + [K]
     kw = {"out_block": out_block} if out_block else {}
+    host = d_in.cpu().numpy() if sliced else None
+    I, D = getattr(desc, "I", 1), getattr(desc, "D", getattr(desc, "factor", 1))
     for a, b in zip(edges[:-1], edges[1:]):
         if b <= a:
             continue
-        (desc.run_u8 if u8 else desc.run)(ptr(d_in), 0, ptr(out) + 4 * out_width * a, a, b, seam, **kw)
+        if sliced:
+            lo, hi = SC.input_range(I, D, desc.num_coeffs, a, b)
+            assert hi <= in_total
+            keep, d, base = SC.upload_slice(host, host.size // in_total, lo, hi, u8) + (lo,)
+        else:
+            d, base = ptr(d_in), 0
+        (desc.run_u8 if u8 else desc.run)(d, base, ptr(out) + 4 * out_width * a, a, b, seam, **kw)
     return to_host(out)
 
 
@@ -61,6 +72,10 @@ def test_decimator_complex_stream(hip, oracle, order, launch_route):
     assert_bit_equal(got, exp, "cut into launches")
     got = _run_ranges(dec, to_dev(u8), nblk * B, 2, K, B, [1024], u8=True)
     assert_bit_equal(got, exp, "u8 input (convert fused)")
+    got = _run_ranges(dec, to_dev(x), nblk * B, 2, K, B, [1, 1000, 1009, 1024, 3000], sliced=True)
+    assert_bit_equal(got, exp, "cut into launches, each on its own slice")
+    got = _run_ranges(dec, to_dev(u8), nblk * B, 2, K, B, [1024], u8=True, sliced=True)
+    assert_bit_equal(got, exp, "u8 input, each launch on its own slice")
 
 
 def test_decimator_lone_block_is_all_one(hip, oracle):
@@ -84,6 +99,8 @@ def test_filter_sym_stream(hip, oracle, order, launch_route):
     assert f.num_coeffs == 128
     got = _run_ranges(f, to_dev(x), 4 * B, 1, exp.size, B, [8065, 8192, 9000])
     assert_bit_equal(got, exp, "sym filter stream")
+    got = _run_ranges(f, to_dev(x), 4 * B, 1, exp.size, B, [8065, 8192, 9000], sliced=True)
+    assert_bit_equal(got, exp, "sym filter stream, each launch on its own slice")
 
 
 @pytest.mark.parametrize("order", [PM.ORDER_AVX, PM.ORDER_SSE, PM.ORDER_SCALAR])
@@ -119,6 +136,8 @@ def test_resampler_stream(hip, oracle, order, complex_, launch_route):
     assert_bit_equal(got, exp, "contiguous")
     got = _run_ranges(r, to_dev(x), 4 * B, w, exp.size // w, B, [1, 2, 2439, 2458, 5000], out_block=512)
     assert_bit_equal(got, exp, "cut into launches")
+    got = _run_ranges(r, to_dev(x), 4 * B, w, exp.size // w, B, [1, 2, 2439, 2458, 5000], out_block=512, sliced=True)
+    assert_bit_equal(got, exp, "cut into launches, each on its own slice")
 
 
 @pytest.mark.parametrize("I,D", [(2, 3), (5, 7), (7, 11), (3, 23), (97, 100), (65, 131)])
