@@ -1,7 +1,7 @@
 /* fm_replay.c -- the FM receiver of the reference's examples/fm/fm.hs:30-41 fed from a file instead of a radio
  * ("file replay source feeding pinned buffers"), in plain C over the C ABI of libsdr_hip.so.
  *
- *     fm_replay [--shift NUM/DEN] <iq_u8_file | udp:PORT> <audio_f32_file> [blocks_per_push] [taps_prefix]
+ *     fm_replay [--shift NUM/DEN | --stations NUM/DEN[,NUM/DEN...]] <iq_u8_file | udp:PORT> <audio_f32_file> [blocks_per_push] [taps_prefix]
  *
  * Reads interleaved unsigned 8-bit IQ (what rtl_sdr writes, what RTLSDRStream.hs:48-67 yields) in source blocks of
  * 8192 samples, `blocks_per_push` of them at a time, straight into the stream operator's pinned staging buffer
@@ -13,6 +13,9 @@
  * --shift NUM/DEN receives a station that is off the centre of the capture: the samples are multiplied by exp(2 pi i NUM n / DEN)
  * (sdrhip_tuner_shift_table, 1 <= DEN <= 65536; sample n of the capture meets entry n mod DEN) in front of the decimator
  * (sdrhip_fm_chain_set_tuner), which moves the station NUM / DEN of the sampling frequency BELOW the centre onto it.
+ * --stations NUM/DEN[,NUM/DEN...] receives 1 to 32 stations of the capture at once: one table per station (sdrhip_tuner_shift_table),
+ * ONE bank (sdrhip_fm_bank_create), ONE stream over it (sdrhip_fm_stream_create_bank) -- every push crosses the link once and is one
+ * launch for all the stations.  Station j's audio goes to <audio_f32_file>.<j> and is what --shift with its NUM/DEN writes.
  * Output is bit-identical to the reference pipeline's (tests/test_gpu_examples.py). */
 #define _POSIX_C_SOURCE 200809L
 #include <arpa/inet.h>
@@ -65,10 +68,19 @@ static void check(int rc, const char *what)
     if (rc < 0) { fprintf(stderr, "fm_replay: %s: %s\n", what, sdrhip_last_error()); exit(1); }
 }
 
+/* one stream over the bank (--stations: a row of audio blocks per station) or over the chain */
+static int make_stream(sdrhip_fm_stream **st, sdrhip_fm_chain *chain, sdrhip_fm_bank *bank, int bpp)
+{
+    if (bank) return sdrhip_fm_stream_create_bank(st, bank, bpp * SOURCE_BLOCK, SOURCE_BLOCK);
+    return sdrhip_fm_stream_create(st, chain, bpp * SOURCE_BLOCK, SOURCE_BLOCK);
+}
+
 int main(int argc, char **argv)
 {
-    /* --shift NUM/DEN, anywhere on the line; what is left are the positional arguments */
+    /* --shift NUM/DEN or --stations NUM/DEN[,...], anywhere on the line; what is left are the positional arguments */
     long long shift_num = 0, shift_den = 0;
+    long long st_num[SDRHIP_FM_BANK_MAX_STATIONS], st_den[SDRHIP_FM_BANK_MAX_STATIONS];
+    int stations = 0;
     {
         int w = 1;
         for (int i = 1; i < argc; i++) {
@@ -78,13 +90,29 @@ int main(int argc, char **argv)
                     return 2;
                 }
                 i++;
+            } else if (strcmp(argv[i], "--stations") == 0) {
+                const char *p = i + 1 < argc ? argv[i + 1] : "";
+                int used = 0;
+                while (stations < SDRHIP_FM_BANK_MAX_STATIONS && sscanf(p, "%lld/%lld%n", &st_num[stations], &st_den[stations], &used) == 2 &&
+                       st_den[stations] >= 1 && st_den[stations] <= 65536) {
+                    stations++;
+                    p += used;
+                    if (*p != ',') break;
+                    p++;
+                }
+                if (stations < 1 || *p != '\0') {
+                    fprintf(stderr, "fm_replay: --stations NUM/DEN[,NUM/DEN...] with 1 to %d stations, 1 <= DEN <= 65536\n", SDRHIP_FM_BANK_MAX_STATIONS);
+                    return 2;
+                }
+                i++;
             } else {
                 argv[w++] = argv[i];
             }
         }
         argc = w;
     }
-    if (argc < 3) { fprintf(stderr, "usage: fm_replay [--shift NUM/DEN] <iq_u8_file | udp:PORT> <audio_f32_file> [blocks_per_push] [taps_prefix]\n"); return 2; }
+    if (stations > 0 && shift_den > 0) { fprintf(stderr, "fm_replay: --shift or --stations, not both\n"); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: fm_replay [--shift NUM/DEN | --stations NUM/DEN[,NUM/DEN...]] <iq_u8_file | udp:PORT> <audio_f32_file> [blocks_per_push] [taps_prefix]\n"); return 2; }
     const int bpp = argc > 3 ? atoi(argv[3]) : 64;
     if (bpp < 1) { fprintf(stderr, "fm_replay: blocks_per_push must be >= 1\n"); return 2; }
     int n_decim, n_resamp, n_audio;
@@ -104,8 +132,22 @@ int main(int argc, char **argv)
         check(sdrhip_fm_chain_set_tuner(chain, osc, (int)shift_den), "sdrhip_fm_chain_set_tuner");   /* copied */
         free(osc);
     }
+    sdrhip_fm_bank *bank = NULL;
+    if (stations > 0) {
+        float *tables[SDRHIP_FM_BANK_MAX_STATIONS];
+        int periods[SDRHIP_FM_BANK_MAX_STATIONS];
+        for (int j = 0; j < stations; j++) {
+            tables[j] = (float *)malloc((size_t)st_den[j] * 2 * sizeof(float));
+            periods[j] = (int)st_den[j];
+            check(sdrhip_tuner_shift_table(st_num[j], st_den[j], tables[j]), "sdrhip_tuner_shift_table");
+        }
+        check(sdrhip_fm_bank_create(&bank, SDRHIP_ORDER_AVX, 8, decim, n_decim, 3, 10, resamp, n_resamp, audio_half, n_audio, 0.2f, SOURCE_BLOCK,
+                                    stations, (const float *const *)tables, periods), "sdrhip_fm_bank_create");   /* copied */
+        for (int j = 0; j < stations; j++) free(tables[j]);
+    }
     sdrhip_fm_stream *st = NULL;
-    check(sdrhip_fm_stream_create(&st, chain, bpp * SOURCE_BLOCK, SOURCE_BLOCK), "sdrhip_fm_stream_create");
+    check(make_stream(&st, chain, bank, bpp), "sdrhip_fm_stream_create");
+    const int rows = sdrhip_fm_stream_rows(st);
 
     source src = {NULL, -1};
     if (is_udp) {
@@ -125,7 +167,7 @@ int main(int argc, char **argv)
         {   /* warm the device up (module load, first allocations) on a throw-away stream, so that the first real push does
              * not stall long enough for the socket buffer to overflow */
             sdrhip_fm_stream *warm = NULL;
-            check(sdrhip_fm_stream_create(&warm, chain, bpp * SOURCE_BLOCK, SOURCE_BLOCK), "sdrhip_fm_stream_create");
+            check(make_stream(&warm, chain, bank, bpp), "sdrhip_fm_stream_create");
             uint8_t *wb = sdrhip_fm_stream_input_buffer(warm);
             if (!wb) check(-1, "sdrhip_fm_stream_input_buffer");
             memset(wb, 128, (size_t)bpp * 2 * SOURCE_BLOCK);
@@ -138,9 +180,17 @@ int main(int argc, char **argv)
     } else {
         src.f = fopen(argv[1], "rb");
     }
-    FILE *out = fopen(argv[2], "wb");
-    if ((!src.f && src.sock < 0) || !out) { fprintf(stderr, "fm_replay: cannot open input/output\n"); return 2; }
-    float *block = (float *)malloc(SOURCE_BLOCK * sizeof(float));
+    /* one audio file per row: <audio_f32_file> itself, or with --stations <audio_f32_file>.<j> for station j */
+    FILE *out[SDRHIP_FM_BANK_MAX_STATIONS];
+    for (int j = 0; j < rows; j++) {
+        char path[4096];
+        if (bank) snprintf(path, sizeof path, "%s.%d", argv[2], j);
+        else snprintf(path, sizeof path, "%s", argv[2]);
+        out[j] = fopen(path, "wb");
+        if (!out[j]) { fprintf(stderr, "fm_replay: cannot open %s\n", path); return 2; }
+    }
+    if (!src.f && src.sock < 0) { fprintf(stderr, "fm_replay: cannot open input/output\n"); return 2; }
+    float *block = (float *)malloc((size_t)rows * SOURCE_BLOCK * sizeof(float));
     long long samples = 0, audio = 0;
     for (;;) {
         uint8_t *buf = sdrhip_fm_stream_input_buffer(st);   /* pinned: the upload needs no intermediate copy */
@@ -157,18 +207,20 @@ int main(int argc, char **argv)
             check(ready, "sdrhip_fm_stream_flush");
         }
         for (int i = 0; i < ready; i++) {
-            check(sdrhip_fm_stream_pop(st, block, SOURCE_BLOCK), "sdrhip_fm_stream_pop");
-            fwrite(block, sizeof(float), SOURCE_BLOCK, out);
+            check(sdrhip_fm_stream_pop_rows(st, block, SOURCE_BLOCK, 1), "sdrhip_fm_stream_pop_rows");   /* one block of every row */
+            for (int j = 0; j < rows; j++) fwrite(block + (size_t)j * SOURCE_BLOCK, sizeof(float), SOURCE_BLOCK, out[j]);
             audio += SOURCE_BLOCK;
         }
         if (got < (size_t)bpp) break;
     }
-    fprintf(stderr, "fm_replay: %lld IQ samples in, %lld audio samples out\n", samples, audio);
+    if (bank) fprintf(stderr, "fm_replay: %lld IQ samples in, %lld audio samples out for each of %d stations\n", samples, audio, rows);
+    else fprintf(stderr, "fm_replay: %lld IQ samples in, %lld audio samples out\n", samples, audio);
     if (src.f) fclose(src.f);
     if (src.sock >= 0) close(src.sock);
-    fclose(out);
+    for (int j = 0; j < rows; j++) fclose(out[j]);
     free(block);
     sdrhip_fm_stream_destroy(st);
+    sdrhip_fm_bank_destroy(bank);
     sdrhip_fm_chain_destroy(chain);
     free(decim);
     free(resamp);

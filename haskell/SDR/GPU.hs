@@ -147,6 +147,11 @@ foreign import ccall safe "sdrhip_fm_bank_workspace_bytes" c_fm_bank_workspace_b
 foreign import ccall safe "sdrhip_fm_bank_run"      c_fm_bank_run      :: Ptr SdrBank -> Ptr () -> Ptr CUChar -> Int64 -> Int64 -> Ptr CFloat -> Int64 -> Int64 -> Int64 -> Ptr () -> CSize -> IO CInt
 foreign import ccall safe "sdrhip_fm_bank_set_route" c_fm_bank_set_route :: Ptr SdrBank -> CInt -> Int64 -> CInt -> IO CInt
 foreign import ccall safe "sdrhip_debug_fm_bank_launches" c_fm_bank_launches :: IO CLLong
+-- the bank's host-block front end: the stream object of sdrhip_fm_stream_create with one row of audio blocks per station (push,
+-- flush, poll and the rest are the calls above; counts are blocks per station); pop_rows: station j's blocks at out + j * row_stride
+foreign import ccall safe "sdrhip_fm_stream_create_bank" c_stream_create_bank :: Ptr (Ptr SdrStream) -> Ptr SdrBank -> CInt -> CInt -> IO CInt
+foreign import ccall safe "sdrhip_fm_stream_rows" c_stream_rows :: Ptr SdrStream -> IO CInt
+foreign import ccall safe "sdrhip_fm_stream_pop_rows" c_stream_pop_rows :: Ptr SdrStream -> Ptr CFloat -> Int64 -> CInt -> IO CInt
 -- the spectrum operator (include/sdr_hip.h, sdrhip_spectrum_*): interleavedIQUnsigned256ToFloat -> halfBandUp x window -> fftw ->
 -- magnitude x scale, rows of Float
 foreign import ccall safe "sdrhip_spectrum_create"     c_spectrum_create     :: Ptr (Ptr SdrSpectrum) -> CInt -> CInt -> CInt -> Ptr CDouble -> CInt -> CDouble -> IO CInt

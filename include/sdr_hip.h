@@ -502,8 +502,8 @@ size_t sdrhip_fm_bank_workspace_bytes(const sdrhip_fm_bank *b, int64_t n_in);
  * touched.  Asynchronous on `stream`.  After the first run of a shape a run makes no allocation, no host synchronisation and no
  * host-to-device copy: what changes from launch to launch (each station's oscillator phase at the launch's first sample, the row
  * stride) travels in the kernel's arguments.  The banked route sends nothing through the workspace and accepts a null one; the
- * station-by-station route needs sdrhip_fm_bank_workspace_bytes(n_in) bytes.  No overlap mode, no hipGraph helper and no
- * host-block stream front end for a bank. */
+ * station-by-station route needs sdrhip_fm_bank_workspace_bytes(n_in) bytes.  No overlap mode and no hipGraph helper for a bank;
+ * its host-block front end is sdrhip_fm_stream_create_bank (below, with the chain's). */
 int sdrhip_fm_bank_run(sdrhip_fm_bank *b, void *stream, const uint8_t *d_in_iq, int64_t s0, int64_t n_in,
                        float *d_audio, int64_t audio_stride, int64_t q0, int64_t q1, void *d_workspace, size_t workspace_bytes);
 /* Routes.  1 = the banked launch: ONE launch of the tuned one-kernel chain (sdrhip_fm_chain_set_small_chain) with a station axis in
@@ -648,13 +648,42 @@ int sdrhip_fm_stream_set_coalesce(sdrhip_fm_stream *st, int samples);
  * audio block then depends on timing; the blocks themselves do not.  0 switches it off.  Call with nothing staged. */
 int sdrhip_fm_stream_set_adaptive(sdrhip_fm_stream *st, int max_samples);
 int sdrhip_fm_stream_pop(sdrhip_fm_stream *st, float *out, int capacity);
+/* A stream over a bank: u8 IQ source blocks in, audio blocks of exactly block_size_out floats out for EVERY station, in lockstep.
+ * Same object type as sdrhip_fm_stream_create gives: push, input_buffer, flush, poll, set_coalesce, set_adaptive, state_bytes,
+ * save, restore and destroy are the same calls and mean the same; counts they return are blocks PER STATION.
+ * Definition: station j's blocks are, bit for bit, those of a sdrhip_fm_stream over a tuned chain of the bank's arguments with
+ * table j, fed the same samples -- whatever the push sizes, coalescing, adaptive submission or route.
+ * Refused like sdrhip_fm_stream_create and at the same point, before any device work: a null argument, max_block_samples not a
+ * multiple of the seam block, block_size_out <= 0.
+ * A submission is ONE run of the bank on [carried tail | staged samples]: the bank's own rule (sdrhip_fm_bank_set_route) picks
+ * the banked launch or station by station, so a push of more than 39322 outputs per station goes station by station; a run the
+ * bank refuses (route 1 where the banked launch does not fit) makes the push fail with nothing written and nothing to pop.
+ * Slots, the default adaptive cap and the SDRHIP_* knobs are the chain stream's.  Routes: a stream of more than one station NEVER
+ * runs in place -- with K stations in the grid every station's workgroups would fetch the same tile over the link, K times the
+ * traffic -- so every submission up to the direct bound is one copy on the slot's stream and one launch on device memory, a lone
+ * source block included.  Measured (tools/fm_bank_stream_bench.py, profiles/fm_bank_stream_bench.txt: lone-block pushes, in place
+ * against the copy, 2 / 4 / 8 / 12 stations): at no K is in place ahead of the copy by more than the spread of the rounds -- its
+ * medians are lower (4.2 .. 4.7 against 5.9 .. 8.8 us per push), but every in-place series holds a round slower than the copy's
+ * fastest -- so no in-place region is kept.  A one-station bank's stream follows the chain's rule.
+ * The bank must outlive the stream and must not be run by another caller meanwhile. */
+int sdrhip_fm_stream_create_bank(sdrhip_fm_stream **st, sdrhip_fm_bank *bank, int max_block_samples, int block_size_out);
+int sdrhip_fm_stream_rows(const sdrhip_fm_stream *st);      /* 1 for a chain's stream, the number of stations for a bank's */
+/* Pops up to max_blocks complete audio blocks of every station: station j's nb * block_size_out floats go to
+ * out + j * row_stride (row_stride >= max_blocks * block_size_out is checked before anything is written).
+ * Returns nb >= 0.  Works on a chain's stream too (one row).  sdrhip_fm_stream_pop keeps its meaning on streams of one row (a bank
+ * of one station included); on a stream of more rows it returns SDRHIP_ERR_ARG and pops nothing. */
+int sdrhip_fm_stream_pop_rows(sdrhip_fm_stream *st, float *out, int64_t row_stride, int max_blocks);
 /* Checkpoint / resume.  Between two pushes the operator's state is the stream position, the last ~4k input samples and
  * the audio not yet popped (the reference keeps the equivalent in Pipe closures: overlap remainder, resampler phase, last
  * demod sample, output fill level -- Filter.hs:536-727, Demod.hs:21-38); everything else is a closed form of the position.
  * state_bytes: drains the operator (like flush) and returns the exact size the save that follows needs (0 = the drain failed);
  * save: drains the operator and writes the state (*used = its size);
  * restore: into a freshly created stream over a chain of the same taps and block sizes; returns the number of audio blocks
- * ready to pop.  A restored stream fed the remaining samples yields the audio the uninterrupted stream would have. */
+ * ready to pop.  A restored stream fed the remaining samples yields the audio the uninterrupted stream would have.
+ * A stream of several stations saves a state of its own version that carries the station count and, per station, the audio not
+ * yet popped (the same count for every station); a one-row stream's state is byte for byte what it always was.  A state is
+ * refused (SDRHIP_ERR_ARG, nothing changed) by a stream whose station count, block_size_out, seam block or halo differs.
+ * Oscillator tables are no part of a state: a station's phase is a closed form of the position. */
 size_t sdrhip_fm_stream_state_bytes(sdrhip_fm_stream *st);   /* not const: it drains (submits, waits, moves results) */
 int sdrhip_fm_stream_save(sdrhip_fm_stream *st, void *buf, size_t capacity, size_t *used);
 int sdrhip_fm_stream_restore(sdrhip_fm_stream *st, const void *buf, size_t bytes);

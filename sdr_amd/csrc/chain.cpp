@@ -848,8 +848,13 @@ int sdrhip_fm_bank_set_route(sdrhip_fm_bank* b, int route, int64_t max_outputs, 
 
 long long sdrhip_debug_fm_bank_launches(void) { return fm_chain_small_bank_launch_count(); }
 
-int sdrhip_fm_bank_run(sdrhip_fm_bank* b, void* stream, const uint8_t* d_in_iq, int64_t s0, int64_t n_in, float* d_audio, int64_t audio_stride,
-                       int64_t q0, int64_t q1, void* d_workspace, size_t workspace_bytes)
+}  // extern "C"
+
+// One run of a bank; sdrhip_fm_bank_run and the submissions of a bank's host-block stream.  input_over_link: as chain_run_on --
+// d_in_iq is pinned HOST memory, so the one-kernel chain takes its largest tile on either route (a tile_outputs beyond the
+// kernel's largest is clamped to it by the launcher; a negative one would mean "chosen from the work" to the banked launcher)
+static int bank_run(sdrhip_fm_bank* b, void* stream, const uint8_t* d_in_iq, int64_t s0, int64_t n_in, float* d_audio, int64_t audio_stride,
+                    int64_t q0, int64_t q1, void* d_workspace, size_t workspace_bytes, bool input_over_link)
 {
     SDRHIP_REQUIRE(b != nullptr, "sdrhip_fm_bank_run");
     SDRHIP_REQUIRE(q1 >= q0 && q0 >= 0 && s0 >= 0 && n_in >= 0, "sdrhip_fm_bank_run");
@@ -863,7 +868,8 @@ int sdrhip_fm_bank_run(sdrhip_fm_bank* b, void* stream, const uint8_t* d_in_iq, 
     // the receptive field of [q0, q1) does not depend on a table: checked once, before either route launches anything
     int rc;
     if ((rc = input_holds("sdrhip_fm_bank_run", plan_run(c0, s0, q0, q1, d_in_iq, d_workspace), s0, n_in, q0, q1)) != SDRHIP_OK) return rc;
-    const bool fits = chain_small_fits(c0, d_in_iq, s0) && fm_chain_small_bank_fits(q0, q1, K, b->tile);
+    const int tile = b->tile != 0 ? b->tile : (input_over_link ? 1 << 20 : 0);
+    const bool fits = chain_small_fits(c0, d_in_iq, s0) && fm_chain_small_bank_fits(q0, q1, K, tile);
     if (b->route == 1 && !fits) {
         set_error("sdrhip_fm_bank_run: the banked launch does not fit this run (decimator / tail shape, seam block, input alignment, "
                   "s0 %% 8, or more than 65535 tiles)");
@@ -876,7 +882,7 @@ int sdrhip_fm_bank_run(sdrhip_fm_bank* b, void* stream, const uint8_t* d_in_iq, 
             return rc;
         if (b->d_tables == nullptr && (rc = upload_floats(&b->d_tables, b->h_tables)) != SDRHIP_OK) return rc;
         launch_fm_chain_small_bank(s, d_in_iq, s0, n_in, d_audio, audio_stride, q0, q1, dec.d_plain, dec.last_tap_is_padding() && b->pskip_ok(),
-                                   c0->tail_tables(), b->tile, b->d_tables, K, b->off, b->period);
+                                   c0->tail_tables(), tile, b->d_tables, K, b->off, b->period);
         return launched(SDRHIP_OK);
     }
     // station by station.  What a station's run would refuse is found for ALL stations first (chain_route, the chain's own
@@ -888,9 +894,18 @@ int sdrhip_fm_bank_run(sdrhip_fm_bank* b, void* stream, const uint8_t* d_in_iq, 
             return rc;
     }
     for (int j = 0; j < K; j++)
-        if ((rc = sdrhip_fm_chain_run(b->ch[j], stream, d_in_iq, s0, n_in, d_audio + (int64_t)j * audio_stride, q0, q1, d_workspace, workspace_bytes)) != SDRHIP_OK)
+        if ((rc = chain_run(b->ch[j], stream, d_in_iq, s0, n_in, d_audio + (int64_t)j * audio_stride, q0, q1, d_workspace, workspace_bytes,
+                            input_over_link)) != SDRHIP_OK)
             return rc;
     return SDRHIP_OK;
+}
+
+extern "C" {
+
+int sdrhip_fm_bank_run(sdrhip_fm_bank* b, void* stream, const uint8_t* d_in_iq, int64_t s0, int64_t n_in, float* d_audio, int64_t audio_stride,
+                       int64_t q0, int64_t q1, void* d_workspace, size_t workspace_bytes)
+{
+    return bank_run(b, stream, d_in_iq, s0, n_in, d_audio, audio_stride, q0, q1, d_workspace, workspace_bytes, false);
 }
 
 }  // extern "C"
@@ -912,6 +927,12 @@ int sdrhip_fm_bank_run(sdrhip_fm_bank* b, void* stream, const uint8_t* d_in_iq, 
 //     beat one CPU thread.
 // Results lag at most nslots - 1 submissions (sdrhip_fm_stream_flush drains); with adaptive submission (the default for
 // operators that run in place) a push that finds the next slot still busy is staged behind the earlier ones and leaves with them.
+//
+// The same stream serves a receiver bank (sdrhip_fm_stream_create_bank): rows = the bank's stations.  Position, carried tail,
+// slots, adaptive cap and knobs are the chain stream's -- they depend on no table -- and three things differ: a submission is ONE
+// run of the bank (bank_run: the banked launch or station by station, by the bank's own rule) writing its rows back to back into
+// the slot's result buffer; the engine's harvest regroups them into one fifo per station; and a stream of several rows never
+// runs in place (stream_create says why).
 // ---------------------------------------------------------------------------
 // Round 5: the caller-side copy of a LARGE push into the pinned staging buffer, split over a few threads.  A push of 4096 source
 // blocks is a 64 MiB memcpy: one thread moves ~23 GB/s while the link behind it takes ~45 (profiles/r04_host_stream.txt: 11.4
@@ -1005,7 +1026,9 @@ struct CopyPool {
 }  // namespace
 
 struct sdrhip_fm_stream {
-    sdrhip_fm_chain* c = nullptr;
+    sdrhip_fm_chain* c = nullptr;        // a bank's stream: station 0's chain -- positions, ranges and sizes depend on no table
+    sdrhip_fm_bank* bank = nullptr;      // set: every submission is ONE run of the bank, rows = its stations
+    int rows = 1;
     CopyPool copier;
     int max_block = 0;
     int block_out = 0;
@@ -1040,23 +1063,29 @@ struct sdrhip_fm_stream {
     HostStream eng;
 };
 
-extern "C" {
-
-int sdrhip_fm_stream_create(sdrhip_fm_stream** out, sdrhip_fm_chain* chain, int max_block_samples, int block_size_out)
+// A stream over a chain (bank == nullptr, one row) or over a bank (chain: its station 0); the arguments are checked by the callers
+static int stream_create(const char* who, sdrhip_fm_stream** out, sdrhip_fm_chain* chain, sdrhip_fm_bank* bank, int max_block_samples,
+                         int block_size_out)
 {
-    SDRHIP_REQUIRE(out != nullptr && chain != nullptr && max_block_samples > 0 && block_size_out > 0, "sdrhip_fm_stream_create");
-    SDRHIP_REQUIRE(chain->block == 0 || max_block_samples % chain->block == 0,
-                   "sdrhip_fm_stream_create: blocks must be whole multiples of the chain's seam block");
     *out = nullptr;
     sdrhip_fm_stream* st = new sdrhip_fm_stream();
     st->c = chain;
+    st->bank = bank;
+    st->rows = bank ? (int)bank->ch.size() : 1;
+    st->eng.set_rows(st->rows);
+    // More than one row never runs in place: with K stations in the grid every station's workgroups would fetch the same tile
+    // over the link.  tools/fm_bank_stream_bench.py (profiles/fm_bank_stream_bench.txt), lone-block pushes at 2 / 4 / 8 / 12
+    // stations: in place has the lower medians (4.2 .. 4.7 against 5.9 .. 8.8 us per push) but is at no K ahead of the copy by
+    // more than the spread of the rounds, which is what an in-place region would have needed -- none is kept.
+    // SDRHIP_STAGE_SAMPLES still moves the bound, for that comparison.
+    if (st->rows > 1 && getenv("SDRHIP_STAGE_SAMPLES") == nullptr) st->stage_samples = 0;
     st->max_block = max_block_samples;
     st->block_out = block_size_out;
     // the carried tail never exceeds the receptive field of one audio output (+ the 8-sample alignment of its start)
     const int64_t head_cap = (sdrhip_fm_chain_max_halo(chain) + 8 + 15) / 8 * 8;
     // four slots when even the largest push runs in place (see the struct), else two
     const int slots = (st->direct_ok && head_cap + (int64_t)max_block_samples <= st->direct_samples) ? HostStream::kMaxSlots : 2;
-    if (st->eng.init(slots, 2, head_cap, "sdrhip_fm_stream_create") != SDRHIP_OK) {
+    if (st->eng.init(slots, 2, head_cap, who) != SDRHIP_OK) {
         delete st;
         return SDRHIP_ERR_HIP;
     }
@@ -1076,6 +1105,30 @@ int sdrhip_fm_stream_create(sdrhip_fm_stream** out, sdrhip_fm_chain* chain, int 
     }
     *out = st;
     return SDRHIP_OK;
+}
+
+extern "C" {
+
+int sdrhip_fm_stream_create(sdrhip_fm_stream** out, sdrhip_fm_chain* chain, int max_block_samples, int block_size_out)
+{
+    SDRHIP_REQUIRE(out != nullptr && chain != nullptr && max_block_samples > 0 && block_size_out > 0, "sdrhip_fm_stream_create");
+    SDRHIP_REQUIRE(chain->block == 0 || max_block_samples % chain->block == 0,
+                   "sdrhip_fm_stream_create: blocks must be whole multiples of the chain's seam block");
+    return stream_create("sdrhip_fm_stream_create", out, chain, nullptr, max_block_samples, block_size_out);
+}
+
+int sdrhip_fm_stream_create_bank(sdrhip_fm_stream** out, sdrhip_fm_bank* bank, int max_block_samples, int block_size_out)
+{
+    SDRHIP_REQUIRE(out != nullptr && bank != nullptr && max_block_samples > 0 && block_size_out > 0, "sdrhip_fm_stream_create_bank");
+    SDRHIP_REQUIRE(bank->ch[0]->block == 0 || max_block_samples % bank->ch[0]->block == 0,
+                   "sdrhip_fm_stream_create_bank: blocks must be whole multiples of the bank's seam block");
+    return stream_create("sdrhip_fm_stream_create_bank", out, bank->ch[0], bank, max_block_samples, block_size_out);
+}
+
+int sdrhip_fm_stream_rows(const sdrhip_fm_stream* st)
+{
+    SDRHIP_REQUIRE(st != nullptr, "sdrhip_fm_stream_rows");
+    return st->rows;
 }
 
 void sdrhip_fm_stream_destroy(sdrhip_fm_stream* st) { delete st; }
@@ -1125,7 +1178,13 @@ static int stream_submit(sdrhip_fm_stream* st)
     // (a paced real-time source: the GPU is idle when it arrives) is read in place by the kernel itself.
     const HostStream::Route route = !direct ? HostStream::kCopyEngines
                                   : tail + n >= st->stage_samples ? HostStream::kSlotStream : HostStream::kInPlace;
-    rc = e.submit(route, cs, first, (size_t)(tail + n) * 2, n_out, [&](hipStream_t s, const void* d_in, void* d_out) {
+    // A bank's stream: ONE run of the bank on the same [tail | staged], its rows back to back in the result buffer (the engine's
+    // harvest regroups them per station).  The bank's own rule picks the banked launch or station by station, on the same
+    // workspace: sdrhip_fm_bank_workspace_bytes is the chain's figure.
+    rc = e.submit(route, cs, first, (size_t)(tail + n) * 2, (int64_t)st->rows * n_out, [&](hipStream_t s, const void* d_in, void* d_out) {
+        if (st->bank)
+            return bank_run(st->bank, (void*)s, (const uint8_t*)d_in, keep_from, tail + n, (float*)d_out, n_out, st->q_done, q_new, wsb_buf.p,
+                            wsb_buf.cap, route == HostStream::kInPlace);
         return chain_run(c, (void*)s, (const uint8_t*)d_in, keep_from, tail + n, (float*)d_out, st->q_done, q_new, wsb_buf.p, wsb_buf.cap,
                          route == HostStream::kInPlace);
     });
@@ -1227,6 +1286,10 @@ struct StreamStateHeader {
     int64_t chain_halo;
 };
 constexpr uint32_t kStateMagic = 0x53444d46u;   // "FMDS"
+// A stream of one row writes version 1, byte for byte what it always wrote.  A stream of several rows (over a bank) writes
+// version 2: the same header with `pending` counted PER ROW, then the row count (int64), then the history and every row's audio
+// not yet popped, row after row.  Oscillator tables are no part of a state: a station's phase is a closed form of the position.
+size_t state_header_bytes(const sdrhip_fm_stream* st) { return sizeof(StreamStateHeader) + (st->rows > 1 ? sizeof(int64_t) : 0); }
 }  // namespace
 
 size_t sdrhip_fm_stream_state_bytes(sdrhip_fm_stream* st)
@@ -1234,7 +1297,7 @@ size_t sdrhip_fm_stream_state_bytes(sdrhip_fm_stream* st)
     if (st == nullptr) return 0;
     // exact: drains the operator exactly as sdrhip_fm_stream_save will (0 = the drain failed, sdrhip_last_error)
     if (sdrhip_fm_stream_flush(st) < 0) return 0;
-    return sizeof(StreamStateHeader) + st->eng.state_bytes(st->eng.hist_n, (int64_t)st->eng.pending());
+    return state_header_bytes(st) + st->eng.state_bytes(st->eng.hist_n, (int64_t)st->eng.pending());
 }
 
 int sdrhip_fm_stream_save(sdrhip_fm_stream* st, void* buf, size_t capacity, size_t* used)
@@ -1245,7 +1308,7 @@ int sdrhip_fm_stream_save(sdrhip_fm_stream* st, void* buf, size_t capacity, size
     StreamStateHeader h;
     memset(&h, 0, sizeof h);
     h.magic = kStateMagic;
-    h.version = 1;
+    h.version = st->rows > 1 ? 2 : 1;
     h.N = st->N;
     h.q_done = st->q_done;
     h.head_cap = st->eng.head_cap;
@@ -1254,13 +1317,17 @@ int sdrhip_fm_stream_save(sdrhip_fm_stream* st, void* buf, size_t capacity, size
     h.block_out = st->block_out;
     h.chain_block = st->c->block;
     h.chain_halo = sdrhip_fm_chain_max_halo(st->c);
-    const size_t need = sizeof h + st->eng.state_bytes(h.hist_n, h.pending);
+    const size_t need = state_header_bytes(st) + st->eng.state_bytes(h.hist_n, h.pending);
     if (capacity < need) {
         set_error("sdrhip_fm_stream_save: %zu bytes needed, %zu given", need, capacity);
         return SDRHIP_ERR_ARG;
     }
     memcpy(buf, &h, sizeof h);
-    st->eng.save((unsigned char*)buf + sizeof h);
+    if (st->rows > 1) {
+        const int64_t rows = st->rows;
+        memcpy((unsigned char*)buf + sizeof h, &rows, sizeof rows);
+    }
+    st->eng.save((unsigned char*)buf + state_header_bytes(st));
     *used = need;
     return SDRHIP_OK;
 }
@@ -1272,14 +1339,20 @@ int sdrhip_fm_stream_restore(sdrhip_fm_stream* st, const void* buf, size_t bytes
                    "sdrhip_fm_stream_restore: only into a stream that has not been pushed to");
     StreamStateHeader h;
     memcpy(&h, buf, sizeof h);
-    SDRHIP_REQUIRE(h.magic == kStateMagic && h.version == 1, "sdrhip_fm_stream_restore: not a stream state");
-    SDRHIP_REQUIRE(h.block_out == st->block_out && h.chain_block == st->c->block && h.head_cap == st->eng.head_cap &&
-                       h.chain_halo == sdrhip_fm_chain_max_halo(st->c),
-                   "sdrhip_fm_stream_restore: the state belongs to a stream of another geometry (chain taps / block sizes)");
-    SDRHIP_REQUIRE(h.hist_n >= 0 && h.hist_n <= h.head_cap && h.pending >= 0 && h.N >= h.hist_n && h.q_done >= 0,
+    SDRHIP_REQUIRE(h.magic == kStateMagic && (h.version == 1 || h.version == 2), "sdrhip_fm_stream_restore: not a stream state");
+    int64_t rows = 1;
+    if (h.version == 2) {
+        SDRHIP_REQUIRE(bytes >= sizeof h + sizeof rows, "sdrhip_fm_stream_restore: truncated state");
+        memcpy(&rows, (const unsigned char*)buf + sizeof h, sizeof rows);
+    }
+    SDRHIP_REQUIRE(rows == st->rows && (h.version == 2) == (st->rows > 1) && h.block_out == st->block_out && h.chain_block == st->c->block &&
+                       h.head_cap == st->eng.head_cap && h.chain_halo == sdrhip_fm_chain_max_halo(st->c),
+                   "sdrhip_fm_stream_restore: the state belongs to a stream of another geometry (stations / chain taps / block sizes)");
+    SDRHIP_REQUIRE(h.hist_n >= 0 && h.hist_n <= h.head_cap && h.pending >= 0 && h.pending <= (int64_t)(bytes / sizeof(float)) && h.N >= h.hist_n &&
+                       h.q_done >= 0,
                    "sdrhip_fm_stream_restore: inconsistent state");
-    SDRHIP_REQUIRE(bytes >= sizeof h + st->eng.state_bytes(h.hist_n, h.pending), "sdrhip_fm_stream_restore: truncated state");
-    st->eng.restore((const unsigned char*)buf + sizeof h, h.hist_n, h.pending);
+    SDRHIP_REQUIRE(bytes >= state_header_bytes(st) + st->eng.state_bytes(h.hist_n, h.pending), "sdrhip_fm_stream_restore: truncated state");
+    st->eng.restore((const unsigned char*)buf + state_header_bytes(st), h.hist_n, h.pending);
     st->N = h.N;
     st->q_done = h.q_done;
     return st->ready();
@@ -1288,10 +1361,20 @@ int sdrhip_fm_stream_restore(sdrhip_fm_stream* st, const void* buf, size_t bytes
 int sdrhip_fm_stream_pop(sdrhip_fm_stream* st, float* out, int capacity)
 {
     SDRHIP_REQUIRE(st != nullptr && out != nullptr, "sdrhip_fm_stream_pop");
+    SDRHIP_REQUIRE(st->rows == 1, "sdrhip_fm_stream_pop: a stream of several stations is popped with sdrhip_fm_stream_pop_rows");
     if (st->ready() <= 0) return 0;
     SDRHIP_REQUIRE(capacity >= st->block_out, "sdrhip_fm_stream_pop: capacity smaller than the block");
     st->eng.take((size_t)st->block_out, out);
     return st->block_out;
+}
+
+int sdrhip_fm_stream_pop_rows(sdrhip_fm_stream* st, float* out, int64_t row_stride, int max_blocks)
+{
+    SDRHIP_REQUIRE(st != nullptr && out != nullptr && max_blocks >= 0, "sdrhip_fm_stream_pop_rows");
+    SDRHIP_REQUIRE(row_stride >= (int64_t)max_blocks * st->block_out, "sdrhip_fm_stream_pop_rows: a station's row holds max_blocks blocks");
+    const int nb = st->ready() < max_blocks ? st->ready() : max_blocks;
+    if (nb > 0) st->eng.take_rows((size_t)nb * (size_t)st->block_out, out, row_stride);
+    return nb;
 }
 
 }  // extern "C"

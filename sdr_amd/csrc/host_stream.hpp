@@ -12,6 +12,11 @@
 //     after theirs -- the upload of submission i overlaps the compute of i-1 and the download of i-2.
 // Up to nslots submissions are in flight, so results lag at most nslots - 1 submissions (flush drains); their output floats go
 // into a fifo in submission order.
+//
+// Rows (sdrhip_fm_stream over a receiver bank): an operator of `rows` > 1 outputs writes, per submission, `rows` rows of
+// out_floats / rows floats each into the result buffer, row after row.  Chunk sizes differ from submission to submission, so the
+// harvest regroups them: one fifo per row, each in submission order, all of the same length and read by ONE cursor.  rows == 1
+// (every Pipe, a chain's stream) is the single fifo it always was.
 #pragma once
 #include <string.h>
 
@@ -67,8 +72,17 @@ struct HostStream {
     int64_t head_cap = 0;           // elements of room in front of the staged ones for the carried tail
     std::vector<uint8_t> hist;      // the stream's last hist_n elements (host copy)
     int64_t hist_n = 0;
-    std::vector<float> fifo;        // produced floats not yet popped: contiguous storage + read cursor
+    std::vector<float> fifo;        // produced floats not yet popped: contiguous storage + read cursor (row 0)
     size_t head = 0;
+    int rows = 1;                   // outputs per operator (set before the first submission)
+    std::vector<std::vector<float>> more;    // rows 1 .. rows - 1: as long as `fifo`, read by the same cursor
+    std::vector<float>& row(int r) { return r == 0 ? fifo : more[(size_t)r - 1]; }
+    const std::vector<float>& row(int r) const { return r == 0 ? fifo : more[(size_t)r - 1]; }
+    void set_rows(int n)
+    {
+        rows = n;
+        more.assign((size_t)n - 1, std::vector<float>());
+    }
 
     // nslots = SDRHIP_STREAM_SLOTS, else default_slots; `who` prefixes the error message
     int init(int default_slots, size_t elem_bytes, int64_t head_room, const char* who)
@@ -117,10 +131,16 @@ struct HostStream {
         const Slot& sl = slot[(cur() + 1) % nslots];
         return sl.busy && hipEventQuery(sl.ev) == hipErrorNotReady;
     }
-    size_t pending() const { return fifo.size() - head; }
+    size_t pending() const { return fifo.size() - head; }     // floats PER ROW
     void take(size_t nfloats, float* out)
     {
         memcpy(out, fifo.data() + head, nfloats * sizeof(float));
+        head += nfloats;
+    }
+    // the next nfloats of every row: row r's to out + r * stride
+    void take_rows(size_t nfloats, float* out, int64_t stride)
+    {
+        for (int r = 0; r < rows; r++) memcpy(out + (int64_t)r * stride, row(r).data() + head, nfloats * sizeof(float));
         head += nfloats;
     }
 
@@ -129,11 +149,16 @@ struct HostStream {
         Slot& sl = slot[si];
         if (!sl.busy) return SDRHIP_OK;
         SDRHIP_CHECK_HIP(hipEventSynchronize(sl.ev));
-        if (head > 0 && head == fifo.size()) { fifo.clear(); head = 0; }
-        else if (head > (1u << 20) && head * 2 > fifo.size()) { fifo.erase(fifo.begin(), fifo.begin() + head); head = 0; }   // compact occasionally
-        const size_t old = fifo.size();
-        fifo.resize(old + (size_t)sl.n_out);
-        memcpy(fifo.data() + old, sl.hout.p, (size_t)sl.n_out * sizeof(float));
+        const size_t old_head = head, per_row = (size_t)sl.n_out / (size_t)rows;
+        for (int r = 0; r < rows; r++) {
+            std::vector<float>& f = row(r);
+            head = old_head;                                     // one cursor: every row is compacted the same way
+            if (head > 0 && head == f.size()) { f.clear(); head = 0; }
+            else if (head > (1u << 20) && head * 2 > f.size()) { f.erase(f.begin(), f.begin() + head); head = 0; }   // compact occasionally
+            const size_t old = f.size();
+            f.resize(old + per_row);
+            memcpy(f.data() + old, (const float*)sl.hout.p + (size_t)r * per_row, per_row * sizeof(float));
+        }
         sl.busy = false;
         return SDRHIP_OK;
     }
@@ -215,7 +240,7 @@ struct HostStream {
     }
 
     // Submit the current slot: `first` .. `first + in_bytes` is its [carried tail | staged] in the staging buffer, out_floats
-    // results are expected (none: no launch).  launch(stream, d_in, d_out) enqueues the operator's kernels on `stream` and
+    // results are expected (none: no launch; with rows > 1 the total of all rows, each out_floats / rows long).  launch(stream, d_in, d_out) enqueues the operator's kernels on `stream` and
     // returns an SDRHIP_* code.  The oldest submission is harvested afterwards: its slot is the next to be filled.
     template <class Launch>
     int submit(Route route, hipStream_t cs, const void* first, size_t in_bytes, int64_t out_floats, Launch&& launch)
@@ -263,15 +288,21 @@ struct HostStream {
         return harvest(cur());
     }
 
-    // ---- checkpoint / resume: the history (hist_n elements) and the fifo (floats not yet popped), in this order, behind the
-    // operator's own header
-    size_t state_bytes(int64_t n_hist, int64_t n_pending) const { return (size_t)n_hist * esz + (size_t)n_pending * sizeof(float); }
+    // ---- checkpoint / resume: the history (hist_n elements) and the fifo (floats not yet popped; n_pending of them PER ROW, row
+    // after row), in this order, behind the operator's own header
+    size_t state_bytes(int64_t n_hist, int64_t n_pending) const
+    {
+        return (size_t)n_hist * esz + (size_t)rows * (size_t)n_pending * sizeof(float);
+    }
     unsigned char* save(unsigned char* o) const
     {
         if (hist_n > 0) memcpy(o, hist.data(), (size_t)hist_n * esz);
         o += (size_t)hist_n * esz;
-        if (pending() > 0) memcpy(o, fifo.data() + head, pending() * sizeof(float));
-        return o + pending() * sizeof(float);
+        for (int r = 0; r < rows; r++) {
+            if (pending() > 0) memcpy(o, row(r).data() + head, pending() * sizeof(float));
+            o += pending() * sizeof(float);
+        }
+        return o;
     }
     const unsigned char* restore(const unsigned char* in, int64_t n_hist, int64_t n_pending)
     {
@@ -280,10 +311,13 @@ struct HostStream {
         if (hist_bytes) memcpy(hist.data(), in, hist_bytes);
         in += hist_bytes;
         hist_n = n_hist;
-        fifo.resize((size_t)n_pending);          // (memcpy: the floats need not be aligned inside the caller's buffer)
         head = 0;
-        if (n_pending > 0) memcpy(fifo.data(), in, (size_t)n_pending * sizeof(float));
-        return in + (size_t)n_pending * sizeof(float);
+        for (int r = 0; r < rows; r++) {
+            row(r).resize((size_t)n_pending);    // (memcpy: the floats need not be aligned inside the caller's buffer)
+            if (n_pending > 0) memcpy(row(r).data(), in, (size_t)n_pending * sizeof(float));
+            in += (size_t)n_pending * sizeof(float);
+        }
+        return in;
     }
 };
 

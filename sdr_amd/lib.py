@@ -265,6 +265,9 @@ lib.sdrhip_fm_stream_set_adaptive.argtypes = [_vp, C.c_int]
 lib.sdrhip_fm_stream_input_buffer.argtypes = [_vp]
 lib.sdrhip_fm_stream_input_buffer.restype = _vp
 lib.sdrhip_fm_stream_pop.argtypes = [_vp, _f32p, C.c_int]
+lib.sdrhip_fm_stream_create_bank.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int]
+lib.sdrhip_fm_stream_rows.argtypes = [_vp]
+lib.sdrhip_fm_stream_pop_rows.argtypes = [_vp, _f32p, C.c_int64, C.c_int]
 
 lib.sdrhip_pipe_fir_filter.argtypes = [C.POINTER(_vp), _vp, C.c_int]
 lib.sdrhip_pipe_fir_decimator.argtypes = [C.POINTER(_vp), _vp, C.c_int]
@@ -924,14 +927,32 @@ class FmGraph(_Handle):
 
 
 class FmStream(_Handle):
-    """u8 IQ host blocks in, audio host blocks out: the FM receiver of fm.hs:34-41 as one operator."""
+    """u8 IQ host blocks in, audio host blocks out: the FM receiver of fm.hs:34-41 as one operator.  Over an FmBank
+    (sdrhip_fm_stream_create_bank) every station's audio comes out in lockstep: push, flush, poll and restore then return a list of
+    arrays of shape [stations, block_size_out] -- row j is, bit for bit, the block an FmStream over FmChain(...).set_tuner(tables[j])
+    yields -- where a chain's stream returns a list of [block_size_out] arrays."""
     _destroy = lib.sdrhip_fm_stream_destroy
 
     def __init__(self, chain, max_block_samples, block_size_out=8192):
         super().__init__()
-        self.chain = chain  # keep alive
+        self.chain = chain  # the chain or the bank: keep alive
         self.block_size_out = block_size_out
-        check(lib.sdrhip_fm_stream_create(C.byref(self.h), chain.h, max_block_samples, block_size_out), "sdrhip_fm_stream_create")
+        self.is_bank = isinstance(chain, FmBank)
+        if self.is_bank:
+            check(lib.sdrhip_fm_stream_create_bank(C.byref(self.h), chain.h, max_block_samples, block_size_out), "sdrhip_fm_stream_create_bank")
+        else:
+            check(lib.sdrhip_fm_stream_create(C.byref(self.h), chain.h, max_block_samples, block_size_out), "sdrhip_fm_stream_create")
+
+    def rows(self):
+        """1 for a chain's stream, the number of stations for a bank's."""
+        return check(lib.sdrhip_fm_stream_rows(self.h), "sdrhip_fm_stream_rows")
+
+    def pop_rows(self, max_blocks):
+        """Up to max_blocks blocks of every station at once: an array [rows, nb, block_size_out] (sdrhip_fm_stream_pop_rows)."""
+        rows, n = self.rows(), self.block_size_out
+        o = np.empty((rows, max(max_blocks, 0) * n), np.float32)
+        nb = check(lib.sdrhip_fm_stream_pop_rows(self.h, _fp(o), o.shape[1], max_blocks), "sdrhip_fm_stream_pop_rows")
+        return o[:, : nb * n].reshape(rows, nb, n)
 
     def set_coalesce(self, samples):
         check(lib.sdrhip_fm_stream_set_coalesce(self.h, samples), "sdrhip_fm_stream_set_coalesce")
@@ -940,6 +961,11 @@ class FmStream(_Handle):
         check(lib.sdrhip_fm_stream_set_adaptive(self.h, max_samples), "sdrhip_fm_stream_set_adaptive")
 
     def _pop(self, ready):
+        if self.is_bank:
+            if ready <= 0:
+                return []
+            got = self.pop_rows(ready)
+            return [np.ascontiguousarray(got[:, k]) for k in range(got.shape[1])]
         outs = []
         for _ in range(ready):
             o = np.empty(self.block_size_out, np.float32)
