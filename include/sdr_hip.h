@@ -277,6 +277,52 @@ int64_t sdrhip_debug_set_tuner_chunk(int64_t samples);
  * cos / sin are the double-precision library functions of an angle in (0, pi/4), rounded once to float32. */
 int sdrhip_tuner_shift_table(int64_t num, int64_t den, float *osc_iq /* den pairs */);
 
+/* ---- Tuner bank: every channel of one capture as complex baseband rows ------------ */
+/* K tuners of the same decimator, each with an oscillator table of its own, over ONE input.
+ * Definition: channel j's row is d_out + j * out_stride floats; it holds outputs [k_begin, k_end) as (re, im) pairs and equals, bit
+ * for bit, what sdrhip_tuner_run / sdrhip_tuner_run_u8 writes for the same (d_in, in_base, k_begin, k_end, seam_block) from a
+ * sdrhip_tuner created with (order, factor, coeffs, ncoeffs, osc_iq[j], periods[j]) -- on every route of the bank, for every
+ * seam_block, in_base, cut into launches and out_stride.  Nothing new is argued: the (*) parity and the One / Cross rule are the
+ * tuner's.  Floats of d_out outside the K rows' [0, 2 (k_end - k_begin)) are not touched.
+ * Create: tables and periods as sdrhip_fm_bank_create -- copied, period 1 .. 65536, every entry finite, 1 .. 32 channels; a channel
+ * on the centre frequency takes the table {1, 0}.  SDRHIP_ERR_ARG (and *b = NULL) for whatever sdrhip_tuner_create refuses, a null
+ * table pointer, a channel count outside 1 .. 32 and a non-finite table entry.
+ * Run: SDRHIP_ERR_ARG before any device work, with nothing written, for whatever sdrhip_tuner_run refuses, out_stride <
+ * 2 (k_end - k_begin) with more than one channel, an odd out_stride (rows stay 8-byte aligned) and route 1 forced on a launch the
+ * banked kernel does not serve.  An empty range is SDRHIP_OK.  Asynchronous on `stream`; after the first run a run makes no
+ * allocation, no host synchronisation and no host-to-device copy on the banked route (each channel's phase at the launch's first
+ * sample and the row stride travel in the kernel's arguments).  A bank is immutable after create (but for set_route) and may be
+ * shared by host threads; it belongs to the device of its first run. */
+#define SDRHIP_TUNER_BANK_MAX_CHANNELS 32
+typedef struct sdrhip_tuner_bank sdrhip_tuner_bank;
+int sdrhip_tuner_bank_create(sdrhip_tuner_bank **b, int order, int factor, const float *coeffs, int ncoeffs, int channels,
+                             const float *const *osc_iq, const int *periods);
+void sdrhip_tuner_bank_destroy(sdrhip_tuner_bank *b);
+int sdrhip_tuner_bank_channels(const sdrhip_tuner_bank *b);
+int sdrhip_tuner_bank_period(const sdrhip_tuner_bank *b, int channel);
+int sdrhip_tuner_bank_num_coeffs(const sdrhip_tuner_bank *b);    /* numCoeffsD */
+int sdrhip_tuner_bank_factor(const sdrhip_tuner_bank *b);
+int sdrhip_tuner_bank_run(const sdrhip_tuner_bank *b, void *stream, const float *d_in, int64_t in_base, float *d_out,
+                          int64_t out_stride, int64_t k_begin, int64_t k_end, int64_t seam_block);
+int sdrhip_tuner_bank_run_u8(const sdrhip_tuner_bank *b, void *stream, const uint8_t *d_in_iq, int64_t in_base, float *d_out,
+                             int64_t out_stride, int64_t k_begin, int64_t k_end, int64_t seam_block);
+/* Routes (same bits).  1 = the banked launch: the tuner's fused tile kernel with a channel axis, one launch for all channels (and one
+ * fix-up launch for all channels where the tuner's fused route takes one) -- the shapes of the tuner's route 1: AVX order, factor
+ * 4 / 8 / 16, up to 128 prepared taps, seam_block >= 0, a 16-byte aligned first window; a launch outside that is SDRHIP_ERR_ARG.
+ * 2 = channel by channel: sdrhip_tuner_run of the bank's own K tuners (their route auto) one after the other on the caller's stream.
+ * 0 = auto (default): the banked launch where it fits AND the launch lies in the part of the measured rectangle where the banked
+ * launch's slowest round was below the K tuner runs' fastest (tools/tuner_bank_bench.py, profiles/tuner_bank_bench.txt: 1 / 2 / 4 /
+ * 8 / 12 / 32 channels x launches of 8192, 2^17, 2^20 and 2^24 input samples, 128 taps / 8, u8 and cfloat input, 7 rounds); everything
+ * else, and everything outside that rectangle, goes channel by channel.  The rule, with n = (k_end - k_begin) * factor the input
+ * samples of the launch:
+ *     banked  iff  channels >= 2  and  n <= 2^24                                  (u8 and cfloat input alike)
+ * Every measured point with K >= 2 is banked by that criterion, so both bounds are edges of the rectangle, not crossovers.  One channel
+ * is one launch either way and was NOT level for cfloat input (8.1 against 7.6 us at 8192 samples, 37.0 against 35.1 at 2^24): it goes
+ * to its tuner.  Launches of the other factors and of fewer taps, and launches shorter than 8192 samples, are held to the same bound
+ * in input samples (no more arithmetic per sample, no less launch-bound); nothing beyond 2^24 samples per launch is measured. */
+int sdrhip_tuner_bank_set_route(sdrhip_tuner_bank *b, int route);   /* 0 auto, 1 banked launch, 2 channel by channel */
+long long sdrhip_debug_tuner_bank_launches(void);                   /* banked launches, process-wide */
+
 /* ---- Resampler (Filter.hs:137-144; constructors :408-502) ---------------- */
 typedef struct sdrhip_resampler sdrhip_resampler;
 int sdrhip_resampler_create(sdrhip_resampler **r, int order, int data_complex, int interpolation,

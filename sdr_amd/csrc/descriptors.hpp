@@ -101,9 +101,30 @@ struct TunerDesc {
 int tuner_run(const TunerDesc* t, hipStream_t s, const void* d_in, bool in_u8, int64_t in_base, float* d_out, int64_t k_begin,
               int64_t k_end, int64_t seam_block);
 
+// The tuner bank (include/sdr_hip.h): K tuners of the same decimator over one input.  The bank OWNS those K tuner descriptors -- they
+// ARE the channel-by-channel route -- and, for the banked launch (kernels_tuner_bank.hip), one device copy of all the tables back to
+// back; the banked launch takes its taps from channel 0's FirDesc (every channel's are the same).  Immutable after create except for
+// the route, so host threads may share one.
+struct TunerBankDesc {
+    std::vector<TunerDesc*> ch;                // channel j as a tuner
+    std::vector<float> h_tables;               // every table, back to back
+    int off[kTunerBankMaxChannels] = {0};      // channel j's first (re, im) pair in h_tables / d_tables
+    int period[kTunerBankMaxChannels] = {0};
+    mutable float* d_tables = nullptr;         // made by the first banked run
+    mutable int route = 0;                     // 0 = auto, 1 = banked, 2 = channel by channel
+    int ensure_device() const;                 // channel 0's taps and the tables
+    TunerBankDesc() = default;
+    ~TunerBankDesc();
+    TunerBankDesc(const TunerBankDesc&) = delete;
+    TunerBankDesc& operator=(const TunerBankDesc&) = delete;
+};
+int tuner_bank_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, bool in_u8, int64_t in_base, float* d_out, int64_t out_stride,
+                   int64_t k_begin, int64_t k_end, int64_t seam_block);
+
 }  // namespace sdrhip
 
 struct sdrhip_filter : sdrhip::FirDesc {};
 struct sdrhip_decimator : sdrhip::FirDesc {};
 struct sdrhip_resampler : sdrhip::ResampDesc {};
 struct sdrhip_tuner : sdrhip::TunerDesc {};
+struct sdrhip_tuner_bank : sdrhip::TunerBankDesc {};

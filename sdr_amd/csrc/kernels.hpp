@@ -324,5 +324,15 @@ bool tuner_fused_fits(const Geom& g, int P, bool has_cross_taps, const void* d_i
 // two-pass route, first pass: d_out[i] = mixed sample i of d_in (cfloat or u8 IQ), i < n < 2^31; ph0 = phase of sample 0
 void launch_tuner_mix(hipStream_t s, const void* d_in, bool in_is_u8, float* d_out, int64_t n, const float* d_osc, int period, int ph0);
 long long tuner_fused_launch_count();   // diagnostics: launches of the fused tile kernel
+// kernels_tuner_bank.hip: the tuner bank (sdrhip_tuner_bank_run) -- `channels` tuners of ONE decimator over ONE input in one launch of
+// the fused tile kernel with a channel axis (flat grid, the channel fastest).  d_tables holds every channel's oscillator table,
+// channel j's `periods[j]` (re, im) pairs from pair offsets[j] on; its outputs go to d_out + j * out_stride floats (out_stride even,
+// and at least 2 g.count when there is more than one channel).  Shapes, taps and Cross outputs as launch_tuner_fused, fit predicate
+// tuner_fused_fits; false = not this shape, nothing launched.  A launch counts once, its fix-up launch not at all.
+constexpr int kTunerBankMaxChannels = 32;
+bool launch_tuner_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in,
+                       bool in_is_u8, float* d_out, int64_t out_stride, const float* d_tables, int channels, const int* offsets,
+                       const int* periods);
+long long tuner_bank_launch_count();    // diagnostics: banked launches
 
 }  // namespace sdrhip

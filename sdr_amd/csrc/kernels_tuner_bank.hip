@@ -1,0 +1,224 @@
+// kernels_tuner_bank.hip -- the tuner bank (sdrhip_tuner_bank_run): K tuners of the same decimator over ONE input in one launch.
+//
+// k_tuner_bank_c4 is k_tuner_c4 (kernels_tuner.hip) with a channel axis: tile geometry, raw loads, mixing loader (tuner_mix.hpp), MAC
+// walk, fold and in-tile Cross outputs are that kernel's, line for line; a channel index j selects the table (osc + off[j],
+// period[j] entries), the phase of the launch's first sample (ph[j] = (k_begin D) mod period[j], the host's one 64-bit modulo per
+// channel and launch) and the output row (out + j * out_stride), nothing else.  The per-channel values travel in the kernel's
+// arguments (BankChannels, 400 bytes, as BankStations of kernels_small.hip): j is uniform over the workgroup, so they are scalar loads
+// from the argument segment, and a run needs no host-to-device copy.
+//
+// Dispatch order: a flat 1-D grid of tiles * K workgroups, channel = b % K the FASTEST axis, tile = b / K.  The K workgroups that read
+// one input tile are handed out back to back, so the tile comes from HBM once and the other K - 1 readers find it in the Infinity
+// Cache while it is fresh there; a 1-D grid has no 65535 limit (a launch of 2^31 outputs x 32 channels is 2^27 workgroups).
+// k_tuner_c4's XCD-aware permutation of blockIdx.x is DROPPED here: it was derived for a grid without a channel axis (XCD = b % 8
+// takes 8 consecutive tiles of every 64), and with the channel in the low bits of b the XCD of a workgroup is (tile K + j) % 8 -- for
+// K a multiple of 8 every channel already stays on one XCD and walks consecutive tiles there, which is what the permutation was
+// for.  No re-derived order was tried and the dropped one was not measured against: the figures of profiles/tuner_bank_bench.txt are
+// of this plain order.
+//
+// Output stores: 16-byte stores where the ROW's pointer is 16-byte aligned, else 8-byte ones -- with out_stride = 2 (mod 4) every
+// odd row is only 8-byte aligned whatever the base is.
+//
+// Cross outputs of launches too long to compute them in the tile: k_tuner_bank_crossfix, k_tuner_crossfix's body with the same
+// channel axis (block b: channel b % K, slots of block b / K), one launch for all channels over seam_span(g).
+#include "decimate_tile.hpp"
+#include "tuner_mix.hpp"
+
+namespace sdrhip {
+
+static std::atomic<long long> g_tuner_bank_launches{0};
+long long tuner_bank_launch_count() { return g_tuner_bank_launches.load(); }
+
+namespace {
+
+struct BankChannels {
+    int64_t out_stride;                        // floats between the channels' output rows
+    int channels;
+    int off[kTunerBankMaxChannels];            // first entry of the channel's table, in (re, im) pairs
+    int period[kTunerBankMaxChannels];
+    int ph[kTunerBankMaxChannels];             // (k_begin D) mod period: the host's one 64-bit modulo per channel and launch
+};
+
+template <int D, int P, int R, int NT, bool U8, int TC, bool GUARD>
+__global__ void __launch_bounds__(NT) k_tuner_bank_c4(const void* __restrict__ in, int64_t x0 /* sample index of output 0's window in `in` */,
+                                                      int count, const float* __restrict__ taps /* plain */, float* __restrict__ out,
+                                                      int p_eff /* GUARD: taps of the filter (multiple of TC, <= P) */,
+                                                      int inl_seam /* > 0: compute the Cross outputs of buffers this long HERE */,
+                                                      int inl_r0 /* window start of output 0 inside its buffer */,
+                                                      const float2* __restrict__ osc /* every table */, BankChannels bank)
+{
+    using T = Tile<D, P, R, NT>;
+    using St = Stage<T, U8, NT>;
+    constexpr int NP = 4, ORD = 0;                           // the AVX "RC" order
+    extern __shared__ __attribute__((aligned(16))) unsigned char tuner_bank_smem[];
+    float2* lds = reinterpret_cast<float2*>(tuner_bank_smem);
+
+    const int ntiles = (count + T::OUTS - 1) / T::OUTS;
+    const unsigned nch = (unsigned)bank.channels;
+    const unsigned j = blockIdx.x % nch;
+    const int tile = (int)(blockIdx.x / nch);
+    if (tile >= ntiles) return;
+    osc += bank.off[j];
+    out += (int64_t)j * bank.out_stride;
+
+    const int out0 = tile * T::OUTS;
+    const int64_t s0 = (int64_t)out0 * D;                     // first sample of the tile, relative to x0
+    {
+        St st;
+        const int64_t total_avail = (int64_t)(count - 1) * D + (GUARD ? p_eff : P);      // samples that exist from x0 on
+        const int64_t av = total_avail - s0;
+        st.load(in, x0 + s0, av > T::SPAN ? T::SPAN : (int)av);
+        const uint32_t n = (uint32_t)bank.period[j];
+        constexpr uint32_t TS = (uint32_t)T::OUTS * D;
+        const uint32_t ph = ((uint32_t)bank.ph[j] + (((uint32_t)tile % n) * (TS % n)) % n + (uint32_t)(threadIdx.x * St::SPV)) % n;
+        tuner_store<T, U8, NT>(st.r, lds, osc, n, ph);
+    }
+    __syncthreads();
+
+    const float2* win = lds + T::lds_idx(threadIdx.x * T::CHUNK);
+    float2 acc[R][NP];
+#pragma unroll
+    for (int r = 0; r < R; r++)
+#pragma unroll
+        for (int k = 0; k < NP; k++) acc[r][k] = make_float2(0.0f, 0.0f);
+    mac_window<D, P, R, T, TC, GUARD, NP, 0>(win, taps, acc, GUARD ? p_eff / TC : 0);
+
+    const int o = out0 + threadIdx.x * R;
+    float2 res[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) res[r] = fold_partials<NP, ORD>(acc[r]);
+    if (inl_seam > 0) {
+        // as decimate_c4_tile: outputs whose window straddles a multiple of inl_seam, sequential order from the same LDS tile
+        const int plen = GUARD ? p_eff : P;
+        const int rt = (int)(((int64_t)inl_r0 + s0) % inl_seam);
+        bool cross[R];
+        bool any = false;
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            int rr = rt + (threadIdx.x * R + r) * D;
+            if (rr >= inl_seam) rr -= inl_seam;
+            cross[r] = rr + plen > inl_seam;
+            any |= cross[r];
+        }
+        if (any) inline_cross_outputs<D, R, T, TC, GUARD>(win, taps, plen, cross, res);
+    }
+    // the ROW's pointer decides: an odd row of a stride that is 2 (mod 4), or a launch cut at an odd output, takes the float2 stores
+    if (R % 2 == 0 && o + R <= count && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
+        float4* dst = reinterpret_cast<float4*>(out + 2 * (int64_t)o);
+#pragma unroll
+        for (int r = 0; r + 1 < R; r += 2) dst[r / 2] = make_float4(res[r].x, res[r].y, res[r + 1].x, res[r + 1].y);
+    } else {
+#pragma unroll
+        for (int r = 0; r < R; r++)
+            if (o + r < count) *reinterpret_cast<float2*>(out + 2 * (int64_t)(o + r)) = res[r];
+    }
+}
+
+// Cross outputs of every channel, one thread per candidate slot of a seam and channel (k_tuner_crossfix with the channel axis)
+template <bool U8>
+__global__ void __launch_bounds__(256) k_tuner_bank_crossfix(Geom g, const float* __restrict__ xtaps, const void* __restrict__ in,
+                                                              float* __restrict__ out, int64_t first_seam, int nseams, int per_seam,
+                                                              const float2* __restrict__ osc, BankChannels bank)
+{
+    const unsigned nch = (unsigned)bank.channels;
+    const unsigned c = blockIdx.x % nch;
+    const int t = (int)(blockIdx.x / nch) * (int)blockDim.x + (int)threadIdx.x;
+    if (t >= nseams * per_seam) return;
+    osc += bank.off[c];
+    out += (int64_t)c * bank.out_stride;
+    const int si = t / per_seam, ci = t - si * per_seam;
+    const int64_t edge = (first_seam + si) * g.seamBI;
+    const int64_t m = (edge + g.D - 1) / g.D - 1 - ci;
+    if (m < g.k_begin || m >= g.k_begin + g.count) return;
+    const int64_t v = m * g.D;
+    if (!(v < edge && v + g.Lp > edge)) return;
+    const uint32_t n = (uint32_t)bank.period[c];
+    uint32_t ph = (uint32_t)((uint64_t)v % n);
+    float re = 0.0f, im = 0.0f;
+    for (int j = 0; j < g.Lp; j++) {
+        float2 x;
+        if constexpr (U8) {
+            const uchar2 u = reinterpret_cast<const uchar2*>(in)[v - g.in_base + j];
+            x = tuner_u8(u.x, u.y);
+        } else {
+            x = reinterpret_cast<const float2*>(in)[v - g.in_base + j];
+        }
+        const float2 mx = tuner_mul(x, osc[ph]);
+        ph = wrap_inc(ph, n);
+        re = re + mx.x * xtaps[j];
+        im = im + mx.y * xtaps[j];
+    }
+    *reinterpret_cast<float2*>(out + 2 * (m - g.k_begin)) = make_float2(re, im);
+}
+
+template <int D, int P, bool U8, int TC, bool GUARD>
+void launch_tuner_bank_c4(hipStream_t s, const Geom& g, const float* taps, const void* in, float* out, bool inline_cross, bool* inlined,
+                          const float* d_tables, const BankChannels& bank)
+{
+    constexpr int R = 2, NT = 256;
+    using T = Tile<D, P, R, NT>;
+    // the dynamic-LDS attribute is per device: one flag per (instantiation, device); idempotent, a race only repeats the call
+    static std::atomic<bool> attr_set[64];
+    auto kern = k_tuner_bank_c4<D, P, R, NT, U8, TC, GUARD>;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::LDS_BYTES);
+        if (dev >= 0 && dev < 64) attr_set[dev] = true;
+    }
+    const int tiles = (g.count + T::OUTS - 1) / T::OUTS;       // at most 2^22: tiles * channels fits a 1-D grid
+    const unsigned grid = (unsigned)tiles * (unsigned)bank.channels;
+    const int64_t x0 = g.k_begin * D - g.in_base;
+    int inl_seam = 0, inl_r0 = 0;
+    if (inline_cross && g.seamBI >= (int64_t)T::OUTS * D + g.Lp && g.seamBI < (1 << 30)) {   // a tile spans less than one buffer
+        inl_seam = (int)g.seamBI;
+        inl_r0 = (int)((g.k_begin * D) % g.seamBI);
+    }
+    *inlined = inl_seam > 0;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), T::LDS_BYTES, s, in, x0, g.count, taps, out, g.Lp, inl_seam, inl_r0,
+                       reinterpret_cast<const float2*>(d_tables), bank);
+}
+
+}  // namespace
+
+bool launch_tuner_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in,
+                       bool in_is_u8, float* d_out, int64_t out_stride, const float* d_tables, int channels, const int* offsets,
+                       const int* periods)
+{
+    if (channels < 1 || channels > kTunerBankMaxChannels || (out_stride & 1) != 0) return false;
+    if (channels > 1 && out_stride < 2 * (int64_t)g.count) return false;
+    for (int j = 0; j < channels; j++)
+        if (!tuner_fused_fits(g, P, d_cross_taps != nullptr, d_in, in_is_u8, d_out, periods[j])) return false;
+    BankChannels bank = {};
+    bank.out_stride = out_stride;
+    bank.channels = channels;
+    for (int j = 0; j < channels; j++) {
+        bank.off[j] = offsets[j];
+        bank.period[j] = periods[j];
+        bank.ph[j] = (int)((g.k_begin * g.D) % periods[j]);
+    }
+    // launch-bound sizes compute their Cross outputs inside the tile kernel: launch_tuner_fused's decision
+    const bool inl = g.seamBI > 0 && g.count <= 5 * (int64_t)small_launch_outputs();
+    bool inlined = false;
+#define TUNER_BANK(DV, TCV, GV) do { if (in_is_u8) launch_tuner_bank_c4<DV, 128, true, TCV, GV>(s, g, d_plain_taps, d_in, d_out, inl, &inlined, d_tables, bank); \
+                                     else launch_tuner_bank_c4<DV, 128, false, TCV, GV>(s, g, d_plain_taps, d_in, d_out, inl, &inlined, d_tables, bank); } while (0)
+    if (g.D == 4) TUNER_BANK(4, 4, true);
+    else if (g.D == 16) { if (P % 8 == 0) TUNER_BANK(16, 8, true); else TUNER_BANK(16, 4, true); }
+    else if (P == 128) TUNER_BANK(8, 8, false);      // the exact-length walk for the full 128 taps
+    else if (P % 8 == 0) TUNER_BANK(8, 8, true);
+    else TUNER_BANK(8, 4, true);
+#undef TUNER_BANK
+    g_tuner_bank_launches.fetch_add(1, std::memory_order_relaxed);
+
+    const SeamSpan sp = seam_span(g);
+    if (sp.nseams > 0 && !inlined) {
+        const unsigned per_channel = (unsigned)(((int64_t)sp.nseams * sp.per + 255) / 256);
+        const dim3 grid(per_channel * (unsigned)channels), block(256);
+        const float2* o2 = reinterpret_cast<const float2*>(d_tables);
+        if (in_is_u8) hipLaunchKernelGGL(k_tuner_bank_crossfix<true>, grid, block, 0, s, g, d_cross_taps, d_in, d_out, sp.first, sp.nseams, sp.per, o2, bank);
+        else hipLaunchKernelGGL(k_tuner_bank_crossfix<false>, grid, block, 0, s, g, d_cross_taps, d_in, d_out, sp.first, sp.nseams, sp.per, o2, bank);
+    }
+    return true;
+}
+
+}  // namespace sdrhip

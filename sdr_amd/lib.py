@@ -106,6 +106,18 @@ lib.sdrhip_debug_tuner_fused_launches.argtypes = []
 lib.sdrhip_debug_tuner_fused_launches.restype = C.c_longlong
 lib.sdrhip_debug_set_tuner_chunk.argtypes = [_i64]
 lib.sdrhip_debug_set_tuner_chunk.restype = _i64
+lib.sdrhip_tuner_bank_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int, _f32p, C.c_int, C.c_int, C.POINTER(_f32p), C.POINTER(C.c_int)]
+lib.sdrhip_tuner_bank_destroy.argtypes = [_vp]
+lib.sdrhip_tuner_bank_destroy.restype = None
+lib.sdrhip_tuner_bank_channels.argtypes = [_vp]
+lib.sdrhip_tuner_bank_period.argtypes = [_vp, C.c_int]
+lib.sdrhip_tuner_bank_num_coeffs.argtypes = [_vp]
+lib.sdrhip_tuner_bank_factor.argtypes = [_vp]
+lib.sdrhip_tuner_bank_run.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64]
+lib.sdrhip_tuner_bank_run_u8.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64]
+lib.sdrhip_tuner_bank_set_route.argtypes = [_vp, C.c_int]
+lib.sdrhip_debug_tuner_bank_launches.argtypes = []
+lib.sdrhip_debug_tuner_bank_launches.restype = C.c_longlong
 
 lib.sdrhip_resampler_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.c_int]
 lib.sdrhip_resampler_num_coeffs.argtypes = [_vp]
@@ -592,6 +604,53 @@ class Tuner(_Handle):
 
     def run_u8(self, d_in, in_base, d_out, k_begin, k_end, seam_block=0, stream=None):
         check(lib.sdrhip_tuner_run_u8(self.h, stream, d_in, in_base, d_out, k_begin, k_end, seam_block), "sdrhip_tuner_run_u8")
+
+
+def tuner_bank_launches():
+    """Banked launches of the tuner bank so far (sdrhip_debug_tuner_bank_launches)."""
+    return int(lib.sdrhip_debug_tuner_bank_launches())
+
+
+class TunerBank(_Handle):
+    """Every channel of one capture as complex baseband rows: K Tuners of the same decimator over ONE input, one launch per run where
+    the banked route fits (sdr_hip.h, sdrhip_tuner_bank_*).  tables: one interleaved float32 (re, im) table per channel
+    (tuner_shift_table builds the usual ones; a channel on the centre frequency takes [1, 0]).  Row j of a run is, bit for bit, what
+    Tuner(factor, coeffs, tables[j], order) writes for the same launch."""
+    _destroy = lib.sdrhip_tuner_bank_destroy
+    ROUTE_AUTO, ROUTE_BANKED, ROUTE_CHANNELS = 0, 1, 2
+    complex = True
+
+    def __init__(self, factor, coeffs, tables, order=ORDER_AVX):
+        super().__init__()
+        c = _f32(coeffs)
+        ts = [_f32(t).reshape(-1) for t in tables]
+        if any(t.size % 2 for t in ts):
+            raise SdrHipError("an oscillator table is interleaved (re, im) pairs")
+        ptrs = (_f32p * max(len(ts), 1))(*[_fp(t) for t in ts])
+        periods = (C.c_int * max(len(ts), 1))(*[t.size // 2 for t in ts])
+        check(lib.sdrhip_tuner_bank_create(C.byref(self.h), order, factor, _fp(c), c.size, len(ts), ptrs, periods), "sdrhip_tuner_bank_create")
+        self.factor = lib.sdrhip_tuner_bank_factor(self.h)
+        self.num_coeffs = lib.sdrhip_tuner_bank_num_coeffs(self.h)
+
+    @property
+    def channels(self):
+        return check(lib.sdrhip_tuner_bank_channels(self.h), "sdrhip_tuner_bank_channels")
+
+    def period(self, channel):
+        return check(lib.sdrhip_tuner_bank_period(self.h, int(channel)), "sdrhip_tuner_bank_period")
+
+    def set_route(self, route):
+        """0 = auto (the banked launch where it fits and was measured ahead of K tuner runs: sdr_hip.h), 1 = the banked launch (a
+        launch it does not serve is an error), 2 = channel by channel."""
+        check(lib.sdrhip_tuner_bank_set_route(self.h, int(route)), "sdrhip_tuner_bank_set_route")
+
+    def run(self, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block=0, stream=None):
+        """cfloat input; channel j's outputs [k_begin, k_end) -> d_out + 4 * j * out_stride bytes."""
+        check(lib.sdrhip_tuner_bank_run(self.h, stream, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block), "sdrhip_tuner_bank_run")
+
+    def run_u8(self, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block=0, stream=None):
+        check(lib.sdrhip_tuner_bank_run_u8(self.h, stream, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block),
+              "sdrhip_tuner_bank_run_u8")
 
 
 class FmChain(_Handle):
