@@ -62,6 +62,7 @@ data SdrResampler
 data SdrFilter
 data SdrPipe
 data SdrTuner
+data SdrTunerBank
 data SdrChain
 data SdrBank
 data SdrStream
@@ -152,6 +153,15 @@ foreign import ccall safe "sdrhip_debug_fm_bank_launches" c_fm_bank_launches :: 
 foreign import ccall safe "sdrhip_fm_stream_create_bank" c_stream_create_bank :: Ptr (Ptr SdrStream) -> Ptr SdrBank -> CInt -> CInt -> IO CInt
 foreign import ccall safe "sdrhip_fm_stream_rows" c_stream_rows :: Ptr SdrStream -> IO CInt
 foreign import ccall safe "sdrhip_fm_stream_pop_rows" c_stream_pop_rows :: Ptr SdrStream -> Ptr CFloat -> Int64 -> CInt -> IO CInt
+-- the tuner bank's Pipe (include/sdr_hip.h, sdrhip_pipe_tuner_bank): cfloat or u8 IQ host blocks in, one row of decimated blocks per
+-- channel out (counts are blocks per channel); pop_rows: channel j's blocks at out + j * row_stride floats.  The bank is made by
+-- sdrhip_tuner_bank_create and must outlive the pipe
+foreign import ccall safe "sdrhip_pipe_tuner_bank"      c_pipe_tuner_bank      :: Ptr (Ptr SdrPipe) -> Ptr SdrTunerBank -> CInt -> CInt -> IO CInt
+foreign import ccall safe "sdrhip_pipe_rows"            c_pipe_rows            :: Ptr SdrPipe -> IO CInt
+foreign import ccall safe "sdrhip_pipe_push_u8"         c_pipe_push_u8         :: Ptr SdrPipe -> Ptr CUChar -> CInt -> IO CInt
+foreign import ccall safe "sdrhip_pipe_input_buffer_u8" c_pipe_input_buffer_u8 :: Ptr SdrPipe -> CInt -> IO (Ptr CUChar)
+foreign import ccall safe "sdrhip_pipe_pop_rows"        c_pipe_pop_rows        :: Ptr SdrPipe -> Ptr CFloat -> Int64 -> CInt -> IO CInt
+foreign import ccall safe "sdrhip_debug_tuner_bank_cross_launches" c_tuner_bank_cross_launches :: IO CLLong
 -- the spectrum operator (include/sdr_hip.h, sdrhip_spectrum_*): interleavedIQUnsigned256ToFloat -> halfBandUp x window -> fftw ->
 -- magnitude x scale, rows of Float
 foreign import ccall safe "sdrhip_spectrum_create"     c_spectrum_create     :: Ptr (Ptr SdrSpectrum) -> CInt -> CInt -> CInt -> Ptr CDouble -> CInt -> CDouble -> IO CInt

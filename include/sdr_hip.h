@@ -322,6 +322,9 @@ int sdrhip_tuner_bank_run_u8(const sdrhip_tuner_bank *b, void *stream, const uin
  * in input samples (no more arithmetic per sample, no less launch-bound); nothing beyond 2^24 samples per launch is measured. */
 int sdrhip_tuner_bank_set_route(sdrhip_tuner_bank *b, int route);   /* 0 auto, 1 banked launch, 2 channel by channel */
 long long sdrhip_debug_tuner_bank_launches(void);                   /* banked launches, process-wide */
+/* launches of the all-Cross kernel of the bank's Pipe (sdrhip_pipe_tuner_bank: the boundary part of a ragged push), process-wide;
+ * sdrhip_tuner_bank_run never takes it */
+long long sdrhip_debug_tuner_bank_cross_launches(void);
 
 /* ---- Resampler (Filter.hs:137-144; constructors :408-502) ---------------- */
 typedef struct sdrhip_resampler sdrhip_resampler;
@@ -829,6 +832,36 @@ int sdrhip_pipe_agc(sdrhip_pipe **p, float mu, float reference);                
  * sdrhip_pipe_fir_decimator; the stream position that selects the oscillator phase is part of the saved state (the table and
  * the taps are the descriptor's, not part of it).  The tuner must outlive the pipe. */
 int sdrhip_pipe_tuner(sdrhip_pipe **p, const sdrhip_tuner *t, int block_size_out);
+/* The tuner bank on host blocks: cfloat blocks (input_u8 = 0) or interleaved u8 IQ blocks (input_u8 = 1) in, every channel's blocks
+ * of exactly block_size_out decimated samples out, in lockstep.
+ * Definition: channel j's blocks equal, bit for bit, those of a sdrhip_pipe_tuner over a sdrhip_tuner of the bank's arguments with
+ * table j, of the same block_size_out, fed the same blocks at the same boundaries -- for a u8 pipe fed (u - 128) * (1 / 128) as
+ * float32, which is exact.  This holds whatever the push sizes, coalescing, adaptive submission or route; nothing new is argued.
+ * Rows: sdrhip_pipe_rows is the bank's channel count (1 for every other pipe).  The counts push / flush / poll / restore return are
+ * blocks PER CHANNEL.  sdrhip_pipe_pop_rows writes up to max_blocks blocks of every row, row j's nb * block_size_out elements to
+ * out + j * row_stride floats, and returns nb; row_stride < max_blocks * block_size_out * (floats per element) is SDRHIP_ERR_ARG
+ * with nothing written.  It serves every filter / decimator / resampler / tuner pipe (one row).  sdrhip_pipe_pop keeps its meaning
+ * on one row (a one-channel bank included); on more rows it is SDRHIP_ERR_ARG and pops nothing.
+ * Input type: a u8 pipe takes sdrhip_pipe_push_u8 / sdrhip_pipe_input_buffer_u8 (n_samples (I, Q) byte pairs), every other pipe
+ * sdrhip_pipe_push / sdrhip_pipe_input_buffer; the wrong call is SDRHIP_ERR_ARG (NULL) with nothing staged.  u8 blocks cross the
+ * link as 2 bytes per sample and are converted in the kernels' loaders.
+ * Submission: equal-sized blocks go out as ONE sdrhip_tuner_bank_run over [carried tail | staged] with the block size as seam_block
+ * (its route rule decides banked or channel by channel); a block of another size as one all-Cross launch for all channels over the
+ * outputs that straddle the boundary (sdrhip_debug_tuner_bank_cross_launches) and one run with seam_block 0 for the rest.  A pipe of
+ * more than one row never reads its input in place over PCIe -- K channels would fetch the same tile over the link K times: up to
+ * 512 KiB a submission is one copy on its slot's stream and the launch behind it, beyond that the copy engines; the copy lands so
+ * that the launch's first window is 16-byte aligned, whatever the block sizes were.  One row follows sdrhip_pipe_tuner's rule.
+ * Coalesce, adaptive (its byte cap counts input bytes: 2 per u8 sample), flush, poll and destroy as for sdrhip_pipe_tuner.
+ * Save / restore: a pipe of more than one row or of u8 input writes a state version of its own -- row count, input type, stream
+ * position, the history in the input's own type and every row's output not yet popped; restore refuses (SDRHIP_ERR_ARG, the pipe
+ * unchanged) a state of another row count, input type, block_size_out, factor or tap count, and a truncated one.
+ * Create: SDRHIP_ERR_ARG (and *p = NULL) before any device work for a null argument, block_size_out <= 0 and input_u8 outside 0 / 1.
+ * The bank must outlive the pipe. */
+int sdrhip_pipe_tuner_bank(sdrhip_pipe **p, const sdrhip_tuner_bank *b, int block_size_out, int input_u8);
+int sdrhip_pipe_rows(const sdrhip_pipe *p);
+int sdrhip_pipe_push_u8(sdrhip_pipe *p, const uint8_t *iq, int n_samples);
+uint8_t *sdrhip_pipe_input_buffer_u8(sdrhip_pipe *p, int n_samples);
+int sdrhip_pipe_pop_rows(sdrhip_pipe *p, float *out, int64_t row_stride, int max_blocks);
 /* Feed one upstream block (n elements: floats, or complex pairs for complex
  * stages).  Returns the number of complete output blocks now ready (>= 0) or a
  * negative error.  A block shorter than numCoeffs is the reference's

@@ -120,6 +120,9 @@ struct TunerBankDesc {
 };
 int tuner_bank_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, bool in_u8, int64_t in_base, float* d_out, int64_t out_stride,
                    int64_t k_begin, int64_t k_end, int64_t seam_block);
+// every output of [k_begin, k_end) Cross, all channels in one launch: the ragged pushes of the bank's Pipe (pipes.cpp)
+int tuner_bank_cross_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, bool in_u8, int64_t in_base, float* d_out,
+                         int64_t out_stride, int64_t k_begin, int64_t k_end);
 
 }  // namespace sdrhip
 

@@ -75,6 +75,9 @@ struct HostStream {
     std::vector<float> fifo;        // produced floats not yet popped: contiguous storage + read cursor (row 0)
     size_t head = 0;
     int rows = 1;                   // outputs per operator (set before the first submission)
+    // Bytes (< 64) the copy routes leave in front of the NEXT submission in the slot's device buffer: the operator's way to put a
+    // window it cares about on a 16-byte boundary there whatever the carried tail's length is.  Back to 0 after every submission.
+    size_t dev_skew = 0;
     std::vector<std::vector<float>> more;    // rows 1 .. rows - 1: as long as `fifo`, read by the same cursor
     std::vector<float>& row(int r) { return r == 0 ? fifo : more[(size_t)r - 1]; }
     const std::vector<float>& row(int r) const { return r == 0 ? fifo : more[(size_t)r - 1]; }
@@ -254,9 +257,9 @@ struct HostStream {
             if (out_floats > 0) {
                 const void* d_in = sl.hin.dev_ptr(first);
                 if (route == kSlotStream) {
-                    if ((rc = sl.din.ensure(in_bytes + 64)) != SDRHIP_OK) return rc;
-                    SDRHIP_CHECK_HIP(hipMemcpyAsync(sl.din.p, first, in_bytes, hipMemcpyHostToDevice, cs));
-                    d_in = sl.din.p;
+                    if ((rc = sl.din.ensure(in_bytes + 64 + dev_skew)) != SDRHIP_OK) return rc;
+                    SDRHIP_CHECK_HIP(hipMemcpyAsync((char*)sl.din.p + dev_skew, first, in_bytes, hipMemcpyHostToDevice, cs));
+                    d_in = (const char*)sl.din.p + dev_skew;
                 }
                 if ((rc = launch(cs, d_in, sl.hout.dev)) != SDRHIP_OK) return rc;
                 sl.n_out = out_floats;
@@ -267,14 +270,14 @@ struct HostStream {
             sl.direct = true;
         } else {
             // the slot's device buffer was last read by submission i - nslots, harvested before the slot was reopened
-            if ((rc = sl.din.ensure(in_bytes + 64)) != SDRHIP_OK) return rc;
-            SDRHIP_CHECK_HIP(hipMemcpyAsync(sl.din.p, first, in_bytes, hipMemcpyHostToDevice, up));
+            if ((rc = sl.din.ensure(in_bytes + 64 + dev_skew)) != SDRHIP_OK) return rc;
+            SDRHIP_CHECK_HIP(hipMemcpyAsync((char*)sl.din.p + dev_skew, first, in_bytes, hipMemcpyHostToDevice, up));
             SDRHIP_CHECK_HIP(hipEventRecord(sl.ev_up, up));
             sl.direct = false;
             if (out_floats > 0) {
                 SDRHIP_CHECK_HIP(hipStreamWaitEvent(cs, sl.ev_up, 0));
                 if ((rc = sl.dout.ensure(out_bytes)) != SDRHIP_OK) return rc;
-                if ((rc = launch(cs, (const void*)sl.din.p, sl.dout.p)) != SDRHIP_OK) return rc;
+                if ((rc = launch(cs, (const void*)((const char*)sl.din.p + dev_skew), sl.dout.p)) != SDRHIP_OK) return rc;
                 SDRHIP_CHECK_HIP(hipEventRecord(sl.ev_k, cs));
                 SDRHIP_CHECK_HIP(hipStreamWaitEvent(down, sl.ev_k, 0));
                 SDRHIP_CHECK_HIP(hipMemcpyAsync(sl.hout.p, sl.dout.p, out_bytes, hipMemcpyDeviceToHost, down));
@@ -285,6 +288,7 @@ struct HostStream {
         }
         pushes++;
         staged = 0;
+        dev_skew = 0;
         return harvest(cur());
     }
 

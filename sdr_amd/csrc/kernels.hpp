@@ -334,5 +334,11 @@ bool launch_tuner_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, 
                        bool in_is_u8, float* d_out, int64_t out_stride, const float* d_tables, int channels, const int* offsets,
                        const int* periods);
 long long tuner_bank_launch_count();    // diagnostics: banked launches
+// Outputs [g.k_begin, g.k_begin + g.count) of every channel in the reference's sequential order, all of them (g.seamBI is not read):
+// the Cross part of a ragged push of the tuner bank's Pipe (pipes.cpp), one thread per (channel, output).  The refusals of
+// launch_tuner_bank for channels and stride, no alignment beyond the element's own; false = refused, nothing launched.
+bool launch_tuner_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_taps, const void* d_in, bool in_is_u8, float* d_out,
+                             int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods);
+long long tuner_bank_cross_launch_count();   // diagnostics: launches of the all-Cross kernel
 
 }  // namespace sdrhip

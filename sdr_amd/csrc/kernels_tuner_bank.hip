@@ -21,6 +21,10 @@
 //
 // Cross outputs of launches too long to compute them in the tile: k_tuner_bank_crossfix, k_tuner_crossfix's body with the same
 // channel axis (block b: channel b % K, slots of block b / K), one launch for all channels over seam_span(g).
+//
+// The bank's Pipe (pipes.cpp): a block of another size than its predecessors has no seam_block, so its submission is the outputs that
+// straddle the boundary (all Cross) and then the outputs inside the block (all One).  k_tuner_bank_cross is the first part for every
+// channel in one launch: k_tuner_bank_crossfix's body over an explicit output range.  sdrhip_tuner_bank_run never takes it.
 #include "decimate_tile.hpp"
 #include "tuner_mix.hpp"
 
@@ -28,6 +32,8 @@ namespace sdrhip {
 
 static std::atomic<long long> g_tuner_bank_launches{0};
 long long tuner_bank_launch_count() { return g_tuner_bank_launches.load(); }
+static std::atomic<long long> g_tuner_bank_cross_launches{0};
+long long tuner_bank_cross_launch_count() { return g_tuner_bank_cross_launches.load(); }
 
 namespace {
 
@@ -151,6 +157,39 @@ __global__ void __launch_bounds__(256) k_tuner_bank_crossfix(Geom g, const float
     *reinterpret_cast<float2*>(out + 2 * (m - g.k_begin)) = make_float2(re, im);
 }
 
+// Outputs [g.k_begin, g.k_begin + g.count) of every channel, ALL of them Cross (the straddlers of a boundary between two blocks of
+// unequal size, which no seam_block describes): k_tuner_bank_crossfix's body on an explicit range instead of a seam's candidate
+// slots.  Block b: channel b % K, outputs of block b / K.
+template <bool U8>
+__global__ void __launch_bounds__(256) k_tuner_bank_cross(Geom g, const float* __restrict__ xtaps, const void* __restrict__ in,
+                                                           float* __restrict__ out, const float2* __restrict__ osc, BankChannels bank)
+{
+    const unsigned nch = (unsigned)bank.channels;
+    const unsigned c = blockIdx.x % nch;
+    const int t = (int)(blockIdx.x / nch) * (int)blockDim.x + (int)threadIdx.x;
+    if (t >= g.count) return;
+    osc += bank.off[c];
+    out += (int64_t)c * bank.out_stride;
+    const int64_t v = (g.k_begin + t) * g.D;
+    const uint32_t n = (uint32_t)bank.period[c];
+    uint32_t ph = (uint32_t)((uint64_t)v % n);
+    float re = 0.0f, im = 0.0f;
+    for (int j = 0; j < g.Lp; j++) {
+        float2 x;
+        if constexpr (U8) {
+            const uchar2 u = reinterpret_cast<const uchar2*>(in)[v - g.in_base + j];
+            x = tuner_u8(u.x, u.y);
+        } else {
+            x = reinterpret_cast<const float2*>(in)[v - g.in_base + j];
+        }
+        const float2 mx = tuner_mul(x, osc[ph]);
+        ph = wrap_inc(ph, n);
+        re = re + mx.x * xtaps[j];
+        im = im + mx.y * xtaps[j];
+    }
+    *reinterpret_cast<float2*>(out + 2 * (int64_t)t) = make_float2(re, im);
+}
+
 template <int D, int P, bool U8, int TC, bool GUARD>
 void launch_tuner_bank_c4(hipStream_t s, const Geom& g, const float* taps, const void* in, float* out, bool inline_cross, bool* inlined,
                           const float* d_tables, const BankChannels& bank)
@@ -218,6 +257,32 @@ bool launch_tuner_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, 
         if (in_is_u8) hipLaunchKernelGGL(k_tuner_bank_crossfix<true>, grid, block, 0, s, g, d_cross_taps, d_in, d_out, sp.first, sp.nseams, sp.per, o2, bank);
         else hipLaunchKernelGGL(k_tuner_bank_crossfix<false>, grid, block, 0, s, g, d_cross_taps, d_in, d_out, sp.first, sp.nseams, sp.per, o2, bank);
     }
+    return true;
+}
+
+bool launch_tuner_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_taps, const void* d_in, bool in_is_u8, float* d_out,
+                             int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods)
+{
+    // launch_tuner_bank's refusals for channels and stride; one thread reads its window sample by sample: no alignment beyond the
+    // element's own
+    if (channels < 1 || channels > kTunerBankMaxChannels || (out_stride & 1) != 0) return false;
+    if (channels > 1 && out_stride < 2 * (int64_t)g.count) return false;
+    if (g.I != 1 || g.count <= 0 || g.k_begin < 0 || g.k_begin * g.D < g.in_base || d_cross_taps == nullptr) return false;
+    if ((reinterpret_cast<uintptr_t>(d_out) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_in) & (in_is_u8 ? 1 : 7)) != 0) return false;
+    BankChannels bank = {};
+    bank.out_stride = out_stride;
+    bank.channels = channels;
+    for (int j = 0; j < channels; j++) {
+        if (periods[j] < 1) return false;
+        bank.off[j] = offsets[j];
+        bank.period[j] = periods[j];
+    }
+    const unsigned per_channel = (unsigned)(((int64_t)g.count + 255) / 256);        // at most 2^23: times 32 channels fits a 1-D grid
+    const dim3 grid(per_channel * (unsigned)channels), block(256);
+    const float2* o2 = reinterpret_cast<const float2*>(d_tables);
+    if (in_is_u8) hipLaunchKernelGGL(k_tuner_bank_cross<true>, grid, block, 0, s, g, d_cross_taps, d_in, d_out, o2, bank);
+    else hipLaunchKernelGGL(k_tuner_bank_cross<false>, grid, block, 0, s, g, d_cross_taps, d_in, d_out, o2, bank);
+    g_tuner_bank_cross_launches.fetch_add(1, std::memory_order_relaxed);
     return true;
 }
 

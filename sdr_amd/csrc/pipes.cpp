@@ -18,6 +18,12 @@
 // kernel launch (seams decided inside it) and one event per push -- the reference's own block sizes (8192 .. 65536 elements)
 // are launch-bound, not bandwidth-bound.  Larger ones go through the copy engines (upload of i over compute of i-1 over
 // download of i-2).  Up to four submissions are in flight, so results lag up to three pushes; sdrhip_pipe_flush() drains.
+//
+// The tuner bank's Pipe (sdrhip_pipe_tuner_bank) is the tuner's Pipe with the engine's rows: one submission computes every
+// channel's outputs into a row-major chunk which the harvest regroups into one fifo per channel.  Its blocks may be u8 IQ (2 bytes
+// per element from the staging buffer to the kernels' loaders).  With more than one row nothing is read in place: up to kDirectBytes
+// a submission is one copy on the slot's stream and the launch behind it, placed in device memory so that the banked launch's first
+// window is 16-byte aligned (HostStream::dev_skew).
 #include <stdlib.h>
 #include <string.h>
 
@@ -28,13 +34,17 @@
 
 using namespace sdrhip;
 
-enum PipeKind { PK_FILTER, PK_DECIMATOR, PK_RESAMPLER, PK_DEMOD, PK_DCBLOCK, PK_AGC, PK_TUNER };
+enum PipeKind { PK_FILTER, PK_DECIMATOR, PK_RESAMPLER, PK_DEMOD, PK_DCBLOCK, PK_AGC, PK_TUNER, PK_TUNER_BANK };
 
 struct sdrhip_pipe {
     PipeKind kind;
     const FirDesc* fir = nullptr;
     const ResampDesc* rs = nullptr;
     const TunerDesc* tuner = nullptr;  // PK_TUNER: the decimator behind the oscillator mix (fir = &tuner->fir)
+    // PK_TUNER_BANK: every channel of the bank in lockstep, one output row per channel (the engine's rows); fir = channel 0's decimator,
+    // which is every channel's.  in_u8: the blocks are interleaved u8 IQ, 2 bytes per element, and stay u8 up to the kernels' loaders
+    const TunerBankDesc* bank = nullptr;
+    bool in_u8 = false;
     int block_out = 0;
     bool cplx_in = false, cplx_out = false;
     int I = 1, D = 1, Lp = 1;
@@ -60,7 +70,7 @@ struct sdrhip_pipe {
     int coalesce_eff(int uni) const
     {
         if (adaptive_on() && uni > 0) {
-            const int64_t esz = (int64_t)(cplx_in ? 2 : 1) * 4;
+            const int64_t esz = (int64_t)ein();
             // (measured, 8192-sample cfloat blocks into firDecimator: batches of up to 0.5 / 1 / 4 / 16 MiB -> 2.7 / 2.3-3.0 /
             // 3.0-4.9 / 3.7-4.8 G elements/s; batches past kDirectBytes go through the copy engines)
             const int64_t fit = adaptive_bytes() / ((int64_t)uni * esz);
@@ -81,6 +91,10 @@ struct sdrhip_pipe {
     bool has_dev_state() const { return (kind == PK_DCBLOCK || kind == PK_AGC) && dc_state.p; }
 
     int esz_in() const { return cplx_in ? 2 : 1; }
+    size_t ein() const { return in_u8 ? 2 : (size_t)esz_in() * 4; }      // bytes per input element
+    // the carried tail starts at a multiple of this many elements: 16 bytes of either input type
+    int64_t tail_align() const { return in_u8 ? 8 : 4; }
+    int rows() const { return eng.rows; }
     int esz_out() const { return cplx_out ? 2 : 1; }
     int64_t in_offset(int64_t m) const { return ceil_div64(m * (int64_t)D, I); }
     // Elements of esz_in() floats; head room for the carried tail of FIR-like pipes.  Declared last: destroyed first, so its
@@ -89,20 +103,21 @@ struct sdrhip_pipe {
 };
 
 // A pipe of the given kind and geometry, with its engine: FIR-like pipes get head room and history for the carried tail,
-// E_prev - in_offset(m_done) < (Lp + D) / I + 1 elements, plus up to 3 of alignment slack; map pipes carry nothing.
+// E_prev - in_offset(m_done) < (Lp + D) / I + 1 elements, plus up to 3 of alignment slack (7 of a u8 pipe); map pipes carry nothing.
 static int pipe_new(sdrhip_pipe** out, PipeKind kind, const FirDesc* fir, const ResampDesc* rs, int block_out, bool cplx_in,
-                    bool cplx_out, int I, int D, int Lp)
+                    bool cplx_out, int I, int D, int Lp, bool in_u8 = false)
 {
     sdrhip_pipe* p = new sdrhip_pipe();
     p->kind = kind; p->fir = fir; p->rs = rs; p->block_out = block_out;
-    p->cplx_in = cplx_in; p->cplx_out = cplx_out;
+    p->cplx_in = cplx_in; p->cplx_out = cplx_out; p->in_u8 = in_u8;
     p->I = I; p->D = D; p->Lp = Lp;
     int64_t head_cap = 0;
     if (!p->is_map()) {
         const int64_t max_tail = ((int64_t)Lp + D) / I + 2;
-        head_cap = (max_tail + 3 + 3) / 4 * 4 + 4;
+        const int64_t a = p->tail_align();                  // (4: the figures every float pipe always had)
+        head_cap = (max_tail + (a - 1) + (a - 1)) / a * a + a;
     }
-    int rc = p->eng.init(HostStream::kMaxSlots, (size_t)p->esz_in() * 4, head_cap, "pipe: stream/event creation failed");
+    int rc = p->eng.init(HostStream::kMaxSlots, p->ein(), head_cap, "pipe: stream/event creation failed");
     if (rc != SDRHIP_OK) {
         delete p;
         return rc;
@@ -135,7 +150,7 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
 {
     HostStream& e = p->eng;
     const int si = e.cur();
-    const size_t ein = (size_t)p->esz_in() * 4;
+    const size_t ein = p->ein();
     const int64_t E_prev = p->E_prev, E = E_prev + n;
     // outputs computable once these samples are in: window end <= E*I
     int64_t m_end = (E * p->I >= p->Lp) ? (E * p->I - p->Lp) / p->D + 1 : 0;
@@ -150,10 +165,10 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
     // it (kernels.hpp: late_output_is_one)
     if (m_split > p->m_done && late_output_is_one(m_split - 1, E_prev * p->I, p->I, p->D, p->block_out)) m_split--;
     // staging buffer = [carried tail | staged elements]: the tail starts at the first input any pending output needs,
-    // rounded down to a multiple of 4 elements (16-byte aligned device reads wherever the block sizes allow)
+    // rounded down to a multiple of 4 elements, 8 of a u8 pipe (16-byte aligned device reads wherever the block sizes allow)
     int64_t keep_from = p->in_offset(p->m_done);
     if (keep_from > E_prev) keep_from = E_prev;
-    keep_from -= keep_from & 3;
+    keep_from -= keep_from & (p->tail_align() - 1);
     const int64_t tail = E_prev - keep_from;
     const uint8_t* first = e.carry(keep_from, E_prev, n, "pipe");
     if (first == nullptr) return SDRHIP_ERR_STATE;
@@ -162,10 +177,31 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
     // device (the carried tail comes from the host-side history), so consecutive pushes overlap on the GPU
     hipStream_t cs = direct ? e.compute[si] : e.compute[0];
     const int64_t in_base = keep_from, m_done = p->m_done;
-    int rc = e.submit(direct ? HostStream::kInPlace : HostStream::kCopyEngines, cs, first, (size_t)(tail + n) * ein,
-                      (m_end - m_done) * p->esz_out(), [&](hipStream_t s, const void* d_in, void* d_out) {
+    // More than one row never reads its input in place: with K channels in the grid every channel's workgroups would fetch the same
+    // tile over the link (the reason the FM bank's stream gives, chain.cpp).  Up to the direct bound such a submission is ONE copy
+    // into device memory on the slot's own stream and the launch behind it.
+    const int rows = p->rows();
+    const HostStream::Route route = !direct ? HostStream::kCopyEngines : rows > 1 ? HostStream::kSlotStream : HostStream::kInPlace;
+    if (p->kind == PK_TUNER_BANK && route != HostStream::kInPlace) {
+        // the copy may land anywhere in the slot's device buffer: put the banked launch's first window on a 16-byte boundary there,
+        // which the staging buffer cannot promise once a block had an odd size
+        const int64_t k0 = uniform_seam > 0 ? m_done : m_split;
+        const size_t off = (size_t)(k0 * p->D - keep_from) * ein;
+        e.dev_skew = (16 - off % 16) % 16;
+    }
+    const int64_t row_floats = (m_end - m_done) * p->esz_out();
+    int rc = e.submit(route, cs, first, (size_t)(tail + n) * ein, rows * row_floats, [&](hipStream_t s, const void* d_in, void* d_out) {
         const float* din = (const float*)d_in;
         float* dout = (float*)d_out;
+        if (p->kind == PK_TUNER_BANK) {
+            // every row [cross | one], row_floats apart: the bank's own rule picks the banked launch or channel by channel
+            if (uniform_seam > 0) return tuner_bank_run(p->bank, s, d_in, p->in_u8, in_base, dout, row_floats, m_done, m_end, uniform_seam);
+            const int64_t ncross = m_split - m_done;
+            int r;
+            if (ncross > 0 && (r = tuner_bank_cross_run(p->bank, s, d_in, p->in_u8, in_base, dout, row_floats, m_done, m_split)) != SDRHIP_OK)
+                return r;
+            return tuner_bank_run(p->bank, s, d_in, p->in_u8, in_base, dout + 2 * ncross, row_floats, m_split, m_end, 0);
+        }
         // filter / decimator, or the tuner's mix + decimator: in_base is the absolute stream position of din[0], which is what
         // selects the oscillator phase
         auto fir_run = [&](const FirDesc* f, hipStream_t st, const float* in, bool, int64_t base, float* out, int64_t k0, int64_t k1, int64_t seam) {
@@ -195,7 +231,7 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
 // was lent behind it (sdrhip_pipe_input_buffer)
 static int fir_open_slot(sdrhip_pipe* p, size_t elems)
 {
-    const size_t ein = (size_t)p->esz_in() * 4;
+    const size_t ein = p->ein();
     return p->eng.open_slot(elems * ein, (size_t)(p->eng.staged + p->lent) * ein);
 }
 
@@ -215,11 +251,11 @@ static int fir_check_block(const sdrhip_pipe* p, int64_t E_at, int64_t m_pending
     return SDRHIP_OK;
 }
 
-static int fir_like_push(sdrhip_pipe* p, const float* block, int n)
+static int fir_like_push(sdrhip_pipe* p, const void* block, int n)
 {
     HostStream& e = p->eng;
     int rc;
-    const size_t ein = (size_t)p->esz_in() * 4;
+    const size_t ein = p->ein();
     // the size of the first ACCEPTED block is the uniform size: a block the checks below refuse must not latch it
     const int uni = p->uniform_n == 0 ? n : p->uniform_n;
     const bool all_uniform = p->all_uniform && n == uni;
@@ -231,7 +267,7 @@ static int fir_like_push(sdrhip_pipe* p, const float* block, int n)
     }
     // zero-copy push: `block` is the staging buffer's own write position (sdrhip_pipe_input_buffer); noted before the
     // buffer can be re-allocated below (growth keeps the lent region, so the data is then already in place)
-    const bool in_place = e.slot[e.cur()].hin.p != nullptr && (const void*)block == e.write_pos();
+    const bool in_place = e.slot[e.cur()].hin.p != nullptr && block == (const void*)e.write_pos();
     const uint64_t pushes_at_entry = (uint64_t)e.pushes;
     if (!coalescing && e.staged > 0) {
         // a block of another size ends the uniform run: what is staged goes out as one uniform batch first
@@ -287,6 +323,28 @@ int sdrhip_pipe_tuner(sdrhip_pipe** pp, const sdrhip_tuner* t, int block_size_ou
     int rc = pipe_new(pp, PK_TUNER, &t->fir, nullptr, block_size_out, true, true, 1, t->fir.factor, t->fir.Lp);
     if (rc == SDRHIP_OK) (*pp)->tuner = t;
     return rc;
+}
+
+int sdrhip_pipe_tuner_bank(sdrhip_pipe** pp, const sdrhip_tuner_bank* b, int block_size_out, int input_u8)
+{
+    // (all of it before pipe_new, whose engine creates streams: a refused create has done no device work)
+    SDRHIP_REQUIRE(pp != nullptr, "sdrhip_pipe_tuner_bank");
+    *pp = nullptr;
+    SDRHIP_REQUIRE(b != nullptr, "sdrhip_pipe_tuner_bank: null bank");
+    SDRHIP_REQUIRE(block_size_out > 0, "sdrhip_pipe_tuner_bank: block_size_out > 0");
+    SDRHIP_REQUIRE(input_u8 == 0 || input_u8 == 1, "sdrhip_pipe_tuner_bank: input_u8 is 0 (cfloat blocks) or 1 (u8 IQ blocks)");
+    const FirDesc* f = &b->ch[0]->fir;
+    int rc = pipe_new(pp, PK_TUNER_BANK, f, nullptr, block_size_out, true, true, 1, f->factor, f->Lp, input_u8 == 1);
+    if (rc != SDRHIP_OK) return rc;
+    (*pp)->bank = b;
+    if (b->ch.size() > 1) (*pp)->eng.set_rows((int)b->ch.size());
+    return SDRHIP_OK;
+}
+
+int sdrhip_pipe_rows(const sdrhip_pipe* p)
+{
+    SDRHIP_REQUIRE(p != nullptr, "sdrhip_pipe_rows");
+    return p->rows();
 }
 
 int sdrhip_pipe_fir_resampler(sdrhip_pipe** pp, const sdrhip_resampler* r, int block_size_out)
@@ -401,7 +459,15 @@ static int map_push(sdrhip_pipe* p, const float* block, int n)
 int sdrhip_pipe_push(sdrhip_pipe* p, const float* block, int n)
 {
     SDRHIP_REQUIRE(p != nullptr && block != nullptr && n > 0, "sdrhip_pipe_push");
+    SDRHIP_REQUIRE(!p->in_u8, "sdrhip_pipe_push: this pipe takes u8 IQ blocks (sdrhip_pipe_push_u8)");
     return p->is_map() ? map_push(p, block, n) : fir_like_push(p, block, n);
+}
+
+int sdrhip_pipe_push_u8(sdrhip_pipe* p, const uint8_t* iq, int n_samples)
+{
+    SDRHIP_REQUIRE(p != nullptr && iq != nullptr && n_samples > 0, "sdrhip_pipe_push_u8");
+    SDRHIP_REQUIRE(p->in_u8, "sdrhip_pipe_push_u8: this pipe takes float blocks (sdrhip_pipe_push)");
+    return fir_like_push(p, iq, n_samples);
 }
 
 int sdrhip_pipe_set_coalesce(sdrhip_pipe* p, int blocks)
@@ -423,9 +489,14 @@ int sdrhip_pipe_set_adaptive(sdrhip_pipe* p, int max_blocks)
     return SDRHIP_OK;
 }
 
-float* sdrhip_pipe_input_buffer(sdrhip_pipe* p, int n)
+// the staging memory of the next push, for both input types (`who` names the caller in a refusal)
+static void* pipe_input_buffer(sdrhip_pipe* p, int n, bool u8, const char* who)
 {
-    if (p == nullptr || n <= 0 || p->is_map()) { set_error("sdrhip_pipe_input_buffer: filter / decimator / resampler pipes, n > 0"); return nullptr; }
+    if (p == nullptr || n <= 0 || p->is_map()) { set_error("%s: filter / decimator / resampler pipes, n > 0", who); return nullptr; }
+    if (p->in_u8 != u8) {
+        set_error("%s: this pipe takes %s", who, p->in_u8 ? "u8 IQ blocks (sdrhip_pipe_input_buffer_u8)" : "float blocks (sdrhip_pipe_input_buffer)");
+        return nullptr;
+    }
     HostStream& e = p->eng;
     const int ce = p->coalesce_eff(p->uniform_n ? p->uniform_n : n);
     const bool coalescing = ce > 1 && p->all_uniform && (p->uniform_n == 0 || p->uniform_n == n);
@@ -433,10 +504,17 @@ float* sdrhip_pipe_input_buffer(sdrhip_pipe* p, int n)
     // a fresh pipe has no uniform size yet: the block about to be pushed defines it, so size the buffer for a whole
     // coalesced batch of such blocks now (growing it at the push would move the block the caller is about to fill)
     const int64_t cap = coalescing ? (int64_t)ce * (p->uniform_n ? p->uniform_n : n) : n;
-    if (cap > (int64_t)1 << 30) { set_error("sdrhip_pipe_input_buffer: coalesced batch too large"); return nullptr; }
+    if (cap > (int64_t)1 << 30) { set_error("%s: coalesced batch too large", who); return nullptr; }
     if (fir_open_slot(p, (size_t)(cap > e.staged + n ? cap : e.staged + n)) != SDRHIP_OK) return nullptr;
     p->lent = n;
-    return (float*)e.write_pos();
+    return e.write_pos();
+}
+
+float* sdrhip_pipe_input_buffer(sdrhip_pipe* p, int n) { return (float*)pipe_input_buffer(p, n, false, "sdrhip_pipe_input_buffer"); }
+
+uint8_t* sdrhip_pipe_input_buffer_u8(sdrhip_pipe* p, int n_samples)
+{
+    return (uint8_t*)pipe_input_buffer(p, n_samples, true, "sdrhip_pipe_input_buffer_u8");
 }
 
 int sdrhip_pipe_poll(sdrhip_pipe* p)
@@ -459,12 +537,25 @@ int sdrhip_pipe_flush(sdrhip_pipe* p)
 int sdrhip_pipe_pop(sdrhip_pipe* p, float* out, int capacity)
 {
     SDRHIP_REQUIRE(p != nullptr && out != nullptr, "sdrhip_pipe_pop");
+    SDRHIP_REQUIRE(p->rows() == 1, "sdrhip_pipe_pop: a pipe of more than one row pops all of them at once (sdrhip_pipe_pop_rows)");
     if (ready_blocks(p) <= 0) return 0;
     int len = p->is_map() ? p->demod_blocks.front() : p->block_out;
     SDRHIP_REQUIRE(capacity >= len, "sdrhip_pipe_pop: capacity smaller than the block");
     p->eng.take((size_t)len * p->esz_out(), out);
     if (p->is_map()) p->demod_blocks.pop_front();
     return len;
+}
+
+int sdrhip_pipe_pop_rows(sdrhip_pipe* p, float* out, int64_t row_stride, int max_blocks)
+{
+    SDRHIP_REQUIRE(p != nullptr && out != nullptr && max_blocks >= 0, "sdrhip_pipe_pop_rows");
+    SDRHIP_REQUIRE(!p->is_map(), "sdrhip_pipe_pop_rows: filter / decimator / resampler / tuner pipes (blocks of block_size_out)");
+    const int64_t block_floats = (int64_t)p->block_out * p->esz_out();
+    SDRHIP_REQUIRE(row_stride >= (int64_t)max_blocks * block_floats, "sdrhip_pipe_pop_rows: a row holds max_blocks blocks");
+    const int ready = ready_blocks(p);
+    const int nb = ready < max_blocks ? ready : max_blocks;
+    if (nb > 0) p->eng.take_rows((size_t)nb * (size_t)block_floats, out, row_stride);
+    return nb;
 }
 
 // ---- checkpoint / resume (as sdrhip_fm_stream_save / _restore, chain.cpp) -------------------------------------------
@@ -479,6 +570,13 @@ struct PipeStateHeader {
     float last_re, last_im, dc[4];
 };
 constexpr uint32_t kPipeMagic = 0x50504453u;   // "SDPP"
+// Version 2: a pipe of more than one row or of u8 input.  The same header, then this, then the engine's state with the history in the
+// input's own type (2 bytes per u8 element) and the fifo row after row.  Every other pipe writes version 1, byte for byte as before.
+struct PipeStateRows {
+    int32_t rows, input_u8;
+};
+static uint32_t pipe_state_version(const sdrhip_pipe* p) { return p->rows() > 1 || p->in_u8 ? 2u : 1u; }
+static size_t pipe_state_header_bytes(const sdrhip_pipe* p) { return sizeof(PipeStateHeader) + (pipe_state_version(p) == 2 ? sizeof(PipeStateRows) : 0); }
 }  // namespace
 
 size_t sdrhip_pipe_state_bytes(sdrhip_pipe* p)
@@ -488,7 +586,7 @@ size_t sdrhip_pipe_state_bytes(sdrhip_pipe* p)
     // slot is harvested into the fifo), so the size returned is what the save that follows needs -- whatever the ratio of
     // the stage and the size of the blocks in flight.  0 = the drain failed (sdrhip_last_error).
     if (sdrhip_pipe_flush(p) < 0) return 0;
-    return sizeof(PipeStateHeader) + p->eng.state_bytes(p->eng.hist_n, (int64_t)p->eng.pending()) + p->demod_blocks.size() * sizeof(int32_t);
+    return pipe_state_header_bytes(p) + p->eng.state_bytes(p->eng.hist_n, (int64_t)p->eng.pending()) + p->demod_blocks.size() * sizeof(int32_t);
 }
 
 int sdrhip_pipe_save(sdrhip_pipe* p, void* buf, size_t capacity, size_t* used)
@@ -499,7 +597,7 @@ int sdrhip_pipe_save(sdrhip_pipe* p, void* buf, size_t capacity, size_t* used)
     PipeStateHeader h;
     memset(&h, 0, sizeof h);
     h.magic = kPipeMagic;
-    h.version = 1;
+    h.version = pipe_state_version(p);
     h.kind = (int32_t)p->kind;
     h.block_out = p->block_out;
     h.I = p->I; h.D = p->D; h.Lp = p->Lp;
@@ -513,13 +611,17 @@ int sdrhip_pipe_save(sdrhip_pipe* p, void* buf, size_t capacity, size_t* used)
         SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));
         SDRHIP_CHECK_HIP(hipMemcpy(h.dc, p->dc_state.p, 16, hipMemcpyDeviceToHost));
     }
-    const size_t need = sizeof h + p->eng.state_bytes(h.hist_n, h.pending) + (size_t)h.n_blocks * sizeof(int32_t);
+    const size_t need = pipe_state_header_bytes(p) + p->eng.state_bytes(h.hist_n, h.pending) + (size_t)h.n_blocks * sizeof(int32_t);
     if (capacity < need) {
         set_error("sdrhip_pipe_save: %zu bytes needed, %zu given", need, capacity);
         return SDRHIP_ERR_ARG;
     }
     memcpy(buf, &h, sizeof h);
-    unsigned char* o = p->eng.save((unsigned char*)buf + sizeof h);
+    if (h.version == 2) {
+        const PipeStateRows x = {p->rows(), p->in_u8 ? 1 : 0};
+        memcpy((unsigned char*)buf + sizeof h, &x, sizeof x);
+    }
+    unsigned char* o = p->eng.save((unsigned char*)buf + pipe_state_header_bytes(p));
     for (int len : p->demod_blocks) { const int32_t v = len; memcpy(o, &v, sizeof v); o += sizeof v; }
     *used = need;
     return SDRHIP_OK;
@@ -532,26 +634,34 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
                    "sdrhip_pipe_restore: only into a pipe that has not been pushed to");
     PipeStateHeader h;
     memcpy(&h, buf, sizeof h);
-    SDRHIP_REQUIRE(h.magic == kPipeMagic && h.version == 1, "sdrhip_pipe_restore: not a pipe state");
+    SDRHIP_REQUIRE(h.magic == kPipeMagic && (h.version == 1 || h.version == 2), "sdrhip_pipe_restore: not a pipe state");
+    SDRHIP_REQUIRE(h.version == pipe_state_version(p), "sdrhip_pipe_restore: the state belongs to a pipe of another row count or input type");
+    if (h.version == 2) {
+        SDRHIP_REQUIRE(bytes >= pipe_state_header_bytes(p), "sdrhip_pipe_restore: truncated state");
+        PipeStateRows x;
+        memcpy(&x, (const unsigned char*)buf + sizeof h, sizeof x);
+        SDRHIP_REQUIRE(x.rows == p->rows() && x.input_u8 == (p->in_u8 ? 1 : 0),
+                       "sdrhip_pipe_restore: the state belongs to a pipe of another row count or input type");
+    }
     SDRHIP_REQUIRE(h.kind == (int32_t)p->kind && h.block_out == p->block_out && h.I == p->I && h.D == p->D && h.Lp == p->Lp &&
                        h.cplx_in == (int32_t)p->cplx_in && h.cplx_out == (int32_t)p->cplx_out && h.head_cap == p->eng.head_cap,
                    "sdrhip_pipe_restore: the state belongs to a pipe of another kind or geometry");
     SDRHIP_REQUIRE(h.hist_n >= 0 && h.hist_n <= h.head_cap && h.pending >= 0 && h.n_blocks >= 0 && h.E_prev >= h.hist_n && h.m_done >= 0,
                    "sdrhip_pipe_restore: inconsistent state");
-    if (p->kind == PK_FILTER || p->kind == PK_DECIMATOR || p->kind == PK_RESAMPLER || p->kind == PK_TUNER) {
+    if (p->kind == PK_FILTER || p->kind == PK_DECIMATOR || p->kind == PK_RESAMPLER || p->kind == PK_TUNER || p->kind == PK_TUNER_BANK) {
         // the next pending output must start inside what the pipe has seen, every output computable from those elements must be
-        // done at most once, and the history must reach back to its first input (3 elements of alignment slack, fir_submit):
+        // done at most once, and the history must reach back to its first input (3 elements of alignment slack, 7 of u8, fir_submit):
         // otherwise the kernels would be sent in front of the staging buffer
         const int64_t first_in = p->in_offset(h.m_done);
         const int64_t m_max = (h.E_prev * p->I >= p->Lp) ? (h.E_prev * p->I - p->Lp) / p->D + 1 : 0;
         int64_t keep_from = first_in < h.E_prev ? first_in : h.E_prev;
-        keep_from -= keep_from & 3;
+        keep_from -= keep_from & (p->tail_align() - 1);
         SDRHIP_REQUIRE(h.m_done <= m_max && first_in <= h.E_prev + (p->Lp + p->D) / p->I + 1 && h.hist_n >= h.E_prev - keep_from,
                        "sdrhip_pipe_restore: the position and the history of the state do not belong together");
     }
-    SDRHIP_REQUIRE(bytes >= sizeof h + p->eng.state_bytes(h.hist_n, h.pending) + (size_t)h.n_blocks * sizeof(int32_t),
+    SDRHIP_REQUIRE(bytes >= pipe_state_header_bytes(p) + p->eng.state_bytes(h.hist_n, h.pending) + (size_t)h.n_blocks * sizeof(int32_t),
                    "sdrhip_pipe_restore: truncated state");
-    const unsigned char* in = p->eng.restore((const unsigned char*)buf + sizeof h, h.hist_n, h.pending);
+    const unsigned char* in = p->eng.restore((const unsigned char*)buf + pipe_state_header_bytes(p), h.hist_n, h.pending);
     p->E_prev = h.E_prev;
     p->m_done = h.m_done;
     p->uniform_n = h.uniform_n;

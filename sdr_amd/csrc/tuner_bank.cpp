@@ -98,6 +98,34 @@ int tuner_bank_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, bool
     return SDRHIP_OK;
 }
 
+// Outputs [k_begin, k_end) of every channel, all Cross, in ONE launch (kernels_tuner_bank.hip: k_tuner_bank_cross): what
+// tuner_bank_run(..., seam_block = -1) computes channel by channel, for the bank's Pipe (pipes.cpp) and nobody else -- the routes and
+// the auto rule of sdrhip_tuner_bank_run are not involved.
+int tuner_bank_cross_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, bool in_u8, int64_t in_base, float* d_out,
+                         int64_t out_stride, int64_t k_begin, int64_t k_end)
+{
+    SDRHIP_REQUIRE(b != nullptr && d_in != nullptr && d_out != nullptr, "tuner_bank_cross_run");
+    const FirDesc* d = &b->ch[0]->fir;
+    SDRHIP_REQUIRE(k_begin >= 0 && k_end > k_begin && k_end - k_begin < (int64_t)0x7fffffff, "tuner_bank_cross_run");
+    SDRHIP_REQUIRE(k_begin * d->factor >= in_base, "tuner_bank_cross_run: first window starts before d_in");
+    int rc = b->ensure_device();
+    if (rc != SDRHIP_OK) return rc;
+    Geom g;
+    g.in_base = in_base;
+    g.k_begin = k_begin;
+    g.count = (int)(k_end - k_begin);
+    g.I = 1;
+    g.D = d->factor;
+    g.Lp = d->Lp;
+    g.seamBI = -1;
+    if (!launch_tuner_bank_cross(s, g, d->d_cross, d_in, in_u8, d_out, out_stride, b->d_tables, (int)b->ch.size(), b->off, b->period)) {
+        set_error("tuner_bank_cross_run: the all-Cross launch refused its channels, stride or pointers");
+        return SDRHIP_ERR_ARG;
+    }
+    SDRHIP_CHECK_HIP(hipGetLastError());
+    return SDRHIP_OK;
+}
+
 }  // namespace sdrhip
 
 using namespace sdrhip;
@@ -173,5 +201,6 @@ int sdrhip_tuner_bank_run_u8(const sdrhip_tuner_bank* b, void* stream, const uin
 }
 
 long long sdrhip_debug_tuner_bank_launches(void) { return tuner_bank_launch_count(); }
+long long sdrhip_debug_tuner_bank_cross_launches(void) { return tuner_bank_cross_launch_count(); }
 
 }  // extern "C"

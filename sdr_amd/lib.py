@@ -118,6 +118,8 @@ lib.sdrhip_tuner_bank_run_u8.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _
 lib.sdrhip_tuner_bank_set_route.argtypes = [_vp, C.c_int]
 lib.sdrhip_debug_tuner_bank_launches.argtypes = []
 lib.sdrhip_debug_tuner_bank_launches.restype = C.c_longlong
+lib.sdrhip_debug_tuner_bank_cross_launches.argtypes = []
+lib.sdrhip_debug_tuner_bank_cross_launches.restype = C.c_longlong
 
 lib.sdrhip_resampler_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.c_int]
 lib.sdrhip_resampler_num_coeffs.argtypes = [_vp]
@@ -288,6 +290,12 @@ lib.sdrhip_pipe_fm_demod.argtypes = [C.POINTER(_vp)]
 lib.sdrhip_pipe_dc_blocker.argtypes = [C.POINTER(_vp)]
 lib.sdrhip_pipe_agc.argtypes = [C.POINTER(_vp), C.c_float, C.c_float]
 lib.sdrhip_pipe_tuner.argtypes = [C.POINTER(_vp), _vp, C.c_int]
+lib.sdrhip_pipe_tuner_bank.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int]
+lib.sdrhip_pipe_rows.argtypes = [_vp]
+lib.sdrhip_pipe_push_u8.argtypes = [_vp, _u8p, C.c_int]
+lib.sdrhip_pipe_input_buffer_u8.argtypes = [_vp, C.c_int]
+lib.sdrhip_pipe_input_buffer_u8.restype = _vp
+lib.sdrhip_pipe_pop_rows.argtypes = [_vp, _f32p, _i64, C.c_int]
 lib.sdrhip_pipe_set_coalesce.argtypes = [_vp, C.c_int]
 lib.sdrhip_pipe_set_adaptive.argtypes = [_vp, C.c_int]
 lib.sdrhip_pipe_input_buffer.argtypes = [_vp, C.c_int]
@@ -609,6 +617,11 @@ class Tuner(_Handle):
 def tuner_bank_launches():
     """Banked launches of the tuner bank so far (sdrhip_debug_tuner_bank_launches)."""
     return int(lib.sdrhip_debug_tuner_bank_launches())
+
+
+def tuner_bank_cross_launches():
+    """Launches of the all-Cross kernel of the bank's Pipe so far (sdrhip_debug_tuner_bank_cross_launches)."""
+    return int(lib.sdrhip_debug_tuner_bank_cross_launches())
 
 
 class TunerBank(_Handle):
@@ -1072,13 +1085,16 @@ class FmStream(_Handle):
 
 class Pipe(_Handle):
     """firFilter / firDecimator / firResampler / fmDemod / dcBlockingFilter / agcPipe on host blocks (Filter.hs:532-739,
-    Demod.hs:40-46, Util.hs:344-348)."""
+    Demod.hs:40-46, Util.hs:344-348).  Pipe.tuner_bank: every channel of a TunerBank in lockstep -- push, flush, poll and restore
+    then return a list of arrays of shape [channels, 2 * block_size_out], row j being the block Pipe.tuner over
+    Tuner(factor, coeffs, tables[j], order) yields."""
     _destroy = lib.sdrhip_pipe_destroy
 
-    def __init__(self, kind, desc=None, block_size_out=8192, mu=None, reference=None):
+    def __init__(self, kind, desc=None, block_size_out=8192, mu=None, reference=None, input_u8=False):
         super().__init__()
         self.desc = desc  # keep the descriptor alive
         self.block_size_out = block_size_out
+        self.input_u8 = False
         self.complex_in = bool(getattr(desc, "complex", False)) or kind in ("fm_demod", "agc")
         self.complex_out = bool(getattr(desc, "complex", False)) or kind == "agc"
         if kind == "filter":
@@ -1089,6 +1105,9 @@ class Pipe(_Handle):
             check(lib.sdrhip_pipe_fir_resampler(C.byref(self.h), desc.h, block_size_out), "sdrhip_pipe_fir_resampler")
         elif kind == "tuner":
             check(lib.sdrhip_pipe_tuner(C.byref(self.h), desc.h, block_size_out), "sdrhip_pipe_tuner")
+        elif kind == "tuner_bank":
+            check(lib.sdrhip_pipe_tuner_bank(C.byref(self.h), desc.h, block_size_out, int(input_u8)), "sdrhip_pipe_tuner_bank")
+            self.input_u8 = bool(input_u8)
         elif kind == "fm_demod":
             check(lib.sdrhip_pipe_fm_demod(C.byref(self.h)), "sdrhip_pipe_fm_demod")
         elif kind == "dc_blocker":
@@ -1106,8 +1125,37 @@ class Pipe(_Handle):
         """The tuner on host blocks: cfloat blocks in, blocks of block_size_out decimated samples out."""
         return Pipe("tuner", tuner, block_size_out)
 
+    @staticmethod
+    def tuner_bank(bank, block_size_out, input_u8=False):
+        """The tuner bank on host blocks: cfloat blocks (or interleaved u8 IQ blocks, input_u8=True) in, every channel's blocks of
+        block_size_out decimated samples out."""
+        return Pipe("tuner_bank", bank, block_size_out, input_u8=input_u8)
+
+    @property
+    def rows(self):
+        """The bank's channel count for Pipe.tuner_bank, 1 for every other pipe."""
+        return check(lib.sdrhip_pipe_rows(self.h), "sdrhip_pipe_rows")
+
+    def pop_rows(self, max_blocks):
+        """Up to max_blocks blocks of every row at once: an array [rows, nb, floats per block] (sdrhip_pipe_pop_rows)."""
+        rows, n = self.rows, self.block_size_out * (2 if self.complex_out else 1)
+        o = np.empty((rows, max(max_blocks, 0) * n), np.float32)
+        nb = check(lib.sdrhip_pipe_pop_rows(self.h, _fp(o), o.shape[1], max_blocks), "sdrhip_pipe_pop_rows")
+        return o[:, : nb * n].reshape(rows, nb, n)
+
+    def _wrong_dtype(self, block, call):
+        """A u8 pipe takes uint8 arrays and every other pipe no uint8 array: converting silently would feed the wrong stream."""
+        is_u8 = getattr(block, "dtype", None) == np.uint8
+        if is_u8 != self.input_u8:
+            raise SdrHipError(f"{call}: this pipe takes {'uint8 IQ' if self.input_u8 else 'float32'} blocks, not "
+                              f"{getattr(block, 'dtype', type(block).__name__)}")
+
     def push(self, block):
-        """block: float32 array (interleaved for complex stages).  Returns list of output blocks."""
+        """block: float32 array (interleaved for complex stages; uint8 IQ for a u8 pipe).  Returns list of output blocks."""
+        self._wrong_dtype(block, "Pipe.push")
+        if self.input_u8:
+            b = np.ascontiguousarray(block, dtype=np.uint8).reshape(-1)
+            return self._pop(check(lib.sdrhip_pipe_push_u8(self.h, b.ctypes.data_as(_u8p), b.size // 2), "sdrhip_pipe_push_u8"))
         b = _f32(block)
         n = b.size // (2 if self.complex_in else 1)
         self._cap = max(getattr(self, "_cap", 0), self.block_size_out, n)
@@ -1122,9 +1170,11 @@ class Pipe(_Handle):
 
     def input_buffer(self, n):
         """numpy view (n elements; interleaved pairs for complex stages) of the pinned staging memory of the next push."""
-        ptr = lib.sdrhip_pipe_input_buffer(self.h, n)
+        ptr = (lib.sdrhip_pipe_input_buffer_u8 if self.input_u8 else lib.sdrhip_pipe_input_buffer)(self.h, n)
         if not ptr:
             raise SdrHipError(lib.sdrhip_last_error().decode())
+        if self.input_u8:
+            return np.ctypeslib.as_array(C.cast(ptr, _u8p), shape=(2 * n,))
         return np.ctypeslib.as_array(C.cast(ptr, _f32p), shape=(n * (2 if self.complex_in else 1),))
 
     def flush(self):
@@ -1154,6 +1204,11 @@ class Pipe(_Handle):
         return self._pop(check(lib.sdrhip_pipe_restore(self.h, state, len(state)), "sdrhip_pipe_restore"))
 
     def _pop(self, ready):
+        if self.kind == "tuner_bank":
+            if ready <= 0:
+                return []
+            got = self.pop_rows(ready)
+            return [np.ascontiguousarray(got[:, k]) for k in range(got.shape[1])]
         outs = []
         cap = max(getattr(self, "_cap", 0), self.block_size_out) * (2 if self.complex_out else 1)
         for _ in range(ready):
