@@ -364,15 +364,20 @@ long long sdrhip_debug_tiled_launches(void);
 /* dcBlocker (c_sources/filter.c:152-161; Pipe dcBlockingFilter, Filter.hs:730-739) on device memory:
  * y[i] = (float)((double)(x[i] - x[i-1]) + 0.997 * (double)y[i-1]), x[-1] = last_sample, y[-1] = last_output.
  * Bit-identical to the sequential loop (speculative chunks, verified and settled on the device).
- * d_final receives {finalSample, finalOutput}.  d_workspace may be NULL (sequential walk); when given
- * it starts with three uint32 statistics {chunks left to the sequential settle pass, samples it rewrote,
- * chunks recomputed by the parallel repair rounds} -- all zero when every speculation converged.  run_in =
- * samples each chunk runs in before its first output (0 = default 12288; a shorter run-in does less
- * redundant work but leaves more chunks to settle; the result never depends on it).  Not in-place. */
+ * d_final receives {finalSample, finalOutput}; n == 0 writes {last_sample, last_output} there.  d_workspace
+ * may be NULL (sequential walk); when given it starts with three uint32 statistics {chunks left to the
+ * sequential settle pass, samples it rewrote, chunks recomputed by the parallel repair rounds} -- all zero when
+ * every speculation converged -- and a fourth word, the chunks the launch speculated on (0 = sequential walk).
+ * run_in = samples each chunk runs in before its first output, rounded up to a multiple of 4 (0 = default 12288;
+ * a shorter run-in does less redundant work but leaves more chunks to settle; the result never depends on it);
+ * blocks shorter than two run-ins take the sequential walk, whatever run_in is.  Not in-place. */
 size_t sdrhip_dc_blocker_workspace_bytes(int64_t n);
 int sdrhip_dc_blocker_run(void *stream, const float *d_in, float *d_out, int64_t n, float last_sample,
                           float last_output, float *d_final, void *d_workspace, size_t workspace_bytes,
                           int run_in);
+/* Diagnostics: the plan sdrhip_dc_blocker_run follows for these arguments when it has a workspace.  Returns the number
+ * of chunks (0 = sequential walk); *chunk and *run_in_used (either may be NULL) receive the chunk length and the run-in. */
+int sdrhip_debug_dc_plan(int64_t n, int run_in, int64_t *chunk, int64_t *run_in_used);
 
 /* agc (hs_sources/SDR/Util.hs:325-342; Pipe agcPipe, Util.hs:344-348) on device memory, interleaved complex samples.
  * Per sample (re, im), everything in f32, no FMA:

@@ -653,13 +653,23 @@ int sdrhip_dc_blocker_run(void* stream, const float* d_in, float* d_out, int64_t
                           float* d_final, void* d_workspace, size_t workspace_bytes, int run_in)
 {
     SDRHIP_REQUIRE(n >= 0 && d_final != nullptr && run_in >= 0, "sdrhip_dc_blocker_run");
-    if (n == 0) return SDRHIP_OK;
-    SDRHIP_REQUIRE(d_in != nullptr && d_out != nullptr && d_in != d_out, "sdrhip_dc_blocker_run: in-place is not supported");
-    SDRHIP_REQUIRE(d_workspace == nullptr || workspace_bytes >= dc_blocker_workspace_bytes(n),
-                   "sdrhip_dc_blocker_run: workspace smaller than sdrhip_dc_blocker_workspace_bytes(n)");
-    launch_dc_blocker((hipStream_t)stream, n, last_sample, last_output, d_in, d_out, d_final, d_workspace, run_in);
+    if (n > 0) {
+        SDRHIP_REQUIRE(d_in != nullptr && d_out != nullptr && d_in != d_out, "sdrhip_dc_blocker_run: in-place is not supported");
+        SDRHIP_REQUIRE(d_workspace == nullptr || workspace_bytes >= dc_blocker_workspace_bytes(n),
+                       "sdrhip_dc_blocker_run: workspace smaller than sdrhip_dc_blocker_workspace_bytes(n)");
+    }
+    launch_dc_blocker((hipStream_t)stream, n, last_sample, last_output, d_in, d_out, d_final, n > 0 ? d_workspace : nullptr, run_in);
     SDRHIP_CHECK_HIP(hipGetLastError());
     return SDRHIP_OK;
+}
+
+int sdrhip_debug_dc_plan(int64_t n, int run_in, int64_t* chunk, int64_t* run_in_used)
+{
+    SDRHIP_REQUIRE(n >= 0 && run_in >= 0, "sdrhip_debug_dc_plan");
+    const DcPlan p = dc_plan(n, run_in);
+    if (chunk) *chunk = p.C;
+    if (run_in_used) *run_in_used = p.W;
+    return p.nchunks;
 }
 
 size_t sdrhip_agc_workspace_bytes(int64_t n) { return agc_workspace_bytes(n); }

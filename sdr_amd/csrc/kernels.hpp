@@ -181,9 +181,12 @@ void launch_fm_demod(hipStream_t s, const float* d_in_iq, float* d_out, int64_t 
                      float last_re, float last_im);
 // filter.c:152-161 (kernels_iir.hip: speculative chunks + verification, bit-exact with the sequential walk).
 // d_final receives {finalSample, finalOutput}; d_ws (dc_blocker_workspace_bytes, may be null = sequential walk)
-// starts with three u32 statistics {chunks left to the sequential settle, samples it rewrote, chunks recomputed in the
-// parallel repair rounds}; run_in <= 0 selects the default.  d_state, when given, holds {lastSample, lastOutput} on
-// the device and overrides the two scalars (it may alias d_final: a Pipe chains its blocks that way).
+// starts with four u32 statistics {chunks left to the sequential settle, samples it rewrote, chunks recomputed in the
+// parallel repair rounds, chunks of the launch (0 = the sequential walk)}; run_in <= 0 selects the default.  d_state, when
+// given, holds {lastSample, lastOutput} on the device and overrides the two scalars (it may alias d_final: a Pipe chains
+// its blocks that way).  num == 0 hands the state on to d_final.
+struct DcPlan { int64_t C, W; int nchunks; };    // chunk length, run-in, chunks (0 = the sequential walk)
+DcPlan dc_plan(int64_t num, int run_in);
 size_t dc_blocker_workspace_bytes(int64_t num);
 void launch_dc_blocker(hipStream_t s, int64_t num, float last_sample, float last_output, const float* d_in,
                        float* d_out, float* d_final, void* d_ws, int run_in, const float* d_state = nullptr);

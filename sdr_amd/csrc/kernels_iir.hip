@@ -29,7 +29,7 @@ __device__ __forceinline__ float dc_step(float x, float xprev, float y)
 }
 
 __global__ void __launch_bounds__(64)
-k_dc_speculate(int64_t num, int C, int W, float last_sample, float last_output, const float* __restrict__ d_state,
+k_dc_speculate(int64_t num, int C, int64_t W, float last_sample, float last_output, const float* __restrict__ d_state,
                const float* __restrict__ in, float* __restrict__ out, uint32_t* __restrict__ y_start,
                uint32_t* __restrict__ y_end, int nchunks, int vec4)
 {
@@ -86,7 +86,7 @@ k_dc_speculate(int64_t num, int C, int W, float last_sample, float last_output, 
 
 // One repair round.  y_end_prev is read, y_end_next written (ping-pong: a round must not see its own updates).
 __global__ void __launch_bounds__(64)
-k_dc_repair(int64_t num, int C, int W, const float* __restrict__ in, float* __restrict__ out, uint32_t* __restrict__ y_start,
+k_dc_repair(int64_t num, int C, int64_t W, const float* __restrict__ in, float* __restrict__ out, uint32_t* __restrict__ y_start,
             const uint32_t* __restrict__ y_end_prev, uint32_t* __restrict__ y_end_next, int nchunks,
             uint32_t* __restrict__ stats)
 {
@@ -114,9 +114,9 @@ k_dc_repair(int64_t num, int C, int W, const float* __restrict__ in, float* __re
 }
 
 // One workgroup.  stats[0] = chunks still inconsistent after the parallel rounds, stats[1] = samples this lane rewrote
-// (stats[2], counted by k_dc_repair = chunks recomputed in the parallel rounds).
+// (stats[2], counted by k_dc_repair = chunks recomputed in the parallel rounds), stats[3] = chunks of the launch.
 __global__ void __launch_bounds__(1024)
-k_dc_settle(int64_t num, int C, int W, const float* __restrict__ in, float* __restrict__ out,
+k_dc_settle(int64_t num, int C, int64_t W, const float* __restrict__ in, float* __restrict__ out,
             const uint32_t* __restrict__ y_start, const uint32_t* __restrict__ y_end, int nchunks,
             uint8_t* __restrict__ bad, float* __restrict__ fin, uint32_t* __restrict__ stats)
 {
@@ -154,12 +154,14 @@ k_dc_settle(int64_t num, int C, int W, const float* __restrict__ in, float* __re
     }
     stats[0] = (uint32_t)nbad;
     stats[1] = rewritten;
+    stats[3] = (uint32_t)nchunks;
     fin[0] = in[num - 1];
     fin[1] = out[num - 1];
 }
 
-// plain sequential walk: short blocks (the run-in would cost more than the block).  Loads run ahead of the
-// dependent f64 chain: the next float4 is requested before the current one is consumed.
+// plain sequential walk: short blocks (the run-in would cost more than the block), a null workspace, and num == 0 (which
+// only hands the state on).  Loads run ahead of the dependent f64 chain: the next float4 is requested before the current
+// one is consumed.
 __global__ void k_dc_sequential(int64_t num, float last_sample, float last_output, const float* d_state,
                                 const float* __restrict__ in, float* __restrict__ out, float* fin,
                                 uint32_t* __restrict__ stats, int vec4)
@@ -191,7 +193,7 @@ __global__ void k_dc_sequential(int64_t num, float last_sample, float last_outpu
     }
     fin[0] = xp;
     fin[1] = y;
-    if (stats) { stats[0] = 0; stats[1] = 0; stats[2] = 0; }
+    if (stats) { stats[0] = 0; stats[1] = 0; stats[2] = 0; stats[3] = 0; }
 }
 
 namespace {
@@ -200,48 +202,58 @@ constexpr int DC_REPAIR_ROUNDS = 3;
 // Every lane walks run-in + chunk samples at the latency of the dependent f64 chain, so the time is ~(C + W) steps whatever
 // the lane count; more lanes than this only add redundant run-in traffic (measured: 2^18 lanes thrash the L2 at n = 2^26).
 constexpr int64_t kDcMaxLanes = 32768;
-struct DcPlan { int C; int nchunks; };
-DcPlan dc_plan(int64_t num)
+int64_t dc_chunk(int64_t num)
 {
     const int64_t lanes = kDcMaxLanes;
     int64_t C = (num + lanes - 1) / lanes;
     if (C < 256) C = 256;
-    C = (C + 3) & ~(int64_t)3;
-    return {(int)C, (int)((num + C - 1) / C)};
+    return (C + 3) & ~(int64_t)3;
 }
 }  // namespace
 
 size_t dc_blocker_workspace_bytes(int64_t num)
 {
-    const DcPlan p = dc_plan(num > 0 ? num : 1);
-    return (size_t)p.nchunks * 13 + 64;   // stats, y_start, y_end x2 (u32 each), bad (u8)
+    if (num < 1) num = 1;
+    const int64_t C = dc_chunk(num);
+    return (size_t)((num + C - 1) / C) * 13 + 64;   // stats, y_start, y_end x2 (u32 each), bad (u8)
+}
+
+// The run-in is the caller's int rounded up to a multiple of 4: kept in 64 bits, and the route is decided on it before
+// anything is narrowed (run_in near INT_MAX rounds past it).  A block shorter than two run-ins takes the sequential walk.
+DcPlan dc_plan(int64_t num, int run_in)
+{
+    DcPlan p;
+    const int64_t W = run_in > 0 ? (int64_t)run_in : (int64_t)DC_RUN_IN;
+    p.W = (W + 3) & ~(int64_t)3;
+    p.C = dc_chunk(num > 0 ? num : 1);
+    p.nchunks = num >= 2 * p.W ? (int)((num + p.C - 1) / p.C) : 0;
+    return p;
 }
 
 void launch_dc_blocker(hipStream_t s, int64_t num, float last_sample, float last_output, const float* d_in,
                        float* d_out, float* d_final, void* d_ws, int run_in, const float* d_state)
 {
-    if (num <= 0) return;
-    const int W = run_in > 0 ? (run_in + 3) & ~3 : DC_RUN_IN;
+    if (num < 0) return;
+    const DcPlan p = dc_plan(num, run_in);
     const int vec4 = (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0;
     uint32_t* stats = reinterpret_cast<uint32_t*>(d_ws);
-    if (d_ws == nullptr || num < 2 * (int64_t)W) {
+    if (d_ws == nullptr || p.nchunks == 0) {
         hipLaunchKernelGGL(k_dc_sequential, dim3(1), dim3(64), 0, s, num, last_sample, last_output, d_state, d_in, d_out, d_final,
                            stats, vec4);
         return;
     }
-    const DcPlan p = dc_plan(num);
     uint32_t* y_start = stats + 16;
     uint32_t* y_end[2] = {y_start + p.nchunks, y_start + 2 * (size_t)p.nchunks};
     uint8_t* bad = reinterpret_cast<uint8_t*>(y_start + 3 * (size_t)p.nchunks);
     const dim3 grid((p.nchunks + 63) / 64);
     (void)hipMemsetAsync(stats, 0, 16, s);
-    hipLaunchKernelGGL(k_dc_speculate, grid, dim3(64), 0, s, num, p.C, W, last_sample, last_output, d_state, d_in, d_out,
+    hipLaunchKernelGGL(k_dc_speculate, grid, dim3(64), 0, s, num, (int)p.C, p.W, last_sample, last_output, d_state, d_in, d_out,
                        y_start, y_end[0], p.nchunks, vec4);
     int cur = 0;
     for (int r = 0; r < DC_REPAIR_ROUNDS; r++, cur ^= 1)
-        hipLaunchKernelGGL(k_dc_repair, grid, dim3(64), 0, s, num, p.C, W, d_in, d_out, y_start, y_end[cur], y_end[cur ^ 1],
+        hipLaunchKernelGGL(k_dc_repair, grid, dim3(64), 0, s, num, (int)p.C, p.W, d_in, d_out, y_start, y_end[cur], y_end[cur ^ 1],
                            p.nchunks, stats);
-    hipLaunchKernelGGL(k_dc_settle, dim3(1), dim3(1024), 0, s, num, p.C, W, d_in, d_out, y_start, y_end[cur], p.nchunks, bad,
+    hipLaunchKernelGGL(k_dc_settle, dim3(1), dim3(1024), 0, s, num, (int)p.C, p.W, d_in, d_out, y_start, y_end[cur], p.nchunks, bad,
                        d_final, stats);
 }
 

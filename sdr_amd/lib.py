@@ -263,6 +263,7 @@ lib.sdrhip_debug_tiled_launches.restype = C.c_longlong
 lib.sdrhip_dc_blocker_workspace_bytes.argtypes = [C.c_int64]
 lib.sdrhip_dc_blocker_workspace_bytes.restype = C.c_size_t
 lib.sdrhip_dc_blocker_run.argtypes = [_vp, _vp, _vp, C.c_int64, C.c_float, C.c_float, _vp, _vp, C.c_size_t, C.c_int]
+lib.sdrhip_debug_dc_plan.argtypes = [C.c_int64, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]
 lib.sdrhip_agc_workspace_bytes.argtypes = [C.c_int64]
 lib.sdrhip_agc_workspace_bytes.restype = C.c_size_t
 lib.sdrhip_agc_run.argtypes = [_vp, _vp, _vp, C.c_int64, C.c_float, C.c_float, C.c_float, _vp, _vp, C.c_size_t, C.c_int]
@@ -429,6 +430,19 @@ class DropIn:
         fs, fo = C.c_float(), C.c_float()
         lib.dcBlocker(x.size, C.c_float(last_sample), C.c_float(last_output), C.byref(fs), C.byref(fo), _fp(x), _fp(out))
         return out, fs.value, fo.value
+
+
+def dc_plan(n, run_in=0):
+    """sdrhip_debug_dc_plan: (chunks, chunk length, run-in) of a dcBlocker run over n samples; chunks == 0: the sequential walk."""
+    c, w = _i64(), _i64()
+    chunks = check(lib.sdrhip_debug_dc_plan(n, run_in, C.byref(c), C.byref(w)), "sdrhip_debug_dc_plan")
+    return chunks, c.value, w.value
+
+
+def dc_stats(ws):
+    """The four statistics words at the start of a dcBlocker / agc workspace (a device tensor of bytes): (chunks left to the
+    settle walk, samples it rewrote, chunks recomputed in the repair rounds, chunks speculated on -- 0 = the sequential walk)."""
+    return tuple(int(v) for v in ws[:16].cpu().numpy().view(np.uint32))
 
 
 def agc_plan(n, mu, run_in=0):

@@ -249,6 +249,16 @@ def test_route_counters_are_declared_exported_and_bound(L):
         assert f() >= 0, n
 
 
+def test_plan_hooks_are_declared_exported_and_bound(L):
+    """The plan hooks of the two speculative operators (tests/test_iir_cases.py reads the route from them without a launch)."""
+    declared = declared_functions()
+    for n in ("sdrhip_debug_dc_plan", "sdrhip_debug_agc_plan"):
+        assert n in declared, f"{n} is not declared in sdr_hip.h"
+        assert getattr(L.lib, n).argtypes is not None, f"{n} is not bound in sdr_amd/lib.py"
+    assert L.dc_plan(1 << 16, 64) == (256, 256, 64) and L.agc_plan(1 << 16, 0.1, 64) == (256, 256, 64)
+    assert L.dc_plan(127, 64)[0] == 0 and L.agc_plan(127, 0.1, 64)[0] == 0
+
+
 def test_halo_staging_size():
     """The staging size of the batched halo exchange (sdrhip_fm_chain_halo_exchange_batch)."""
     import sdr_amd.lib as L

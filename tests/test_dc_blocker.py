@@ -29,6 +29,23 @@ def test_oracle_matches_reference(oracle, ref, n):
         assert np.float32(fs).tobytes() == np.float32(efs).tobytes() and np.float32(fo).tobytes() == np.float32(efo).tobytes()
 
 
+def test_oracle_matches_reference_on_the_iir_cases(oracle, ref):
+    """The dcBlocker streams of tests/iir_cases.py -- the cancellation stream, +-Inf and NaN samples, differences and roundings
+    that overflow, subnormals, the subnormal fixed point: the oracle is the reference's C there too.  NaN positions are compared,
+    not a NaN's sign or payload (value_classes.assert_same_classes); everything else bit for bit."""
+    import iir_cases as IC
+    import value_classes as V
+    with ref.canonical():
+        for case in IC.CASES:
+            if case.op != "dc":
+                continue
+            x = IC.stream(case)
+            exp, efs, efo = ref.dc_blocker(x, *case.state)
+            got, fs, fo = oracle.dc_blocker(x, *case.state)
+            V.assert_same_classes(exp, got, f"dcBlocker {case.name}", max_nan_share=0.5)
+            assert IC.same(np.array([fs, fo], np.float32), np.array([efs, efo], np.float32)).all(), f"{case.name}: final state"
+
+
 def _gpu_run(hip, x, ls, lo, run_in=0, use_ws=True, misalign=0):
     from gpu_util import ptr
     n = x.size
