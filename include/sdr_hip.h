@@ -402,6 +402,54 @@ int sdrhip_agc_run(void *stream, const float *d_in_iq, float *d_out_iq, int64_t 
  * chunks (0 = sequential walk); *chunk and *run_in_used (either may be NULL) receive the chunk length and the run-in. */
 int sdrhip_debug_agc_plan(int64_t n, float mu, int run_in, int64_t *chunk, int64_t *run_in_used);
 
+/* ---- row forms: every row of a bank (sdrhip_tuner_bank_run, sdrhip_fm_bank_run) in one launch set ----
+ * Row r is d_in + r * in_stride -> d_out + r * out_stride, strides in floats.  Row r's output and final state are, bit
+ * for bit, what the one-row call writes for that row alone from state d_state[r] (dcBlocker: the pair d_state[2r],
+ * d_state[2r+1]), for any rows, strides, run_in, workspace or none, and whatever the other rows hold; the magnitude
+ * parity and the NaN caveat are those of sdrhip_agc_run.  Floats of d_out outside the rows' [0, 2n) (dcBlocker and
+ * fmDemod: [0, n)) are not touched.
+ * States are device memory on both sides, so a stream of pushes needs no host synchronisation.  d_final may be the same
+ * pointer as d_state: every read of d_state is ordered before the first write of d_final (a lane reads its row's state
+ * before it writes it, or the reads are in a launch before the one that writes).  n == 0 copies the states and touches
+ * nothing else.
+ * d_workspace, when given, starts with rows x four uint32 statistics, row r's at word 4r, with the meanings of the
+ * one-row operators.  NULL sends every row to the sequential walk: still one launch for all rows.
+ * The plan is the one-row plan of (n, mu, run_in); the chunk grows, rounded up to 8 samples, only where rows x chunks
+ * would pass the one-row lane cap (32768), so the route edge n == 2 * run-in does not depend on rows.
+ * SDRHIP_ERR_ARG, before any device work and with nothing written: rows outside 1 .. SDRHIP_ROWS_MAX, a null pointer
+ * (other than d_workspace), n < 0, run_in < 0, with rows > 1 a stride shorter than a row, an odd stride on an
+ * interleaved-complex side (both of agc), d_in == d_out, a workspace smaller than *_rows_workspace_bytes(rows, n). */
+#define SDRHIP_ROWS_MAX 1024
+size_t sdrhip_agc_rows_workspace_bytes(int rows, int64_t n);
+int sdrhip_agc_run_rows(void *stream, const float *d_in_iq, int64_t in_stride, float *d_out_iq, int64_t out_stride,
+                        int rows, int64_t n /* complex samples per row */, float mu, float reference,
+                        const float *d_state /* rows floats, device */, float *d_final /* rows floats, device */,
+                        void *d_workspace, size_t workspace_bytes, int run_in);
+/* As sdrhip_debug_agc_plan; rows == 1 gives exactly that plan. */
+int sdrhip_debug_agc_rows_plan(int rows, int64_t n, float mu, int run_in, int64_t *chunk, int64_t *run_in_used);
+
+size_t sdrhip_dc_blocker_rows_workspace_bytes(int rows, int64_t n);
+int sdrhip_dc_blocker_run_rows(void *stream, const float *d_in, int64_t in_stride, float *d_out, int64_t out_stride,
+                               int rows, int64_t n, const float *d_state /* rows x {last_sample, last_output} */,
+                               float *d_final /* rows x {finalSample, finalOutput} */,
+                               void *d_workspace, size_t workspace_bytes, int run_in);
+int sdrhip_debug_dc_rows_plan(int rows, int64_t n, int run_in, int64_t *chunk, int64_t *run_in_used);
+
+/* fmDemod over rows: in_base / k_begin / k_end as sdrhip_fm_demod_run, the same for every row.  Row r's predecessor of
+ * k_begin is d_in[k_begin - 1 - in_base] of its row when k_begin > in_base, otherwise d_last_iq[2r], d_last_iq[2r+1].
+ * d_last_out, if given, receives each row's sample k_end - 1; with an empty range the row's d_last_iq, or (0, 0) when
+ * d_last_iq is NULL.  It is the next call's d_last_iq, and the two may be the same pointer (each row's pair is read
+ * before it is written, by the same lane).  in_stride must be even, and with rows > 1 cover 2 * (k_end - in_base)
+ * floats; out_stride k_end - k_begin. */
+int sdrhip_fm_demod_run_rows(void *stream, const float *d_in_iq, int64_t in_stride, int64_t in_base, float *d_out,
+                             int64_t out_stride, int rows, int64_t k_begin, int64_t k_end,
+                             const float *d_last_iq /* rows x (re, im); NULL = (0, 0) */,
+                             float *d_last_out /* NULL, or rows x (re, im) */);
+
+/* Diagnostics: kernel launches of the row forms, process-wide: 1 per call on the sequential walk and for fmDemod, 5 per
+ * call (speculate, three repair rounds, settle) with chunks. */
+long long sdrhip_debug_rows_launches(void);
+
 /* ---- the record seam on HOST vectors (hs_sources/SDR/Filter.hs:116-144) ---- */
 /* The closures a Haskell constructor puts into the reference's own Filter / Decimator / Resampler records, so that
  * the reference's UNCHANGED Pipes (firFilter / firDecimator / firResampler, Filter.hs:532-727) drive the device:

@@ -697,4 +697,85 @@ int sdrhip_debug_agc_plan(int64_t n, float mu, int run_in, int64_t* chunk, int64
     return p.nchunks;
 }
 
+// ---- row forms ------------------------------------------------------------------------------------------------------
+size_t sdrhip_agc_rows_workspace_bytes(int rows, int64_t n)
+{
+    return rows >= 1 && rows <= SDRHIP_ROWS_MAX ? agc_rows_workspace_bytes(rows, n) : 0;
+}
+
+int sdrhip_agc_run_rows(void* stream, const float* d_in_iq, int64_t in_stride, float* d_out_iq, int64_t out_stride, int rows,
+                        int64_t n, float mu, float reference, const float* d_state, float* d_final, void* d_workspace,
+                        size_t workspace_bytes, int run_in)
+{
+    SDRHIP_REQUIRE(rows >= 1 && rows <= SDRHIP_ROWS_MAX, "sdrhip_agc_run_rows: rows outside 1 .. SDRHIP_ROWS_MAX");
+    SDRHIP_REQUIRE(n >= 0 && run_in >= 0 && d_state != nullptr && d_final != nullptr, "sdrhip_agc_run_rows");
+    SDRHIP_REQUIRE(d_in_iq != nullptr && d_out_iq != nullptr && d_in_iq != d_out_iq, "sdrhip_agc_run_rows: in-place is not supported");
+    SDRHIP_REQUIRE((in_stride & 1) == 0 && (out_stride & 1) == 0, "sdrhip_agc_run_rows: odd stride on interleaved complex samples");
+    SDRHIP_REQUIRE(rows == 1 || (n <= INT64_MAX / 2 && in_stride >= 2 * n && out_stride >= 2 * n),
+                   "sdrhip_agc_run_rows: stride shorter than a row");
+    SDRHIP_REQUIRE(d_workspace == nullptr || workspace_bytes >= agc_rows_workspace_bytes(rows, n),
+                   "sdrhip_agc_run_rows: workspace smaller than sdrhip_agc_rows_workspace_bytes(rows, n)");
+    launch_agc_rows((hipStream_t)stream, rows, n, mu, reference, d_in_iq, in_stride, d_out_iq, out_stride, d_state, d_final,
+                    n > 0 ? d_workspace : nullptr, run_in);
+    SDRHIP_CHECK_HIP(hipGetLastError());
+    return SDRHIP_OK;
+}
+
+int sdrhip_debug_agc_rows_plan(int rows, int64_t n, float mu, int run_in, int64_t* chunk, int64_t* run_in_used)
+{
+    SDRHIP_REQUIRE(rows >= 1 && rows <= SDRHIP_ROWS_MAX && n >= 0 && run_in >= 0, "sdrhip_debug_agc_rows_plan");
+    const AgcPlan p = agc_rows_plan(rows, n, mu, run_in);
+    if (chunk) *chunk = p.C;
+    if (run_in_used) *run_in_used = p.W;
+    return p.nchunks;
+}
+
+size_t sdrhip_dc_blocker_rows_workspace_bytes(int rows, int64_t n)
+{
+    return rows >= 1 && rows <= SDRHIP_ROWS_MAX ? dc_blocker_rows_workspace_bytes(rows, n) : 0;
+}
+
+int sdrhip_dc_blocker_run_rows(void* stream, const float* d_in, int64_t in_stride, float* d_out, int64_t out_stride, int rows,
+                               int64_t n, const float* d_state, float* d_final, void* d_workspace, size_t workspace_bytes,
+                               int run_in)
+{
+    SDRHIP_REQUIRE(rows >= 1 && rows <= SDRHIP_ROWS_MAX, "sdrhip_dc_blocker_run_rows: rows outside 1 .. SDRHIP_ROWS_MAX");
+    SDRHIP_REQUIRE(n >= 0 && run_in >= 0 && d_state != nullptr && d_final != nullptr, "sdrhip_dc_blocker_run_rows");
+    SDRHIP_REQUIRE(d_in != nullptr && d_out != nullptr && d_in != d_out, "sdrhip_dc_blocker_run_rows: in-place is not supported");
+    SDRHIP_REQUIRE(rows == 1 || (in_stride >= n && out_stride >= n), "sdrhip_dc_blocker_run_rows: stride shorter than a row");
+    SDRHIP_REQUIRE(d_workspace == nullptr || workspace_bytes >= dc_blocker_rows_workspace_bytes(rows, n),
+                   "sdrhip_dc_blocker_run_rows: workspace smaller than sdrhip_dc_blocker_rows_workspace_bytes(rows, n)");
+    launch_dc_blocker_rows((hipStream_t)stream, rows, n, d_in, in_stride, d_out, out_stride, d_state, d_final,
+                           n > 0 ? d_workspace : nullptr, run_in);
+    SDRHIP_CHECK_HIP(hipGetLastError());
+    return SDRHIP_OK;
+}
+
+int sdrhip_debug_dc_rows_plan(int rows, int64_t n, int run_in, int64_t* chunk, int64_t* run_in_used)
+{
+    SDRHIP_REQUIRE(rows >= 1 && rows <= SDRHIP_ROWS_MAX && n >= 0 && run_in >= 0, "sdrhip_debug_dc_rows_plan");
+    const DcPlan p = dc_rows_plan(rows, n, run_in);
+    if (chunk) *chunk = p.C;
+    if (run_in_used) *run_in_used = p.W;
+    return p.nchunks;
+}
+
+int sdrhip_fm_demod_run_rows(void* stream, const float* d_in_iq, int64_t in_stride, int64_t in_base, float* d_out,
+                             int64_t out_stride, int rows, int64_t k_begin, int64_t k_end, const float* d_last_iq,
+                             float* d_last_out)
+{
+    SDRHIP_REQUIRE(rows >= 1 && rows <= SDRHIP_ROWS_MAX, "sdrhip_fm_demod_run_rows: rows outside 1 .. SDRHIP_ROWS_MAX");
+    SDRHIP_REQUIRE(k_end >= k_begin && k_begin >= in_base, "sdrhip_fm_demod_run_rows");
+    SDRHIP_REQUIRE(d_in_iq != nullptr && d_out != nullptr && d_in_iq != d_out, "sdrhip_fm_demod_run_rows: in-place is not supported");
+    SDRHIP_REQUIRE((in_stride & 1) == 0, "sdrhip_fm_demod_run_rows: odd stride on interleaved complex samples");
+    SDRHIP_REQUIRE(rows == 1 || (k_end - in_base <= INT64_MAX / 2 && in_stride >= 2 * (k_end - in_base) && out_stride >= k_end - k_begin),
+                   "sdrhip_fm_demod_run_rows: stride shorter than a row");
+    launch_fm_demod_rows((hipStream_t)stream, rows, d_in_iq + 2 * (k_begin - in_base), in_stride, d_out, out_stride, k_end - k_begin,
+                         k_begin > in_base, d_last_iq, d_last_out);
+    SDRHIP_CHECK_HIP(hipGetLastError());
+    return SDRHIP_OK;
+}
+
+long long sdrhip_debug_rows_launches(void) { return rows_launch_count(); }
+
 }  // extern "C"

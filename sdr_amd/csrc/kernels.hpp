@@ -201,6 +201,26 @@ size_t agc_workspace_bytes(int64_t num);         // enough for any run_in
 void launch_agc(hipStream_t s, int64_t num, float mu, float reference, float state, const float* d_in, float* d_out,
                 float* d_final, void* d_ws, int run_in, const float* d_state = nullptr);
 
+// Row forms (the "rows" sections of kernels_agc.hip, kernels_iir.hip, kernels_chain.hip): row r is d_in + r * in_stride ->
+// d_out + r * out_stride, strides in floats.  States in and out live on the device (agc: rows floats; dcBlocker: rows pairs;
+// d_final may alias d_state).  The workspace starts with four statistics words per row, then the rows' chunk arrays.  The plan
+// is the one-row plan, its chunk grown (to a multiple of 8 samples) only where rows * chunks would pass the lane cap.
+int64_t rows_min_chunk(int rows, int64_t num, int64_t cap);
+AgcPlan agc_rows_plan(int rows, int64_t num, float mu, int run_in);
+size_t agc_rows_workspace_bytes(int rows, int64_t num);
+void launch_agc_rows(hipStream_t s, int rows, int64_t num, float mu, float reference, const float* d_in, int64_t in_stride,
+                     float* d_out, int64_t out_stride, const float* d_state, float* d_final, void* d_ws, int run_in);
+DcPlan dc_rows_plan(int rows, int64_t num, int run_in);
+size_t dc_blocker_rows_workspace_bytes(int rows, int64_t num);
+void launch_dc_blocker_rows(hipStream_t s, int rows, int64_t num, const float* d_in, int64_t in_stride, float* d_out,
+                            int64_t out_stride, const float* d_state, float* d_final, void* d_ws, int run_in);
+// d_in_iq: row 0's first sample of the range; d_last_iq (may be null: (0, 0)) the rows' predecessors when !has_prev;
+// d_last_out (may be null, may alias d_last_iq) receives each row's newest sample
+void launch_fm_demod_rows(hipStream_t s, int rows, const float* d_in_iq, int64_t in_stride, float* d_out, int64_t out_stride,
+                          int64_t count, bool has_prev, const float* d_last_iq, float* d_last_out);
+void rows_launches_add(int launches);
+long long rows_launch_count();    // diagnostics: kernel launches of the row forms so far
+
 // Lane-split tiled kernels (kernels_split.hip): every SIMD order of the filter / decimator / resampler families,
 // any factor and tap count that fits a tile.  Plain taps (sym: the half taps).  false = not applicable.
 bool launch_fir_split(hipStream_t s, const Geom& g, bool cplx, int lanes, ComplexOrder corder, bool sym, const float* d_taps,

@@ -26,6 +26,8 @@
 // chunk length is tied to it: a chunk shorter than the run-in would spend most of a lane on redundant work.
 #include <stdlib.h>
 
+#include <atomic>
+
 #include "kernels.hpp"
 
 namespace sdrhip {
@@ -289,6 +291,195 @@ void launch_agc(hipStream_t s, int64_t num, float mu, float reference, float sta
                            s_end[cur ^ 1], p.nchunks, stats, acc);
     hipLaunchKernelGGL(k_agc_settle, dim3(1), dim3(1024), 0, s, num, p.C, p.W, mu, reference, d_in, d_out, s_start, s_end[cur],
                        p.nchunks, bad, d_final, stats, acc);
+}
+
+// ---- rows: every row of a bank in one launch set ----------------------------------------------------------------------------
+// Row r is in + r * in_stride -> out + r * out_stride (strides in floats, every offset 64-bit); its state is d_state[r], its
+// final state fin[r], its statistics stats[4r .. 4r+3].  The walks are agc_walk as above, so a row's bits are those of the
+// one-row kernels on that row alone.  acc is decided on the host from the base pointers AND the strides: one value for all rows.
+//
+// Sequential rows: one workgroup per row, one walking lane in it (k_agc_sequential with blockIdx.x = the row): every row's
+// dependent chain runs at the rate of the one-row kernel, on a compute unit of its own, with the same load pattern.
+__global__ void __launch_bounds__(64)
+k_agc_rows_sequential(int64_t num, float mu, float ref, const float* d_state, const float* __restrict__ in, int64_t in_stride,
+                      float* __restrict__ out, int64_t out_stride, float* fin, uint32_t* __restrict__ stats, int acc)
+{
+    if (threadIdx.x != 0) return;
+    const int64_t row = blockIdx.x;
+    float s = d_state[row];
+    s = agc_walk<true>(acc, in + row * in_stride, out + row * out_stride, 0, num, s, mu, ref);
+    fin[row] = s;
+    if (stats) { uint32_t* st = stats + 4 * row; st[0] = 0; st[1] = 0; st[2] = 0; st[3] = 0; }
+}
+
+// lane = (row, chunk), rows packed densely into waves: lane g walks chunk g % nchunks of row g / nchunks.  The lane of chunk 0
+// clears its row's statistics words (the repair rounds add to word 2 in later launches of the same stream).
+__global__ void __launch_bounds__(64)
+k_agc_rows_speculate(int64_t num, int64_t C, int64_t W, float mu, float ref, const float* __restrict__ d_state,
+                     const float* __restrict__ in, int64_t in_stride, float* __restrict__ out, int64_t out_stride,
+                     uint32_t* __restrict__ s_start, uint32_t* __restrict__ s_end, int nchunks, int lanes,
+                     uint32_t* __restrict__ stats, int acc)
+{
+    const int g = blockIdx.x * 64 + threadIdx.x;
+    if (g >= lanes) return;
+    const int64_t row = g / nchunks;
+    const int j = g - (int)row * nchunks;
+    in += row * in_stride;
+    out += row * out_stride;
+    if (j == 0) { uint32_t* st = stats + 4 * row; st[0] = 0; st[1] = 0; st[2] = 0; st[3] = 0; }
+    const int64_t begin = (int64_t)j * C;
+    const int64_t end = begin + C < num ? begin + C : num;
+    int64_t i = begin - W;
+    if (i < 0) i = 0;
+    float s = d_state[row];
+    s = agc_walk<false>(acc, in, out, i, begin, s, mu, ref);
+    s_start[g] = __float_as_uint(s);
+    s = agc_walk<true>(acc, in, out, begin, end, s, mu, ref);
+    s_end[g] = __float_as_uint(s);
+}
+
+__global__ void __launch_bounds__(64)
+k_agc_rows_repair(int64_t num, int64_t C, int64_t W, float mu, float ref, const float* __restrict__ in, int64_t in_stride,
+                  float* __restrict__ out, int64_t out_stride, uint32_t* __restrict__ s_start,
+                  const uint32_t* __restrict__ s_end_prev, uint32_t* __restrict__ s_end_next, int nchunks, int lanes,
+                  uint32_t* __restrict__ stats, int acc)
+{
+    const int g = blockIdx.x * 64 + threadIdx.x;
+    if (g >= lanes) return;
+    const int64_t row = g / nchunks;
+    const int j = g - (int)row * nchunks;
+    const int64_t begin = (int64_t)j * C;
+    uint32_t e = s_end_prev[g];
+    if (begin - W > 0) {
+        const uint32_t s_true = s_end_prev[g - 1];   // j >= 1 here: the same row's chunk before
+        if (s_start[g] != s_true) {
+            const int64_t end = begin + C < num ? begin + C : num;
+            e = __float_as_uint(agc_walk<true>(acc, in + row * in_stride, out + row * out_stride, begin, end,
+                                               __uint_as_float(s_true), mu, ref));
+            s_start[g] = s_true;
+            atomicAdd(&stats[4 * row + 2], 1u);
+        }
+    }
+    s_end_next[g] = e;
+}
+
+// One workgroup per row: k_agc_settle's check and whole-chunk walk on the row's own arrays, all rows at the same time.
+__global__ void __launch_bounds__(256)
+k_agc_rows_settle(int64_t num, int64_t C, int64_t W, float mu, float ref, const float* __restrict__ in, int64_t in_stride,
+                  float* __restrict__ out, int64_t out_stride, uint32_t* __restrict__ s_start, uint32_t* __restrict__ s_end,
+                  int nchunks, uint8_t* __restrict__ bad, float* fin, uint32_t* __restrict__ stats, int acc)
+{
+    const int64_t row = blockIdx.x;
+    in += row * in_stride;
+    out += row * out_stride;
+    s_start += row * nchunks;
+    s_end += row * nchunks;
+    bad += row * nchunks;
+    stats += 4 * row;
+    __shared__ int nbad;
+    if (threadIdx.x == 0) nbad = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int j = threadIdx.x; j < nchunks; j += blockDim.x) {
+        const bool exact_start = (int64_t)j * C - W <= 0;
+        const bool b = !exact_start && s_start[j] != s_end[j - 1];
+        bad[j] = b;
+        mine += b;
+    }
+    if (mine) atomicAdd(&nbad, mine);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    uint32_t rewritten = 0;
+    if (nbad > 0) {
+        int j = 1;
+        while (j < nchunks) {
+            if (!bad[j] || s_start[j] == s_end[j - 1]) { j++; continue; }
+            uint32_t s = s_end[j - 1];
+            do {
+                const int64_t begin = (int64_t)j * C;
+                const int64_t end = begin + C < num ? begin + C : num;
+                s_start[j] = s;
+                s = __float_as_uint(agc_walk<true>(acc, in, out, begin, end, __uint_as_float(s), mu, ref));
+                s_end[j] = s;
+                rewritten += (uint32_t)(end - begin);
+                j++;
+            } while (j < nchunks && s_start[j] != s);
+        }
+    }
+    stats[0] = (uint32_t)nbad;
+    stats[1] = rewritten;
+    stats[3] = (uint32_t)nchunks;
+    fin[row] = __uint_as_float(s_end[nchunks - 1]);
+}
+
+namespace {
+std::atomic<long long> g_rows_launches{0};
+}  // namespace
+
+// the shortest chunk a row may have when `rows` rows share a lane cap: a multiple of 8 samples
+int64_t rows_min_chunk(int rows, int64_t num, int64_t cap)
+{
+    int64_t per_row = cap / (rows > 0 ? rows : 1);
+    if (per_row < 1) per_row = 1;
+    const int64_t C = (num + per_row - 1) / per_row;
+    return (C + 7) & ~(int64_t)7;
+}
+
+void rows_launches_add(int launches) { g_rows_launches.fetch_add(launches); }
+long long rows_launch_count() { return g_rows_launches.load(); }
+
+AgcPlan agc_rows_plan(int rows, int64_t num, float mu, int run_in)
+{
+    AgcPlan p = agc_plan(num, mu, run_in);
+    if ((int64_t)rows * p.nchunks > kAgcMaxLanes) {
+        const int64_t C = rows_min_chunk(rows, num, kAgcMaxLanes);
+        if (C > p.C) p.C = C;
+        p.nchunks = (int)((num + p.C - 1) / p.C);
+    }
+    return p;
+}
+
+size_t agc_rows_workspace_bytes(int rows, int64_t num)
+{
+    if (num < 1) num = 1;
+    int64_t C = (num + kAgcMaxLanes - 1) / kAgcMaxLanes;   // as agc_workspace_bytes: the shortest chunk any run-in gives
+    if (C < kAgcMinChunk) C = kAgcMinChunk;
+    C = (C + 7) & ~(int64_t)7;
+    const int64_t Cr = rows_min_chunk(rows, num, kAgcMaxLanes);
+    if ((int64_t)rows * ((num + C - 1) / C) > kAgcMaxLanes && Cr > C) C = Cr;
+    const size_t nchunks = (size_t)((num + C - 1) / C);
+    return (size_t)rows * 16 + (size_t)rows * nchunks * 13 + 64;   // per row: stats; s_start, s_end x2 (u32 each), bad (u8)
+}
+
+void launch_agc_rows(hipStream_t s, int rows, int64_t num, float mu, float reference, const float* d_in, int64_t in_stride,
+                     float* d_out, int64_t out_stride, const float* d_state, float* d_final, void* d_ws, int run_in)
+{
+    if (num < 0 || rows < 1) return;
+    uintptr_t both = (uintptr_t)d_in | (uintptr_t)d_out;
+    if (rows > 1) both |= (uintptr_t)(in_stride * 4) | (uintptr_t)(out_stride * 4);   // row r starts at base + r * stride
+    const int acc = (both & 15) == 0 ? 2 : (both & 7) == 0 ? 1 : 0;
+    uint32_t* stats = reinterpret_cast<uint32_t*>(d_ws);
+    const AgcPlan p = agc_rows_plan(rows, num, mu, run_in);
+    if (d_ws == nullptr || p.nchunks == 0) {
+        hipLaunchKernelGGL(k_agc_rows_sequential, dim3(rows), dim3(64), 0, s, num, mu, reference, d_state, d_in, in_stride, d_out,
+                           out_stride, d_final, stats, acc);
+        rows_launches_add(1);
+        return;
+    }
+    const int lanes = rows * p.nchunks;
+    uint32_t* s_start = stats + 4 * (size_t)rows;
+    uint32_t* s_end[2] = {s_start + lanes, s_start + 2 * (size_t)lanes};
+    uint8_t* bad = reinterpret_cast<uint8_t*>(s_start + 3 * (size_t)lanes);
+    const dim3 grid((lanes + 63) / 64);
+    hipLaunchKernelGGL(k_agc_rows_speculate, grid, dim3(64), 0, s, num, p.C, p.W, mu, reference, d_state, d_in, in_stride, d_out,
+                       out_stride, s_start, s_end[0], p.nchunks, lanes, stats, acc);
+    int cur = 0;
+    for (int r = 0; r < AGC_REPAIR_ROUNDS; r++, cur ^= 1)
+        hipLaunchKernelGGL(k_agc_rows_repair, grid, dim3(64), 0, s, num, p.C, p.W, mu, reference, d_in, in_stride, d_out, out_stride,
+                           s_start, s_end[cur], s_end[cur ^ 1], p.nchunks, lanes, stats, acc);
+    hipLaunchKernelGGL(k_agc_rows_settle, dim3(rows), dim3(256), 0, s, num, p.C, p.W, mu, reference, d_in, in_stride, d_out,
+                       out_stride, s_start, s_end[cur], p.nchunks, bad, d_final, stats, acc);
+    rows_launches_add(2 + AGC_REPAIR_ROUNDS);
 }
 
 }  // namespace sdrhip

@@ -80,6 +80,55 @@ __global__ void __launch_bounds__(256) k_fm_demod_fast(const float* __restrict__
     }
 }
 
+// K3 over rows: k_fm_demod_fast's body with blockIdx.y = the row.  Row r reads in + r * in_stride (its sample k_begin; floats,
+// 64-bit offsets) and writes out + r * out_stride.  Without a predecessor in the buffer the row's is last_iq[2r], last_iq[2r+1]
+// (null: (0, 0)).  last_out, if given, receives the row's newest sample -- or its predecessor when the range is empty -- from
+// the one lane that reads last_iq[2r .. 2r+1], after it has read them: the two may be the same array.
+__global__ void __launch_bounds__(256) k_fm_demod_rows(const float* __restrict__ in, int64_t in_stride, float* __restrict__ out,
+                                                        int64_t out_stride, int64_t count, int has_prev, const float* last_iq,
+                                                        float* last_out, int out_vec)
+{
+    const int64_t row = blockIdx.y;
+    const float2* in2 = reinterpret_cast<const float2*>(in + row * in_stride);
+    out += row * out_stride;
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;   // holds quad 0 and, when there is no quad, tail sample 0
+    float2 last = make_float2(0.0f, 0.0f);
+    if (first && (!has_prev || count == 0) && last_iq) last = make_float2(last_iq[2 * row], last_iq[2 * row + 1]);
+    const int64_t nquad = count >> 2;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    __shared__ __attribute__((aligned(16))) float atbl[kAtanRows * kAtanRowFloats];
+    atan_table_fill(atbl, threadIdx.x);
+    __syncthreads();
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nquad; q += stride) {
+        const float2 s0 = in2[4 * q], s1 = in2[4 * q + 1], s2 = in2[4 * q + 2], s3 = in2[4 * q + 3];
+        float2 prev;
+        if (q > 0 || has_prev) prev = in2[4 * q - 1];
+        else prev = last;
+        const float4 r = fm_phase_quad(prev, s0, s1, s2, s3, atbl);
+        if (out_vec) {
+            reinterpret_cast<float4*>(out)[q] = r;
+        } else {
+            out[4 * q] = r.x; out[4 * q + 1] = r.y; out[4 * q + 2] = r.z; out[4 * q + 3] = r.w;
+        }
+    }
+    // tail (< 4 samples)
+    if (blockIdx.x == 0 && threadIdx.x < (count & 3)) {
+        const int64_t i = (nquad << 2) + threadIdx.x;
+        const float2 cur = in2[i];
+        float2 prev;
+        if (i > 0 || has_prev) prev = in2[i - 1];
+        else prev = last;
+        out[i] = fm_phase_sel(cur, prev);
+    }
+    if (first && last_out) {
+        float2 v;
+        if (count > 0) v = in2[count - 1];
+        else v = last;
+        last_out[2 * row] = v.x;
+        last_out[2 * row + 1] = v.y;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // K5  real FIR filters (D = 1), 8 lanes:
 //   SYM  (filterAVXSymmetricRR, filter.c:60-68 -> avx_sym_dotprod_R common.h:181-201):
@@ -683,6 +732,23 @@ void launch_fm_demod_fast(hipStream_t s, const float* d_in_iq, float* d_out, int
     constexpr int64_t cap = 256 * 64;
     if (blocks > cap) blocks = cap;
     hipLaunchKernelGGL(k_fm_demod_fast, dim3((int)blocks), dim3(256), 0, s, d_in_iq, d_out, count, has_prev ? 1 : 0, last_re, last_im, out_vec);
+}
+
+// d_in_iq: row 0's sample k_begin.  One launch for all rows (none when there is nothing to write).
+void launch_fm_demod_rows(hipStream_t s, int rows, const float* d_in_iq, int64_t in_stride, float* d_out, int64_t out_stride,
+                          int64_t count, bool has_prev, const float* d_last_iq, float* d_last_out)
+{
+    if (rows < 1 || count < 0 || (count == 0 && d_last_out == nullptr)) return;
+    // a row starts at d_out + r * out_stride: 16-byte stores need the base and, with more than one row, the stride aligned
+    const int out_vec = ((reinterpret_cast<uintptr_t>(d_out) & 15) == 0 && (rows == 1 || (out_stride & 3) == 0)) ? 1 : 0;
+    int64_t blocks = ((count >> 2) + 255) / 256;
+    if (blocks < 1) blocks = 1;
+    int64_t cap = 256 * 64 / rows;   // launch_fm_demod_fast's cap on the workgroups, shared among the rows
+    if (cap < 1) cap = 1;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(k_fm_demod_rows, dim3((int)blocks, rows), dim3(256), 0, s, d_in_iq, in_stride, d_out, out_stride, count,
+                       has_prev ? 1 : 0, d_last_iq, d_last_out, out_vec);
+    rows_launches_add(1);
 }
 
 bool launch_fir_real8_fast(hipStream_t s, const Geom& g, bool sym, const float* d_taps, int nk, const float* d_cross_taps,

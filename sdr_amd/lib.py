@@ -268,6 +268,17 @@ lib.sdrhip_agc_workspace_bytes.argtypes = [C.c_int64]
 lib.sdrhip_agc_workspace_bytes.restype = C.c_size_t
 lib.sdrhip_agc_run.argtypes = [_vp, _vp, _vp, C.c_int64, C.c_float, C.c_float, C.c_float, _vp, _vp, C.c_size_t, C.c_int]
 lib.sdrhip_debug_agc_plan.argtypes = [C.c_int64, C.c_float, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]
+lib.sdrhip_agc_rows_workspace_bytes.argtypes = [C.c_int, C.c_int64]
+lib.sdrhip_agc_rows_workspace_bytes.restype = C.c_size_t
+lib.sdrhip_agc_run_rows.argtypes = [_vp, _vp, _i64, _vp, _i64, C.c_int, _i64, C.c_float, C.c_float, _vp, _vp, _vp, C.c_size_t, C.c_int]
+lib.sdrhip_debug_agc_rows_plan.argtypes = [C.c_int, C.c_int64, C.c_float, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]
+lib.sdrhip_dc_blocker_rows_workspace_bytes.argtypes = [C.c_int, C.c_int64]
+lib.sdrhip_dc_blocker_rows_workspace_bytes.restype = C.c_size_t
+lib.sdrhip_dc_blocker_run_rows.argtypes = [_vp, _vp, _i64, _vp, _i64, C.c_int, _i64, _vp, _vp, _vp, C.c_size_t, C.c_int]
+lib.sdrhip_debug_dc_rows_plan.argtypes = [C.c_int, C.c_int64, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]
+lib.sdrhip_fm_demod_run_rows.argtypes = [_vp, _vp, _i64, _i64, _vp, _i64, C.c_int, _i64, _i64, _vp, _vp]
+lib.sdrhip_debug_rows_launches.argtypes = []
+lib.sdrhip_debug_rows_launches.restype = C.c_longlong
 
 lib.sdrhip_fm_stream_create.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int]
 lib.sdrhip_fm_stream_destroy.argtypes = [_vp]
@@ -488,6 +499,130 @@ def agc(x, mu, reference, state=1.0, run_in=0):
             if b:
                 lib.sdrhip_free(b)
     return out, float(fin[0])
+
+
+# ---- row forms: every row of a bank in one launch set ---------------------------------------------------------------------------
+ROWS_MAX = 1024
+
+
+def agc_rows_plan(rows, n, mu, run_in=0):
+    """sdrhip_debug_agc_rows_plan: (chunks per row, chunk length, run-in); rows == 1 gives agc_plan(n, mu, run_in)."""
+    c, w = _i64(), _i64()
+    chunks = check(lib.sdrhip_debug_agc_rows_plan(rows, n, mu, run_in, C.byref(c), C.byref(w)), "sdrhip_debug_agc_rows_plan")
+    return chunks, c.value, w.value
+
+
+def dc_rows_plan(rows, n, run_in=0):
+    """sdrhip_debug_dc_rows_plan: (chunks per row, chunk length, run-in); rows == 1 gives dc_plan(n, run_in)."""
+    c, w = _i64(), _i64()
+    chunks = check(lib.sdrhip_debug_dc_rows_plan(rows, n, run_in, C.byref(c), C.byref(w)), "sdrhip_debug_dc_rows_plan")
+    return chunks, c.value, w.value
+
+
+def rows_stats(ws, rows):
+    """The statistics words at the start of a rows workspace (a device tensor of bytes): per row the four words of dc_stats."""
+    w = ws[:16 * rows].cpu().numpy().view(np.uint32).reshape(rows, 4)
+    return [tuple(int(v) for v in r) for r in w]
+
+
+def rows_launches():
+    """sdrhip_debug_rows_launches: kernel launches of the row forms in this process."""
+    return int(lib.sdrhip_debug_rows_launches())
+
+
+def _rows_of(t, what, floats_per_sample=1):
+    """(rows, samples per row, row stride in floats) of a 2-D device tensor whose rows are contiguous: complex64 (a sample is one
+    element) or float32 (a sample is floats_per_sample floats).  The stride may be anything: a view into a bank's output works."""
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{what}: a 2-D tensor with contiguous rows is needed")
+    if t.is_complex():
+        return t.shape[0], t.shape[1], 2 * t.stride(0)
+    if t.shape[1] % floats_per_sample:
+        raise ValueError(f"{what}: {t.shape[1]} floats per row is not a whole number of samples")
+    return t.shape[0], t.shape[1] // floats_per_sample, t.stride(0)
+
+
+def _dptr(t):
+    """data_ptr(), also for a view without elements (torch reports 0 there, and the library refuses null pointers)"""
+    return t.data_ptr() if t.numel() else t.untyped_storage().data_ptr() + t.storage_offset() * t.element_size()
+
+
+def _rows_empty(rows, width, dtype, device):
+    import torch
+    return torch.empty(max(rows * width, 1), dtype=dtype, device=device)[:rows * width].view(rows, width)
+
+
+def _rows_workspace(workspace, nbytes, device):
+    """workspace: "auto" = allocate; None = none (every row takes the sequential walk); or a device tensor of bytes."""
+    import torch
+    if workspace is None:
+        return None, 0, 0
+    if isinstance(workspace, str):
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return workspace, workspace.data_ptr(), workspace.numel()
+
+
+def agc_rows(x, mu, reference, states, run_in=0, out=None, final=None, workspace="auto"):
+    """sdrhip_agc_run_rows on the current stream -> (out, final).  x: rows x n complex64, or rows x 2n float32 interleaved, on the
+    device, rows contiguous, any row stride (a view will do).  states: rows float32 on the device.  out (default: a new
+    contiguous tensor like x) and final (default: new; may be `states`) as given.  No synchronisation."""
+    import torch
+    rows, n, in_stride = _rows_of(x, "agc_rows", 2)
+    if out is None:
+        out = _rows_empty(rows, x.shape[1], x.dtype, x.device)
+    orows, on, out_stride = _rows_of(out, "agc_rows", 2)
+    if (orows, on) != (rows, n) or states.numel() != rows or states.dtype != torch.float32:
+        raise ValueError("agc_rows: out and states must match x's rows")
+    if final is None:
+        final = torch.empty(rows, dtype=torch.float32, device=x.device)
+    ws, ws_ptr, ws_bytes = _rows_workspace(workspace, lib.sdrhip_agc_rows_workspace_bytes(rows, n), x.device)
+    check(lib.sdrhip_agc_run_rows(torch.cuda.current_stream().cuda_stream, _dptr(x), in_stride, _dptr(out), out_stride, rows, n,
+                                  mu, reference, states.data_ptr(), final.data_ptr(), ws_ptr, ws_bytes, run_in), "sdrhip_agc_run_rows")
+    return out, final
+
+
+def dc_blocker_rows(x, states, run_in=0, out=None, final=None, workspace="auto"):
+    """sdrhip_dc_blocker_run_rows on the current stream -> (out, final).  x: rows x n float32 on the device, rows contiguous, any
+    row stride.  states: rows x 2 float32 (last_sample, last_output) on the device; final likewise (default: new; may be `states`)."""
+    import torch
+    rows, n, in_stride = _rows_of(x, "dc_blocker_rows")
+    if out is None:
+        out = _rows_empty(rows, n, torch.float32, x.device)
+    orows, on, out_stride = _rows_of(out, "dc_blocker_rows")
+    if (orows, on) != (rows, n) or states.numel() != 2 * rows or states.dtype != torch.float32 or not states.is_contiguous():
+        raise ValueError("dc_blocker_rows: out and states must match x's rows")
+    if final is None:
+        final = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
+    ws, ws_ptr, ws_bytes = _rows_workspace(workspace, lib.sdrhip_dc_blocker_rows_workspace_bytes(rows, n), x.device)
+    check(lib.sdrhip_dc_blocker_run_rows(torch.cuda.current_stream().cuda_stream, _dptr(x), in_stride, _dptr(out), out_stride,
+                                         rows, n, states.data_ptr(), final.data_ptr(), ws_ptr, ws_bytes, run_in),
+          "sdrhip_dc_blocker_run_rows")
+    return out, final
+
+
+def fm_demod_rows(x, last=None, out=None, last_out=None, in_base=0, k_begin=None, k_end=None):
+    """sdrhip_fm_demod_run_rows on the current stream -> out (rows x (k_end - k_begin) float32).  x: rows x m complex64 or rows x 2m
+    float32 interleaved on the device: each row holds its samples in_base .. in_base + m.  k_begin / k_end default to the whole
+    row.  last: rows x 2 float32 on the device, the rows' predecessors when k_begin == in_base (None: (0, 0)); last_out, if given
+    (it may be `last`), receives each row's sample k_end - 1."""
+    import torch
+    rows, m, in_stride = _rows_of(x, "fm_demod_rows", 2)
+    k_begin = in_base if k_begin is None else k_begin
+    k_end = in_base + m if k_end is None else k_end
+    if not in_base <= k_begin <= k_end <= in_base + m:
+        raise ValueError("fm_demod_rows: [k_begin, k_end) must lie inside the rows")
+    if out is None:
+        out = _rows_empty(rows, k_end - k_begin, torch.float32, x.device)
+    orows, on, out_stride = _rows_of(out, "fm_demod_rows")
+    if (orows, on) != (rows, k_end - k_begin) or out.dtype != torch.float32:
+        raise ValueError("fm_demod_rows: out must be rows x (k_end - k_begin) float32")
+    for t in (last, last_out):
+        if t is not None and (t.numel() != 2 * rows or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError("fm_demod_rows: last / last_out are rows x 2 float32")
+    check(lib.sdrhip_fm_demod_run_rows(torch.cuda.current_stream().cuda_stream, _dptr(x), in_stride, in_base, _dptr(out),
+                                       out_stride, rows, k_begin, k_end, last.data_ptr() if last is not None else None,
+                                       last_out.data_ptr() if last_out is not None else None), "sdrhip_fm_demod_run_rows")
+    return out
 
 
 # ---- descriptors ----------------------------------------------------------------------
