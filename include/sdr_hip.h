@@ -450,6 +450,64 @@ int sdrhip_fm_demod_run_rows(void *stream, const float *d_in_iq, int64_t in_stri
  * call (speculate, three repair rounds, settle) with chunks. */
 long long sdrhip_debug_rows_launches(void);
 
+/* The FIR operators over rows: the filter, decimator and resampler stages behind a bank (second decimator per channel, resampler
+ * and audio filter per station) in one launch set instead of one call per row.  in_base, k_begin, k_end, seam_block and out_block
+ * mean what they mean to sdrhip_filter_run / sdrhip_decimator_run / sdrhip_resampler_run and are the same for every row; row r's
+ * d_in[0] is ITS stream element in_base.  Row r's outputs [k_begin, k_end) equal, bit for bit, what the one-row call writes for
+ * that row alone with the same arguments -- on every route, for every rows, stride, in_base and cut into launches, and whatever the
+ * other rows hold.  Nothing new is argued: the summation orders, the One / Cross rule and the resampler's two corner cases (a seam
+ * without crossover, the late first output of an output block) are the one-row operators'.  Floats of d_out outside the rows'
+ * outputs are not touched.  Asynchronous on `stream`; after the descriptor's first run no allocation, no host synchronisation and
+ * no host-to-device copy (a row's base and stride travel in the kernel's arguments).  No alignment is asked of bases or strides
+ * beyond the element's own.
+ * Routes (same bits).  1 = banked: ONE launch of the lane-split tile kernel with the row on the grid's second axis, and ONE fix-up
+ * launch for the Cross outputs of all rows when a seam lies inside the range -- whatever rows is.  It serves a SIMD order (SSE / AVX),
+ * real or complex data, the symmetric real filters, up to 64 chunks of lane-count taps, resamplers of up to 64 polyphase groups,
+ * seam_block >= 0; on anything else (the scalar order, longer filters, more groups, seam_block < 0) it returns SDRHIP_ERR_ARG.
+ * There is no minimum length.  2 = row by row: the one-row operator per row on the caller's stream, every shape.  0 = auto: see the
+ * rule below; where it does not bank, row by row.
+ * SDRHIP_ERR_ARG, before any device work and with nothing written: whatever the one-row call refuses, rows outside
+ * 1 .. SDRHIP_ROWS_MAX, a route outside 0 .. 2, and with a non-empty range a null pointer, d_in == d_out, an odd stride on a complex
+ * side, with rows > 1 an out_stride shorter than a row's outputs or an in_stride shorter than the inputs the one-row call is
+ * guaranteed, counted from in_base (complex: two floats each).  An empty range is SDRHIP_OK and touches nothing.
+ * Auto rule.  Auto banks a launch only where the banked route serves the shape AND the launch lies in the part of the measured
+ * sweep where the banked call's slowest round was below the K one-row calls' fastest (tools/fir_rows_bench.py,
+ * profiles/fir_rows_bench.txt: 1 / 2 / 8 / 32 rows x 128 / 1024 / 16384 / 2^20 outputs per row, 7 rounds; a complex AVX decimator
+ * 64 taps / 4, a real AVX resampler 3/10 and a real symmetric AVX filter, each with seam_block 0 and with one seam inside the
+ * range).  Those three stand for their family and data type; a real decimator, a complex filter and a complex resampler were not
+ * measured and go row by row, as do one row, more than 32 rows and fewer than 128 or more than 2^20 outputs per row.  With n the
+ * outputs per row, the fewest rows that are banked at the measured sizes n = 128 / 1024 / 16384 / 2^20:
+ *                          seam_block 0          a seam inside the range
+ *     complex decimator    2 / 2 / 2 / 8         2 / 8 / 8 / 8
+ *     real resampler       2 / 2 / 2 / 2         2 / 8 / 8 / 8
+ *     real filter          2 / 2 / 8 / 32        2 / 8 / 8 / 8
+ * An n between two measured sizes takes the larger of their two entries; a seam_block > 0 with no seam inside the range takes the
+ * larger of the two columns.  Every entry is the smallest measured row count from which all larger ones were ahead (8 where 2 was
+ * not, so 3 .. 7 rows wait with it): the crossovers are real -- from 1024 outputs on a seamed one-row call is a single launch of
+ * the generic or a specialised kernel (7 .. 40 us for two rows against 12 .. 45 us banked), and at 2^20 outputs the one-row
+ * filter kernel is as fast per row as the tile kernel (43 against 45 us for 8 rows).  One row is ahead only at 128 outputs
+ * (the decimator, 4.6 against 5.2 us, and the resampler without a seam, 4.2 against 5.9 us), an edge of the sweep, and behind by
+ * 1.2x .. 3.1x elsewhere: it stays row by row. */
+int sdrhip_filter_run_rows(const sdrhip_filter *f, void *stream, const float *d_in, int64_t in_stride, int64_t in_base,
+                           float *d_out, int64_t out_stride, int rows, int64_t k_begin, int64_t k_end, int64_t seam_block,
+                           int route);
+int sdrhip_decimator_run_rows(const sdrhip_decimator *d, void *stream, const float *d_in, int64_t in_stride, int64_t in_base,
+                              float *d_out, int64_t out_stride, int rows, int64_t k_begin, int64_t k_end, int64_t seam_block,
+                              int route);
+int sdrhip_resampler_run_rows(const sdrhip_resampler *r, void *stream, const float *d_in, int64_t in_stride, int64_t in_base,
+                              float *d_out, int64_t out_stride, int rows, int64_t k_begin, int64_t k_end, int64_t seam_block,
+                              int64_t out_block, int route);
+/* Diagnostics: the tile plan of the banked route for rows of outputs [k_begin, k_end) of a descriptor (kind 0 = sdrhip_filter,
+ * 1 = sdrhip_decimator, 2 = sdrhip_resampler).  Host arithmetic, no device.  Returns 1 and fills plan[0 .. 5] = {cycles per tile,
+ * tiles per row, independent outputs per lane (1 or 2), outputs per cycle (1; a resampler: its groups), and the cycles per tile
+ * and outputs per lane the one-row lane-split kernel plans for ONE such row}; 0 when the banked route does not serve the shape
+ * (plan untouched).  A tile holds cycles per tile x outputs per cycle outputs.  The rows plan is the one-row plan capped at the
+ * row's own cycles (rounded up to a whole run of lanes), so a long row gets plan[0] == plan[4] and plan[2] == plan[5]. */
+int sdrhip_debug_fir_rows_plan(const void *desc, int kind, int rows, int64_t k_begin, int64_t k_end, int64_t seam_block,
+                               int *plan /* 6 ints */);
+long long sdrhip_debug_fir_rows_launches(void);   /* banked tile launches, process-wide; fix-up launches not counted */
+long long sdrhip_debug_fir_rows_fixups(void);     /* banked fix-up launches, process-wide */
+
 /* ---- the record seam on HOST vectors (hs_sources/SDR/Filter.hs:116-144) ---- */
 /* The closures a Haskell constructor puts into the reference's own Filter / Decimator / Resampler records, so that
  * the reference's UNCHANGED Pipes (firFilter / firDecimator / firResampler, Filter.hs:532-727) drive the device:

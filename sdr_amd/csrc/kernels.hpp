@@ -230,6 +230,25 @@ bool launch_resample_split(hipStream_t s, const Geom& g, bool cplx, int lanes, C
 
 long long split_launch_count();   // diagnostics: launches the lane-split kernels have taken so far
 
+// kernels_fir_rows.hip: the lane-split tile with a row axis (sdrhip_*_run_rows, route 1).  Row r is d_in + r * in_stride ->
+// d_out + r * out_stride (floats; even on a complex side); g, taps and tables are the one-row launch's and the same for every row.
+// Shapes: those of launch_fir_split / launch_resample_split without their minimum length (g.seamBI >= 0, a SIMD order, 1 .. 64
+// chunks, up to 64 groups).  One tile launch, and one fix-up launch when seam_span(g).nseams > 0; false = not this shape, nothing
+// launched.  No gain, no u8 input.
+struct FirRowsPlan { int cycles_per_tile, tiles_per_row, U, outputs_per_cycle; };
+// host arithmetic only (CPU-testable): the plan launch_*_rows follows, and (if asked) the tile plan_tile gives k_split for one such row
+bool fir_rows_plan(const Geom& g, int rows, bool cplx, int lanes, ComplexOrder corder, bool sym, int ntaps, FirRowsPlan* rows_plan,
+                   FirRowsPlan* one_row_split_plan = nullptr);
+bool resample_rows_plan(const Geom& g, int rows, bool cplx, int lanes, ComplexOrder corder, const ResampTable& t, FirRowsPlan* rows_plan,
+                        FirRowsPlan* one_row_split_plan = nullptr);
+bool launch_fir_rows(hipStream_t s, const Geom& g, int rows, int64_t in_stride, int64_t out_stride, bool cplx, int lanes,
+                     ComplexOrder corder, bool sym, const float* d_taps, int ntaps, const float* d_cross_taps, const float* d_in, float* d_out);
+bool launch_resample_rows(hipStream_t s, const Geom& g, int rows, int64_t in_stride, int64_t out_stride, bool cplx, int lanes,
+                          ComplexOrder corder, const ResampTable& t, const float* d_groups, const float* d_plain_taps, const float* d_in,
+                          float* d_out);
+long long fir_rows_launch_count();   // diagnostics: banked tile launches
+long long fir_rows_fixup_count();    // diagnostics: banked fix-up launches
+
 // kernels_decimate_real.hip: real decimators by 2 / 4 / 8 / 16, AVX / SSE lane order, up to 2048 taps (sym: d_taps = nk half-taps,
 // a multiple of 8, g.Lp = 2 nk): 16 / D
 // outputs per thread, scalar-loaded taps, rolled walk.  False = not this kernel's shape.

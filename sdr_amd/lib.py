@@ -279,6 +279,14 @@ lib.sdrhip_debug_dc_rows_plan.argtypes = [C.c_int, C.c_int64, C.c_int, C.POINTER
 lib.sdrhip_fm_demod_run_rows.argtypes = [_vp, _vp, _i64, _i64, _vp, _i64, C.c_int, _i64, _i64, _vp, _vp]
 lib.sdrhip_debug_rows_launches.argtypes = []
 lib.sdrhip_debug_rows_launches.restype = C.c_longlong
+lib.sdrhip_filter_run_rows.argtypes = [_vp, _vp, _vp, _i64, _i64, _vp, _i64, C.c_int, _i64, _i64, _i64, C.c_int]
+lib.sdrhip_decimator_run_rows.argtypes = [_vp, _vp, _vp, _i64, _i64, _vp, _i64, C.c_int, _i64, _i64, _i64, C.c_int]
+lib.sdrhip_resampler_run_rows.argtypes = [_vp, _vp, _vp, _i64, _i64, _vp, _i64, C.c_int, _i64, _i64, _i64, _i64, C.c_int]
+lib.sdrhip_debug_fir_rows_plan.argtypes = [_vp, C.c_int, C.c_int, _i64, _i64, _i64, C.POINTER(C.c_int)]
+lib.sdrhip_debug_fir_rows_launches.argtypes = []
+lib.sdrhip_debug_fir_rows_launches.restype = C.c_longlong
+lib.sdrhip_debug_fir_rows_fixups.argtypes = []
+lib.sdrhip_debug_fir_rows_fixups.restype = C.c_longlong
 
 lib.sdrhip_fm_stream_create.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int]
 lib.sdrhip_fm_stream_destroy.argtypes = [_vp]
@@ -625,6 +633,58 @@ def fm_demod_rows(x, last=None, out=None, last_out=None, in_base=0, k_begin=None
     return out
 
 
+# ---- row forms of the FIR operators --------------------------------------------------------
+FIR_ROWS_AUTO, FIR_ROWS_BANKED, FIR_ROWS_ROW_BY_ROW = 0, 1, 2
+
+
+def fir_rows_launches():
+    """sdrhip_debug_fir_rows_launches: banked tile launches of the FIR row forms in this process (fix-ups not counted)."""
+    return int(lib.sdrhip_debug_fir_rows_launches())
+
+
+def fir_rows_fixups():
+    """sdrhip_debug_fir_rows_fixups: banked seam fix-up launches of the FIR row forms in this process."""
+    return int(lib.sdrhip_debug_fir_rows_fixups())
+
+
+def fir_rows_plan(desc, k_begin, k_end, rows=1, seam_block=0):
+    """sdrhip_debug_fir_rows_plan for a Filter / Decimator / Resampler: None where the banked route does not serve the shape, else a
+    dict: cycles_per_tile, tiles_per_row, per_lane (independent outputs per lane), per_cycle (outputs per cycle: a resampler's
+    groups), tile_outputs, and split_cycles_per_tile / split_per_lane: what the one-row lane-split kernel plans for one such row."""
+    kind = 0 if isinstance(desc, Filter) else 1 if isinstance(desc, Decimator) else 2
+    p = (C.c_int * 6)()
+    if not check(lib.sdrhip_debug_fir_rows_plan(desc.h, kind, rows, k_begin, k_end, seam_block, p), "sdrhip_debug_fir_rows_plan"):
+        return None
+    return {"cycles_per_tile": p[0], "tiles_per_row": p[1], "per_lane": p[2], "per_cycle": p[3], "tile_outputs": p[0] * p[3],
+            "split_cycles_per_tile": p[4], "split_per_lane": p[5]}
+
+
+def _fir_rows_side(t, stride, rows, cplx, what):
+    """(pointer, stride in floats, rows or None) of one side of a FIR rows call: a 2-D device tensor with contiguous rows (complex64,
+    or float32 -- interleaved pairs on a complex operator), any row stride, or a device pointer with the stride given."""
+    if isinstance(t, int) or t is None:
+        if stride is None:
+            raise ValueError(f"{what}: a pointer needs its row stride")
+        return t, int(stride), rows
+    r, _, st = _rows_of(t, what, 2 if cplx and not t.is_complex() else 1)
+    if t.is_complex() != bool(cplx) and t.is_complex():
+        raise ValueError(f"{what}: complex rows on a real operator")
+    return _dptr(t), st if stride is None else int(stride), r
+
+
+def _fir_rows_call(fn, name, desc, x, out, k_begin, k_end, in_base, tail, route, stream, in_stride, out_stride, rows):
+    px, ist, r_in = _fir_rows_side(x, in_stride, rows, desc.complex, name)
+    po, ost, r_out = _fir_rows_side(out, out_stride, rows, desc.complex, name)
+    rows = rows if rows is not None else r_in if r_in is not None else r_out
+    if rows is None or any(r is not None and r != rows for r in (r_in, r_out)):
+        raise ValueError(f"{name}: the two sides must have the same number of rows (pointers: pass rows=)")
+    if stream is None and not (isinstance(x, int) and isinstance(out, int)):
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    check(fn(desc.h, stream, px, ist, in_base, po, ost, rows, k_begin, k_end, *tail, route), name)
+    return out
+
+
 # ---- descriptors ----------------------------------------------------------------------
 class _Handle:
     _destroy = None
@@ -661,6 +721,14 @@ class Filter(_Handle):
     def run(self, d_in, in_base, d_out, k_begin, k_end, seam_block=0, stream=None):
         check(lib.sdrhip_filter_run(self.h, stream, d_in, in_base, d_out, k_begin, k_end, seam_block), "sdrhip_filter_run")
 
+    def run_rows(self, x, out, k_begin, k_end, in_base=0, seam_block=0, route=FIR_ROWS_AUTO, stream=None, in_stride=None,
+                 out_stride=None, rows=None):
+        """sdrhip_filter_run_rows: outputs [k_begin, k_end) of every row, row r of x (its stream from element in_base on) -> row r of
+        out.  x / out: 2-D device tensors with contiguous rows and any row stride (a view into a bank's output will do), on the
+        current stream -- or device pointers with in_stride / out_stride (floats) and rows.  No synchronisation.  -> out"""
+        return _fir_rows_call(lib.sdrhip_filter_run_rows, "sdrhip_filter_run_rows", self, x, out, k_begin, k_end, in_base, (seam_block,),
+                              route, stream, in_stride, out_stride, rows)
+
 
 class Decimator(_Handle):
     """fastDecimator{C,SSE,AVX}{R,C} / fastDecimatorSym{SSE,AVX}R (Filter.hs:277-387)."""
@@ -679,6 +747,12 @@ class Decimator(_Handle):
 
     def run(self, d_in, in_base, d_out, k_begin, k_end, seam_block=0, stream=None):
         check(lib.sdrhip_decimator_run(self.h, stream, d_in, in_base, d_out, k_begin, k_end, seam_block), "sdrhip_decimator_run")
+
+    def run_rows(self, x, out, k_begin, k_end, in_base=0, seam_block=0, route=FIR_ROWS_AUTO, stream=None, in_stride=None,
+                 out_stride=None, rows=None):
+        """sdrhip_decimator_run_rows: as Filter.run_rows (row r of x holds its inputs from element in_base on)."""
+        return _fir_rows_call(lib.sdrhip_decimator_run_rows, "sdrhip_decimator_run_rows", self, x, out, k_begin, k_end, in_base,
+                              (seam_block,), route, stream, in_stride, out_stride, rows)
 
     def run_u8(self, d_in, in_base, d_out, k_begin, k_end, seam_block=0, stream=None):
         check(lib.sdrhip_decimator_run_u8(self.h, stream, d_in, in_base, d_out, k_begin, k_end, seam_block), "sdrhip_decimator_run_u8")
@@ -710,6 +784,12 @@ class Resampler(_Handle):
     def run(self, d_in, in_base, d_out, k_begin, k_end, seam_block=0, stream=None, out_block=0):
         check(lib.sdrhip_resampler_run(self.h, stream, d_in, in_base, d_out, k_begin, k_end, seam_block, out_block),
               "sdrhip_resampler_run")
+
+    def run_rows(self, x, out, k_begin, k_end, in_base=0, seam_block=0, out_block=0, route=FIR_ROWS_AUTO, stream=None, in_stride=None,
+                 out_stride=None, rows=None):
+        """sdrhip_resampler_run_rows: as Filter.run_rows, with the Pipe's output block size as in run()."""
+        return _fir_rows_call(lib.sdrhip_resampler_run_rows, "sdrhip_resampler_run_rows", self, x, out, k_begin, k_end, in_base,
+                              (seam_block, out_block), route, stream, in_stride, out_stride, rows)
 
 
 TUNER_ROUTE_AUTO, TUNER_ROUTE_FUSED, TUNER_ROUTE_TWO_PASS = 0, 1, 2
