@@ -1,8 +1,9 @@
-/* channel_replay.c -- every channel of one u8 IQ capture as complex baseband files, through nothing but the C ABI.
+/* channel_replay.c -- every channel of one u8 or int16 IQ capture as complex baseband files, through nothing but the C ABI.
  *
- *     channel_replay CAPTURE.u8 TAPS.f32 OUT_PREFIX --channels NUM/DEN[,NUM/DEN...] [--factor D] [--block-out N] [--push SAMPLES]
+ *     channel_replay CAPTURE TAPS.f32 OUT_PREFIX --channels NUM/DEN[,NUM/DEN...] [--factor D] [--block-out N] [--push SAMPLES] [--s16]
  *
- * CAPTURE.u8: interleaved unsigned 8-bit (I, Q) pairs (an RTL-SDR dump).  TAPS.f32: the decimator's coefficients, raw float32.
+ * CAPTURE: interleaved unsigned 8-bit (I, Q) pairs (an RTL-SDR dump); with --s16 interleaved signed 16-bit pairs in host byte order (a
+ * BladeRF dump), which go through the int16 Pipe (sdrhip_pipe_tuner_bank_i16: 4 bytes per sample over the link).  TAPS.f32: the decimator's coefficients, raw float32.
  * Channel j is the capture shifted by NUM/DEN cycles per sample (sdrhip_tuner_shift_table; 0/1 is the centre frequency) and
  * decimated by D (default 8); its samples go to OUT_PREFIX.chJ.cf32 as interleaved float32 (re, im), whole blocks of N (default
  * 1024) only, as the Pipe yields them.  The capture is pushed SAMPLES (default 8192) at a time, the rest in one shorter push:
@@ -58,12 +59,14 @@ static void drain(sdrhip_pipe *p, int ready, int channels, int block_out, float 
 int main(int argc, char **argv)
 {
     const char *spec = NULL;
-    int factor = 8, block_out = 1024, push = 8192;
+    int factor = 8, block_out = 1024, push = 8192, s16 = 0;
     if (argc < 4) {
-        fprintf(stderr, "usage: %s CAPTURE.u8 TAPS.f32 OUT_PREFIX --channels NUM/DEN[,...] [--factor D] [--block-out N] [--push SAMPLES]\n", argv[0]);
+        fprintf(stderr, "usage: %s CAPTURE.u8 TAPS.f32 OUT_PREFIX --channels NUM/DEN[,...] [--factor D] [--block-out N] [--push SAMPLES] [--s16]\n", argv[0]);
         return 2;
     }
-    for (int i = 4; i + 1 < argc; i += 2) {
+    for (int i = 4; i < argc; i += 2) {
+        if (!strcmp(argv[i], "--s16")) { s16 = 1; i--; continue; }
+        if (i + 1 >= argc) { fprintf(stderr, "channel_replay: %s needs a value\n", argv[i]); return 2; }
         if (!strcmp(argv[i], "--channels")) spec = argv[i + 1];
         else if (!strcmp(argv[i], "--factor")) factor = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--block-out")) block_out = atoi(argv[i + 1]);
@@ -96,7 +99,9 @@ int main(int argc, char **argv)
     if (sdrhip_tuner_bank_create(&bank, 2 /* the AVX order */, factor, taps, ntaps, channels, (const float *const *)tables, periods) != SDRHIP_OK)
         die("sdrhip_tuner_bank_create");
     sdrhip_pipe *pipe = NULL;
-    if (sdrhip_pipe_tuner_bank(&pipe, bank, block_out, 1) != SDRHIP_OK) die("sdrhip_pipe_tuner_bank");
+    if (s16) {
+        if (sdrhip_pipe_tuner_bank_i16(&pipe, bank, block_out) != SDRHIP_OK) die("sdrhip_pipe_tuner_bank_i16");
+    } else if (sdrhip_pipe_tuner_bank(&pipe, bank, block_out, 1) != SDRHIP_OK) die("sdrhip_pipe_tuner_bank");
 
     FILE *cap = fopen(argv[1], "rb");
     if (!cap) { perror(argv[1]); return 1; }
@@ -114,12 +119,12 @@ int main(int argc, char **argv)
     long long total = 0;
     for (;;) {
         /* read straight into the pinned staging memory of the next push */
-        uint8_t *dst = sdrhip_pipe_input_buffer_u8(pipe, push);
-        if (!dst) die("sdrhip_pipe_input_buffer_u8");
-        const int n = (int)(fread(dst, 2, (size_t)push, cap));
+        void *dst = s16 ? (void *)sdrhip_pipe_input_buffer_i16(pipe, push) : (void *)sdrhip_pipe_input_buffer_u8(pipe, push);
+        if (!dst) die(s16 ? "sdrhip_pipe_input_buffer_i16" : "sdrhip_pipe_input_buffer_u8");
+        const int n = (int)(fread(dst, s16 ? 4 : 2, (size_t)push, cap));
         if (n < lp) break;                    /* the end of the capture: a rest shorter than the filter computes nothing */
-        const int ready = sdrhip_pipe_push_u8(pipe, dst, n);
-        if (ready < 0) die("sdrhip_pipe_push_u8");
+        const int ready = s16 ? sdrhip_pipe_push_i16(pipe, (const int16_t *)dst, n) : sdrhip_pipe_push_u8(pipe, (const uint8_t *)dst, n);
+        if (ready < 0) die(s16 ? "sdrhip_pipe_push_i16" : "sdrhip_pipe_push_u8");
         drain(pipe, ready, channels, block_out, rows, out);
         total += n;
         if (n < push) break;

@@ -129,6 +129,8 @@ foreign import ccall safe "sdrhip_tuner_factor"      c_tuner_factor      :: Ptr 
 foreign import ccall safe "sdrhip_tuner_period"      c_tuner_period      :: Ptr SdrTuner -> IO CInt
 foreign import ccall safe "sdrhip_tuner_run"         c_tuner_run         :: Ptr SdrTuner -> Ptr () -> Ptr CFloat -> Int64 -> Ptr CFloat -> Int64 -> Int64 -> Int64 -> IO CInt
 foreign import ccall safe "sdrhip_tuner_run_u8"      c_tuner_run_u8      :: Ptr SdrTuner -> Ptr () -> Ptr CUChar -> Int64 -> Ptr CFloat -> Int64 -> Int64 -> Int64 -> IO CInt
+foreign import ccall safe "sdrhip_tuner_run_i16"     c_tuner_run_i16     :: Ptr SdrTuner -> Ptr () -> Ptr CShort -> Int64 -> Ptr CFloat -> Int64 -> Int64 -> Int64 -> IO CInt
+foreign import ccall safe "sdrhip_debug_tuner_i16_launches" c_tuner_i16_launches :: IO CLLong
 foreign import ccall safe "sdrhip_tuner_set_route"   c_tuner_set_route   :: Ptr SdrTuner -> CInt -> IO CInt
 foreign import ccall safe "sdrhip_tuner_shift_table" c_tuner_shift_table :: Int64 -> Int64 -> Ptr CFloat -> IO CInt
 foreign import ccall safe "sdrhip_debug_tuner_fused_launches" c_tuner_fused_launches :: IO CLLong
@@ -160,7 +162,12 @@ foreign import ccall safe "sdrhip_pipe_tuner_bank"      c_pipe_tuner_bank      :
 foreign import ccall safe "sdrhip_pipe_rows"            c_pipe_rows            :: Ptr SdrPipe -> IO CInt
 foreign import ccall safe "sdrhip_pipe_push_u8"         c_pipe_push_u8         :: Ptr SdrPipe -> Ptr CUChar -> CInt -> IO CInt
 foreign import ccall safe "sdrhip_pipe_input_buffer_u8" c_pipe_input_buffer_u8 :: Ptr SdrPipe -> CInt -> IO (Ptr CUChar)
-foreign import ccall safe "sdrhip_pipe_pop_rows"        c_pipe_pop_rows        :: Ptr SdrPipe -> Ptr CFloat -> Int64 -> CInt -> IO CInt
+-- the same Pipe on interleaved int16 IQ host blocks (a BladeRF's samples, s / 2048 in the kernels' loaders)
+foreign import ccall safe "sdrhip_tuner_bank_run_i16"    c_tuner_bank_run_i16    :: Ptr SdrTunerBank -> Ptr () -> Ptr CShort -> Int64 -> Ptr CFloat -> Int64 -> Int64 -> Int64 -> Int64 -> IO CInt
+foreign import ccall safe "sdrhip_pipe_tuner_bank_i16"   c_pipe_tuner_bank_i16   :: Ptr (Ptr SdrPipe) -> Ptr SdrTunerBank -> CInt -> IO CInt
+foreign import ccall safe "sdrhip_pipe_push_i16"         c_pipe_push_i16         :: Ptr SdrPipe -> Ptr CShort -> CInt -> IO CInt
+foreign import ccall safe "sdrhip_pipe_input_buffer_i16" c_pipe_input_buffer_i16 :: Ptr SdrPipe -> CInt -> IO (Ptr CShort)
+foreign import ccall safe "sdrhip_pipe_pop_rows"        c_pipe_pop_rows      :: Ptr SdrPipe -> Ptr CFloat -> Int64 -> CInt -> IO CInt
 foreign import ccall safe "sdrhip_debug_tuner_bank_cross_launches" c_tuner_bank_cross_launches :: IO CLLong
 -- the spectrum operator (include/sdr_hip.h, sdrhip_spectrum_*): interleavedIQUnsigned256ToFloat -> halfBandUp x window -> fftw ->
 -- magnitude x scale, rows of Float

@@ -256,6 +256,18 @@ int sdrhip_tuner_run(const sdrhip_tuner *t, void *stream, const float *d_in, int
                      int64_t k_begin, int64_t k_end, int64_t seam_block);
 int sdrhip_tuner_run_u8(const sdrhip_tuner *t, void *stream, const uint8_t *d_in_iq, int64_t in_base, float *d_out,
                         int64_t k_begin, int64_t k_end, int64_t seam_block);
+/* 16-bit signed IQ (the BladeRF's samples): d_in_iq is interleaved (I, Q) int16, element i of the stream is d_in_iq[2 (i - in_base)]
+ * and [... + 1], lengths and positions in complex samples as for u8.  With c(s) = (float)s * 2^-11 for EVERY int16 s (convertCBladeRF,
+ * convert.c:52-85; exact in f32, c(0) = +0) the call writes, bit for bit, what sdrhip_tuner_run writes from the cfloat buffer
+ * sdrhip_convert_i16_run makes of the same int16 buffer -- nothing new is argued.  The conversion happens first, in the kernels'
+ * loaders (then the mix, then the taps; the 2^-11 is folded neither into the taps nor into the table: a product that underflows does
+ * not commute with a power of two).  Routes as below: 1 = fused is the tuner bank's int16 tile kernel with one channel
+ * (sdrhip_debug_tuner_i16_launches counts it, sdrhip_debug_tuner_fused_launches does not), its first window (d_in_iq + 4 bytes per
+ * sample) 16-byte aligned; 2 = two-pass with an int16 mix kernel.  d_in_iq must be 4-byte aligned on every route (SDRHIP_ERR_ARG). */
+int sdrhip_tuner_run_i16(const sdrhip_tuner *t, void *stream, const int16_t *d_in_iq, int64_t in_base, float *d_out,
+                         int64_t k_begin, int64_t k_end, int64_t seam_block);
+/* process-wide: launches of the int16 tile kernel, from a bank or from a one-row tuner (tests assert that no conversion pass stood in) */
+long long sdrhip_debug_tuner_i16_launches(void);
 /* Routes (same bits).  1 = fused: one tile kernel whose loader converts, fetches the oscillator entry and mixes on the way into
  * LDS, so m never reaches memory -- AVX order, factor 4 / 8 / 16, up to 128 prepared taps, seam_block >= 0, a 16-byte aligned
  * first window; a launch outside that returns SDRHIP_ERR_ARG.  2 = two-pass: a mix kernel writes m into a bounded
@@ -306,6 +318,19 @@ int sdrhip_tuner_bank_run(const sdrhip_tuner_bank *b, void *stream, const float 
                           int64_t out_stride, int64_t k_begin, int64_t k_end, int64_t seam_block);
 int sdrhip_tuner_bank_run_u8(const sdrhip_tuner_bank *b, void *stream, const uint8_t *d_in_iq, int64_t in_base, float *d_out,
                              int64_t out_stride, int64_t k_begin, int64_t k_end, int64_t seam_block);
+/* 16-bit signed IQ, as sdrhip_tuner_run_i16: every row holds, bit for bit, what sdrhip_tuner_bank_run writes from the cfloat buffer
+ * sdrhip_convert_i16_run makes of the same int16 buffer, on every route, for every seam_block, in_base, cut into launches and
+ * out_stride.  Refusals as sdrhip_tuner_bank_run_u8, plus a d_in_iq that is not 4-byte aligned.  Routes: 1 = the banked launch of the
+ * int16 tile kernel (it counts in sdrhip_debug_tuner_bank_launches AND in sdrhip_debug_tuner_i16_launches), 2 = sdrhip_tuner_run_i16
+ * channel by channel, 0 = auto.  Auto rule for int16 input, with n = (k_end - k_begin) * factor:
+ *     banked  iff  channels >= 2  and  n <= 2^24
+ * read from `tools/tuner_bank_bench.py --i16` (profiles/tuner_i16_bench.txt: 1 / 2 / 4 / 8 / 12 / 32 channels x 8192, 2^17, 2^20 and 2^24
+ * input samples, 128 taps / 8, 7 rounds) by the criterion of the rule below: at every measured point with K >= 2 the banked launch's
+ * slowest round was below the K sdrhip_tuner_run_i16 calls' fastest, so the sweep confirms the u8 / cfloat rectangle and both bounds are
+ * its edges; nothing beyond 2^24 samples per launch is measured.  One channel goes to its tuner, which for int16 is the same kernel with
+ * one channel (measured level: 0.995 .. 1.001). */
+int sdrhip_tuner_bank_run_i16(const sdrhip_tuner_bank *b, void *stream, const int16_t *d_in_iq, int64_t in_base, float *d_out,
+                              int64_t out_stride, int64_t k_begin, int64_t k_end, int64_t seam_block);
 /* Routes (same bits).  1 = the banked launch: the tuner's fused tile kernel with a channel axis, one launch for all channels (and one
  * fix-up launch for all channels where the tuner's fused route takes one) -- the shapes of the tuner's route 1: AVX order, factor
  * 4 / 8 / 16, up to 128 prepared taps, seam_block >= 0, a 16-byte aligned first window; a launch outside that is SDRHIP_ERR_ARG.
@@ -972,6 +997,17 @@ int sdrhip_pipe_tuner_bank(sdrhip_pipe **p, const sdrhip_tuner_bank *b, int bloc
 int sdrhip_pipe_rows(const sdrhip_pipe *p);
 int sdrhip_pipe_push_u8(sdrhip_pipe *p, const uint8_t *iq, int n_samples);
 uint8_t *sdrhip_pipe_input_buffer_u8(sdrhip_pipe *p, int n_samples);
+/* The tuner bank on host blocks of interleaved int16 IQ (4 bytes per sample from the staging buffer to the kernels' loaders).
+ * Definition: sdrhip_pipe_tuner_bank's, with c(s) = (float)s * 2^-11 in place of (u - 128) * (1 / 128): channel j's blocks are those
+ * of a one-row sdrhip_pipe_tuner with table j fed the same blocks as c(.) floats at the same boundaries.  Such a pipe takes
+ * sdrhip_pipe_push_i16 / sdrhip_pipe_input_buffer_i16 (n_samples (I, Q) int16 pairs); the wrong call for a pipe's input type -- any
+ * of the three -- is SDRHIP_ERR_ARG (NULL) with nothing staged.  The carried tail starts at a multiple of 4 samples; rows, submission,
+ * coalesce, adaptive (4 bytes per sample) and flush as above.  Saved states are version 2 with input type 2 and the history as
+ * int16; restore refuses an int16 state on a cfloat or u8 pipe and the reverse, the pipe unchanged.
+ * Create: SDRHIP_ERR_ARG (and *p = NULL) before any device work for a null argument and block_size_out <= 0. */
+int sdrhip_pipe_tuner_bank_i16(sdrhip_pipe **p, const sdrhip_tuner_bank *b, int block_size_out);
+int sdrhip_pipe_push_i16(sdrhip_pipe *p, const int16_t *iq, int n_samples);
+int16_t *sdrhip_pipe_input_buffer_i16(sdrhip_pipe *p, int n_samples);
 int sdrhip_pipe_pop_rows(sdrhip_pipe *p, float *out, int64_t row_stride, int max_blocks);
 /* Feed one upstream block (n elements: floats, or complex pairs for complex
  * stages).  Returns the number of complete output blocks now ready (>= 0) or a

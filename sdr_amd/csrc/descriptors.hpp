@@ -84,6 +84,9 @@ int resamp_run_demod(const ResampDesc* r, hipStream_t s, const float* d_iq, bool
 
 // The tuner (include/sdr_hip.h): a complex decimator's prepared taps plus the oscillator table.  Immutable after create except for
 // the route and the scratch lanes of the two-pass route, so host threads may share one.
+// The input of the tuner family: cfloat, interleaved u8 IQ (RTL-SDR: (u - 128) / 128) or interleaved int16 IQ (BladeRF: s / 2048)
+enum InFmt : int { IN_CF32 = 0, IN_U8 = 1, IN_I16 = 2 };
+inline int in_fmt_bytes(InFmt f) { return f == IN_U8 ? 2 : f == IN_I16 ? 4 : 8; }      // per complex sample
 struct TunerScratch;
 struct TunerDesc {
     FirDesc fir;                       // as sdrhip_decimator_create(order, data_complex = 1, ...) prepares it
@@ -98,7 +101,7 @@ struct TunerDesc {
     TunerDesc(const TunerDesc&) = delete;
     TunerDesc& operator=(const TunerDesc&) = delete;
 };
-int tuner_run(const TunerDesc* t, hipStream_t s, const void* d_in, bool in_u8, int64_t in_base, float* d_out, int64_t k_begin,
+int tuner_run(const TunerDesc* t, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out, int64_t k_begin,
               int64_t k_end, int64_t seam_block);
 
 // The tuner bank (include/sdr_hip.h): K tuners of the same decimator over one input.  The bank OWNS those K tuner descriptors -- they
@@ -118,10 +121,10 @@ struct TunerBankDesc {
     TunerBankDesc(const TunerBankDesc&) = delete;
     TunerBankDesc& operator=(const TunerBankDesc&) = delete;
 };
-int tuner_bank_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, bool in_u8, int64_t in_base, float* d_out, int64_t out_stride,
+int tuner_bank_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out, int64_t out_stride,
                    int64_t k_begin, int64_t k_end, int64_t seam_block);
 // every output of [k_begin, k_end) Cross, all channels in one launch: the ragged pushes of the bank's Pipe (pipes.cpp)
-int tuner_bank_cross_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, bool in_u8, int64_t in_base, float* d_out,
+int tuner_bank_cross_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out,
                          int64_t out_stride, int64_t k_begin, int64_t k_end);
 
 }  // namespace sdrhip

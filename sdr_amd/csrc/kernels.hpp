@@ -382,5 +382,19 @@ long long tuner_bank_launch_count();    // diagnostics: banked launches
 bool launch_tuner_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_taps, const void* d_in, bool in_is_u8, float* d_out,
                              int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods);
 long long tuner_bank_cross_launch_count();   // diagnostics: launches of the all-Cross kernel
+// kernels_tuner_i16.hip: the tuner family on 16-bit signed IQ (interleaved int16, 4 bytes per sample, (float)s * 2^-11 in the loader).
+// launch_tuner_bank_i16 is launch_tuner_bank for such input -- with channels = 1, offsets = {0} it is the one-row tuner's fused route
+// (counts_as_bank = false then) -- and launch_tuner_bank_cross_i16 / launch_tuner_mix_i16 are launch_tuner_bank_cross / launch_tuner_mix.
+// Fit predicate: tuner_fused_fits with the first window at d_in + 4 x0 bytes, and d_in at least 4-byte aligned.
+bool tuner_i16_fused_fits(const Geom& g, int P, bool has_cross_taps, const void* d_in, const void* d_out, int period);
+bool launch_tuner_bank_i16(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in,
+                           float* d_out, int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods,
+                           bool counts_as_bank);
+bool launch_tuner_bank_cross_i16(hipStream_t s, const Geom& g, const float* d_cross_taps, const void* d_in, float* d_out,
+                                 int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods);
+void launch_tuner_mix_i16(hipStream_t s, const void* d_in, float* d_out, int64_t n, const float* d_osc, int period, int ph0);
+long long tuner_i16_launch_count();              // diagnostics: launches of k_tuner_bank_c4_i16, bank or one-row
+long long tuner_i16_bank_launch_count();         // ... those of them that were banked launches
+long long tuner_i16_bank_cross_launch_count();   // ... launches of the all-Cross int16 kernel
 
 }  // namespace sdrhip

@@ -21,7 +21,7 @@
 //
 // The tuner bank's Pipe (sdrhip_pipe_tuner_bank) is the tuner's Pipe with the engine's rows: one submission computes every
 // channel's outputs into a row-major chunk which the harvest regroups into one fifo per channel.  Its blocks may be u8 IQ (2 bytes
-// per element from the staging buffer to the kernels' loaders).  With more than one row nothing is read in place: up to kDirectBytes
+// per element from the staging buffer to the kernels' loaders) or int16 IQ (4 bytes per element, sdrhip_pipe_tuner_bank_i16).  With more than one row nothing is read in place: up to kDirectBytes
 // a submission is one copy on the slot's stream and the launch behind it, placed in device memory so that the banked launch's first
 // window is 16-byte aligned (HostStream::dev_skew).
 #include <stdlib.h>
@@ -42,9 +42,10 @@ struct sdrhip_pipe {
     const ResampDesc* rs = nullptr;
     const TunerDesc* tuner = nullptr;  // PK_TUNER: the decimator behind the oscillator mix (fir = &tuner->fir)
     // PK_TUNER_BANK: every channel of the bank in lockstep, one output row per channel (the engine's rows); fir = channel 0's decimator,
-    // which is every channel's.  in_u8: the blocks are interleaved u8 IQ, 2 bytes per element, and stay u8 up to the kernels' loaders
+    // which is every channel's.  fmt: the blocks are cfloat, interleaved u8 IQ (2 bytes per element) or interleaved int16 IQ (4 bytes
+    // per element), and stay in that type up to the kernels' loaders
     const TunerBankDesc* bank = nullptr;
-    bool in_u8 = false;
+    InFmt fmt = IN_CF32;
     int block_out = 0;
     bool cplx_in = false, cplx_out = false;
     int I = 1, D = 1, Lp = 1;
@@ -91,9 +92,9 @@ struct sdrhip_pipe {
     bool has_dev_state() const { return (kind == PK_DCBLOCK || kind == PK_AGC) && dc_state.p; }
 
     int esz_in() const { return cplx_in ? 2 : 1; }
-    size_t ein() const { return in_u8 ? 2 : (size_t)esz_in() * 4; }      // bytes per input element
-    // the carried tail starts at a multiple of this many elements: 16 bytes of either input type
-    int64_t tail_align() const { return in_u8 ? 8 : 4; }
+    size_t ein() const { return fmt == IN_U8 ? 2 : fmt == IN_I16 ? 4 : (size_t)esz_in() * 4; }      // bytes per input element
+    // the carried tail starts at a multiple of this many elements: 16 bytes of u8 or int16 input (and the 4 every float pipe always had)
+    int64_t tail_align() const { return fmt == IN_U8 ? 8 : 4; }
     int rows() const { return eng.rows; }
     int esz_out() const { return cplx_out ? 2 : 1; }
     int64_t in_offset(int64_t m) const { return ceil_div64(m * (int64_t)D, I); }
@@ -105,11 +106,11 @@ struct sdrhip_pipe {
 // A pipe of the given kind and geometry, with its engine: FIR-like pipes get head room and history for the carried tail,
 // E_prev - in_offset(m_done) < (Lp + D) / I + 1 elements, plus up to 3 of alignment slack (7 of a u8 pipe); map pipes carry nothing.
 static int pipe_new(sdrhip_pipe** out, PipeKind kind, const FirDesc* fir, const ResampDesc* rs, int block_out, bool cplx_in,
-                    bool cplx_out, int I, int D, int Lp, bool in_u8 = false)
+                    bool cplx_out, int I, int D, int Lp, InFmt fmt = IN_CF32)
 {
     sdrhip_pipe* p = new sdrhip_pipe();
     p->kind = kind; p->fir = fir; p->rs = rs; p->block_out = block_out;
-    p->cplx_in = cplx_in; p->cplx_out = cplx_out; p->in_u8 = in_u8;
+    p->cplx_in = cplx_in; p->cplx_out = cplx_out; p->fmt = fmt;
     p->I = I; p->D = D; p->Lp = Lp;
     int64_t head_cap = 0;
     if (!p->is_map()) {
@@ -195,17 +196,17 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
         float* dout = (float*)d_out;
         if (p->kind == PK_TUNER_BANK) {
             // every row [cross | one], row_floats apart: the bank's own rule picks the banked launch or channel by channel
-            if (uniform_seam > 0) return tuner_bank_run(p->bank, s, d_in, p->in_u8, in_base, dout, row_floats, m_done, m_end, uniform_seam);
+            if (uniform_seam > 0) return tuner_bank_run(p->bank, s, d_in, p->fmt, in_base, dout, row_floats, m_done, m_end, uniform_seam);
             const int64_t ncross = m_split - m_done;
             int r;
-            if (ncross > 0 && (r = tuner_bank_cross_run(p->bank, s, d_in, p->in_u8, in_base, dout, row_floats, m_done, m_split)) != SDRHIP_OK)
+            if (ncross > 0 && (r = tuner_bank_cross_run(p->bank, s, d_in, p->fmt, in_base, dout, row_floats, m_done, m_split)) != SDRHIP_OK)
                 return r;
-            return tuner_bank_run(p->bank, s, d_in, p->in_u8, in_base, dout + 2 * ncross, row_floats, m_split, m_end, 0);
+            return tuner_bank_run(p->bank, s, d_in, p->fmt, in_base, dout + 2 * ncross, row_floats, m_split, m_end, 0);
         }
         // filter / decimator, or the tuner's mix + decimator: in_base is the absolute stream position of din[0], which is what
         // selects the oscillator phase
         auto fir_run = [&](const FirDesc* f, hipStream_t st, const float* in, bool, int64_t base, float* out, int64_t k0, int64_t k1, int64_t seam) {
-            if (p->kind == PK_TUNER) return tuner_run(p->tuner, st, in, false, base, out, k0, k1, seam);
+            if (p->kind == PK_TUNER) return tuner_run(p->tuner, st, in, IN_CF32, base, out, k0, k1, seam);
             return sdrhip::fir_run(f, st, in, false, base, out, k0, k1, seam);
         };
         if (uniform_seam > 0) {
@@ -334,7 +335,22 @@ int sdrhip_pipe_tuner_bank(sdrhip_pipe** pp, const sdrhip_tuner_bank* b, int blo
     SDRHIP_REQUIRE(block_size_out > 0, "sdrhip_pipe_tuner_bank: block_size_out > 0");
     SDRHIP_REQUIRE(input_u8 == 0 || input_u8 == 1, "sdrhip_pipe_tuner_bank: input_u8 is 0 (cfloat blocks) or 1 (u8 IQ blocks)");
     const FirDesc* f = &b->ch[0]->fir;
-    int rc = pipe_new(pp, PK_TUNER_BANK, f, nullptr, block_size_out, true, true, 1, f->factor, f->Lp, input_u8 == 1);
+    int rc = pipe_new(pp, PK_TUNER_BANK, f, nullptr, block_size_out, true, true, 1, f->factor, f->Lp, input_u8 == 1 ? IN_U8 : IN_CF32);
+    if (rc != SDRHIP_OK) return rc;
+    (*pp)->bank = b;
+    if (b->ch.size() > 1) (*pp)->eng.set_rows((int)b->ch.size());
+    return SDRHIP_OK;
+}
+
+int sdrhip_pipe_tuner_bank_i16(sdrhip_pipe** pp, const sdrhip_tuner_bank* b, int block_size_out)
+{
+    // (all of it before pipe_new, as above)
+    SDRHIP_REQUIRE(pp != nullptr, "sdrhip_pipe_tuner_bank_i16");
+    *pp = nullptr;
+    SDRHIP_REQUIRE(b != nullptr, "sdrhip_pipe_tuner_bank_i16: null bank");
+    SDRHIP_REQUIRE(block_size_out > 0, "sdrhip_pipe_tuner_bank_i16: block_size_out > 0");
+    const FirDesc* f = &b->ch[0]->fir;
+    int rc = pipe_new(pp, PK_TUNER_BANK, f, nullptr, block_size_out, true, true, 1, f->factor, f->Lp, IN_I16);
     if (rc != SDRHIP_OK) return rc;
     (*pp)->bank = b;
     if (b->ch.size() > 1) (*pp)->eng.set_rows((int)b->ch.size());
@@ -459,14 +475,24 @@ static int map_push(sdrhip_pipe* p, const float* block, int n)
 int sdrhip_pipe_push(sdrhip_pipe* p, const float* block, int n)
 {
     SDRHIP_REQUIRE(p != nullptr && block != nullptr && n > 0, "sdrhip_pipe_push");
-    SDRHIP_REQUIRE(!p->in_u8, "sdrhip_pipe_push: this pipe takes u8 IQ blocks (sdrhip_pipe_push_u8)");
+    SDRHIP_REQUIRE(p->fmt == IN_CF32, p->fmt == IN_U8 ? "sdrhip_pipe_push: this pipe takes u8 IQ blocks (sdrhip_pipe_push_u8)"
+                                                       : "sdrhip_pipe_push: this pipe takes int16 IQ blocks (sdrhip_pipe_push_i16)");
     return p->is_map() ? map_push(p, block, n) : fir_like_push(p, block, n);
 }
 
 int sdrhip_pipe_push_u8(sdrhip_pipe* p, const uint8_t* iq, int n_samples)
 {
     SDRHIP_REQUIRE(p != nullptr && iq != nullptr && n_samples > 0, "sdrhip_pipe_push_u8");
-    SDRHIP_REQUIRE(p->in_u8, "sdrhip_pipe_push_u8: this pipe takes float blocks (sdrhip_pipe_push)");
+    SDRHIP_REQUIRE(p->fmt == IN_U8, p->fmt == IN_I16 ? "sdrhip_pipe_push_u8: this pipe takes int16 IQ blocks (sdrhip_pipe_push_i16)"
+                                                     : "sdrhip_pipe_push_u8: this pipe takes float blocks (sdrhip_pipe_push)");
+    return fir_like_push(p, iq, n_samples);
+}
+
+int sdrhip_pipe_push_i16(sdrhip_pipe* p, const int16_t* iq, int n_samples)
+{
+    SDRHIP_REQUIRE(p != nullptr && iq != nullptr && n_samples > 0, "sdrhip_pipe_push_i16");
+    SDRHIP_REQUIRE(p->fmt == IN_I16, p->fmt == IN_U8 ? "sdrhip_pipe_push_i16: this pipe takes u8 IQ blocks (sdrhip_pipe_push_u8)"
+                                                     : "sdrhip_pipe_push_i16: this pipe takes float blocks (sdrhip_pipe_push)");
     return fir_like_push(p, iq, n_samples);
 }
 
@@ -489,12 +515,14 @@ int sdrhip_pipe_set_adaptive(sdrhip_pipe* p, int max_blocks)
     return SDRHIP_OK;
 }
 
-// the staging memory of the next push, for both input types (`who` names the caller in a refusal)
-static void* pipe_input_buffer(sdrhip_pipe* p, int n, bool u8, const char* who)
+// the staging memory of the next push, for the three input types (`who` names the caller in a refusal)
+static void* pipe_input_buffer(sdrhip_pipe* p, int n, InFmt fmt, const char* who)
 {
     if (p == nullptr || n <= 0 || p->is_map()) { set_error("%s: filter / decimator / resampler pipes, n > 0", who); return nullptr; }
-    if (p->in_u8 != u8) {
-        set_error("%s: this pipe takes %s", who, p->in_u8 ? "u8 IQ blocks (sdrhip_pipe_input_buffer_u8)" : "float blocks (sdrhip_pipe_input_buffer)");
+    if (p->fmt != fmt) {
+        set_error("%s: this pipe takes %s", who, p->fmt == IN_U8 ? "u8 IQ blocks (sdrhip_pipe_input_buffer_u8)"
+                                               : p->fmt == IN_I16 ? "int16 IQ blocks (sdrhip_pipe_input_buffer_i16)"
+                                                                  : "float blocks (sdrhip_pipe_input_buffer)");
         return nullptr;
     }
     HostStream& e = p->eng;
@@ -510,11 +538,16 @@ static void* pipe_input_buffer(sdrhip_pipe* p, int n, bool u8, const char* who)
     return e.write_pos();
 }
 
-float* sdrhip_pipe_input_buffer(sdrhip_pipe* p, int n) { return (float*)pipe_input_buffer(p, n, false, "sdrhip_pipe_input_buffer"); }
+float* sdrhip_pipe_input_buffer(sdrhip_pipe* p, int n) { return (float*)pipe_input_buffer(p, n, IN_CF32, "sdrhip_pipe_input_buffer"); }
 
 uint8_t* sdrhip_pipe_input_buffer_u8(sdrhip_pipe* p, int n_samples)
 {
-    return (uint8_t*)pipe_input_buffer(p, n_samples, true, "sdrhip_pipe_input_buffer_u8");
+    return (uint8_t*)pipe_input_buffer(p, n_samples, IN_U8, "sdrhip_pipe_input_buffer_u8");
+}
+
+int16_t* sdrhip_pipe_input_buffer_i16(sdrhip_pipe* p, int n_samples)
+{
+    return (int16_t*)pipe_input_buffer(p, n_samples, IN_I16, "sdrhip_pipe_input_buffer_i16");
 }
 
 int sdrhip_pipe_poll(sdrhip_pipe* p)
@@ -570,12 +603,13 @@ struct PipeStateHeader {
     float last_re, last_im, dc[4];
 };
 constexpr uint32_t kPipeMagic = 0x50504453u;   // "SDPP"
-// Version 2: a pipe of more than one row or of u8 input.  The same header, then this, then the engine's state with the history in the
-// input's own type (2 bytes per u8 element) and the fifo row after row.  Every other pipe writes version 1, byte for byte as before.
+// Version 2: a pipe of more than one row or of u8 / int16 input.  The same header, then this, then the engine's state with the history
+// in the input's own type (2 bytes per u8 element, 4 per int16 one) and the fifo row after row; input_u8 is the input type: 0 = cfloat,
+// 1 = u8, 2 = int16.  Every other pipe writes version 1, byte for byte as before.
 struct PipeStateRows {
     int32_t rows, input_u8;
 };
-static uint32_t pipe_state_version(const sdrhip_pipe* p) { return p->rows() > 1 || p->in_u8 ? 2u : 1u; }
+static uint32_t pipe_state_version(const sdrhip_pipe* p) { return p->rows() > 1 || p->fmt != IN_CF32 ? 2u : 1u; }
 static size_t pipe_state_header_bytes(const sdrhip_pipe* p) { return sizeof(PipeStateHeader) + (pipe_state_version(p) == 2 ? sizeof(PipeStateRows) : 0); }
 }  // namespace
 
@@ -618,7 +652,7 @@ int sdrhip_pipe_save(sdrhip_pipe* p, void* buf, size_t capacity, size_t* used)
     }
     memcpy(buf, &h, sizeof h);
     if (h.version == 2) {
-        const PipeStateRows x = {p->rows(), p->in_u8 ? 1 : 0};
+        const PipeStateRows x = {p->rows(), (int32_t)p->fmt};
         memcpy((unsigned char*)buf + sizeof h, &x, sizeof x);
     }
     unsigned char* o = p->eng.save((unsigned char*)buf + pipe_state_header_bytes(p));
@@ -640,7 +674,7 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
         SDRHIP_REQUIRE(bytes >= pipe_state_header_bytes(p), "sdrhip_pipe_restore: truncated state");
         PipeStateRows x;
         memcpy(&x, (const unsigned char*)buf + sizeof h, sizeof x);
-        SDRHIP_REQUIRE(x.rows == p->rows() && x.input_u8 == (p->in_u8 ? 1 : 0),
+        SDRHIP_REQUIRE(x.rows == p->rows() && x.input_u8 == (int32_t)p->fmt,
                        "sdrhip_pipe_restore: the state belongs to a pipe of another row count or input type");
     }
     SDRHIP_REQUIRE(h.kind == (int32_t)p->kind && h.block_out == p->block_out && h.I == p->I && h.D == p->D && h.Lp == p->Lp &&

@@ -4,6 +4,8 @@
 // taps, aligned tile starts).  Two-pass: k_tuner_mix writes the mixed samples of a bounded chunk of the launch into a leased
 // scratch buffer and the stock decimator (fir_run, every order and factor) runs on it; chunks overlap by numCoeffs - factor
 // samples, which are mixed twice.  Both give sdrhip_decimator_run's bits on the mixed stream.
+// Input formats (InFmt): cfloat and u8 IQ take the kernels of kernels_tuner.hip; int16 IQ (sdrhip_tuner_run_i16) takes those of
+// kernels_tuner_i16.hip -- its fused route is the tuner bank's int16 tile kernel with one channel, its two-pass route an int16 mix.
 #include <math.h>
 
 #include <atomic>
@@ -49,7 +51,7 @@ int TunerDesc::ensure_device() const
     return upload_floats(&d_osc, h_osc);
 }
 
-static int tuner_two_pass(const TunerDesc* t, hipStream_t s, const void* d_in, bool in_u8, const Geom& g, float* d_out, int64_t seam_block)
+static int tuner_two_pass(const TunerDesc* t, hipStream_t s, const void* d_in, InFmt fmt, const Geom& g, float* d_out, int64_t seam_block)
 {
     TunerScratch* sc = t->scratch;
     TunerScratch::Lane lane = {nullptr, nullptr};
@@ -85,13 +87,14 @@ static int tuner_two_pass(const TunerDesc* t, hipStream_t s, const void* d_in, b
     if (e == hipSuccess) rc = lane.ctx->work.ensure(bytes);
     if (e == hipSuccess && rc == SDRHIP_OK) {
         float* work = static_cast<float*>(lane.ctx->work.p);
-        const int esz = in_u8 ? 2 : 8;
+        const int esz = in_fmt_bytes(fmt);
         const int64_t k_end = g.k_begin + g.count;
         for (int64_t kb = g.k_begin; kb < k_end && rc == SDRHIP_OK; kb += cnt_max) {
             const int64_t ke = kb + cnt_max < k_end ? kb + cnt_max : k_end;
             const int64_t a0 = kb * D, nin = (ke - kb - 1) * D + Lp;
-            launch_tuner_mix(s, static_cast<const char*>(d_in) + esz * (a0 - g.in_base), in_u8, work, nin, t->d_osc, t->period,
-                             (int)(a0 % t->period));
+            const char* src = static_cast<const char*>(d_in) + esz * (a0 - g.in_base);
+            if (fmt == IN_I16) launch_tuner_mix_i16(s, src, work, nin, t->d_osc, t->period, (int)(a0 % t->period));
+            else launch_tuner_mix(s, src, fmt == IN_U8, work, nin, t->d_osc, t->period, (int)(a0 % t->period));
             rc = fir_run(&t->fir, s, work, false, a0, d_out + 2 * (kb - g.k_begin), kb, ke, seam_block);
         }
         if (rc == SDRHIP_OK) e = hipGetLastError();
@@ -106,7 +109,7 @@ static int tuner_two_pass(const TunerDesc* t, hipStream_t s, const void* d_in, b
     return rc;
 }
 
-int tuner_run(const TunerDesc* t, hipStream_t s, const void* d_in, bool in_u8, int64_t in_base, float* d_out, int64_t k_begin,
+int tuner_run(const TunerDesc* t, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out, int64_t k_begin,
               int64_t k_end, int64_t seam_block)
 {
     SDRHIP_REQUIRE(t != nullptr, "tuner_run");
@@ -116,6 +119,7 @@ int tuner_run(const TunerDesc* t, hipStream_t s, const void* d_in, bool in_u8, i
     SDRHIP_REQUIRE(seam_block <= 0 || seam_block >= d->Lp, "tuner_run: seam block shorter than the filter (Filter.hs:586)");
     if (k_end == k_begin) return SDRHIP_OK;
     SDRHIP_REQUIRE(d_in != nullptr && d_out != nullptr, "tuner_run");
+    SDRHIP_REQUIRE(fmt != IN_I16 || (reinterpret_cast<uintptr_t>(d_in) & 3) == 0, "tuner_run: int16 IQ at an address that is no multiple of 4");
     int rc = t->ensure_device();
     if (rc != SDRHIP_OK) return rc;
     Geom g;
@@ -128,7 +132,12 @@ int tuner_run(const TunerDesc* t, hipStream_t s, const void* d_in, bool in_u8, i
     g.seamBI = seam_block;
     const int route = t->route;
     if (route != 2) {
-        if (d->corder == CO_L4 && launch_tuner_fused(s, g, d->d_plain, d->Lp, d->d_cross, d_in, in_u8, d_out, t->d_osc, t->period)) {
+        // int16 input: the bank's int16 tile kernel with one channel (its table at offset 0), kernels_tuner_i16.hip
+        const int off0 = 0;
+        const bool fused = d->corder != CO_L4 ? false
+                         : fmt == IN_I16 ? launch_tuner_bank_i16(s, g, d->d_plain, d->Lp, d->d_cross, d_in, d_out, 0, t->d_osc, 1, &off0, &t->period, false)
+                                         : launch_tuner_fused(s, g, d->d_plain, d->Lp, d->d_cross, d_in, fmt == IN_U8, d_out, t->d_osc, t->period);
+        if (fused) {
             SDRHIP_CHECK_HIP(hipGetLastError());
             return SDRHIP_OK;
         }
@@ -138,7 +147,7 @@ int tuner_run(const TunerDesc* t, hipStream_t s, const void* d_in, bool in_u8, i
             return SDRHIP_ERR_ARG;
         }
     }
-    return tuner_two_pass(t, s, d_in, in_u8, g, d_out, seam_block);
+    return tuner_two_pass(t, s, d_in, fmt, g, d_out, seam_block);
 }
 
 // exp(2 pi i r / den) as float32, r in [0, den): the reduction documented in include/sdr_hip.h
@@ -201,12 +210,17 @@ int sdrhip_tuner_set_route(sdrhip_tuner* t, int route)
 int sdrhip_tuner_run(const sdrhip_tuner* t, void* stream, const float* d_in, int64_t in_base, float* d_out, int64_t k_begin,
                      int64_t k_end, int64_t seam_block)
 {
-    return tuner_run(t, (hipStream_t)stream, d_in, false, in_base, d_out, k_begin, k_end, seam_block);
+    return tuner_run(t, (hipStream_t)stream, d_in, IN_CF32, in_base, d_out, k_begin, k_end, seam_block);
+}
+int sdrhip_tuner_run_i16(const sdrhip_tuner* t, void* stream, const int16_t* d_in_iq, int64_t in_base, float* d_out, int64_t k_begin,
+                         int64_t k_end, int64_t seam_block)
+{
+    return tuner_run(t, (hipStream_t)stream, d_in_iq, IN_I16, in_base, d_out, k_begin, k_end, seam_block);
 }
 int sdrhip_tuner_run_u8(const sdrhip_tuner* t, void* stream, const uint8_t* d_in_iq, int64_t in_base, float* d_out, int64_t k_begin,
                         int64_t k_end, int64_t seam_block)
 {
-    return tuner_run(t, (hipStream_t)stream, d_in_iq, true, in_base, d_out, k_begin, k_end, seam_block);
+    return tuner_run(t, (hipStream_t)stream, d_in_iq, IN_U8, in_base, d_out, k_begin, k_end, seam_block);
 }
 
 int sdrhip_tuner_shift_table(int64_t num, int64_t den, float* osc_iq)
@@ -224,6 +238,7 @@ int sdrhip_tuner_shift_table(int64_t num, int64_t den, float* osc_iq)
 }
 
 long long sdrhip_debug_tuner_fused_launches(void) { return tuner_fused_launch_count(); }
+long long sdrhip_debug_tuner_i16_launches(void) { return tuner_i16_launch_count(); }
 
 int64_t sdrhip_debug_set_tuner_chunk(int64_t samples)
 {

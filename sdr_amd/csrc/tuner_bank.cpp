@@ -32,6 +32,16 @@ static bool bank_auto(int channels, int64_t samples)
     return channels >= kBankAutoMinChannels && samples <= kBankAutoMaxSamples;
 }
 
+// auto for int16 input, read from `tools/tuner_bank_bench.py --i16` (profiles/tuner_i16_bench.txt) by the same criterion over the same
+// rectangle: at EVERY point with K >= 2 the banked int16 launch's slowest round is below the K run_i16 calls' fastest (0.52 .. 0.03 of
+// their time at one block, 0.90 .. 0.78 at 2^24 samples), so the sweep confirms the u8 / cfloat rectangle and the bounds are again its
+// edges, not crossovers; nothing beyond 2^24 samples per launch is measured and the rule is not widened.  One channel goes to its tuner,
+// which for int16 launches the same kernel with one channel: level by construction, and measured so (0.995 .. 1.001).
+static bool bank_auto_i16(int channels, int64_t samples)
+{
+    return channels >= kBankAutoMinChannels && samples <= kBankAutoMaxSamples;
+}
+
 static std::mutex g_bank_upload_mu;
 
 TunerBankDesc::~TunerBankDesc()
@@ -49,7 +59,7 @@ int TunerBankDesc::ensure_device() const
     return upload_floats(&d_tables, h_tables);
 }
 
-int tuner_bank_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, bool in_u8, int64_t in_base, float* d_out, int64_t out_stride,
+int tuner_bank_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out, int64_t out_stride,
                    int64_t k_begin, int64_t k_end, int64_t seam_block)
 {
     SDRHIP_REQUIRE(b != nullptr, "sdrhip_tuner_bank_run");
@@ -63,6 +73,8 @@ int tuner_bank_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, bool
     SDRHIP_REQUIRE(K == 1 || out_stride >= 2 * (k_end - k_begin), "sdrhip_tuner_bank_run: a channel's row holds its outputs");
     if (k_end == k_begin) return SDRHIP_OK;
     SDRHIP_REQUIRE(d_in != nullptr && d_out != nullptr, "sdrhip_tuner_bank_run");
+    SDRHIP_REQUIRE(fmt != IN_I16 || (reinterpret_cast<uintptr_t>(d_in) & 3) == 0,
+                   "sdrhip_tuner_bank_run: int16 IQ at an address that is no multiple of 4");
     Geom g;
     g.in_base = in_base;
     g.k_begin = k_begin;
@@ -73,16 +85,21 @@ int tuner_bank_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, bool
     g.seamBI = seam_block;
     const int route = b->route;
     // the Cross taps are the prepared plain taps, on the device once the descriptor is (FirDesc::ensure_device)
-    const bool fits = d->corder == CO_L4 && tuner_fused_fits(g, d->Lp, true, d_in, in_u8, d_out, 1);
+    const bool fits = d->corder == CO_L4 && (fmt == IN_I16 ? tuner_i16_fused_fits(g, d->Lp, true, d_in, d_out, 1)
+                                                           : tuner_fused_fits(g, d->Lp, true, d_in, fmt == IN_U8, d_out, 1));
     if (route == 1 && !fits) {
         set_error("sdrhip_tuner_bank_run: the banked launch serves the AVX order, factors 4 / 8 / 16, up to 128 prepared taps, seam_block >= 0 "
                   "and a 16-byte aligned first window; this launch is none of that (route 0 or 2 runs it)");
         return SDRHIP_ERR_ARG;
     }
-    if (fits && (route == 1 || (route == 0 && bank_auto(K, (int64_t)g.count * g.D)))) {
+    const bool banked_by_rule = fmt == IN_I16 ? bank_auto_i16(K, (int64_t)g.count * g.D) : bank_auto(K, (int64_t)g.count * g.D);
+    if (fits && (route == 1 || (route == 0 && banked_by_rule))) {
         int rc = b->ensure_device();
         if (rc != SDRHIP_OK) return rc;
-        if (launch_tuner_bank(s, g, d->d_plain, d->Lp, d->d_cross, d_in, in_u8, d_out, out_stride, b->d_tables, K, b->off, b->period)) {
+        const bool launched = fmt == IN_I16
+            ? launch_tuner_bank_i16(s, g, d->d_plain, d->Lp, d->d_cross, d_in, d_out, out_stride, b->d_tables, K, b->off, b->period, true)
+            : launch_tuner_bank(s, g, d->d_plain, d->Lp, d->d_cross, d_in, fmt == IN_U8, d_out, out_stride, b->d_tables, K, b->off, b->period);
+        if (launched) {
             SDRHIP_CHECK_HIP(hipGetLastError());
             return SDRHIP_OK;
         }
@@ -92,7 +109,7 @@ int tuner_bank_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, bool
         }
     }
     for (int j = 0; j < K; j++) {
-        int rc = tuner_run(b->ch[j], s, d_in, in_u8, in_base, d_out + (int64_t)j * out_stride, k_begin, k_end, seam_block);
+        int rc = tuner_run(b->ch[j], s, d_in, fmt, in_base, d_out + (int64_t)j * out_stride, k_begin, k_end, seam_block);
         if (rc != SDRHIP_OK) return rc;
     }
     return SDRHIP_OK;
@@ -101,7 +118,7 @@ int tuner_bank_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, bool
 // Outputs [k_begin, k_end) of every channel, all Cross, in ONE launch (kernels_tuner_bank.hip: k_tuner_bank_cross): what
 // tuner_bank_run(..., seam_block = -1) computes channel by channel, for the bank's Pipe (pipes.cpp) and nobody else -- the routes and
 // the auto rule of sdrhip_tuner_bank_run are not involved.
-int tuner_bank_cross_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, bool in_u8, int64_t in_base, float* d_out,
+int tuner_bank_cross_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out,
                          int64_t out_stride, int64_t k_begin, int64_t k_end)
 {
     SDRHIP_REQUIRE(b != nullptr && d_in != nullptr && d_out != nullptr, "tuner_bank_cross_run");
@@ -118,7 +135,10 @@ int tuner_bank_cross_run(const TunerBankDesc* b, hipStream_t s, const void* d_in
     g.D = d->factor;
     g.Lp = d->Lp;
     g.seamBI = -1;
-    if (!launch_tuner_bank_cross(s, g, d->d_cross, d_in, in_u8, d_out, out_stride, b->d_tables, (int)b->ch.size(), b->off, b->period)) {
+    const bool launched = fmt == IN_I16
+        ? launch_tuner_bank_cross_i16(s, g, d->d_cross, d_in, d_out, out_stride, b->d_tables, (int)b->ch.size(), b->off, b->period)
+        : launch_tuner_bank_cross(s, g, d->d_cross, d_in, fmt == IN_U8, d_out, out_stride, b->d_tables, (int)b->ch.size(), b->off, b->period);
+    if (!launched) {
         set_error("tuner_bank_cross_run: the all-Cross launch refused its channels, stride or pointers");
         return SDRHIP_ERR_ARG;
     }
@@ -192,15 +212,21 @@ int sdrhip_tuner_bank_set_route(sdrhip_tuner_bank* b, int route)
 int sdrhip_tuner_bank_run(const sdrhip_tuner_bank* b, void* stream, const float* d_in, int64_t in_base, float* d_out, int64_t out_stride,
                           int64_t k_begin, int64_t k_end, int64_t seam_block)
 {
-    return tuner_bank_run(b, (hipStream_t)stream, d_in, false, in_base, d_out, out_stride, k_begin, k_end, seam_block);
+    return tuner_bank_run(b, (hipStream_t)stream, d_in, IN_CF32, in_base, d_out, out_stride, k_begin, k_end, seam_block);
 }
 int sdrhip_tuner_bank_run_u8(const sdrhip_tuner_bank* b, void* stream, const uint8_t* d_in_iq, int64_t in_base, float* d_out,
                              int64_t out_stride, int64_t k_begin, int64_t k_end, int64_t seam_block)
 {
-    return tuner_bank_run(b, (hipStream_t)stream, d_in_iq, true, in_base, d_out, out_stride, k_begin, k_end, seam_block);
+    return tuner_bank_run(b, (hipStream_t)stream, d_in_iq, IN_U8, in_base, d_out, out_stride, k_begin, k_end, seam_block);
+}
+int sdrhip_tuner_bank_run_i16(const sdrhip_tuner_bank* b, void* stream, const int16_t* d_in_iq, int64_t in_base, float* d_out,
+                              int64_t out_stride, int64_t k_begin, int64_t k_end, int64_t seam_block)
+{
+    return tuner_bank_run(b, (hipStream_t)stream, d_in_iq, IN_I16, in_base, d_out, out_stride, k_begin, k_end, seam_block);
 }
 
-long long sdrhip_debug_tuner_bank_launches(void) { return tuner_bank_launch_count(); }
-long long sdrhip_debug_tuner_bank_cross_launches(void) { return tuner_bank_cross_launch_count(); }
+// the int16 kernels (kernels_tuner_i16.hip) keep counters of their own: a banked launch is a banked launch whatever it reads
+long long sdrhip_debug_tuner_bank_launches(void) { return tuner_bank_launch_count() + tuner_i16_bank_launch_count(); }
+long long sdrhip_debug_tuner_bank_cross_launches(void) { return tuner_bank_cross_launch_count() + tuner_i16_bank_cross_launch_count(); }
 
 }  // extern "C"

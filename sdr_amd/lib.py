@@ -100,6 +100,9 @@ lib.sdrhip_tuner_destroy.argtypes = [_vp]
 lib.sdrhip_tuner_destroy.restype = None
 lib.sdrhip_tuner_run.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64]
 lib.sdrhip_tuner_run_u8.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64]
+lib.sdrhip_tuner_run_i16.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64]
+lib.sdrhip_debug_tuner_i16_launches.argtypes = []
+lib.sdrhip_debug_tuner_i16_launches.restype = C.c_longlong
 lib.sdrhip_tuner_set_route.argtypes = [_vp, C.c_int]
 lib.sdrhip_tuner_shift_table.argtypes = [_i64, _i64, _f32p]
 lib.sdrhip_debug_tuner_fused_launches.argtypes = []
@@ -115,6 +118,7 @@ lib.sdrhip_tuner_bank_num_coeffs.argtypes = [_vp]
 lib.sdrhip_tuner_bank_factor.argtypes = [_vp]
 lib.sdrhip_tuner_bank_run.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64]
 lib.sdrhip_tuner_bank_run_u8.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64]
+lib.sdrhip_tuner_bank_run_i16.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64]
 lib.sdrhip_tuner_bank_set_route.argtypes = [_vp, C.c_int]
 lib.sdrhip_debug_tuner_bank_launches.argtypes = []
 lib.sdrhip_debug_tuner_bank_launches.restype = C.c_longlong
@@ -315,6 +319,10 @@ lib.sdrhip_pipe_rows.argtypes = [_vp]
 lib.sdrhip_pipe_push_u8.argtypes = [_vp, _u8p, C.c_int]
 lib.sdrhip_pipe_input_buffer_u8.argtypes = [_vp, C.c_int]
 lib.sdrhip_pipe_input_buffer_u8.restype = _vp
+lib.sdrhip_pipe_tuner_bank_i16.argtypes = [C.POINTER(_vp), _vp, C.c_int]
+lib.sdrhip_pipe_push_i16.argtypes = [_vp, _i16p, C.c_int]
+lib.sdrhip_pipe_input_buffer_i16.argtypes = [_vp, C.c_int]
+lib.sdrhip_pipe_input_buffer_i16.restype = _vp
 lib.sdrhip_pipe_pop_rows.argtypes = [_vp, _f32p, _i64, C.c_int]
 lib.sdrhip_pipe_set_coalesce.argtypes = [_vp, C.c_int]
 lib.sdrhip_pipe_set_adaptive.argtypes = [_vp, C.c_int]
@@ -842,6 +850,15 @@ class Tuner(_Handle):
     def run_u8(self, d_in, in_base, d_out, k_begin, k_end, seam_block=0, stream=None):
         check(lib.sdrhip_tuner_run_u8(self.h, stream, d_in, in_base, d_out, k_begin, k_end, seam_block), "sdrhip_tuner_run_u8")
 
+    def run_i16(self, d_in, in_base, d_out, k_begin, k_end, seam_block=0, stream=None):
+        """interleaved int16 IQ input (4 bytes per sample), converted by s / 2048 in the kernels' loaders."""
+        check(lib.sdrhip_tuner_run_i16(self.h, stream, d_in, in_base, d_out, k_begin, k_end, seam_block), "sdrhip_tuner_run_i16")
+
+
+def tuner_i16_launches():
+    """Launches of the int16 tile kernel so far, from a bank or a one-row tuner (sdrhip_debug_tuner_i16_launches)."""
+    return int(lib.sdrhip_debug_tuner_i16_launches())
+
 
 def tuner_bank_launches():
     """Banked launches of the tuner bank so far (sdrhip_debug_tuner_bank_launches)."""
@@ -893,6 +910,11 @@ class TunerBank(_Handle):
     def run_u8(self, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block=0, stream=None):
         check(lib.sdrhip_tuner_bank_run_u8(self.h, stream, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block),
               "sdrhip_tuner_bank_run_u8")
+
+    def run_i16(self, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block=0, stream=None):
+        """interleaved int16 IQ input (4 bytes per sample); rows as run."""
+        check(lib.sdrhip_tuner_bank_run_i16(self.h, stream, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block),
+              "sdrhip_tuner_bank_run_i16")
 
 
 class FmChain(_Handle):
@@ -1319,11 +1341,12 @@ class Pipe(_Handle):
     Tuner(factor, coeffs, tables[j], order) yields."""
     _destroy = lib.sdrhip_pipe_destroy
 
-    def __init__(self, kind, desc=None, block_size_out=8192, mu=None, reference=None, input_u8=False):
+    def __init__(self, kind, desc=None, block_size_out=8192, mu=None, reference=None, input_u8=False, input_i16=False):
         super().__init__()
         self.desc = desc  # keep the descriptor alive
         self.block_size_out = block_size_out
         self.input_u8 = False
+        self.input_i16 = False
         self.complex_in = bool(getattr(desc, "complex", False)) or kind in ("fm_demod", "agc")
         self.complex_out = bool(getattr(desc, "complex", False)) or kind == "agc"
         if kind == "filter":
@@ -1334,6 +1357,11 @@ class Pipe(_Handle):
             check(lib.sdrhip_pipe_fir_resampler(C.byref(self.h), desc.h, block_size_out), "sdrhip_pipe_fir_resampler")
         elif kind == "tuner":
             check(lib.sdrhip_pipe_tuner(C.byref(self.h), desc.h, block_size_out), "sdrhip_pipe_tuner")
+        elif kind == "tuner_bank" and input_i16:
+            if input_u8:
+                raise ValueError("Pipe.tuner_bank: input_u8 and input_i16 exclude each other")
+            check(lib.sdrhip_pipe_tuner_bank_i16(C.byref(self.h), desc.h, block_size_out), "sdrhip_pipe_tuner_bank_i16")
+            self.input_i16 = True
         elif kind == "tuner_bank":
             check(lib.sdrhip_pipe_tuner_bank(C.byref(self.h), desc.h, block_size_out, int(input_u8)), "sdrhip_pipe_tuner_bank")
             self.input_u8 = bool(input_u8)
@@ -1355,10 +1383,10 @@ class Pipe(_Handle):
         return Pipe("tuner", tuner, block_size_out)
 
     @staticmethod
-    def tuner_bank(bank, block_size_out, input_u8=False):
-        """The tuner bank on host blocks: cfloat blocks (or interleaved u8 IQ blocks, input_u8=True) in, every channel's blocks of
-        block_size_out decimated samples out."""
-        return Pipe("tuner_bank", bank, block_size_out, input_u8=input_u8)
+    def tuner_bank(bank, block_size_out, input_u8=False, input_i16=False):
+        """The tuner bank on host blocks: cfloat blocks (or interleaved u8 IQ blocks, input_u8=True, or interleaved int16 IQ blocks,
+        input_i16=True; the two exclude each other) in, every channel's blocks of block_size_out decimated samples out."""
+        return Pipe("tuner_bank", bank, block_size_out, input_u8=input_u8, input_i16=input_i16)
 
     @property
     def rows(self):
@@ -1374,6 +1402,10 @@ class Pipe(_Handle):
 
     def _wrong_dtype(self, block, call):
         """A u8 pipe takes uint8 arrays and every other pipe no uint8 array: converting silently would feed the wrong stream."""
+        if self.input_i16:
+            if getattr(block, "dtype", None) != np.int16:
+                raise SdrHipError(f"{call}: this pipe takes int16 IQ blocks, not {getattr(block, 'dtype', type(block).__name__)}")
+            return
         is_u8 = getattr(block, "dtype", None) == np.uint8
         if is_u8 != self.input_u8:
             raise SdrHipError(f"{call}: this pipe takes {'uint8 IQ' if self.input_u8 else 'float32'} blocks, not "
@@ -1385,6 +1417,9 @@ class Pipe(_Handle):
         if self.input_u8:
             b = np.ascontiguousarray(block, dtype=np.uint8).reshape(-1)
             return self._pop(check(lib.sdrhip_pipe_push_u8(self.h, b.ctypes.data_as(_u8p), b.size // 2), "sdrhip_pipe_push_u8"))
+        if self.input_i16:
+            b = np.ascontiguousarray(block, dtype=np.int16).reshape(-1)
+            return self._pop(check(lib.sdrhip_pipe_push_i16(self.h, b.ctypes.data_as(_i16p), b.size // 2), "sdrhip_pipe_push_i16"))
         b = _f32(block)
         n = b.size // (2 if self.complex_in else 1)
         self._cap = max(getattr(self, "_cap", 0), self.block_size_out, n)
@@ -1399,9 +1434,12 @@ class Pipe(_Handle):
 
     def input_buffer(self, n):
         """numpy view (n elements; interleaved pairs for complex stages) of the pinned staging memory of the next push."""
-        ptr = (lib.sdrhip_pipe_input_buffer_u8 if self.input_u8 else lib.sdrhip_pipe_input_buffer)(self.h, n)
+        fn = lib.sdrhip_pipe_input_buffer_i16 if self.input_i16 else lib.sdrhip_pipe_input_buffer_u8 if self.input_u8 else lib.sdrhip_pipe_input_buffer
+        ptr = fn(self.h, n)
         if not ptr:
             raise SdrHipError(lib.sdrhip_last_error().decode())
+        if self.input_i16:
+            return np.ctypeslib.as_array(C.cast(ptr, _i16p), shape=(2 * n,))
         if self.input_u8:
             return np.ctypeslib.as_array(C.cast(ptr, _u8p), shape=(2 * n,))
         return np.ctypeslib.as_array(C.cast(ptr, _f32p), shape=(n * (2 if self.complex_in else 1),))

@@ -1,6 +1,7 @@
 """The tuner bank against K tuner objects of the same build, alternating the two in one process.
 
     python tools/tuner_bank_bench.py [--rounds R] [--out profiles/tuner_bank_bench.txt]
+    python tools/tuner_bank_bench.py --i16 [--rounds R] [--out profiles/tuner_i16_bench.txt]
 
 Sweep: K = 1, 2, 4, 8, 12, 32 channels x resident launches of 1 block (8192 samples), 16 blocks, 2^20 and 2^24 samples of the 128-tap
 / 8 shape (contiguous stream), u8 and cfloat input.
@@ -14,7 +15,15 @@ of one call that launches nothing (an empty output range) is printed, because th
 leg once.  Before it is timed, a point's two legs are compared bit for bit.
 No number is fixed in advance: the yardstick is the K-tuner loop.  The last lines derive the auto rule per input type with the FM
 bank's criterion -- a point is banked where the banked launch's SLOWEST round is below the loop's FASTEST -- as the largest launch
-size up to which every measured K >= 2 is banked, and say what K = 1 did.  A missing GPU is an error."""
+size up to which every measured K >= 2 is banked, and say what K = 1 did.  A missing GPU is an error.
+
+--i16: the same sweep and protocol on 16-bit signed IQ (sdrhip_tuner_bank_run_i16), three legs alternating in each round:
+  banked    one sdrhip_tuner_bank_run_i16 on the banked route
+  tuners    K sdrhip_tuner_run_i16 calls of K tuner objects (each the int16 tile kernel with one channel)
+  convert   what a caller had before the int16 entry points: sdrhip_convert_i16_run into a cfloat buffer, then the cfloat
+            sdrhip_tuner_bank_run on its default route
+The auto rule for int16 input is read from banked against tuners; banked against convert is reported point by point and no rule
+depends on it."""
 import argparse
 import os
 import statistics
@@ -78,6 +87,103 @@ def legs(K, n_samples, u8):
     return {"banked": banked, "tuners": loop}, n, (bank, tuners, d_in, out)
 
 
+def legs_i16(K, n_samples):
+    taps = S.taps_decim127()
+    tabs = tables(K)
+    bank = L.TunerBank(8, taps, tabs)
+    bank.set_route(L.TunerBank.ROUTE_BANKED)
+    bank_cf = L.TunerBank(8, taps, tabs)                     # the cfloat bank as a caller gets it: route auto
+    tuners = [L.Tuner(8, taps, t) for t in tabs]
+    n = (n_samples - 128) // 8 + 1
+    d_in = torch.randint(-32768, 32768, (2 * n_samples,), dtype=torch.int16, device="cuda")
+    d_cf = torch.empty(2 * n_samples, dtype=torch.float32, device="cuda")
+    out = torch.empty(K * 2 * n, dtype=torch.float32, device="cuda")
+    pi, pc, po = d_in.data_ptr(), d_cf.data_ptr(), out.data_ptr()
+
+    def banked(reps):
+        for _ in range(reps):
+            bank.run_i16(pi, 0, po, 2 * n, 0, n)
+        torch.cuda.synchronize()
+
+    def loop(reps):
+        for _ in range(reps):
+            for j, t in enumerate(tuners):
+                t.run_i16(pi, 0, po + 8 * j * n, 0, n)
+        torch.cuda.synchronize()
+
+    def convert(reps):
+        for _ in range(reps):
+            L.check(L.lib.sdrhip_convert_i16_run(None, pi, pc, 2 * n_samples), "sdrhip_convert_i16_run")
+            bank_cf.run(pc, 0, po, 2 * n, 0, n)
+        torch.cuda.synchronize()
+
+    loop(1)
+    ref = out.clone()
+    for name, fn in (("banked", banked), ("convert", convert)):
+        out.zero_()
+        fn(1)
+        if not torch.equal(out.view(torch.int32), ref.view(torch.int32)):
+            sys.exit(f"tuner_bank_bench: the {name} leg and the tuner loop differ at K = {K}, {n_samples} samples, i16")
+    del ref
+    return {"banked": banked, "tuners": loop, "convert": convert}, n, (bank, bank_cf, tuners, d_in, d_cf, out)
+
+
+def main_i16(a):
+    lines = [f"# {L.device_name()}; {a.rounds} rounds, int16 IQ input; banked int16 launch, K-tuner loop (run_i16) and convert + cfloat bank "
+             "alternating; us per run of ALL K channels: median (min .. max)"]
+    print(lines[0], flush=True)
+    points = []
+    for size_name, n_samples in SIZES:
+        for K in CHANNELS:
+            fns, n, keep = legs_i16(K, n_samples)
+            reps = {}
+            for name, fn in fns.items():
+                fn(5)
+                per = timed(fn, 10) * 1e-6
+                reps[name] = max(5, min(20000, int(WINDOW_S / per)))
+            i0, f0 = L.tuner_i16_launches(), L.tuner_fused_launches()
+            times = {k: [] for k in fns}
+            for _ in range(a.rounds):
+                for name, fn in fns.items():
+                    times[name].append(timed(fn, reps[name]))
+            ni = L.tuner_i16_launches() - i0
+            assert ni == a.rounds * (reps["banked"] + reps["tuners"] * K), "an int16 leg took another route than the one it is named for"
+            med = {k: statistics.median(v) for k, v in times.items()}
+            fmt = lambda v: f"{statistics.median(v):10.1f} ({min(v):.1f} .. {max(v):.1f})"
+            clear = max(times["banked"]) < min(times["tuners"])
+            clear_c = max(times["banked"]) < min(times["convert"])
+            behind_c = min(times["banked"]) > max(times["convert"])
+            line = (f"i16  {size_name:13s} K {K:2d}  outputs {n:7d} x {K:2d}   banked {fmt(times['banked'])}   tuners {fmt(times['tuners'])}   "
+                    f"convert+cf32 {fmt(times['convert'])}   banked / tuners {med['banked'] / med['tuners']:.3f}"
+                    f"{'' if clear else ' (not clear of the spread)'}   banked / convert+cf32 {med['banked'] / med['convert']:.3f}"
+                    f"{' ahead' if clear_c else ' BEHIND' if behind_c else ' (within the spread)'}")
+            print(line, flush=True)
+            lines.append(line)
+            points.append((n_samples, size_name, K, med["banked"] / med["tuners"], clear, med["banked"] / med["convert"], clear_c))
+            del fns, keep
+            torch.cuda.empty_cache()
+    bound, bound_name = 0, "none"
+    for size_name, n_samples in SIZES:
+        if not all(c for ns, _, K, _, c, _, _ in points if ns == n_samples and K > 1):
+            break
+        bound, bound_name = n_samples, size_name
+    lost = [(s, K, r) for ns, s, K, r, c, _, _ in points if K > 1 and not c]
+    lines.append(f"# i16: every measured K >= 2 is banked (slowest banked round below the loop's fastest) at every launch size up to "
+                 f"{bound_name} ({bound} samples)" + ("; points that are not: " + ", ".join(f"{s} K {K} (ratio {r:.3f})" for s, K, r in lost)
+                                                      if lost else ": the whole sweep, the bound is its end, not a crossover"))
+    lines.append("# i16: K = 1 (the same kernel with one channel either way) banked / tuners "
+                 + ", ".join(f"{s} {r:.3f}{' clear' if c else ''}" for ns, s, K, r, c, _, _ in points if K == 1))
+    notc = [(s, K, r) for ns, s, K, _, _, r, c in points if not c]
+    lines.append("# i16 against convert + cfloat bank (no rule depends on it): the fused int16 launch is ahead by more than the spread at "
+                 f"{sum(1 for p in points if p[6])} of {len(points)} points" + ("; not ahead at: " + ", ".join(f"{s} K {K} (ratio {r:.3f})" for s, K, r in notc)
+                                                                                if notc else ""))
+    print("\n".join(lines[-3:]), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def timed(fn, reps):
     t0 = time.perf_counter()
     fn(reps)
@@ -108,12 +214,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--i16", action="store_true", help="the int16 legs instead of the u8 / cfloat sweep")
     a = ap.parse_args()
     if a.rounds < 7:
         sys.exit("tuner_bank_bench: at least 7 rounds")
     if L.device_count() < 1:
         sys.exit("tuner_bank_bench: no HIP device")
     torch.cuda.set_device(0)
+    if a.i16:
+        return main_i16(a)
     call_us = host_call_us()
     lines = [f"# {L.device_name()}; {a.rounds} rounds, banked launch and K-tuner loop alternating; us per run of ALL K channels: median (min .. max)",
              f"# host time of one call that launches nothing (k_end = k_begin): Tuner.run_u8 {call_us['tuner']:.2f} us, "

@@ -2,6 +2,7 @@
 in one process, alternating.
 
     python tools/tuner_bank_pipe_bench.py [--rounds R] [--out profiles/tuner_bank_pipe_bench.txt]
+    python tools/tuner_bank_pipe_bench.py --i16 [--rounds R] [--out profiles/tuner_i16_pipe_bench.txt]
 
 Sweep: K = 1, 2, 8, 12, 32 channels x pushes of 1, 16 and 128 source blocks (8192 samples each, one push = one block of that many
 samples) x two ways of pushing, 128 prepared taps / 8, block_size_out 1024:
@@ -23,7 +24,11 @@ bank Pipe itself.  Reading rule (the project's): for K >= 2 the bank Pipe is ahe
 FASTEST; at K = 1 the two are level when their medians differ by no more than the larger spread.  Points that miss the rule are
 marked and listed at the end; no threshold is fixed and nothing in the library is switched on the outcome.  The last column is the
 output volume of a push: K = 32 at factor 8 returns 32 bytes per 2 bytes of u8 input, and the return crossing is what large pushes
-are expected to cost.  A missing GPU is an error."""
+are expected to cost.  A missing GPU is an error.
+
+--i16: ONE int16 bank Pipe (sdrhip_pipe_tuner_bank_i16, 4 bytes per sample over the link) against ONE cfloat bank Pipe and against K
+one-row cfloat Pipes, both fed floats converted BEFORE the clock starts (the u8 leg's convention); K = 2, 8, 32 x pushes of 1, 16 and
+128 blocks, memcpy and buffer pushes, the three legs alternating.  This leg is reported; no rule depends on it."""
 import argparse
 import ctypes as C
 import os
@@ -45,7 +50,8 @@ PUSH_BLOCKS = (1, 16, 128)
 RAGGED_CHANNELS = (2, 8, 32)
 WINDOW_S = 0.05
 TAPS = S.taps_decim127()
-_f32p, _u8p = C.POINTER(C.c_float), C.POINTER(C.c_uint8)
+_f32p, _u8p, _i16p = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int16)
+I16_CHANNELS = (2, 8, 32)
 
 
 def tables(K):
@@ -53,8 +59,8 @@ def tables(K):
     return [L.tuner_shift_table((j - K // 2) % 64, 64) if j != K // 2 else np.array([1.0, 0.0], np.float32) for j in range(K)]
 
 
-def bank_pipe(K, u8):
-    return [L.Pipe.tuner_bank(L.TunerBank(8, TAPS, tables(K)), BLOCK_OUT, input_u8=u8)]
+def bank_pipe(K, u8, i16=False):
+    return [L.Pipe.tuner_bank(L.TunerBank(8, TAPS, tables(K)), BLOCK_OUT, input_u8=u8, input_i16=i16)]
 
 
 def tuner_pipes(K):
@@ -63,7 +69,9 @@ def tuner_pipes(K):
 
 def push_ptr(p, arr):
     """one push of a contiguous array of the pipe's input type; every ready block of every row popped at once"""
-    if p.input_u8:
+    if p.input_i16:
+        ready = L.check(L.lib.sdrhip_pipe_push_i16(p.h, arr.ctypes.data_as(_i16p), arr.size // 2), "sdrhip_pipe_push_i16")
+    elif p.input_u8:
         ready = L.check(L.lib.sdrhip_pipe_push_u8(p.h, arr.ctypes.data_as(_u8p), arr.size // 2), "sdrhip_pipe_push_u8")
     else:
         ready = L.check(L.lib.sdrhip_pipe_push(p.h, arr.ctypes.data_as(_f32p), arr.size // 2), "sdrhip_pipe_push")
@@ -149,13 +157,54 @@ def verdict(K, t, name="bank", other="pipes"):
     return ok, "ahead by more than the spread" if ok else "NOT ahead by more than the spread"
 
 
+def main_i16(a):
+    rng = np.random.default_rng(16)
+    i16_all = rng.integers(-32768, 32768, 2 * 128 * B, dtype=np.int64).astype(np.int16)
+    f32_all = i16_all.astype(np.float32) * np.float32(2.0 ** -11)                         # converted before any clock starts
+    lines = [f"# {L.device_name()}; {a.rounds} rounds; ONE int16 bank Pipe, ONE cfloat bank Pipe and K one-row cfloat Pipes alternating (the "
+             "cfloat sides fed floats converted outside the clock); host clock around push ... flush, us PER PUSH (all K channels): "
+             "median (min .. max); 128 taps / 8, block_size_out 1024"]
+    print(lines[0], flush=True)
+    for nblk in PUSH_BLOCKS:
+        cf = [np.ascontiguousarray(f32_all[:2 * nblk * B])]
+        ci = [np.ascontiguousarray(i16_all[:2 * nblk * B])]
+        for K in I16_CHANNELS:
+            reps = 4
+            ra = rows_of(leg(bank_pipe(K, False, True), ci, "memcpy")(reps), K)
+            rb = rows_of(leg(tuner_pipes(K), cf, "memcpy")(reps), K)
+            if ra.shape != rb.shape or not np.array_equal(ra.view(np.uint32), rb.view(np.uint32)):
+                sys.exit(f"tuner_bank_pipe_bench: the int16 bank Pipe and the K Pipes differ ({nblk} blocks per push, K {K})")
+            for how in ("memcpy", "buffer"):
+                b16, bcf, pipes = bank_pipe(K, False, True), bank_pipe(K, False), tuner_pipes(K)
+                i0, b0 = L.tuner_i16_launches(), L.tuner_bank_launches()
+                t = measure({"i16 bank": leg(b16, ci, how), "cf32 bank": leg(bcf, cf, how), "pipes": leg(pipes, cf, how)}, a.rounds)
+                ni, nb = L.tuner_i16_launches() - i0, L.tuner_bank_launches() - b0
+                m = {k: statistics.median(v) for k, v in t.items()}
+                vs_cf = "ahead" if max(t["i16 bank"]) < min(t["cf32 bank"]) else "BEHIND" if min(t["i16 bank"]) > max(t["cf32 bank"]) else "within the spread"
+                vs_p = "ahead" if max(t["i16 bank"]) < min(t["pipes"]) else "BEHIND" if min(t["i16 bank"]) > max(t["pipes"]) else "within the spread"
+                line = (f"i16 {nblk:3d} blocks per push  {how:6s}  K {K:2d}   i16 bank {fmt(t['i16 bank'])}   cf32 bank {fmt(t['cf32 bank'])}   "
+                        f"pipes {fmt(t['pipes'])}   i16 / cf32 bank {m['i16 bank'] / m['cf32 bank']:.3f} {vs_cf}   i16 bank / pipes "
+                        f"{m['i16 bank'] / m['pipes']:.3f} {vs_p}   [launches: int16 tile kernel {ni}, banked (both banks) {nb}; "
+                        f"{K * nblk * B // 8 * 8 / 1024:.0f} KiB out per push]")
+                print(line, flush=True)
+                lines.append(line)
+                del b16, bcf, pipes
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--i16", action="store_true", help="the int16 bank Pipe's leg instead of the cfloat / u8 sweep")
     a = ap.parse_args()
     if L.device_count() < 1:
         sys.exit("tuner_bank_pipe_bench: no HIP device")
+    if a.i16:
+        return main_i16(a)
     u8_all = S.iq_u8(128 * B)
     f32_all = ((u8_all.astype(np.float32) - np.float32(128.0)) * np.float32(1.0 / 128.0))        # converted before any clock starts
     lines = [f"# {L.device_name()}; {a.rounds} rounds, the bank Pipe and K one-row tuner Pipes alternating; host clock around push ... flush, "
