@@ -1,7 +1,7 @@
 /* fm_replay.c -- the FM receiver of the reference's examples/fm/fm.hs:30-41 fed from a file instead of a radio
  * ("file replay source feeding pinned buffers"), in plain C over the C ABI of libsdr_hip.so.
  *
- *     fm_replay [--shift NUM/DEN | --stations NUM/DEN[,NUM/DEN...]] <iq_u8_file | udp:PORT> <audio_f32_file> [blocks_per_push] [taps_prefix]
+ *     fm_replay [--s16] [--shift NUM/DEN | --stations NUM/DEN[,NUM/DEN...]] <iq_file | udp:PORT> <audio_f32_file> [blocks_per_push] [taps_prefix]
  *
  * Reads interleaved unsigned 8-bit IQ (what rtl_sdr writes, what RTLSDRStream.hs:48-67 yields) in source blocks of
  * 8192 samples, `blocks_per_push` of them at a time, straight into the stream operator's pinned staging buffer
@@ -16,6 +16,10 @@
  * --stations NUM/DEN[,NUM/DEN...] receives 1 to 32 stations of the capture at once: one table per station (sdrhip_tuner_shift_table),
  * ONE bank (sdrhip_fm_bank_create), ONE stream over it (sdrhip_fm_stream_create_bank) -- every push crosses the link once and is one
  * launch for all the stations.  Station j's audio goes to <audio_f32_file>.<j> and is what --shift with its NUM/DEN writes.
+ * --s16: the capture is interleaved signed 16-bit IQ (a BladeRF's samples, s / 2048), 4 bytes per sample.  16-bit input reaches the
+ * FM side through a bank, so the receiver is then always a bank and an int16 stream over it (sdrhip_fm_stream_create_bank_i16,
+ * sdrhip_fm_stream_push_i16): the --stations given, or ONE station -- the --shift table, or {1, 0} when neither is given, which is
+ * the plain receiver (a converted int16 sample times 1 + 0i keeps its bits) -- whose audio goes to <audio_f32_file> itself.
  * Output is bit-identical to the reference pipeline's (tests/test_gpu_examples.py). */
 #define _POSIX_C_SOURCE 200809L
 #include <arpa/inet.h>
@@ -69,10 +73,24 @@ static void check(int rc, const char *what)
 }
 
 /* one stream over the bank (--stations: a row of audio blocks per station) or over the chain */
+static int s16 = 0;   /* --s16: int16 IQ in, 4 bytes per sample */
+
 static int make_stream(sdrhip_fm_stream **st, sdrhip_fm_chain *chain, sdrhip_fm_bank *bank, int bpp)
 {
+    if (s16) return sdrhip_fm_stream_create_bank_i16(st, bank, bpp * SOURCE_BLOCK, SOURCE_BLOCK);
     if (bank) return sdrhip_fm_stream_create_bank(st, bank, bpp * SOURCE_BLOCK, SOURCE_BLOCK);
     return sdrhip_fm_stream_create(st, chain, bpp * SOURCE_BLOCK, SOURCE_BLOCK);
+}
+
+/* the stream's pinned staging buffer and the push of what was written there, for either input type */
+static uint8_t *input_buffer(sdrhip_fm_stream *st)
+{
+    return s16 ? (uint8_t *)sdrhip_fm_stream_input_buffer_i16(st) : sdrhip_fm_stream_input_buffer(st);
+}
+
+static int push(sdrhip_fm_stream *st, const uint8_t *buf, int n_samples)
+{
+    return s16 ? sdrhip_fm_stream_push_i16(st, (const int16_t *)buf, n_samples) : sdrhip_fm_stream_push(st, buf, n_samples);
 }
 
 int main(int argc, char **argv)
@@ -90,6 +108,8 @@ int main(int argc, char **argv)
                     return 2;
                 }
                 i++;
+            } else if (strcmp(argv[i], "--s16") == 0) {
+                s16 = 1;
             } else if (strcmp(argv[i], "--stations") == 0) {
                 const char *p = i + 1 < argc ? argv[i + 1] : "";
                 int used = 0;
@@ -112,7 +132,7 @@ int main(int argc, char **argv)
         argc = w;
     }
     if (stations > 0 && shift_den > 0) { fprintf(stderr, "fm_replay: --shift or --stations, not both\n"); return 2; }
-    if (argc < 3) { fprintf(stderr, "usage: fm_replay [--shift NUM/DEN | --stations NUM/DEN[,NUM/DEN...]] <iq_u8_file | udp:PORT> <audio_f32_file> [blocks_per_push] [taps_prefix]\n"); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: fm_replay [--s16] [--shift NUM/DEN | --stations NUM/DEN[,NUM/DEN...]] <iq_file | udp:PORT> <audio_f32_file> [blocks_per_push] [taps_prefix]\n"); return 2; }
     const int bpp = argc > 3 ? atoi(argv[3]) : 64;
     if (bpp < 1) { fprintf(stderr, "fm_replay: blocks_per_push must be >= 1\n"); return 2; }
     int n_decim, n_resamp, n_audio;
@@ -133,6 +153,14 @@ int main(int argc, char **argv)
         free(osc);
     }
     sdrhip_fm_bank *bank = NULL;
+    const int per_station_files = stations > 0;
+    const size_t sample_bytes = s16 ? 4 : 2;
+    if (s16 && stations == 0) {
+        /* int16 without --stations: a bank of one station, the --shift table or {1, 0} */
+        stations = 1;
+        st_num[0] = shift_den > 0 ? shift_num : 0;
+        st_den[0] = shift_den > 0 ? shift_den : 1;
+    }
     if (stations > 0) {
         float *tables[SDRHIP_FM_BANK_MAX_STATIONS];
         int periods[SDRHIP_FM_BANK_MAX_STATIONS];
@@ -168,10 +196,10 @@ int main(int argc, char **argv)
              * not stall long enough for the socket buffer to overflow */
             sdrhip_fm_stream *warm = NULL;
             check(make_stream(&warm, chain, bank, bpp), "sdrhip_fm_stream_create");
-            uint8_t *wb = sdrhip_fm_stream_input_buffer(warm);
+            uint8_t *wb = input_buffer(warm);
             if (!wb) check(-1, "sdrhip_fm_stream_input_buffer");
-            memset(wb, 128, (size_t)bpp * 2 * SOURCE_BLOCK);
-            for (int i = 0; i < 3; i++) check(sdrhip_fm_stream_push(warm, wb, bpp * SOURCE_BLOCK), "warm-up push");
+            memset(wb, s16 ? 0 : 128, (size_t)bpp * sample_bytes * SOURCE_BLOCK);
+            for (int i = 0; i < 3; i++) check(push(warm, wb, bpp * SOURCE_BLOCK), "warm-up push");
             check(sdrhip_fm_stream_flush(warm), "warm-up flush");
             sdrhip_fm_stream_destroy(warm);
         }
@@ -184,7 +212,7 @@ int main(int argc, char **argv)
     FILE *out[SDRHIP_FM_BANK_MAX_STATIONS];
     for (int j = 0; j < rows; j++) {
         char path[4096];
-        if (bank) snprintf(path, sizeof path, "%s.%d", argv[2], j);
+        if (per_station_files) snprintf(path, sizeof path, "%s.%d", argv[2], j);
         else snprintf(path, sizeof path, "%s", argv[2]);
         out[j] = fopen(path, "wb");
         if (!out[j]) { fprintf(stderr, "fm_replay: cannot open %s\n", path); return 2; }
@@ -193,12 +221,12 @@ int main(int argc, char **argv)
     float *block = (float *)malloc((size_t)rows * SOURCE_BLOCK * sizeof(float));
     long long samples = 0, audio = 0;
     for (;;) {
-        uint8_t *buf = sdrhip_fm_stream_input_buffer(st);   /* pinned: the upload needs no intermediate copy */
+        uint8_t *buf = input_buffer(st);   /* pinned: the upload needs no intermediate copy */
         if (!buf) check(-1, "sdrhip_fm_stream_input_buffer");
-        size_t got = fill(&src, buf, (size_t)bpp * 2 * SOURCE_BLOCK) / (2 * SOURCE_BLOCK);   /* whole source blocks only */
+        size_t got = fill(&src, buf, (size_t)bpp * sample_bytes * SOURCE_BLOCK) / (sample_bytes * SOURCE_BLOCK);   /* whole source blocks only */
         int ready = 0;
         if (got > 0) {
-            ready = sdrhip_fm_stream_push(st, buf, (int)got * SOURCE_BLOCK);
+            ready = push(st, buf, (int)got * SOURCE_BLOCK);
             check(ready, "sdrhip_fm_stream_push");
             samples += (long long)got * SOURCE_BLOCK;
         }
@@ -213,7 +241,7 @@ int main(int argc, char **argv)
         }
         if (got < (size_t)bpp) break;
     }
-    if (bank) fprintf(stderr, "fm_replay: %lld IQ samples in, %lld audio samples out for each of %d stations\n", samples, audio, rows);
+    if (per_station_files) fprintf(stderr, "fm_replay: %lld IQ samples in, %lld audio samples out for each of %d stations\n", samples, audio, rows);
     else fprintf(stderr, "fm_replay: %lld IQ samples in, %lld audio samples out\n", samples, audio);
     if (src.f) fclose(src.f);
     if (src.sock >= 0) close(src.sock);

@@ -153,6 +153,12 @@ foreign import ccall safe "sdrhip_debug_fm_bank_launches" c_fm_bank_launches :: 
 -- the bank's host-block front end: the stream object of sdrhip_fm_stream_create with one row of audio blocks per station (push,
 -- flush, poll and the rest are the calls above; counts are blocks per station); pop_rows: station j's blocks at out + j * row_stride
 foreign import ccall safe "sdrhip_fm_stream_create_bank" c_stream_create_bank :: Ptr (Ptr SdrStream) -> Ptr SdrBank -> CInt -> CInt -> IO CInt
+-- the bank and its stream on 16-bit signed IQ (the BladeRF's interleaved int16): the same bank and stream objects, int16 in
+foreign import ccall safe "sdrhip_fm_bank_run_i16"  c_fm_bank_run_i16  :: Ptr SdrBank -> Ptr () -> Ptr CShort -> Int64 -> Int64 -> Ptr CFloat -> Int64 -> Int64 -> Int64 -> Ptr () -> CSize -> IO CInt
+foreign import ccall safe "sdrhip_debug_fm_bank_i16_launches" c_fm_bank_i16_launches :: IO CLLong
+foreign import ccall safe "sdrhip_fm_stream_create_bank_i16" c_stream_create_bank_i16 :: Ptr (Ptr SdrStream) -> Ptr SdrBank -> CInt -> CInt -> IO CInt
+foreign import ccall safe "sdrhip_fm_stream_push_i16" c_stream_push_i16 :: Ptr SdrStream -> Ptr CShort -> CInt -> IO CInt
+foreign import ccall safe "sdrhip_fm_stream_input_buffer_i16" c_stream_input_buffer_i16 :: Ptr SdrStream -> IO (Ptr CShort)
 foreign import ccall safe "sdrhip_fm_stream_rows" c_stream_rows :: Ptr SdrStream -> IO CInt
 foreign import ccall safe "sdrhip_fm_stream_pop_rows" c_stream_pop_rows :: Ptr SdrStream -> Ptr CFloat -> Int64 -> CInt -> IO CInt
 -- the tuner bank's Pipe (include/sdr_hip.h, sdrhip_pipe_tuner_bank): cfloat or u8 IQ host blocks in, one row of decimated blocks per

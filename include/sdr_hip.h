@@ -705,6 +705,32 @@ int sdrhip_fm_bank_run(sdrhip_fm_bank *b, void *stream, const uint8_t *d_in_iq, 
 int sdrhip_fm_bank_set_route(sdrhip_fm_bank *b, int route, int64_t max_outputs, int tile_outputs);
 /* banked launches so far, process-wide (they do NOT count in sdrhip_debug_small_chain_launches: those are the chains') */
 long long sdrhip_debug_fm_bank_launches(void);
+/* The bank on 16-bit signed IQ (the BladeRF's samples, as sdrhip_tuner_run_i16): d_in_iq is interleaved (I, Q) int16, 4 bytes per
+ * sample, d_in_iq[0 .. 1] is stream sample s0; a sample is converted first, (float)s * 2^-11 (exact in float32 over the whole int16
+ * range), then mixed.  The SAME bank object serves u8 and int16 runs: plan, ready, max_halo and workspace_bytes are the bank's.
+ * Definition: station j's row equals, bit for bit, on every route and for any tile_outputs, the composition
+ *     sdrhip_tuner_run_i16 -> sdrhip_fm_demod_run -> sdrhip_resampler_run -> sdrhip_filter_run -> sdrhip_scale_run
+ * driven by hand on the same (s0, n_in, q0, q1): a tuner of the bank's decimator arguments with table j, every later stage with the
+ * bank's arguments, all of them with the bank's block as their seam block.  A bank of one station with the table {1, 0} is the
+ * plain FM receiver on int16 input (the product of a converted sample with 1 + 0i keeps its bits: converted int16 holds no -0 and
+ * no subnormal).
+ * Routes (sdrhip_fm_bank_set_route; the same setting serves both input types).  1 = the banked launch: ONE launch of the tuned
+ * one-kernel chain with a station axis and an int16 loader; it fits where the u8 banked launch fits, under int16's alignment rule:
+ * d_in_iq 16-byte aligned and s0 a multiple of 4 (u8: 8).  It accepts a null workspace.  The zero tap that create padded is skipped
+ * only while 16 (|re| + |im|) is finite in float32 for every table entry of every station (converted int16 reaches |x| = 16; the
+ * u8 run's condition is |re| + |im|).  2 = station by station: the bank's own tuned chains with the tuner's int16 first stage
+ * (sdrhip_tuner_run_i16's two routes: its tile kernel where the first window is 16-byte aligned, else the int16 mix into the
+ * workspace and the cfloat decimator), everything behind it the code a u8 run takes.  0 = auto: the u8 rule, the banked launch
+ * where it fits while q1 - q0 <= 39322 and stations * (q1 - q0) <= max_outputs.  The int16 sweep confirms the u8 rectangle
+ * (tools/fm_bank_bench.py --i16, profiles/fm_bank_i16_bench.txt: 2 .. 32 stations x runs of 1 block, 16 blocks and 2^20 samples,
+ * the banked launch against route 2 of the same bank): at every point the banked launch's slowest round is below route 2's
+ * fastest (0.016 .. 0.27 of its time); with one station it is 0.39 .. 0.50.
+ * SDRHIP_ERR_ARG before any device work, nothing written: whatever sdrhip_fm_bank_run refuses, d_in_iq not 4-byte aligned, route 1
+ * forced where the banked launch does not fit.  There is no sdrhip_fm_chain_run_i16: int16 reaches the FM side through a bank. */
+int sdrhip_fm_bank_run_i16(sdrhip_fm_bank *b, void *stream, const int16_t *d_in_iq, int64_t s0, int64_t n_in,
+                           float *d_audio, int64_t audio_stride, int64_t q0, int64_t q1, void *d_workspace, size_t workspace_bytes);
+/* banked launches on int16 input so far, process-wide (each of them counts in sdrhip_debug_fm_bank_launches too) */
+long long sdrhip_debug_fm_bank_i16_launches(void);
 /* launches of the thread-per-polyphase-cycle resampler (real I/D with an odd decimation: 2/3, 5/7, ...; any filter length),
  * process-wide (tests assert that this kernel, not the lane-split one, served those ratios) */
 long long sdrhip_debug_resample_cycle_launches(void);
@@ -852,6 +878,22 @@ int sdrhip_fm_stream_pop(sdrhip_fm_stream *st, float *out, int capacity);
  * fastest -- so no in-place region is kept.  A one-station bank's stream follows the chain's rule.
  * The bank must outlive the stream and must not be run by another caller meanwhile. */
 int sdrhip_fm_stream_create_bank(sdrhip_fm_stream **st, sdrhip_fm_bank *bank, int max_block_samples, int block_size_out);
+/* A bank's stream on 16-bit signed IQ: interleaved int16 source blocks in (4 bytes per sample), every station's audio blocks out.
+ * The object sdrhip_fm_stream_create_bank gives, and the same calls with the same meaning: flush, poll, set_coalesce, set_adaptive,
+ * pop, pop_rows, rows, state_bytes, save, restore, destroy.  Samples go in through sdrhip_fm_stream_push_i16 and
+ * sdrhip_fm_stream_input_buffer_i16 (max_block_samples int16 pairs are writable); the wrong push or input_buffer call for a
+ * stream's input type is refused (SDRHIP_ERR_ARG / NULL) with nothing staged.  A submission is ONE sdrhip_fm_bank_run_i16 on
+ * [carried tail | staged samples]; the tail starts at a multiple of 8 samples, so the run is 16-byte aligned on the device.
+ * Definition: station j's blocks are those of sdrhip_fm_bank_run_i16's composition run over the whole stream -- whatever the push
+ * sizes, coalescing, adaptive submission or route.
+ * An int16 stream NEVER reads its input in place, whatever the station count: every submission up to the direct bound is one copy
+ * on the slot's stream and one run on device memory.  This is a stated choice, not a measured one (for one station it differs from
+ * the u8 stream's rule).
+ * A state of an int16 stream has a version of its own: it carries the input type, the station count and the history as int16.
+ * restore refuses an int16 state on a u8 stream and the reverse; the states of u8 streams keep every byte. */
+int sdrhip_fm_stream_create_bank_i16(sdrhip_fm_stream **st, sdrhip_fm_bank *bank, int max_block_samples, int block_size_out);
+int sdrhip_fm_stream_push_i16(sdrhip_fm_stream *st, const int16_t *iq, int n_samples);
+int16_t *sdrhip_fm_stream_input_buffer_i16(sdrhip_fm_stream *st);
 int sdrhip_fm_stream_rows(const sdrhip_fm_stream *st);      /* 1 for a chain's stream, the number of stations for a bank's */
 /* Pops up to max_blocks complete audio blocks of every station: station j's nb * block_size_out floats go to
  * out + j * row_stride (row_stride >= max_blocks * block_size_out is checked before anything is written).

@@ -371,8 +371,10 @@ static Geom tuner_geom(const sdrhip_fm_chain* c, int64_t s0, int64_t kd0, int64_
     return g;
 }
 
-// d_in_iq, d_workspace: only their alignment counts (a tuned run takes the tuner's tile kernel where its 16-byte loads are aligned)
-static RunPlan plan_run(const sdrhip_fm_chain* c, int64_t s0, int64_t q0, int64_t q1, const void* d_in_iq, const void* d_workspace)
+// d_in_iq, d_workspace: only their alignment counts (a tuned run takes the tuner's tile kernel where its 16-byte loads are aligned).
+// fmt: IN_U8, or IN_I16 for the runs of a receiver bank on 16-bit signed IQ (tuned chains only; the int16 tile kernel's predicate)
+static RunPlan plan_run(const sdrhip_fm_chain* c, int64_t s0, int64_t q0, int64_t q1, const void* d_in_iq, const void* d_workspace,
+                        InFmt fmt = IN_U8)
 {
     RunPlan r;
     r.m1 = q1 + c->audio.Lp - 1;
@@ -384,8 +386,10 @@ static RunPlan plan_run(const sdrhip_fm_chain* c, int64_t s0, int64_t q0, int64_
     r.n_hi = (r.kd1 - 1) * c->decim.factor + c->decim.Lp;
     bool staged = !c->fused_first_stage();      // the first stage reads cfloat samples from the workspace's start
     if (c->tuner_period != 0) {
+        const Geom g = tuner_geom(c, s0, r.kd0, r.kd1);
         r.tuner_tile = c->tuner_tile_shape() && r.kd1 - r.kd0 < (int64_t)0x7fffffff &&
-                       tuner_fused_fits(tuner_geom(c, s0, r.kd0, r.kd1), c->decim.Lp, true, d_in_iq, true, d_workspace, c->tuner_period);
+                       (fmt == IN_I16 ? tuner_i16_fused_fits(g, c->decim.Lp, true, d_in_iq, d_workspace, c->tuner_period)
+                                      : tuner_fused_fits(g, c->decim.Lp, true, d_in_iq, true, d_workspace, c->tuner_period));
         staged = !r.tuner_tile;
     }
     if (staged) {
@@ -432,14 +436,17 @@ struct RunRoute {
     bool small = false, tail = false;     // the first of the two fused kernels that is wanted (mode and size) and fits, else the stage kernels
 };
 static int chain_route(const sdrhip_fm_chain* c, const char* who, const uint8_t* d_in_iq, int64_t s0, int64_t n_in, const float* d_audio,
-                       int64_t q0, int64_t q1, const void* d_workspace, size_t workspace_bytes, RunRoute* out)
+                       int64_t q0, int64_t q1, const void* d_workspace, size_t workspace_bytes, RunRoute* out, InFmt fmt = IN_U8)
 {
     SDRHIP_REQUIRE(d_in_iq && d_audio && d_workspace, who);
+    SDRHIP_REQUIRE(fmt == IN_U8 || (fmt == IN_I16 && c->tuner_period != 0), who);      // int16 reaches a chain through its bank only
     RunRoute& t = *out;
-    t.r = plan_run(c, s0, q0, q1, d_in_iq, d_workspace);
+    t.r = plan_run(c, s0, q0, q1, d_in_iq, d_workspace, fmt);
     int rc;
     if ((rc = input_holds(who, t.r, s0, n_in, q0, q1)) != SDRHIP_OK) return rc;
-    t.small = c->mode_takes(c->small_chain, q1 - q0, c->small_chain_max) && chain_small_fits(c, d_in_iq, s0);
+    // int16: the one-kernel chain exists in the bank's form only (the banked launch, bank_run); a station's own run starts with the
+    // tuner's int16 first stage and goes on as any run
+    t.small = fmt == IN_U8 && c->mode_takes(c->small_chain, q1 - q0, c->small_chain_max) && chain_small_fits(c, d_in_iq, s0);
     t.tail = !t.small && c->fm_tail && c->mode_takes(c->fused_tail, q1 - q0, kFusedTailAutoOutputs) && fm_tail_fused_fits(c->resamp.Lp, c->block);
     if (!t.small && t.r.ws_need > workspace_bytes) {       // the one-kernel chain sends nothing through the workspace
         set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, t.r.ws_need);
@@ -452,9 +459,11 @@ static int chain_route(const sdrhip_fm_chain* c, const char* who, const uint8_t*
     return SDRHIP_OK;
 }
 
-// input_over_link: d_in_iq is pinned HOST memory (the host-block operator's in-place pushes): the one-kernel chain takes its largest tile
+// input_over_link: d_in_iq is pinned HOST memory (the host-block operator's in-place pushes): the one-kernel chain takes its largest tile.
+// fmt == IN_I16 (a receiver bank's station-by-station route on 16-bit signed IQ): d_in_iq holds interleaved int16, 4 bytes per sample;
+// the first stage is the tuner's on such input, everything behind it is the same code.
 static int chain_run_on(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq, int64_t s0, int64_t n_in, float* d_audio,
-                        int64_t q0, int64_t q1, void* d_workspace, size_t workspace_bytes, bool input_over_link)
+                        int64_t q0, int64_t q1, void* d_workspace, size_t workspace_bytes, bool input_over_link, InFmt fmt = IN_U8)
 {
     SDRHIP_REQUIRE(q1 >= q0 && q0 >= 0 && s0 >= 0 && n_in >= 0, "sdrhip_fm_chain_run");
     if (q1 == q0) return SDRHIP_OK;
@@ -462,7 +471,7 @@ static int chain_run_on(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq
 
     RunRoute route;
     int rc;
-    if ((rc = chain_route(c, "sdrhip_fm_chain_run", d_in_iq, s0, n_in, d_audio, q0, q1, d_workspace, workspace_bytes, &route)) != SDRHIP_OK) return rc;
+    if ((rc = chain_route(c, "sdrhip_fm_chain_run", d_in_iq, s0, n_in, d_audio, q0, q1, d_workspace, workspace_bytes, &route, fmt)) != SDRHIP_OK) return rc;
     const RunPlan& r = route.r;
     const bool small = route.small, tail = route.tail;
     const FirDesc& dec = c->decim;
@@ -492,6 +501,21 @@ static int chain_run_on(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq
     float* d_z = (float*)(ws + r.off_z);
     // K1+K2: u8 -> cfloat -> decimate (convert.c:37-50 fused into decimate.c:105-113)
     rc = c->timed(kDecimate, s, [&] {
+        if (tuned && fmt == IN_I16) {
+            // sdrhip_tuner_run_i16's two routes (tuner.cpp): the bank's int16 tile kernel with one channel, or the int16 mix into
+            // the workspace's start and the stock cfloat decimator on it
+            if (r.tuner_tile) {
+                const int off0 = 0;
+                if (!launch_tuner_bank_i16(s, tuner_geom(c, s0, r.kd0, r.kd1), dec.d_plain, dec.Lp, dec.d_cross, d_in_iq, d_d, 0, c->d_osc, 1, &off0,
+                                           &c->tuner_period, false)) {
+                    set_error("sdrhip_fm_bank_run_i16: the tuner's int16 tile kernel refused a launch its predicate accepted");
+                    return SDRHIP_ERR_STATE;
+                }
+                return SDRHIP_OK;
+            }
+            launch_tuner_mix_i16(s, d_in_iq + 4 * (r.xa - s0), (float*)ws, r.xb - r.xa, c->d_osc, c->tuner_period, (int)(r.xa % c->tuner_period));
+            return fir_run(&dec, s, ws, false, r.xa, d_d, r.kd0, r.kd1, c->block);
+        }
         if (tuned) {
             // the tuner's own routes on the caller's workspace and this run's stream (no leased scratch, no events: runs are captured
             // into graphs and alternate between the overlap lanes): its tile kernel, or the mix into the workspace's start and the
@@ -538,9 +562,9 @@ static int chain_run_on(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq
 
 // One run in the chain's current mode; sdrhip_fm_chain_run and the host-block operator's submissions
 static int chain_run(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq, int64_t s0, int64_t n_in, float* d_audio, int64_t q0,
-                     int64_t q1, void* d_workspace, size_t workspace_bytes, bool input_over_link)
+                     int64_t q1, void* d_workspace, size_t workspace_bytes, bool input_over_link, InFmt fmt = IN_U8)
 {
-    if (!c->overlap) return chain_run_on(c, stream, d_in_iq, s0, n_in, d_audio, q0, q1, d_workspace, workspace_bytes, input_over_link);
+    if (!c->overlap) return chain_run_on(c, stream, d_in_iq, s0, n_in, d_audio, q0, q1, d_workspace, workspace_bytes, input_over_link, fmt);
     // two runs in flight: this run goes to lane j, after everything queued on the caller's stream so far (its input's
     // producer); the caller's stream is then made to wait for the PREVIOUS run (lane 1 - j), not for this one
     hipStream_t s = (hipStream_t)stream;
@@ -551,7 +575,7 @@ static int chain_run(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq, i
     SDRHIP_CHECK_HIP(hipStreamWaitEvent(c->lane[j], c->ev_in[j], 0));
     const size_t half = (workspace_bytes / 2) & ~(size_t)255;
     rc = chain_run_on(c, (void*)c->lane[j], d_in_iq, s0, n_in, d_audio, q0, q1, d_workspace ? (char*)d_workspace + (size_t)j * half : nullptr, half,
-                      input_over_link);
+                      input_over_link, fmt);
     // (also when the run failed half way: kernels it did enqueue on the lane may still be reading the input and writing the
     // audio and the workspace half, and a later run or join must be ordered behind them)
     const hipError_t erec = hipEventRecord(c->ev_out[j], c->lane[j]);
@@ -772,6 +796,9 @@ struct sdrhip_fm_bank {
             if (!c->tuner_pskip_ok) return false;
         return true;
     }
+    // ... on 16-bit signed IQ: the chains' flag is decided under |x| <= 1, which holds for converted u8; converted int16 reaches
+    // |x| = 16, so an int16 run may skip only while 16 (|re| + |im|) is finite in float for every entry of every table (set at create)
+    bool pskip_ok_i16 = false;
     ~sdrhip_fm_bank()
     {
         for (sdrhip_fm_chain* c : ch) delete c;
@@ -811,6 +838,9 @@ int sdrhip_fm_bank_create(sdrhip_fm_bank** b, int order, int decim_factor, const
         bk->h_tables.insert(bk->h_tables.end(), osc_iq[j], osc_iq[j] + 2 * (size_t)periods[j]);
         pairs += (size_t)periods[j];
     }
+    bk->pskip_ok_i16 = true;
+    for (size_t i = 0; i + 1 < bk->h_tables.size(); i += 2)
+        if (16.0 * (fabs((double)bk->h_tables[i]) + fabs((double)bk->h_tables[i + 1])) > (double)FLT_MAX) bk->pskip_ok_i16 = false;
     *b = bk;
     return SDRHIP_OK;
 }
@@ -847,20 +877,25 @@ int sdrhip_fm_bank_set_route(sdrhip_fm_bank* b, int route, int64_t max_outputs, 
 }
 
 long long sdrhip_debug_fm_bank_launches(void) { return fm_chain_small_bank_launch_count(); }
+long long sdrhip_debug_fm_bank_i16_launches(void) { return fm_chain_small_bank_i16_launch_count(); }
 
 }  // extern "C"
 
 // One run of a bank; sdrhip_fm_bank_run and the submissions of a bank's host-block stream.  input_over_link: as chain_run_on --
 // d_in_iq is pinned HOST memory, so the one-kernel chain takes its largest tile on either route (a tile_outputs beyond the
-// kernel's largest is clamped to it by the launcher; a negative one would mean "chosen from the work" to the banked launcher)
+// kernel's largest is clamped to it by the launcher; a negative one would mean "chosen from the work" to the banked launcher).
+// fmt: IN_U8, or IN_I16 for sdrhip_fm_bank_run_i16 (d_in_iq: interleaved int16, 4 bytes per sample): the same object, plan and
+// workspace; the banked launch is the kernel's int16 form under int16's alignment rule and its own skip predicate, and the
+// stations' own runs take the tuner's int16 first stage (chain_run_on).
 static int bank_run(sdrhip_fm_bank* b, void* stream, const uint8_t* d_in_iq, int64_t s0, int64_t n_in, float* d_audio, int64_t audio_stride,
-                    int64_t q0, int64_t q1, void* d_workspace, size_t workspace_bytes, bool input_over_link)
+                    int64_t q0, int64_t q1, void* d_workspace, size_t workspace_bytes, bool input_over_link, InFmt fmt = IN_U8)
 {
     SDRHIP_REQUIRE(b != nullptr, "sdrhip_fm_bank_run");
     SDRHIP_REQUIRE(q1 >= q0 && q0 >= 0 && s0 >= 0 && n_in >= 0, "sdrhip_fm_bank_run");
     SDRHIP_REQUIRE(audio_stride >= q1 - q0, "sdrhip_fm_bank_run: a station's row holds its outputs");
     if (q1 == q0) return SDRHIP_OK;
     SDRHIP_REQUIRE(d_in_iq && d_audio, "sdrhip_fm_bank_run");
+    SDRHIP_REQUIRE(fmt != IN_I16 || (reinterpret_cast<uintptr_t>(d_in_iq) & 3) == 0, "sdrhip_fm_bank_run_i16: int16 IQ at an address that is no multiple of 4");
     hipStream_t s = (hipStream_t)stream;
     const int K = (int)b->ch.size();
     sdrhip_fm_chain* c0 = b->ch[0];         // ranges, taps and tail tables are the same for every station
@@ -869,10 +904,12 @@ static int bank_run(sdrhip_fm_bank* b, void* stream, const uint8_t* d_in_iq, int
     int rc;
     if ((rc = input_holds("sdrhip_fm_bank_run", plan_run(c0, s0, q0, q1, d_in_iq, d_workspace), s0, n_in, q0, q1)) != SDRHIP_OK) return rc;
     const int tile = b->tile != 0 ? b->tile : (input_over_link ? 1 << 20 : 0);
-    const bool fits = chain_small_fits(c0, d_in_iq, s0) && fm_chain_small_bank_fits(q0, q1, K, tile);
+    const bool fits = (fmt == IN_I16 ? c0->fm_tail && fm_chain_small_i16_fits(c0->decim.factor, c0->decim.Lp, c0->decim.corder, c0->block, d_in_iq, s0)
+                                     : chain_small_fits(c0, d_in_iq, s0)) &&
+                      fm_chain_small_bank_fits(q0, q1, K, tile);
     if (b->route == 1 && !fits) {
         set_error("sdrhip_fm_bank_run: the banked launch does not fit this run (decimator / tail shape, seam block, input alignment, "
-                  "s0 %% 8, or more than 65535 tiles)");
+                  "s0 %% %d, or more than 65535 tiles)", fmt == IN_I16 ? 4 : 8);
         return SDRHIP_ERR_ARG;
     }
     const bool banked = fits && (b->route == 1 || (b->route == 0 && (int64_t)K * (q1 - q0) <= b->max_outputs && q1 - q0 <= kBankAutoStationOutputs));
@@ -881,8 +918,13 @@ static int bank_run(sdrhip_fm_bank* b, void* stream, const uint8_t* d_in_iq, int
         if ((rc = dec.ensure_device()) != SDRHIP_OK || (rc = c0->resamp.ensure_device()) != SDRHIP_OK || (rc = c0->audio.ensure_device()) != SDRHIP_OK)
             return rc;
         if (b->d_tables == nullptr && (rc = upload_floats(&b->d_tables, b->h_tables)) != SDRHIP_OK) return rc;
-        launch_fm_chain_small_bank(s, d_in_iq, s0, n_in, d_audio, audio_stride, q0, q1, dec.d_plain, dec.last_tap_is_padding() && b->pskip_ok(),
-                                   c0->tail_tables(), tile, b->d_tables, K, b->off, b->period);
+        if (fmt == IN_I16)
+            launch_fm_chain_small_bank_i16(s, reinterpret_cast<const int16_t*>(d_in_iq), s0, n_in, d_audio, audio_stride, q0, q1, dec.d_plain,
+                                           dec.last_tap_is_padding() && b->pskip_ok() && b->pskip_ok_i16, c0->tail_tables(), tile, b->d_tables, K,
+                                           b->off, b->period);
+        else
+            launch_fm_chain_small_bank(s, d_in_iq, s0, n_in, d_audio, audio_stride, q0, q1, dec.d_plain, dec.last_tap_is_padding() && b->pskip_ok(),
+                                       c0->tail_tables(), tile, b->d_tables, K, b->off, b->period);
         return launched(SDRHIP_OK);
     }
     // station by station.  What a station's run would refuse is found for ALL stations first (chain_route, the chain's own
@@ -890,12 +932,12 @@ static int bank_run(sdrhip_fm_bank* b, void* stream, const uint8_t* d_in_iq, int
     // workspace it needs, depends on its period
     for (int j = 0; j < K; j++) {
         RunRoute route;
-        if ((rc = chain_route(b->ch[j], "sdrhip_fm_bank_run", d_in_iq, s0, n_in, d_audio, q0, q1, d_workspace, workspace_bytes, &route)) != SDRHIP_OK)
+        if ((rc = chain_route(b->ch[j], "sdrhip_fm_bank_run", d_in_iq, s0, n_in, d_audio, q0, q1, d_workspace, workspace_bytes, &route, fmt)) != SDRHIP_OK)
             return rc;
     }
     for (int j = 0; j < K; j++)
         if ((rc = chain_run(b->ch[j], stream, d_in_iq, s0, n_in, d_audio + (int64_t)j * audio_stride, q0, q1, d_workspace, workspace_bytes,
-                            input_over_link)) != SDRHIP_OK)
+                            input_over_link, fmt)) != SDRHIP_OK)
             return rc;
     return SDRHIP_OK;
 }
@@ -906,6 +948,13 @@ int sdrhip_fm_bank_run(sdrhip_fm_bank* b, void* stream, const uint8_t* d_in_iq, 
                        int64_t q0, int64_t q1, void* d_workspace, size_t workspace_bytes)
 {
     return bank_run(b, stream, d_in_iq, s0, n_in, d_audio, audio_stride, q0, q1, d_workspace, workspace_bytes, false);
+}
+
+int sdrhip_fm_bank_run_i16(sdrhip_fm_bank* b, void* stream, const int16_t* d_in_iq, int64_t s0, int64_t n_in, float* d_audio, int64_t audio_stride,
+                           int64_t q0, int64_t q1, void* d_workspace, size_t workspace_bytes)
+{
+    return bank_run(b, stream, reinterpret_cast<const uint8_t*>(d_in_iq), s0, n_in, d_audio, audio_stride, q0, q1, d_workspace, workspace_bytes, false,
+                    IN_I16);
 }
 
 }  // extern "C"
@@ -1029,6 +1078,10 @@ struct sdrhip_fm_stream {
     sdrhip_fm_chain* c = nullptr;        // a bank's stream: station 0's chain -- positions, ranges and sizes depend on no table
     sdrhip_fm_bank* bank = nullptr;      // set: every submission is ONE run of the bank, rows = its stations
     int rows = 1;
+    // what is pushed: u8 IQ (2 bytes per sample) or, over a bank only (sdrhip_fm_stream_create_bank_i16), interleaved int16 IQ
+    // (4 bytes per sample): staging, history and states hold the samples as they came
+    InFmt fmt = IN_U8;
+    size_t esz() const { return (size_t)in_fmt_bytes(fmt); }
     CopyPool copier;
     int max_block = 0;
     int block_out = 0;
@@ -1058,19 +1111,20 @@ struct sdrhip_fm_stream {
         return adaptive > c ? adaptive : c;
     }
     int ready() const { return (int)(eng.pending() / (size_t)block_out); }
-    // u8 IQ samples (2 bytes); head room = the carried tail, a multiple of 8 samples.  Declared last: destroyed first, so its
+    // u8 IQ samples (2 bytes) or int16 IQ samples (4 bytes: esz()); head room = the carried tail, a multiple of 8 samples.  Declared last: destroyed first, so its
     // streams are idle before the workspaces are freed.
     HostStream eng;
 };
 
 // A stream over a chain (bank == nullptr, one row) or over a bank (chain: its station 0); the arguments are checked by the callers
 static int stream_create(const char* who, sdrhip_fm_stream** out, sdrhip_fm_chain* chain, sdrhip_fm_bank* bank, int max_block_samples,
-                         int block_size_out)
+                         int block_size_out, InFmt fmt = IN_U8)
 {
     *out = nullptr;
     sdrhip_fm_stream* st = new sdrhip_fm_stream();
     st->c = chain;
     st->bank = bank;
+    st->fmt = fmt;
     st->rows = bank ? (int)bank->ch.size() : 1;
     st->eng.set_rows(st->rows);
     // More than one row never runs in place: with K stations in the grid every station's workgroups would fetch the same tile
@@ -1079,13 +1133,17 @@ static int stream_create(const char* who, sdrhip_fm_stream** out, sdrhip_fm_chai
     // more than the spread of the rounds, which is what an in-place region would have needed -- none is kept.
     // SDRHIP_STAGE_SAMPLES still moves the bound, for that comparison.
     if (st->rows > 1 && getenv("SDRHIP_STAGE_SAMPLES") == nullptr) st->stage_samples = 0;
+    // An int16 stream never reads its input in place, whatever the station count and whatever the knob says: a stated choice, not a
+    // measured one (for K >= 2 it is the rule above; for K = 1 it differs from the u8 stream's).  The carried tail starts at a
+    // multiple of 8 samples, so the copy puts the run's first sample on a 16-byte boundary of the slot's device buffer.
+    if (fmt == IN_I16) st->stage_samples = 0;
     st->max_block = max_block_samples;
     st->block_out = block_size_out;
     // the carried tail never exceeds the receptive field of one audio output (+ the 8-sample alignment of its start)
     const int64_t head_cap = (sdrhip_fm_chain_max_halo(chain) + 8 + 15) / 8 * 8;
     // four slots when even the largest push runs in place (see the struct), else two
     const int slots = (st->direct_ok && head_cap + (int64_t)max_block_samples <= st->direct_samples) ? HostStream::kMaxSlots : 2;
-    if (st->eng.init(slots, 2, head_cap, who) != SDRHIP_OK) {
+    if (st->eng.init(slots, st->esz(), head_cap, who) != SDRHIP_OK) {
         delete st;
         return SDRHIP_ERR_HIP;
     }
@@ -1123,6 +1181,14 @@ int sdrhip_fm_stream_create_bank(sdrhip_fm_stream** out, sdrhip_fm_bank* bank, i
     SDRHIP_REQUIRE(bank->ch[0]->block == 0 || max_block_samples % bank->ch[0]->block == 0,
                    "sdrhip_fm_stream_create_bank: blocks must be whole multiples of the bank's seam block");
     return stream_create("sdrhip_fm_stream_create_bank", out, bank->ch[0], bank, max_block_samples, block_size_out);
+}
+
+int sdrhip_fm_stream_create_bank_i16(sdrhip_fm_stream** out, sdrhip_fm_bank* bank, int max_block_samples, int block_size_out)
+{
+    SDRHIP_REQUIRE(out != nullptr && bank != nullptr && max_block_samples > 0 && block_size_out > 0, "sdrhip_fm_stream_create_bank_i16");
+    SDRHIP_REQUIRE(bank->ch[0]->block == 0 || max_block_samples % bank->ch[0]->block == 0,
+                   "sdrhip_fm_stream_create_bank_i16: blocks must be whole multiples of the bank's seam block");
+    return stream_create("sdrhip_fm_stream_create_bank_i16", out, bank->ch[0], bank, max_block_samples, block_size_out, IN_I16);
 }
 
 int sdrhip_fm_stream_rows(const sdrhip_fm_stream* st)
@@ -1181,10 +1247,10 @@ static int stream_submit(sdrhip_fm_stream* st)
     // A bank's stream: ONE run of the bank on the same [tail | staged], its rows back to back in the result buffer (the engine's
     // harvest regroups them per station).  The bank's own rule picks the banked launch or station by station, on the same
     // workspace: sdrhip_fm_bank_workspace_bytes is the chain's figure.
-    rc = e.submit(route, cs, first, (size_t)(tail + n) * 2, (int64_t)st->rows * n_out, [&](hipStream_t s, const void* d_in, void* d_out) {
+    rc = e.submit(route, cs, first, (size_t)(tail + n) * st->esz(), (int64_t)st->rows * n_out, [&](hipStream_t s, const void* d_in, void* d_out) {
         if (st->bank)
             return bank_run(st->bank, (void*)s, (const uint8_t*)d_in, keep_from, tail + n, (float*)d_out, n_out, st->q_done, q_new, wsb_buf.p,
-                            wsb_buf.cap, route == HostStream::kInPlace);
+                            wsb_buf.cap, route == HostStream::kInPlace, st->fmt);
         return chain_run(c, (void*)s, (const uint8_t*)d_in, keep_from, tail + n, (float*)d_out, st->q_done, q_new, wsb_buf.p, wsb_buf.cap,
                          route == HostStream::kInPlace);
     });
@@ -1219,27 +1285,43 @@ int sdrhip_fm_stream_set_adaptive(sdrhip_fm_stream* st, int max_samples)
     return SDRHIP_OK;
 }
 
-uint8_t* sdrhip_fm_stream_input_buffer(sdrhip_fm_stream* st)
+}  // extern "C"
+
+// the wrong push / input_buffer call for the stream's input type is refused with nothing staged
+static const char* stream_wrong_type(const sdrhip_fm_stream* st, InFmt fmt)
 {
-    if (st == nullptr) { set_error("sdrhip_fm_stream_input_buffer: null stream"); return nullptr; }
+    if (st->fmt == fmt) return nullptr;
+    return st->fmt == IN_I16 ? "this stream takes int16 IQ (sdrhip_fm_stream_push_i16 / sdrhip_fm_stream_input_buffer_i16)"
+                             : "this stream takes u8 IQ (sdrhip_fm_stream_push / sdrhip_fm_stream_input_buffer)";
+}
+
+static uint8_t* stream_input_buffer(sdrhip_fm_stream* st, InFmt fmt, const char* who)
+{
+    if (st == nullptr) { set_error("%s: null stream", who); return nullptr; }
+    if (const char* wrong = stream_wrong_type(st, fmt)) { set_error("%s: %s", who, wrong); return nullptr; }
     HostStream& e = st->eng;
     // the caller may write up to max_block samples: make room for all of them behind what is already staged
     if (e.staged + st->max_block > st->capacity() && stream_submit(st) != SDRHIP_OK) return nullptr;
-    if (e.open_slot((size_t)st->capacity() * 2, (size_t)e.staged * 2) != SDRHIP_OK) return nullptr;
+    if (e.open_slot((size_t)st->capacity() * st->esz(), (size_t)e.staged * st->esz()) != SDRHIP_OK) return nullptr;
     return e.write_pos();
 }
 
-int sdrhip_fm_stream_push(sdrhip_fm_stream* st, const uint8_t* iq, int n)
+static int stream_push(sdrhip_fm_stream* st, const void* iq_v, int n, InFmt fmt, const char* who)
 {
-    SDRHIP_REQUIRE(st != nullptr && iq != nullptr && n > 0 && n <= st->max_block, "sdrhip_fm_stream_push");
+    SDRHIP_REQUIRE(st != nullptr && iq_v != nullptr && n > 0 && n <= st->max_block, who);
+    if (const char* wrong = stream_wrong_type(st, fmt)) {
+        set_error("%s: %s", who, wrong);
+        return SDRHIP_ERR_ARG;
+    }
     SDRHIP_REQUIRE(st->c->block == 0 || n % st->c->block == 0,
                    "sdrhip_fm_stream_push: the chain reproduces the seams of `block`-sample source buffers (fm.hs:17,24)");
+    const uint8_t* iq = static_cast<const uint8_t*>(iq_v);
     HostStream& e = st->eng;
     int rc;
     if (e.staged + n > st->capacity() && (rc = stream_submit(st)) != SDRHIP_OK) return rc;
-    if ((rc = e.open_slot((size_t)st->capacity() * 2, (size_t)e.staged * 2)) != SDRHIP_OK) return rc;
+    if ((rc = e.open_slot((size_t)st->capacity() * st->esz(), (size_t)e.staged * st->esz())) != SDRHIP_OK) return rc;
     uint8_t* dst = e.write_pos();
-    if (iq != dst) st->copier.copy(dst, iq, (size_t)n * 2);   // else: the caller filled our staging buffer in place
+    if (iq != dst) st->copier.copy(dst, iq, (size_t)n * st->esz());   // else: the caller filled our staging buffer in place
     e.staged += n;
     bool submit = e.staged >= st->coalesce;
     if (st->adaptive > 0 && st->coalesce == 0 && submit) {     // an explicit set_coalesce takes precedence: fixed batches
@@ -1255,6 +1337,22 @@ int sdrhip_fm_stream_push(sdrhip_fm_stream* st, const uint8_t* iq, int n)
         if ((rc = e.harvest_done()) != SDRHIP_OK) return rc;
     }
     return st->ready();
+}
+
+extern "C" {
+
+uint8_t* sdrhip_fm_stream_input_buffer(sdrhip_fm_stream* st) { return stream_input_buffer(st, IN_U8, "sdrhip_fm_stream_input_buffer"); }
+
+int16_t* sdrhip_fm_stream_input_buffer_i16(sdrhip_fm_stream* st)
+{
+    return reinterpret_cast<int16_t*>(stream_input_buffer(st, IN_I16, "sdrhip_fm_stream_input_buffer_i16"));
+}
+
+int sdrhip_fm_stream_push(sdrhip_fm_stream* st, const uint8_t* iq, int n) { return stream_push(st, iq, n, IN_U8, "sdrhip_fm_stream_push"); }
+
+int sdrhip_fm_stream_push_i16(sdrhip_fm_stream* st, const int16_t* iq, int n_samples)
+{
+    return stream_push(st, iq, n_samples, IN_I16, "sdrhip_fm_stream_push_i16");
 }
 
 int sdrhip_fm_stream_poll(sdrhip_fm_stream* st)
@@ -1289,7 +1387,12 @@ constexpr uint32_t kStateMagic = 0x53444d46u;   // "FMDS"
 // A stream of one row writes version 1, byte for byte what it always wrote.  A stream of several rows (over a bank) writes
 // version 2: the same header with `pending` counted PER ROW, then the row count (int64), then the history and every row's audio
 // not yet popped, row after row.  Oscillator tables are no part of a state: a station's phase is a closed form of the position.
-size_t state_header_bytes(const sdrhip_fm_stream* st) { return sizeof(StreamStateHeader) + (st->rows > 1 ? sizeof(int64_t) : 0); }
+// An int16 stream writes version 3 whatever its row count: version 2's layout (the row count is always there) with the history as
+// int16 IQ, 4 bytes per sample.  The version IS the input type: restore refuses a version 3 state on a u8 stream and the reverse.
+size_t state_header_bytes(const sdrhip_fm_stream* st)
+{
+    return sizeof(StreamStateHeader) + (st->rows > 1 || st->fmt == IN_I16 ? sizeof(int64_t) : 0);
+}
 }  // namespace
 
 size_t sdrhip_fm_stream_state_bytes(sdrhip_fm_stream* st)
@@ -1308,7 +1411,7 @@ int sdrhip_fm_stream_save(sdrhip_fm_stream* st, void* buf, size_t capacity, size
     StreamStateHeader h;
     memset(&h, 0, sizeof h);
     h.magic = kStateMagic;
-    h.version = st->rows > 1 ? 2 : 1;
+    h.version = st->fmt == IN_I16 ? 3 : st->rows > 1 ? 2 : 1;
     h.N = st->N;
     h.q_done = st->q_done;
     h.head_cap = st->eng.head_cap;
@@ -1323,7 +1426,7 @@ int sdrhip_fm_stream_save(sdrhip_fm_stream* st, void* buf, size_t capacity, size
         return SDRHIP_ERR_ARG;
     }
     memcpy(buf, &h, sizeof h);
-    if (st->rows > 1) {
+    if (state_header_bytes(st) > sizeof h) {
         const int64_t rows = st->rows;
         memcpy((unsigned char*)buf + sizeof h, &rows, sizeof rows);
     }
@@ -1339,13 +1442,15 @@ int sdrhip_fm_stream_restore(sdrhip_fm_stream* st, const void* buf, size_t bytes
                    "sdrhip_fm_stream_restore: only into a stream that has not been pushed to");
     StreamStateHeader h;
     memcpy(&h, buf, sizeof h);
-    SDRHIP_REQUIRE(h.magic == kStateMagic && (h.version == 1 || h.version == 2), "sdrhip_fm_stream_restore: not a stream state");
+    SDRHIP_REQUIRE(h.magic == kStateMagic && h.version >= 1 && h.version <= 3, "sdrhip_fm_stream_restore: not a stream state");
+    SDRHIP_REQUIRE((h.version == 3) == (st->fmt == IN_I16),
+                   "sdrhip_fm_stream_restore: the state belongs to a stream of another input type (u8 / int16 IQ)");
     int64_t rows = 1;
-    if (h.version == 2) {
+    if (h.version >= 2) {
         SDRHIP_REQUIRE(bytes >= sizeof h + sizeof rows, "sdrhip_fm_stream_restore: truncated state");
         memcpy(&rows, (const unsigned char*)buf + sizeof h, sizeof rows);
     }
-    SDRHIP_REQUIRE(rows == st->rows && (h.version == 2) == (st->rows > 1) && h.block_out == st->block_out && h.chain_block == st->c->block &&
+    SDRHIP_REQUIRE(rows == st->rows && (h.version == 3 || (h.version == 2) == (st->rows > 1)) && h.block_out == st->block_out && h.chain_block == st->c->block &&
                        h.head_cap == st->eng.head_cap && h.chain_halo == sdrhip_fm_chain_max_halo(st->c),
                    "sdrhip_fm_stream_restore: the state belongs to a stream of another geometry (stations / chain taps / block sizes)");
     SDRHIP_REQUIRE(h.hist_n >= 0 && h.hist_n <= h.head_cap && h.pending >= 0 && h.pending <= (int64_t)(bytes / sizeof(float)) && h.N >= h.hist_n &&

@@ -396,5 +396,14 @@ void launch_tuner_mix_i16(hipStream_t s, const void* d_in, float* d_out, int64_t
 long long tuner_i16_launch_count();              // diagnostics: launches of k_tuner_bank_c4_i16, bank or one-row
 long long tuner_i16_bank_launch_count();         // ... those of them that were banked launches
 long long tuner_i16_bank_cross_launch_count();   // ... launches of the all-Cross int16 kernel
+// kernels_small.hip: launch_fm_chain_small_bank on 16-bit signed IQ (sdrhip_fm_bank_run_i16): the tuned one-kernel chain with a station
+// axis and an int16 phase 0 (small_i16.hpp).  fm_chain_small_i16_fits: the tuned chain's shape and seam conditions with int16's
+// alignment (d_in 16-byte aligned, s0 a multiple of 4); the grid's condition is fm_chain_small_bank_fits.  A launch counts in
+// fm_chain_small_bank_launch_count AND in the int16 counter.
+bool fm_chain_small_i16_fits(int dD, int dP, ComplexOrder order, int64_t seam, const void* d_in, int64_t s0);
+void launch_fm_chain_small_bank_i16(hipStream_t s, const int16_t* d_in, int64_t s0, int64_t n_in, float* d_audio, int64_t audio_stride,
+                                    int64_t q0, int64_t q1, const float* d_dtaps, bool last_tap_zero, const FmTailTables& t, int tile_outputs,
+                                    const float* d_tables, int stations, const int* offsets, const int* periods);
+long long fm_chain_small_bank_i16_launch_count();
 
 }  // namespace sdrhip

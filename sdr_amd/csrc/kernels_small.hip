@@ -29,6 +29,7 @@
 #include "decimate_tile.hpp"
 #include "demod.hpp"
 #include "kernels.hpp"
+#include "small_i16.hpp"
 #include "tuner_mix.hpp"
 
 #include <type_traits>
@@ -206,8 +207,12 @@ struct BankStations {
     int period[kFmBankMaxStations];
     int ph[kFmBankMaxStations];                // (80 (q0 / 3) - 8) mod period: the host's one 64-bit modulo per station and launch
 };
+// I16: the bank's launch on 16-bit signed IQ (sdrhip_fm_bank_run_i16): `in` holds interleaved int16, 4 bytes per sample, and phase 0
+// is small_load_i16 + tuner_store_i16 (small_i16.hpp, tuner_i16.hpp: convert (float)s * 2^-11 first, then the mix), 4 samples per
+// 16-byte vector, so a thread's first vector starts 4 tid samples into the tile.  Phases 1-4 start from the mixed float2 samples in
+// LDS and are the same code.  Only the bank form exists: one station is a bank of one.
 struct NoBank {};
-template <int PSKIP, bool TUNED, bool BANK = false>
+template <int PSKIP, bool TUNED, bool BANK = false, bool I16 = false>
 __global__ void __launch_bounds__(SM_NT, 2) k_fm_chain_small(const uint8_t* __restrict__ in, float* __restrict__ audio,
                                                              const float* __restrict__ dtaps, const float* __restrict__ groups,
                                                              const float* __restrict__ rplain, const float* __restrict__ fplain,
@@ -215,6 +220,7 @@ __global__ void __launch_bounds__(SM_NT, 2) k_fm_chain_small(const uint8_t* __re
                                                              typename std::conditional<BANK, BankStations, NoBank>::type bank)
 {
     static_assert(TUNED || !BANK, "a bank is tuned chains");
+    static_assert(BANK || !I16, "int16 input enters through the bank only");
     unsigned tile = blockIdx.x;
     if constexpr (BANK) {
         const unsigned j = blockIdx.x;
@@ -246,7 +252,26 @@ __global__ void __launch_bounds__(SM_NT, 2) k_fm_chain_small(const uint8_t* __re
 
     // ---- phase 0: the tile's input, [8 kb, 8 kb + SPAN), into LDS.  Samples outside [s0, s0 + n_in) feed no output this
     // launch owns (sdrhip_fm_chain_run checks the receptive field of [q0, q1)): they read as u8 128 = 0.0f.
-    {
+    if constexpr (I16) {
+        // int16 0 = +0.0f outside the input; rel0 is a multiple of 4 samples here (s0 % 4 == 0): 16-byte aligned vectors
+        StageI16<SmT, SM_NT> st;
+        small_load_i16<SmT, SM_NT>(st, in, kb * 8 - p.s0, p.n_in);
+        // the small tables ride behind the tile's loads, as below
+        float t_g = 0.0f, t_r = 0.0f, t_f = 0.0f;
+        if (tid < 3 * SM_NL) {
+            t_g = groups[(tid / SM_NL) * p.row_stride + (tid % SM_NL)];
+            t_r = tid < p.ntaps ? rplain[tid] : 0.0f;
+        }
+        if (tid < SM_LF) t_f = fplain[tid];
+        else if (tid < SM_LF + 128) t_f = dtaps[tid - SM_LF];
+        const uint32_t n = (uint32_t)period;
+        const uint32_t ts = (uint32_t)(80 * (A / 3)) % n;
+        const uint32_t ph = ((uint32_t)ph_launch + (((uint32_t)tile % n) * ts) % n + (uint32_t)(tid * 4) % n) % n;
+        tuner_store_i16<SmT, SM_NT>(st.r, lds, osc, n, ph);
+        if (tid < 3 * SM_NL) { gtab[tid] = t_g; rpl[tid] = t_r; }
+        if (tid < SM_LF) fpl[tid] = t_f;
+        else if (tid < SM_LF + 128) dtl[tid - SM_LF] = t_f;
+    } else {
         Stage<SmT, true, SM_NT> st;
         const int64_t rel0 = kb * 8 - p.s0;                           // tile start relative to in[0], a multiple of 8 samples
         const bool interior = rel0 >= 0 && rel0 + SmT::SPAN <= p.n_in;
@@ -505,13 +530,14 @@ __global__ void __launch_bounds__(SM_NT, 2) k_fm_chain_small(const uint8_t* __re
 }
 
 
-std::atomic<long long> g_small_launches{0}, g_small_tuned_launches{0}, g_small_bank_launches{0};
+std::atomic<long long> g_small_launches{0}, g_small_tuned_launches{0}, g_small_bank_launches{0}, g_small_bank_i16_launches{0};
 
 }  // namespace
 
 long long fm_chain_small_launch_count() { return g_small_launches.load(); }
 long long fm_chain_small_tuned_launch_count() { return g_small_tuned_launches.load(); }
 long long fm_chain_small_bank_launch_count() { return g_small_bank_launches.load(); }
+long long fm_chain_small_bank_i16_launch_count() { return g_small_bank_i16_launches.load(); }
 
 int fm_chain_small_tile_outputs(int64_t n_out)
 {
@@ -596,10 +622,13 @@ bool fm_chain_small_bank_fits(int64_t q0, int64_t q1, int stations, int tile_out
     return bank_tiles(q0, q1, bank_tile_outputs(q0, q1, stations, tile_outputs)) <= kBankMaxTiles;
 }
 
-void launch_fm_chain_small_bank(hipStream_t s, const uint8_t* d_in, int64_t s0, int64_t n_in, float* d_audio, int64_t audio_stride,
-                                int64_t q0, int64_t q1, const float* d_dtaps, bool last_tap_zero, const FmTailTables& t, int tile_outputs,
-                                const float* d_tables, int stations, const int* offsets, const int* periods)
+namespace {
+// the banked launch on u8 IQ or (i16) on interleaved int16 IQ: the same grid, tiles and phases, another phase 0
+void launch_bank(hipStream_t s, const void* d_in_v, bool i16, int64_t s0, int64_t n_in, float* d_audio, int64_t audio_stride,
+                 int64_t q0, int64_t q1, const float* d_dtaps, bool last_tap_zero, const FmTailTables& t, int tile_outputs,
+                 const float* d_tables, int stations, const int* offsets, const int* periods)
 {
+    const uint8_t* d_in = static_cast<const uint8_t*>(d_in_v);
     const int A = bank_tile_outputs(q0, q1, stations, tile_outputs);
     SmallParams p;
     p.s0 = s0; p.n_in = n_in; p.q0 = q0; p.q1 = q1; p.A = A;
@@ -613,7 +642,7 @@ void launch_fm_chain_small_bank(hipStream_t s, const uint8_t* d_in, int64_t s0, 
         st.period[j] = periods[j];
         st.ph[j] = (int)(((first % periods[j]) + periods[j]) % periods[j]);
     }
-    static std::atomic<bool> attr_set[2][64];
+    static std::atomic<bool> attr_set[4][64];
     int dev = 0;
     (void)hipGetDevice(&dev);
     auto launch = [&](auto kern, int which) {
@@ -624,9 +653,37 @@ void launch_fm_chain_small_bank(hipStream_t s, const uint8_t* d_in, int64_t s0, 
         hipLaunchKernelGGL(kern, dim3((unsigned)stations, (unsigned)tiles), dim3(SM_NT), SmT::LDS_BYTES, s, d_in, d_audio, d_dtaps, t.d_groups, t.d_rplain,
                            t.d_fplain, p, reinterpret_cast<const float2*>(d_tables), 0, 0, st);
     };
-    if (last_tap_zero) launch(k_fm_chain_small<1, true, true>, 1);
+    if (i16) {
+        static_assert(StageI16<SmT, SM_NT>::NV * StageI16<SmT, SM_NT>::SPV == SmT::SPAN, "the int16 loader reads exactly the tile");
+        if (last_tap_zero) launch(k_fm_chain_small<1, true, true, true>, 3);
+        else launch(k_fm_chain_small<0, true, true, true>, 2);
+        g_small_bank_i16_launches++;
+    } else if (last_tap_zero) launch(k_fm_chain_small<1, true, true>, 1);
     else launch(k_fm_chain_small<0, true, true>, 0);
     g_small_bank_launches++;
+}
+}  // namespace
+
+void launch_fm_chain_small_bank(hipStream_t s, const uint8_t* d_in, int64_t s0, int64_t n_in, float* d_audio, int64_t audio_stride,
+                                int64_t q0, int64_t q1, const float* d_dtaps, bool last_tap_zero, const FmTailTables& t, int tile_outputs,
+                                const float* d_tables, int stations, const int* offsets, const int* periods)
+{
+    launch_bank(s, d_in, false, s0, n_in, d_audio, audio_stride, q0, q1, d_dtaps, last_tap_zero, t, tile_outputs, d_tables, stations, offsets, periods);
+}
+
+bool fm_chain_small_i16_fits(int dD, int dP, ComplexOrder order, int64_t seam, const void* d_in, int64_t s0)
+{
+    // fm_chain_small_fits for the tuned chain (plain taps: nothing pre-scaled is needed) with int16's alignment: a sample is 4 bytes,
+    // tiles start at multiples of 8 samples of the stream, so 16-byte vectors need a 16-byte aligned d_in and s0 a multiple of 4
+    if (!fm_chain_small_fits(dD, dP, order, true, seam, nullptr, 0)) return false;
+    return (reinterpret_cast<uintptr_t>(d_in) & 15) == 0 && (s0 & 3) == 0;
+}
+
+void launch_fm_chain_small_bank_i16(hipStream_t s, const int16_t* d_in, int64_t s0, int64_t n_in, float* d_audio, int64_t audio_stride,
+                                    int64_t q0, int64_t q1, const float* d_dtaps, bool last_tap_zero, const FmTailTables& t, int tile_outputs,
+                                    const float* d_tables, int stations, const int* offsets, const int* periods)
+{
+    launch_bank(s, d_in, true, s0, n_in, d_audio, audio_stride, q0, q1, d_dtaps, last_tap_zero, t, tile_outputs, d_tables, stations, offsets, periods);
 }
 
 }  // namespace sdrhip

@@ -184,6 +184,9 @@ lib.sdrhip_fm_bank_run.argtypes = [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _
 lib.sdrhip_fm_bank_set_route.argtypes = [_vp, C.c_int, _i64, C.c_int]
 lib.sdrhip_debug_fm_bank_launches.argtypes = []
 lib.sdrhip_debug_fm_bank_launches.restype = C.c_longlong
+lib.sdrhip_fm_bank_run_i16.argtypes = [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, C.c_size_t]
+lib.sdrhip_debug_fm_bank_i16_launches.argtypes = []
+lib.sdrhip_debug_fm_bank_i16_launches.restype = C.c_longlong
 lib.sdrhip_debug_resample_cycle_launches.restype = C.c_longlong
 lib.sdrhip_debug_decimate_real16_launches.restype = C.c_longlong
 lib.sdrhip_debug_systolic_launches.restype = C.c_longlong
@@ -304,6 +307,10 @@ lib.sdrhip_fm_stream_input_buffer.argtypes = [_vp]
 lib.sdrhip_fm_stream_input_buffer.restype = _vp
 lib.sdrhip_fm_stream_pop.argtypes = [_vp, _f32p, C.c_int]
 lib.sdrhip_fm_stream_create_bank.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int]
+lib.sdrhip_fm_stream_create_bank_i16.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int]
+lib.sdrhip_fm_stream_push_i16.argtypes = [_vp, _vp, C.c_int]
+lib.sdrhip_fm_stream_input_buffer_i16.argtypes = [_vp]
+lib.sdrhip_fm_stream_input_buffer_i16.restype = _vp
 lib.sdrhip_fm_stream_rows.argtypes = [_vp]
 lib.sdrhip_fm_stream_pop_rows.argtypes = [_vp, _f32p, C.c_int64, C.c_int]
 
@@ -1008,6 +1015,11 @@ def fm_bank_launches():
     return int(lib.sdrhip_debug_fm_bank_launches())
 
 
+def fm_bank_i16_launches():
+    """Banked launches on int16 input so far (sdrhip_debug_fm_bank_i16_launches); each counts in fm_bank_launches() too."""
+    return int(lib.sdrhip_debug_fm_bank_i16_launches())
+
+
 class FmBank(_Handle):
     """Every station of one capture: K tuned FmChains of the same arguments over ONE input, one launch per run where the banked route
     fits (sdr_hip.h, sdrhip_fm_bank_*).  tables: one interleaved float32 (re, im) table per station (tuner_shift_table builds the
@@ -1058,6 +1070,11 @@ class FmBank(_Handle):
     def run(self, d_in_u8, s0, n_in, d_audio, audio_stride, q0, q1, d_ws=None, ws_bytes=0, stream=None):
         """Station j's outputs [q0, q1) -> d_audio + 4 * j * audio_stride bytes."""
         check(lib.sdrhip_fm_bank_run(self.h, stream, d_in_u8, s0, n_in, d_audio, audio_stride, q0, q1, d_ws, ws_bytes), "sdrhip_fm_bank_run")
+
+    def run_i16(self, d_in_i16, s0, n_in, d_audio, audio_stride, q0, q1, d_ws=None, ws_bytes=0, stream=None):
+        """run on 16-bit signed IQ (interleaved int16, 4 bytes per sample; sdrhip_fm_bank_run_i16): row j is, bit for bit,
+        Tuner.run_i16 -> fm_demod -> Resampler.run -> Filter.run -> scale driven by hand with table j."""
+        check(lib.sdrhip_fm_bank_run_i16(self.h, stream, d_in_i16, s0, n_in, d_audio, audio_stride, q0, q1, d_ws, ws_bytes), "sdrhip_fm_bank_run_i16")
 
 
 class Fft(_Handle):
@@ -1253,15 +1270,22 @@ class FmStream(_Handle):
     """u8 IQ host blocks in, audio host blocks out: the FM receiver of fm.hs:34-41 as one operator.  Over an FmBank
     (sdrhip_fm_stream_create_bank) every station's audio comes out in lockstep: push, flush, poll and restore then return a list of
     arrays of shape [stations, block_size_out] -- row j is, bit for bit, the block an FmStream over FmChain(...).set_tuner(tables[j])
-    yields -- where a chain's stream returns a list of [block_size_out] arrays."""
+    yields -- where a chain's stream returns a list of [block_size_out] arrays.  input_i16=True (a bank only,
+    sdrhip_fm_stream_create_bank_i16): the stream takes interleaved int16 IQ through push_i16 / input_buffer_i16."""
     _destroy = lib.sdrhip_fm_stream_destroy
 
-    def __init__(self, chain, max_block_samples, block_size_out=8192):
+    def __init__(self, chain, max_block_samples, block_size_out=8192, input_i16=False):
         super().__init__()
         self.chain = chain  # the chain or the bank: keep alive
         self.block_size_out = block_size_out
         self.is_bank = isinstance(chain, FmBank)
-        if self.is_bank:
+        self.input_i16 = bool(input_i16)
+        if self.input_i16:
+            if not self.is_bank:
+                raise SdrHipError("FmStream(input_i16=True): int16 IQ reaches the FM side through an FmBank")
+            check(lib.sdrhip_fm_stream_create_bank_i16(C.byref(self.h), chain.h, max_block_samples, block_size_out),
+                  "sdrhip_fm_stream_create_bank_i16")
+        elif self.is_bank:
             check(lib.sdrhip_fm_stream_create_bank(C.byref(self.h), chain.h, max_block_samples, block_size_out), "sdrhip_fm_stream_create_bank")
         else:
             check(lib.sdrhip_fm_stream_create(C.byref(self.h), chain.h, max_block_samples, block_size_out), "sdrhip_fm_stream_create")
@@ -1309,6 +1333,18 @@ class FmStream(_Handle):
 
     def push_inplace(self, view):
         return self._pop(check(lib.sdrhip_fm_stream_push(self.h, view.ctypes.data_as(_u8p), view.size // 2), "sdrhip_fm_stream_push"))
+
+    def push_i16(self, i16_iq):
+        """interleaved int16 IQ (a view input_buffer_i16 gave is pushed in place)"""
+        b = np.ascontiguousarray(i16_iq, dtype=np.int16)
+        return self._pop(check(lib.sdrhip_fm_stream_push_i16(self.h, b.ctypes.data_as(_vp), b.size // 2), "sdrhip_fm_stream_push_i16"))
+
+    def input_buffer_i16(self, n_samples):
+        """numpy int16 view of the pinned staging buffer of the next push (fill it, then push_i16 the view)."""
+        p = lib.sdrhip_fm_stream_input_buffer_i16(self.h)
+        if not p:
+            raise SdrHipError(lib.sdrhip_last_error().decode())
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int16)), shape=(2 * n_samples,))
 
     def flush(self):
         return self._pop(check(lib.sdrhip_fm_stream_flush(self.h), "sdrhip_fm_stream_flush"))

@@ -17,7 +17,18 @@ No number is fixed in advance: the yardstick is the K-chain loop.  The last line
 because the sweep is a rectangle (stations x outputs per station): the largest total, stations * outputs, below which EVERY
 measured point has the banked launch ahead of the loop by more than the spread, and the longest run per station the sweep holds --
 sdrhip_fm_bank_run takes the banked launch on its own inside both, and nothing outside the rectangle is measured.  A missing GPU
-is an error."""
+is an error.
+
+    python tools/fm_bank_bench.py --i16 [--rounds R] [--out profiles/fm_bank_i16_bench.txt]
+
+The same sweep on 16-bit signed IQ (sdrhip_fm_bank_run_i16), three legs alternating in one process:
+  banked   one FmBank.run_i16 on the banked route (route 1): ONE launch for all K stations
+  route 2  the same bank station by station (route 2): per station the tuner's int16 first stage, then the stage kernels
+  rows     what a caller could do without the int16 bank: TunerBank.run_i16 -> fm_demod_rows -> Resampler.run_rows ->
+           Filter.run_rows -> sdrhip_scale_run, every stage one launch set for all K rows
+Leg A (banked against route 2) decides the bank's auto rule for int16 input by the project's criterion: at a point with K >= 2 the
+banked launch's slowest round is below route 2's fastest.  K = 1 and leg B (banked against rows) are reported; no rule depends
+on them."""
 import argparse
 import os
 import statistics
@@ -83,6 +94,112 @@ def legs(K, n_samples):
     return {"banked": banked, "chains": loop}, n, (bank, chains, d_in, out, ws)
 
 
+def legs_i16(K, n_samples):
+    """-> ({name: function(reps)}, outputs per station, what must stay alive)"""
+    args = (8, S.taps_decim127(), 3, 10, S.taps_resamp191(), S.taps_audio_half64())
+    tabs = tables(K)
+    banks = {}
+    for name, route in (("banked", L.FmBank.ROUTE_BANKED), ("route 2", L.FmBank.ROUTE_STATIONS)):
+        banks[name] = L.FmBank(*args, tabs, 0.2, B)
+        banks[name].set_route(route)
+    bank = banks["banked"]
+    n_in = n_samples + L.FmChain(*args, 0.2, B).halo_samples()
+    q0, q1, _ = bank.plan(0, n_samples, -1)
+    n = q1 - q0
+    d_in = torch.randint(-32768, 32768, (2 * n_in,), dtype=torch.int16, device="cuda")
+    out = torch.empty(K * n, dtype=torch.float32, device="cuda")
+    wsb = bank.workspace_bytes(n_in)
+    ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
+    pi, po, pw = d_in.data_ptr(), out.data_ptr(), ws.data_ptr()
+    # the row forms over the chain's ranges (chain.cpp's plan_run)
+    tb = L.TunerBank(8, S.taps_decim127(), tabs)
+    res = L.Resampler(3, 10, S.taps_resamp191())
+    filt = L.Filter(S.taps_audio_half64(), sym=True)
+    m1 = q1 + filt.num_coeffs - 1
+    ky0, ky1 = res.in_offset(q0), res.in_offset(m1 - 1) + 64
+    kd0, kd1 = max(ky0 - 1, 0), ky1
+    d = torch.empty((K, 2 * (kd1 - kd0)), dtype=torch.float32, device="cuda")
+    y = torch.empty((K, ky1 - ky0), dtype=torch.float32, device="cuda")
+    z = torch.empty((K, m1 - q0), dtype=torch.float32, device="cuda")
+    au = torch.empty((K, n), dtype=torch.float32, device="cuda")
+    out_rows = torch.empty(K * n, dtype=torch.float32, device="cuda")
+
+    def run_bank(which):
+        def fn(reps):
+            for _ in range(reps):
+                banks[which].run_i16(pi, 0, n_in, po, n, q0, q1, pw, wsb)
+            torch.cuda.synchronize()
+        return fn
+
+    def rows(reps):
+        cs = torch.cuda.current_stream().cuda_stream
+        for _ in range(reps):
+            tb.run_i16(pi, 0, d.data_ptr(), d.shape[1], kd0, kd1, B, stream=cs)
+            L.fm_demod_rows(d, out=y, in_base=kd0, k_begin=ky0, k_end=ky1)
+            res.run_rows(y, z, q0, m1, in_base=ky0, seam_block=B, out_block=B)
+            filt.run_rows(z, au, q0, q1, in_base=q0, seam_block=B)
+            L.check(L.lib.sdrhip_scale_run(cs, 0.2, au.data_ptr(), out_rows.data_ptr(), K * n), "sdrhip_scale_run")
+        torch.cuda.synchronize()
+
+    fns = {"banked": run_bank("banked"), "route 2": run_bank("route 2"), "rows": rows}
+    # the three legs compute the same audio (tests/test_gpu_fm_bank_i16.py holds the bank's routes to the hand-driven composition)
+    rows(1)
+    fns["route 2"](1)
+    ref = out.clone()
+    if not torch.equal(out_rows.view(torch.int32), ref.view(torch.int32)):
+        sys.exit(f"fm_bank_bench: route 2 and the row forms differ at K = {K}, {n_samples} samples")
+    out.zero_()
+    fns["banked"](1)
+    if not torch.equal(out.view(torch.int32), ref.view(torch.int32)):
+        sys.exit(f"fm_bank_bench: banked launch and route 2 differ at K = {K}, {n_samples} samples")
+    return fns, n, (banks, tb, res, filt, d_in, out, ws, d, y, z, au, out_rows)
+
+
+def main_i16(a):
+    lines = [f"# {L.device_name()}; int16 IQ; {a.rounds} rounds, the three legs alternating; us per run of ALL K stations: median (min .. max)",
+             "# leg A: banked (route 1) against route 2 of the same bank; leg B: banked against the row forms a caller could drive by hand"]
+    print("\n".join(lines), flush=True)
+    fails = []
+    for size_name, n_samples in SIZES:
+        for K in STATIONS:
+            fns, n, keep = legs_i16(K, n_samples)
+            reps = {}
+            for name, fn in fns.items():
+                fn(20)
+                per = timed(fn, 50) * 1e-6
+                reps[name] = max(50, min(20000, int(WINDOW_S / per)))
+            b0, i0 = L.fm_bank_launches(), L.fm_bank_i16_launches()
+            times = {k: [] for k in fns}
+            for _ in range(a.rounds):
+                for name, fn in fns.items():
+                    times[name].append(timed(fn, reps[name]))
+            nb, ni = L.fm_bank_launches() - b0, L.fm_bank_i16_launches() - i0
+            assert nb == ni == a.rounds * reps["banked"], "a leg took another route than the one it is named for"
+            med = {k: statistics.median(v) for k, v in times.items()}
+            fmt = lambda v: f"{statistics.median(v):9.1f} ({min(v):.1f} .. {max(v):.1f})"
+            clear = max(times["banked"]) < min(times["route 2"])
+            line = (f"{size_name:13s} K {K:2d}  outputs {n:6d} x {K:2d} = {K * n:8d}   banked {fmt(times['banked'])}   route 2 {fmt(times['route 2'])}   "
+                    f"rows {fmt(times['rows'])}   A: banked / route 2 {med['banked'] / med['route 2']:.3f}{'' if clear else ' (not clear of the spread)'}   "
+                    f"B: banked / rows {med['banked'] / med['rows']:.3f}")
+            print(line, flush=True)
+            lines.append(line)
+            if K >= 2 and not clear:
+                fails.append((size_name, K))
+            del fns, keep
+            torch.cuda.empty_cache()
+    if fails:
+        lines.append(f"# leg A: the criterion (K >= 2: the banked launch's slowest round below route 2's fastest) FAILS at {fails}: auto "
+                     "must shrink to the part of the rectangle where it holds")
+    else:
+        lines.append("# leg A: the criterion (K >= 2: the banked launch's slowest round below route 2's fastest) holds on the WHOLE rectangle: "
+                     "auto for int16 input is the u8 rule (outputs per station <= 39322, stations * outputs <= 32 * 39322)")
+    print(lines[-1], flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def timed(fn, reps):
     t0 = time.perf_counter()
     fn(reps)
@@ -113,10 +230,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--i16", action="store_true", help="the sweep on 16-bit signed IQ: banked against route 2 and against the row forms")
     a = ap.parse_args()
     if L.device_count() < 1:
         sys.exit("fm_bank_bench: no HIP device")
     torch.cuda.set_device(0)
+    if a.i16:
+        return main_i16(a)
     call_us = host_call_us()
     lines = [f"# {L.device_name()}; {a.rounds} rounds, banked launch and K-chain loop alternating; us per push of ALL K stations: median (min .. max)",
              f"# host time of one call that launches nothing (q1 = q0, the run's own arguments): FmChain.run {call_us['chain']:.2f} us, "

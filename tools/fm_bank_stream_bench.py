@@ -19,7 +19,13 @@ spread (max - min).  Points that miss the rule are marked and listed at the end;
 Second table, the lone source block at K = 2, 4, 8, 12: the same bank stream with the lone block read IN PLACE over the link by
 the banked launch (largest tile) against the slot-stream COPY (one pass over the link, then the launch on device memory),
 selected for this comparison by SDRHIP_STAGE_SAMPLES at stream creation.  It decides whether streams of several stations keep an
-in-place route.  A missing GPU is an error."""
+in-place route.  A missing GPU is an error.
+
+    python tools/fm_bank_stream_bench.py --i16 [--rounds R] [--out profiles/fm_bank_stream_i16_bench.txt]
+
+One int16 bank stream (FmStream(bank, ..., input_i16=True), push_i16) against a u8 bank stream of the same pushes, the two
+alternating: K = 2, 8, 32 stations x pushes of 1, 16 and 128 source blocks, memcpy pushes.  An int16 push carries twice the bytes
+and never runs in place.  Reported; no rule depends on it."""
 import argparse
 import os
 import statistics
@@ -84,6 +90,43 @@ def leg(streams, chunk, how):
     return run
 
 
+def leg_i16(st, chunk):
+    def run(reps):
+        got = []
+        for _ in range(reps):
+            got += st.push_i16(chunk)
+        got += st.flush()
+        return [got]
+    return run
+
+
+def main_i16(a):
+    rng = np.random.default_rng(1601)
+    i16 = rng.integers(-32768, 32768, 2 * 128 * B, dtype=np.int64).astype(np.int16)
+    u8 = S.iq_u8_fm(128 * B)
+    lines = [f"# {L.device_name()}; {a.rounds} rounds, an int16 bank stream and a u8 bank stream of the same pushes alternating; memcpy pushes; "
+             "host clock around push ... flush, us PER PUSH (all K stations): median (min .. max)"]
+    print(lines[0], flush=True)
+    for nblk in PUSH_BLOCKS:
+        c16, c8 = np.ascontiguousarray(i16[:2 * nblk * B]), np.ascontiguousarray(u8[:2 * nblk * B])
+        for K in (2, 8, 32):
+            s16 = L.FmStream(L.FmBank(*ARGS, tables(K), 0.2, B), nblk * B, B, input_i16=True)
+            s8 = bank_stream(K, nblk)
+            b0, i0 = L.fm_bank_launches(), L.fm_bank_i16_launches()
+            t = measure({"int16": leg_i16(s16, c16), "u8": leg([s8], c8, "memcpy")}, a.rounds)
+            nb, ni = L.fm_bank_launches() - b0, L.fm_bank_i16_launches() - i0
+            assert ni > 0 and nb > ni, "a leg took another route than the one it is named for"
+            line = (f"{nblk:3d} blocks per push  K {K:2d}   int16 {fmt(t['int16'])}   u8 {fmt(t['u8'])}   "
+                    f"int16 / u8 {statistics.median(t['int16']) / statistics.median(t['u8']):.3f}")
+            print(line, flush=True)
+            lines.append(line)
+            del s16, s8
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def timed(fn, reps):
     t0 = time.perf_counter()
     fn(reps)
@@ -123,9 +166,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--i16", action="store_true", help="an int16 bank stream against a u8 bank stream of the same pushes")
     a = ap.parse_args()
     if L.device_count() < 1:
         sys.exit("fm_bank_stream_bench: no HIP device")
+    if a.i16:
+        return main_i16(a)
     u8 = S.iq_u8_fm(128 * B)
     lines = [f"# {L.device_name()}; {a.rounds} rounds, the bank's stream and K chain streams alternating; host clock around push ... flush, "
              "us PER PUSH (all K stations): median (min .. max)"]
