@@ -382,6 +382,23 @@ int sdrhip_scale_run(void *stream, float factor, const float *d_in, float *d_out
  * (the Pipe's carried state; (0,0) at stream start, Demod.hs:41). */
 int sdrhip_fm_demod_run(void *stream, const float *d_in_iq, int64_t in_base, float *d_out,
                         int64_t k_begin, int64_t k_end, float last_re, float last_im);
+/* amDemod: the AM receiver's envelope detector, `P.map (VG.map magnitude)`.  n interleaved complex float32 samples ->
+ * n float32, d_out[i] = magnitude(d_in_iq[2i], d_in_iq[2i+1]) with GHC base's Data.Complex.magnitude at Float, the
+ * function sdrhip_agc_run steps with.  Every step f32, no FMA:
+ *     k = max(exponent re, exponent im)                      -- exponent 0 = 0, else frexp's (denormals normalised)
+ *     m = ldexpf(sqrtf(a*a + b*b), k),  a = ldexpf(re, -k), b = ldexpf(im, -k)          -- correctly rounded sqrt
+ * which is neither sqrtf(re*re + im*im) nor hypotf.  The definition's consequences are the reference's and are kept:
+ * magnitude(1e-30, 0) = +0 (k = 0, the square underflows), magnitude(1e-30, 1e-30) = 0x0de57822, magnitude(FLT_MAX, 1)
+ * = FLT_MAX.  Non-finite input is in contract: a NaN part gives NaN (payload unspecified), otherwise an infinite part
+ * gives +Inf.  The parity with `base` is argued, not executed, as for agc.
+ * Asynchronous on `stream`; exactly one kernel launch for any n > 0; n == 0 is SDRHIP_OK with no launch.  Any
+ * 4-byte-aligned pointers: 16-byte loads and stores where d_in_iq, respectively d_out, is 16-byte aligned, else 8- or
+ * 4-byte ones, the two sides chosen independently.  No float outside [0, 2n) of d_in_iq is read, none outside [0, n) of
+ * d_out written.  Not in-place.  SDRHIP_ERR_ARG, before any device work and with nothing written: a null pointer, n < 0,
+ * d_in_iq == d_out. */
+int sdrhip_am_demod_run(void *stream, const float *d_in_iq, float *d_out, int64_t n);
+/* Diagnostics: kernel launches of sdrhip_am_demod_run and sdrhip_am_demod_run_rows, process-wide. */
+long long sdrhip_debug_am_demod_launches(void);
 /* Diagnostics: how many stream-API launches the general LDS-tiled kernels (kernels_split.hip) have served in
  * this process -- the tests use it to prove the tiled path, not the one-thread-per-output fallback, ran. */
 long long sdrhip_debug_tiled_launches(void);
@@ -474,6 +491,18 @@ int sdrhip_fm_demod_run_rows(void *stream, const float *d_in_iq, int64_t in_stri
 /* Diagnostics: kernel launches of the row forms, process-wide: 1 per call on the sequential walk and for fmDemod, 5 per
  * call (speculate, three repair rounds, settle) with chunks. */
 long long sdrhip_debug_rows_launches(void);
+
+/* amDemod over rows: row r's n samples at d_in_iq + r * in_stride -> n floats at d_out + r * out_stride, bit for bit the
+ * one-row call (sdrhip_am_demod_run) on that row, whatever the other rows hold; it is the same kernel with the row on
+ * the grid's second axis.  Exactly one launch for any rows and n > 0 (the workgroups loop over a row's samples, so no
+ * grid limit cuts a call); none for n == 0.  The access width is one for all rows: 16 / 8 / 4-byte loads as d_in_iq and
+ * in_stride * 4 allow, 16 / 8 / 4-byte stores as d_out and out_stride * 4 allow.  Floats of d_out outside the rows'
+ * [0, n), and of d_in_iq outside their [0, 2n), are not touched.  Launches count in sdrhip_debug_am_demod_launches, not
+ * in sdrhip_debug_rows_launches.
+ * SDRHIP_ERR_ARG, before any device work and with nothing written: rows outside 1 .. SDRHIP_ROWS_MAX, a null pointer,
+ * n < 0, d_in_iq == d_out, and with rows > 1 in_stride < 2n, an odd in_stride, out_stride < n. */
+int sdrhip_am_demod_run_rows(void *stream, const float *d_in_iq, int64_t in_stride, float *d_out, int64_t out_stride,
+                             int rows, int64_t n);
 
 /* The FIR operators over rows: the filter, decimator and resampler stages behind a bank (second decimator per channel, resampler
  * and audio filter per station) in one launch set instead of one call per row.  in_base, k_begin, k_end, seam_block and out_block
@@ -1001,6 +1030,13 @@ int sdrhip_pipe_fir_filter(sdrhip_pipe **p, const sdrhip_filter *f, int block_si
 int sdrhip_pipe_fir_decimator(sdrhip_pipe **p, const sdrhip_decimator *d, int block_size_out);    /* firDecimator */
 int sdrhip_pipe_fir_resampler(sdrhip_pipe **p, const sdrhip_resampler *r, int block_size_out);    /* firResampler */
 int sdrhip_pipe_fm_demod(sdrhip_pipe **p);                                                         /* fmDemod      */
+/* amDemod (sdrhip_am_demod_run) on host blocks: complex blocks in, float blocks of the same length out, like
+ * sdrhip_pipe_fm_demod, and with its submission rule: staged blocks go out as one run, read and written in place over PCIe up
+ * to 512 KiB of input, through the copy engines beyond.  Nothing is carried from block to block, so save / restore carry
+ * only the output not yet popped; restore refuses (SDRHIP_ERR_ARG, the pipe unchanged) a state of another kind -- an fmDemod
+ * pipe's included -- and a truncated one.  set_adaptive, flush, poll and pop as for the other map pipes; set_coalesce,
+ * input_buffer and pop_rows are the filter-like pipes' and refuse a map pipe. */
+int sdrhip_pipe_am_demod(sdrhip_pipe **p);                                       /* P.map (VG.map magnitude) */
 int sdrhip_pipe_dc_blocker(sdrhip_pipe **p);                                     /* dcBlockingFilter, Filter.hs:730-739 */
 /* complex blocks in, complex blocks out at the length they came in; the state starts at 1 and is carried across blocks on the
  * device (sdrhip_agc_run).  save / restore carry the state; mu and reference are the constructor's, not part of it. */

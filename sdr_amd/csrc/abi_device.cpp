@@ -7,6 +7,7 @@
 #include <atomic>
 #include <mutex>
 
+#include "am.hpp"
 #include "descriptors.hpp"
 
 namespace sdrhip {
@@ -777,5 +778,33 @@ int sdrhip_fm_demod_run_rows(void* stream, const float* d_in_iq, int64_t in_stri
 }
 
 long long sdrhip_debug_rows_launches(void) { return rows_launch_count(); }
+
+// amDemod: one kernel, the one-row call is rows == 1 of the rows call (am.hpp)
+int sdrhip_am_demod_run_rows(void* stream, const float* d_in_iq, int64_t in_stride, float* d_out, int64_t out_stride, int rows,
+                             int64_t n)
+{
+    SDRHIP_REQUIRE(rows >= 1 && rows <= SDRHIP_ROWS_MAX, "sdrhip_am_demod_run_rows: rows outside 1 .. SDRHIP_ROWS_MAX");
+    SDRHIP_REQUIRE(n >= 0, "sdrhip_am_demod_run_rows");
+    SDRHIP_REQUIRE(d_in_iq != nullptr && d_out != nullptr && d_in_iq != d_out, "sdrhip_am_demod_run_rows: in-place is not supported");
+    SDRHIP_REQUIRE(rows == 1 || (in_stride & 1) == 0, "sdrhip_am_demod_run_rows: odd stride on interleaved complex samples");
+    SDRHIP_REQUIRE(rows == 1 || (n <= INT64_MAX / 2 && in_stride >= 2 * n && out_stride >= n),
+                   "sdrhip_am_demod_run_rows: stride shorter than a row");
+    if (n == 0) return SDRHIP_OK;
+    launch_am_demod_rows((hipStream_t)stream, rows, d_in_iq, in_stride, d_out, out_stride, n);
+    SDRHIP_CHECK_HIP(hipGetLastError());
+    return SDRHIP_OK;
+}
+
+int sdrhip_am_demod_run(void* stream, const float* d_in_iq, float* d_out, int64_t n)
+{
+    SDRHIP_REQUIRE(n >= 0, "sdrhip_am_demod_run");
+    SDRHIP_REQUIRE(d_in_iq != nullptr && d_out != nullptr && d_in_iq != d_out, "sdrhip_am_demod_run: in-place is not supported");
+    if (n == 0) return SDRHIP_OK;
+    launch_am_demod_rows((hipStream_t)stream, 1, d_in_iq, 0, d_out, 0, n);
+    SDRHIP_CHECK_HIP(hipGetLastError());
+    return SDRHIP_OK;
+}
+
+long long sdrhip_debug_am_demod_launches(void) { return am_demod_launch_count(); }
 
 }  // extern "C"

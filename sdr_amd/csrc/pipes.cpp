@@ -2,6 +2,7 @@
 //
 //   firFilter    Filter.hs:532-569      firDecimator  Filter.hs:574-611
 //   firResampler Filter.hs:679-727      fmDemod       Demod.hs:40-46
+//   amDemod      P.map (VG.map magnitude), the Readme's AM receiver
 //
 // The reference's state machines alternate `simple` (outputs whose window fits in
 // the current input buffer: the C SIMD kernel) and `crossover` (outputs straddling
@@ -29,12 +30,13 @@
 
 #include <deque>
 
+#include "am.hpp"
 #include "descriptors.hpp"
 #include "host_stream.hpp"
 
 using namespace sdrhip;
 
-enum PipeKind { PK_FILTER, PK_DECIMATOR, PK_RESAMPLER, PK_DEMOD, PK_DCBLOCK, PK_AGC, PK_TUNER, PK_TUNER_BANK };
+enum PipeKind { PK_FILTER, PK_DECIMATOR, PK_RESAMPLER, PK_DEMOD, PK_DCBLOCK, PK_AGC, PK_TUNER, PK_TUNER_BANK, PK_AM };   // saved states hold the number: new kinds go at the end
 
 struct sdrhip_pipe {
     PipeKind kind;
@@ -85,10 +87,10 @@ struct sdrhip_pipe {
     bool all_uniform = true;
     int lent = 0;              // elements behind the staged ones the caller may have filled through sdrhip_pipe_input_buffer
 
-    std::deque<int> demod_blocks;      // fmDemod / dcBlockingFilter: output block lengths (one per input block)
+    std::deque<int> demod_blocks;      // fmDemod / amDemod / dcBlockingFilter: output block lengths (one per input block)
     DevBuf dc_state, dc_ws;            // dcBlockingFilter: {lastSample, lastOutput} carried on the device; agcPipe: {state}
     float agc_mu = 0.0f, agc_ref = 0.0f;
-    bool is_map() const { return kind == PK_DEMOD || kind == PK_DCBLOCK || kind == PK_AGC; }
+    bool is_map() const { return kind == PK_DEMOD || kind == PK_DCBLOCK || kind == PK_AGC || kind == PK_AM; }
     bool has_dev_state() const { return (kind == PK_DCBLOCK || kind == PK_AGC) && dc_state.p; }
 
     int esz_in() const { return cplx_in ? 2 : 1; }
@@ -377,6 +379,12 @@ int sdrhip_pipe_fm_demod(sdrhip_pipe** pp)
     return pipe_new(pp, PK_DEMOD, nullptr, nullptr, 0, true, false, 1, 1, 1);
 }
 
+int sdrhip_pipe_am_demod(sdrhip_pipe** pp)
+{
+    SDRHIP_REQUIRE(pp != nullptr, "sdrhip_pipe_am_demod");
+    return pipe_new(pp, PK_AM, nullptr, nullptr, 0, true, false, 1, 1, 1);
+}
+
 int sdrhip_pipe_dc_blocker(sdrhip_pipe** pp)
 {
     SDRHIP_REQUIRE(pp != nullptr, "sdrhip_pipe_dc_blocker");
@@ -404,10 +412,10 @@ int sdrhip_pipe_agc(sdrhip_pipe** pp, float mu, float reference)
     return SDRHIP_OK;
 }
 
-// ---- map stages (fmDemod, dcBlockingFilter, agcPipe): one output vector per input vector ------------------------------
+// ---- map stages (fmDemod, amDemod, dcBlockingFilter, agcPipe): one output vector per input vector ------------------------------
 // Blocks are staged one behind the other in the slot's pinned buffer and go out as ONE run over all of them -- the carry of a
 // block is its predecessor's last sample (fmDemod, Demod.hs:41,46) / the filter's running pair kept on the device
-// (dcBlockingFilter, Filter.hs:730-739), which is exactly what a run over the concatenation computes; the block lengths are
+// (dcBlockingFilter, Filter.hs:730-739), which is exactly what a run over the concatenation computes (amDemod carries nothing); the block lengths are
 // remembered for the pops.  Submission is adaptive as for the FIR-like stages.  Runs of up to kDirectBytes read and write
 // pinned memory in place; larger ones go through the copy engines.  Both launch on the first compute stream.
 static int map_submit(sdrhip_pipe* p)
@@ -418,7 +426,7 @@ static int map_submit(sdrhip_pipe* p)
     const size_t ein = (size_t)p->esz_in() * 4;
     // (dcBlockingFilter and agcPipe never in place: their lanes re-read their run-in and a short block is one lane's dependent
     // loads)
-    const bool direct = p->direct_ok && p->kind == PK_DEMOD && (size_t)n * ein <= sdrhip_pipe::kDirectBytes;
+    const bool direct = p->direct_ok && (p->kind == PK_DEMOD || p->kind == PK_AM) && (size_t)n * ein <= sdrhip_pipe::kDirectBytes;
     const float* h = (const float*)e.staged_base();
     return e.submit(direct ? HostStream::kInPlace : HostStream::kCopyEngines, e.compute[0], h, (size_t)n * ein,
                     (int64_t)n * p->esz_out(), [&](hipStream_t s, const void* d_in, void* d_out) {
@@ -426,6 +434,8 @@ static int map_submit(sdrhip_pipe* p)
             launch_fm_demod_fast(s, (const float*)d_in, (float*)d_out, n, false, p->last_re, p->last_im);
             p->last_re = h[2 * (size_t)(n - 1)];
             p->last_im = h[2 * (size_t)(n - 1) + 1];
+        } else if (p->kind == PK_AM) {
+            launch_am_demod_rows(s, 1, (const float*)d_in, 0, (float*)d_out, 0, n);
         } else if (p->kind == PK_AGC) {
             if (agc_workspace_bytes(n) > p->dc_ws.cap) SDRHIP_CHECK_HIP(hipStreamSynchronize(s));            // growing frees the old buffer
             int rc = p->dc_ws.ensure(agc_workspace_bytes(n));

@@ -284,6 +284,10 @@ lib.sdrhip_dc_blocker_rows_workspace_bytes.restype = C.c_size_t
 lib.sdrhip_dc_blocker_run_rows.argtypes = [_vp, _vp, _i64, _vp, _i64, C.c_int, _i64, _vp, _vp, _vp, C.c_size_t, C.c_int]
 lib.sdrhip_debug_dc_rows_plan.argtypes = [C.c_int, C.c_int64, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]
 lib.sdrhip_fm_demod_run_rows.argtypes = [_vp, _vp, _i64, _i64, _vp, _i64, C.c_int, _i64, _i64, _vp, _vp]
+lib.sdrhip_am_demod_run.argtypes = [_vp, _vp, _vp, _i64]
+lib.sdrhip_am_demod_run_rows.argtypes = [_vp, _vp, _i64, _vp, _i64, C.c_int, _i64]
+lib.sdrhip_debug_am_demod_launches.argtypes = []
+lib.sdrhip_debug_am_demod_launches.restype = C.c_longlong
 lib.sdrhip_debug_rows_launches.argtypes = []
 lib.sdrhip_debug_rows_launches.restype = C.c_longlong
 lib.sdrhip_filter_run_rows.argtypes = [_vp, _vp, _vp, _i64, _i64, _vp, _i64, C.c_int, _i64, _i64, _i64, C.c_int]
@@ -318,6 +322,7 @@ lib.sdrhip_pipe_fir_filter.argtypes = [C.POINTER(_vp), _vp, C.c_int]
 lib.sdrhip_pipe_fir_decimator.argtypes = [C.POINTER(_vp), _vp, C.c_int]
 lib.sdrhip_pipe_fir_resampler.argtypes = [C.POINTER(_vp), _vp, C.c_int]
 lib.sdrhip_pipe_fm_demod.argtypes = [C.POINTER(_vp)]
+lib.sdrhip_pipe_am_demod.argtypes = [C.POINTER(_vp)]
 lib.sdrhip_pipe_dc_blocker.argtypes = [C.POINTER(_vp)]
 lib.sdrhip_pipe_agc.argtypes = [C.POINTER(_vp), C.c_float, C.c_float]
 lib.sdrhip_pipe_tuner.argtypes = [C.POINTER(_vp), _vp, C.c_int]
@@ -645,6 +650,35 @@ def fm_demod_rows(x, last=None, out=None, last_out=None, in_base=0, k_begin=None
     check(lib.sdrhip_fm_demod_run_rows(torch.cuda.current_stream().cuda_stream, _dptr(x), in_stride, in_base, _dptr(out),
                                        out_stride, rows, k_begin, k_end, last.data_ptr() if last is not None else None,
                                        last_out.data_ptr() if last_out is not None else None), "sdrhip_fm_demod_run_rows")
+    return out
+
+
+def am_demod_launches():
+    """sdrhip_debug_am_demod_launches: kernel launches of am_demod / am_demod_rows in this process."""
+    return int(lib.sdrhip_debug_am_demod_launches())
+
+
+def am_demod(d_in, n, d_out, stream=None):
+    """sdrhip_am_demod_run: n interleaved complex float32 samples at device address d_in -> n float32 at d_out,
+    out[i] = Data.Complex.magnitude at Float of sample i (the envelope detector of an AM receiver).  d_in / d_out: device tensors or
+    raw device addresses, any 4-byte alignment.  Asynchronous on `stream` (a raw stream handle; None: the null stream)."""
+    pin = _dptr(d_in) if hasattr(d_in, "data_ptr") else d_in
+    pout = _dptr(d_out) if hasattr(d_out, "data_ptr") else d_out
+    check(lib.sdrhip_am_demod_run(stream, pin, pout, n), "sdrhip_am_demod_run")
+
+
+def am_demod_rows(x, out=None):
+    """sdrhip_am_demod_run_rows on the current stream -> out (rows x n float32).  x: rows x n complex64 or rows x 2n float32
+    interleaved on the device, rows contiguous, any row stride: a view into a TunerBank output works.  No synchronisation."""
+    import torch
+    rows, n, in_stride = _rows_of(x, "am_demod_rows", 2)
+    if out is None:
+        out = _rows_empty(rows, n, torch.float32, x.device)
+    orows, on, out_stride = _rows_of(out, "am_demod_rows")
+    if (orows, on) != (rows, n) or out.dtype != torch.float32:
+        raise ValueError("am_demod_rows: out must be rows x n float32")
+    check(lib.sdrhip_am_demod_run_rows(torch.cuda.current_stream().cuda_stream, _dptr(x), in_stride, _dptr(out), out_stride, rows, n),
+          "sdrhip_am_demod_run_rows")
     return out
 
 
@@ -1371,7 +1405,7 @@ class FmStream(_Handle):
 
 
 class Pipe(_Handle):
-    """firFilter / firDecimator / firResampler / fmDemod / dcBlockingFilter / agcPipe on host blocks (Filter.hs:532-739,
+    """firFilter / firDecimator / firResampler / fmDemod / amDemod / dcBlockingFilter / agcPipe on host blocks (Filter.hs:532-739,
     Demod.hs:40-46, Util.hs:344-348).  Pipe.tuner_bank: every channel of a TunerBank in lockstep -- push, flush, poll and restore
     then return a list of arrays of shape [channels, 2 * block_size_out], row j being the block Pipe.tuner over
     Tuner(factor, coeffs, tables[j], order) yields."""
@@ -1383,7 +1417,7 @@ class Pipe(_Handle):
         self.block_size_out = block_size_out
         self.input_u8 = False
         self.input_i16 = False
-        self.complex_in = bool(getattr(desc, "complex", False)) or kind in ("fm_demod", "agc")
+        self.complex_in = bool(getattr(desc, "complex", False)) or kind in ("fm_demod", "am_demod", "agc")
         self.complex_out = bool(getattr(desc, "complex", False)) or kind == "agc"
         if kind == "filter":
             check(lib.sdrhip_pipe_fir_filter(C.byref(self.h), desc.h, block_size_out), "sdrhip_pipe_fir_filter")
@@ -1403,6 +1437,8 @@ class Pipe(_Handle):
             self.input_u8 = bool(input_u8)
         elif kind == "fm_demod":
             check(lib.sdrhip_pipe_fm_demod(C.byref(self.h)), "sdrhip_pipe_fm_demod")
+        elif kind == "am_demod":
+            check(lib.sdrhip_pipe_am_demod(C.byref(self.h)), "sdrhip_pipe_am_demod")
         elif kind == "dc_blocker":
             check(lib.sdrhip_pipe_dc_blocker(C.byref(self.h)), "sdrhip_pipe_dc_blocker")
         elif kind == "agc":
@@ -1423,6 +1459,11 @@ class Pipe(_Handle):
         """The tuner bank on host blocks: cfloat blocks (or interleaved u8 IQ blocks, input_u8=True, or interleaved int16 IQ blocks,
         input_i16=True; the two exclude each other) in, every channel's blocks of block_size_out decimated samples out."""
         return Pipe("tuner_bank", bank, block_size_out, input_u8=input_u8, input_i16=input_i16)
+
+    @staticmethod
+    def am_demod():
+        """The AM envelope detector on host blocks: interleaved complex float32 blocks in, float blocks of the same length out."""
+        return Pipe("am_demod")
 
     @property
     def rows(self):
@@ -1536,6 +1577,11 @@ def firResampler(resampler, block_size_out):
 
 def fmDemod():
     return Pipe("fm_demod")
+
+
+def amDemod():
+    """`P.map (VG.map magnitude)`: the AM receiver's envelope detector."""
+    return Pipe("am_demod")
 
 
 def dcBlockingFilter():
