@@ -388,8 +388,7 @@ static RunPlan plan_run(const sdrhip_fm_chain* c, int64_t s0, int64_t q0, int64_
     if (c->tuner_period != 0) {
         const Geom g = tuner_geom(c, s0, r.kd0, r.kd1);
         r.tuner_tile = c->tuner_tile_shape() && r.kd1 - r.kd0 < (int64_t)0x7fffffff &&
-                       (fmt == IN_I16 ? tuner_i16_fused_fits(g, c->decim.Lp, true, d_in_iq, d_workspace, c->tuner_period)
-                                      : tuner_fused_fits(g, c->decim.Lp, true, d_in_iq, true, d_workspace, c->tuner_period));
+                       tuner_fused_fits(g, c->decim.Lp, true, d_in_iq, fmt, d_workspace, c->tuner_period);
         staged = !r.tuner_tile;
     }
     if (staged) {
@@ -501,33 +500,20 @@ static int chain_run_on(sdrhip_fm_chain* c, void* stream, const uint8_t* d_in_iq
     float* d_z = (float*)(ws + r.off_z);
     // K1+K2: u8 -> cfloat -> decimate (convert.c:37-50 fused into decimate.c:105-113)
     rc = c->timed(kDecimate, s, [&] {
-        if (tuned && fmt == IN_I16) {
-            // sdrhip_tuner_run_i16's two routes (tuner.cpp): the bank's int16 tile kernel with one channel, or the int16 mix into
-            // the workspace's start and the stock cfloat decimator on it
-            if (r.tuner_tile) {
-                const int off0 = 0;
-                if (!launch_tuner_bank_i16(s, tuner_geom(c, s0, r.kd0, r.kd1), dec.d_plain, dec.Lp, dec.d_cross, d_in_iq, d_d, 0, c->d_osc, 1, &off0,
-                                           &c->tuner_period, false)) {
-                    set_error("sdrhip_fm_bank_run_i16: the tuner's int16 tile kernel refused a launch its predicate accepted");
-                    return SDRHIP_ERR_STATE;
-                }
-                return SDRHIP_OK;
-            }
-            launch_tuner_mix_i16(s, d_in_iq + 4 * (r.xa - s0), (float*)ws, r.xb - r.xa, c->d_osc, c->tuner_period, (int)(r.xa % c->tuner_period));
-            return fir_run(&dec, s, ws, false, r.xa, d_d, r.kd0, r.kd1, c->block);
-        }
         if (tuned) {
             // the tuner's own routes on the caller's workspace and this run's stream (no leased scratch, no events: runs are captured
-            // into graphs and alternate between the overlap lanes): its tile kernel, or the mix into the workspace's start and the
-            // stock cfloat decimator on it
+            // into graphs and alternate between the overlap lanes): its tile kernel (for int16 the bank's with one channel), or the mix
+            // into the workspace's start and the stock cfloat decimator on it
             if (r.tuner_tile) {
-                if (!launch_tuner_fused(s, tuner_geom(c, s0, r.kd0, r.kd1), dec.d_plain, dec.Lp, dec.d_cross, d_in_iq, true, d_d, c->d_osc, c->tuner_period)) {
-                    set_error("sdrhip_fm_chain_run: the tuner's tile kernel refused a launch its predicate accepted");
+                if (!launch_tuner_fused(s, tuner_geom(c, s0, r.kd0, r.kd1), dec.d_plain, dec.Lp, dec.d_cross, d_in_iq, fmt, d_d, c->d_osc, c->tuner_period)) {
+                    set_error(fmt == IN_I16 ? "sdrhip_fm_bank_run_i16: the tuner's int16 tile kernel refused a launch its predicate accepted"
+                                            : "sdrhip_fm_chain_run: the tuner's tile kernel refused a launch its predicate accepted");
                     return SDRHIP_ERR_STATE;
                 }
                 return SDRHIP_OK;
             }
-            launch_tuner_mix(s, d_in_iq + 2 * (r.xa - s0), true, (float*)ws, r.xb - r.xa, c->d_osc, c->tuner_period, (int)(r.xa % c->tuner_period));
+            launch_tuner_mix(s, d_in_iq + in_fmt_bytes(fmt) * (r.xa - s0), fmt, (float*)ws, r.xb - r.xa, c->d_osc, c->tuner_period,
+                             (int)(r.xa % c->tuner_period));
             return fir_run(&dec, s, ws, false, r.xa, d_d, r.kd0, r.kd1, c->block);
         }
         if (c->fused_first_stage()) return fir_run(&dec, s, d_in_iq, true, s0, d_d, r.kd0, r.kd1, c->block);

@@ -131,18 +131,25 @@ __device__ __forceinline__ void mac_window(const float2* __restrict__ win, const
 }
 
 // Staging of one tile: all of a thread's 16-byte global loads are issued before the first wait, then
-// converted (u8) and written to the padded LDS layout.
-template <class T, bool U8, int NT>
+// converted (u8) and written to the padded LDS layout.  FMT is the InFmt of the samples: 8 / 2 / 4 bytes each, so 2 / 8 / 4 to a
+// 16-byte vector.  The decimator's kernels keep their `bool U8` and pass it as FMT: false and true ARE IN_CF32 and IN_U8.  int16
+// samples are loaded here for the tuner family alone (tuner_mix.hpp converts and mixes them): the decimator has no int16 store.
+static_assert(IN_CF32 == (int)false && IN_U8 == (int)true, "Stage<T, U8, NT> with a bool U8 names the cfloat and the u8 stage");
+template <class T, int FMT, int NT>
 struct Stage {
-    static constexpr int SPV = U8 ? 8 : 2;                       // samples per 16-byte vector
+    static constexpr bool U8 = FMT == IN_U8;
+    static constexpr int BPS = in_fmt_bytes(FMT);                // bytes per sample
+    static constexpr int SPV = 16 / BPS;                         // samples per 16-byte vector
     static constexpr int NV = (T::SPAN + SPV - 1) / SPV;         // vectors per tile
     static constexpr int PER = (NV + NT - 1) / NT;               // vectors per thread
+    // T::SPAN is a multiple of 4 for every shape the tuner's fit predicate admits (D and P multiples of 4)
+    static_assert(FMT != IN_I16 || T::SPAN % SPV == 0, "a whole tile is whole vectors: no read past the tile's last sample");
     uint4 r[PER];
 
     // a whole tile: unconditional 16-byte loads into a plain register array, all in flight together
     static __device__ __forceinline__ void load_whole(const void* __restrict__ src_v, int64_t sample0, uint4 (&regs)[PER])
     {
-        const uint4* src = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(src_v) + (U8 ? 2 : 8) * sample0);
+        const uint4* src = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(src_v) + BPS * sample0);
 #pragma unroll
         for (int i = 0; i < PER; i++) {
             const int v = threadIdx.x + i * NT;
@@ -152,7 +159,7 @@ struct Stage {
 
     __device__ __forceinline__ void load(const void* __restrict__ src_v, int64_t sample0, int avail)
     {
-        const char* src = reinterpret_cast<const char*>(src_v) + (U8 ? 2 : 8) * sample0;
+        const char* src = reinterpret_cast<const char*>(src_v) + BPS * sample0;
         if (avail >= T::SPAN) {
             // every tile but the last: unconditional 16-byte loads, all in flight together
 #pragma unroll
@@ -162,7 +169,7 @@ struct Stage {
             }
             return;
         }
-        // ragged end of the stream (one workgroup per launch): element-wise, zero-filled (u8 128 == 0.0f)
+        // ragged end of the stream (one workgroup per launch and channel): element-wise, zero-filled (u8 128 == 0.0f, int16 0 == +0.0f)
 #pragma unroll 1
         for (int i = 0; i < PER; i++) {
             const int v = threadIdx.x + i * NT;
@@ -175,6 +182,10 @@ struct Stage {
                     const uint8_t* b = reinterpret_cast<const uint8_t*>(src) + 16 * (int64_t)v;
                     for (int e = 0; e < 16; e++)
                         if (s + e / 2 < avail) w[e >> 2] = (w[e >> 2] & ~(0xffu << (8 * (e & 3)))) | ((uint32_t)b[e] << (8 * (e & 3)));
+                } else if constexpr (FMT == IN_I16) {
+                    const uint16_t* h = reinterpret_cast<const uint16_t*>(src) + 8 * (int64_t)v;
+                    for (int e = 0; e < 8; e++)
+                        if (s + e / 2 < avail) w[e >> 1] |= (uint32_t)h[e] << (16 * (e & 1));
                 } else {
                     const uint32_t* f = reinterpret_cast<const uint32_t*>(src) + 4 * (int64_t)v;
                     for (int e = 0; e < 4; e++)
@@ -192,6 +203,7 @@ struct Stage {
 
     static __device__ __forceinline__ void store_regs(const uint4 (&r)[PER], float2* __restrict__ lds)
     {
+        static_assert(FMT != IN_I16, "the decimator takes no int16 input");
 #pragma unroll
         for (int i = 0; i < PER; i++) {
             const int v = threadIdx.x + i * NT;

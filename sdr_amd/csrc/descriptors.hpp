@@ -84,9 +84,7 @@ int resamp_run_demod(const ResampDesc* r, hipStream_t s, const float* d_iq, bool
 
 // The tuner (include/sdr_hip.h): a complex decimator's prepared taps plus the oscillator table.  Immutable after create except for
 // the route and the scratch lanes of the two-pass route, so host threads may share one.
-// The input of the tuner family: cfloat, interleaved u8 IQ (RTL-SDR: (u - 128) / 128) or interleaved int16 IQ (BladeRF: s / 2048)
-enum InFmt : int { IN_CF32 = 0, IN_U8 = 1, IN_I16 = 2 };
-inline int in_fmt_bytes(InFmt f) { return f == IN_U8 ? 2 : f == IN_I16 ? 4 : 8; }      // per complex sample
+// (its input format: InFmt, kernels.hpp)
 struct TunerScratch;
 struct TunerDesc {
     FirDesc fir;                       // as sdrhip_decimator_create(order, data_complex = 1, ...) prepares it

@@ -355,47 +355,42 @@ long long fused_demod_launch_count();  // abi_device.cpp, diagnostics: resampler
 bool launch_decimate_c_orders_fast(hipStream_t s, const Geom& g, ComplexOrder order, const float* d_plain_taps, int P,
                                    const float* d_cross_taps, const void* d_in, bool in_is_u8, float* d_out);
 
+// The input of the tuner family: cfloat, interleaved u8 IQ (RTL-SDR: (u - 128) / 128) or interleaved int16 IQ (BladeRF: s / 2048).
+// Host code passes it as an argument, kernels take it as an `int FMT` template argument.
+enum InFmt : int { IN_CF32 = 0, IN_U8 = 1, IN_I16 = 2 };
+constexpr int in_fmt_bytes(int f) { return f == IN_U8 ? 2 : f == IN_I16 ? 4 : 8; }      // per complex sample
+
 // kernels_tuner.hip: the tuner = multiplication by a periodic complex oscillator (d_osc: `period` (re, im) pairs, indexed by the
 // ABSOLUTE stream index mod period) in front of the complex decimator.  Fused route: the tiled decimator with the mix in its loader,
 // AVX "RC" order, decimation 4 / 8 / 16, up to 128 prepared taps (d_plain_taps, never pre-scaled), 16-byte aligned tile starts;
 // Cross outputs in the tile kernel for short launches, else by a fix-up launch over seam_span(g).  false = not this shape, nothing launched.
+// int16 input has no one-row kernel: it is launch_tuner_bank with one channel (table offset 0, counts_as_bank = false).
 bool launch_tuner_fused(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in,
-                        bool in_is_u8, float* d_out, const float* d_osc, int period);
-// the conditions launch_tuner_fused checks, for callers that plan before they launch (chain.cpp); only the alignment of d_out counts
-bool tuner_fused_fits(const Geom& g, int P, bool has_cross_taps, const void* d_in, bool in_is_u8, const void* d_out, int period);
-// two-pass route, first pass: d_out[i] = mixed sample i of d_in (cfloat or u8 IQ), i < n < 2^31; ph0 = phase of sample 0
-void launch_tuner_mix(hipStream_t s, const void* d_in, bool in_is_u8, float* d_out, int64_t n, const float* d_osc, int period, int ph0);
-long long tuner_fused_launch_count();   // diagnostics: launches of the fused tile kernel
+                        InFmt fmt, float* d_out, const float* d_osc, int period);
+// the conditions launch_tuner_fused checks, for callers that plan before they launch (chain.cpp); only the alignment of d_out counts.
+// The first window lies at d_in + in_fmt_bytes(fmt) * x0 and is 16-byte aligned; int16 also wants x0 >= 0 and d_in 4-byte aligned.
+bool tuner_fused_fits(const Geom& g, int P, bool has_cross_taps, const void* d_in, InFmt fmt, const void* d_out, int period);
+// two-pass route, first pass: d_out[i] = mixed sample i of d_in, i < n < 2^31; ph0 = phase of sample 0
+void launch_tuner_mix(hipStream_t s, const void* d_in, InFmt fmt, float* d_out, int64_t n, const float* d_osc, int period, int ph0);
+long long tuner_fused_launch_count();   // diagnostics: launches of the one-row tile kernel (k_tuner_c4: cfloat and u8)
 // kernels_tuner_bank.hip: the tuner bank (sdrhip_tuner_bank_run) -- `channels` tuners of ONE decimator over ONE input in one launch of
 // the fused tile kernel with a channel axis (flat grid, the channel fastest).  d_tables holds every channel's oscillator table,
 // channel j's `periods[j]` (re, im) pairs from pair offsets[j] on; its outputs go to d_out + j * out_stride floats (out_stride even,
 // and at least 2 g.count when there is more than one channel).  Shapes, taps and Cross outputs as launch_tuner_fused, fit predicate
-// tuner_fused_fits; false = not this shape, nothing launched.  A launch counts once, its fix-up launch not at all.
+// tuner_fused_fits; false = not this shape, nothing launched.  A launch counts once, its fix-up launch not at all; counts_as_bank =
+// false is the one-row int16 tuner's launch, which counts as an int16 launch only.
 constexpr int kTunerBankMaxChannels = 32;
 bool launch_tuner_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in,
-                       bool in_is_u8, float* d_out, int64_t out_stride, const float* d_tables, int channels, const int* offsets,
-                       const int* periods);
-long long tuner_bank_launch_count();    // diagnostics: banked launches
+                       InFmt fmt, float* d_out, int64_t out_stride, const float* d_tables, int channels, const int* offsets,
+                       const int* periods, bool counts_as_bank);
+long long tuner_bank_launch_count();    // diagnostics: banked launches, every format
+long long tuner_i16_launch_count();     // diagnostics: int16 launches of the tile kernel, bank or one-row
 // Outputs [g.k_begin, g.k_begin + g.count) of every channel in the reference's sequential order, all of them (g.seamBI is not read):
 // the Cross part of a ragged push of the tuner bank's Pipe (pipes.cpp), one thread per (channel, output).  The refusals of
 // launch_tuner_bank for channels and stride, no alignment beyond the element's own; false = refused, nothing launched.
-bool launch_tuner_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_taps, const void* d_in, bool in_is_u8, float* d_out,
+bool launch_tuner_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_taps, const void* d_in, InFmt fmt, float* d_out,
                              int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods);
-long long tuner_bank_cross_launch_count();   // diagnostics: launches of the all-Cross kernel
-// kernels_tuner_i16.hip: the tuner family on 16-bit signed IQ (interleaved int16, 4 bytes per sample, (float)s * 2^-11 in the loader).
-// launch_tuner_bank_i16 is launch_tuner_bank for such input -- with channels = 1, offsets = {0} it is the one-row tuner's fused route
-// (counts_as_bank = false then) -- and launch_tuner_bank_cross_i16 / launch_tuner_mix_i16 are launch_tuner_bank_cross / launch_tuner_mix.
-// Fit predicate: tuner_fused_fits with the first window at d_in + 4 x0 bytes, and d_in at least 4-byte aligned.
-bool tuner_i16_fused_fits(const Geom& g, int P, bool has_cross_taps, const void* d_in, const void* d_out, int period);
-bool launch_tuner_bank_i16(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in,
-                           float* d_out, int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods,
-                           bool counts_as_bank);
-bool launch_tuner_bank_cross_i16(hipStream_t s, const Geom& g, const float* d_cross_taps, const void* d_in, float* d_out,
-                                 int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods);
-void launch_tuner_mix_i16(hipStream_t s, const void* d_in, float* d_out, int64_t n, const float* d_osc, int period, int ph0);
-long long tuner_i16_launch_count();              // diagnostics: launches of k_tuner_bank_c4_i16, bank or one-row
-long long tuner_i16_bank_launch_count();         // ... those of them that were banked launches
-long long tuner_i16_bank_cross_launch_count();   // ... launches of the all-Cross int16 kernel
+long long tuner_bank_cross_launch_count();   // diagnostics: launches of the all-Cross kernel, every format
 // kernels_small.hip: launch_fm_chain_small_bank on 16-bit signed IQ (sdrhip_fm_bank_run_i16): the tuned one-kernel chain with a station
 // axis and an int16 phase 0 (small_i16.hpp).  fm_chain_small_i16_fits: the tuned chain's shape and seam conditions with int16's
 // alignment (d_in 16-byte aligned, s0 a multiple of 4); the grid's condition is fm_chain_small_bank_fits.  A launch counts in

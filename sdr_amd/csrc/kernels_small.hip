@@ -208,7 +208,7 @@ struct BankStations {
     int ph[kFmBankMaxStations];                // (80 (q0 / 3) - 8) mod period: the host's one 64-bit modulo per station and launch
 };
 // I16: the bank's launch on 16-bit signed IQ (sdrhip_fm_bank_run_i16): `in` holds interleaved int16, 4 bytes per sample, and phase 0
-// is small_load_i16 + tuner_store_i16 (small_i16.hpp, tuner_i16.hpp: convert (float)s * 2^-11 first, then the mix), 4 samples per
+// is small_load_i16 + tuner_store (small_i16.hpp, tuner_mix.hpp: convert (float)s * 2^-11 first, then the mix), 4 samples per
 // 16-byte vector, so a thread's first vector starts 4 tid samples into the tile.  Phases 1-4 start from the mixed float2 samples in
 // LDS and are the same code.  Only the bank form exists: one station is a bank of one.
 struct NoBank {};
@@ -254,7 +254,7 @@ __global__ void __launch_bounds__(SM_NT, 2) k_fm_chain_small(const uint8_t* __re
     // launch owns (sdrhip_fm_chain_run checks the receptive field of [q0, q1)): they read as u8 128 = 0.0f.
     if constexpr (I16) {
         // int16 0 = +0.0f outside the input; rel0 is a multiple of 4 samples here (s0 % 4 == 0): 16-byte aligned vectors
-        StageI16<SmT, SM_NT> st;
+        Stage<SmT, IN_I16, SM_NT> st;
         small_load_i16<SmT, SM_NT>(st, in, kb * 8 - p.s0, p.n_in);
         // the small tables ride behind the tile's loads, as below
         float t_g = 0.0f, t_r = 0.0f, t_f = 0.0f;
@@ -267,12 +267,12 @@ __global__ void __launch_bounds__(SM_NT, 2) k_fm_chain_small(const uint8_t* __re
         const uint32_t n = (uint32_t)period;
         const uint32_t ts = (uint32_t)(80 * (A / 3)) % n;
         const uint32_t ph = ((uint32_t)ph_launch + (((uint32_t)tile % n) * ts) % n + (uint32_t)(tid * 4) % n) % n;
-        tuner_store_i16<SmT, SM_NT>(st.r, lds, osc, n, ph);
+        tuner_store<SmT, IN_I16, SM_NT>(st.r, lds, osc, n, ph);
         if (tid < 3 * SM_NL) { gtab[tid] = t_g; rpl[tid] = t_r; }
         if (tid < SM_LF) fpl[tid] = t_f;
         else if (tid < SM_LF + 128) dtl[tid - SM_LF] = t_f;
     } else {
-        Stage<SmT, true, SM_NT> st;
+        Stage<SmT, IN_U8, SM_NT> st;
         const int64_t rel0 = kb * 8 - p.s0;                           // tile start relative to in[0], a multiple of 8 samples
         const bool interior = rel0 >= 0 && rel0 + SmT::SPAN <= p.n_in;
         if (interior) {
@@ -318,7 +318,7 @@ __global__ void __launch_bounds__(SM_NT, 2) k_fm_chain_small(const uint8_t* __re
             const uint32_t n = (uint32_t)period;
             const uint32_t ts = (uint32_t)(80 * (A / 3)) % n;
             const uint32_t ph = ((uint32_t)ph_launch + (((uint32_t)tile % n) * ts) % n + (uint32_t)(tid * 8) % n) % n;
-            tuner_store<SmT, true, SM_NT>(st.r, lds, osc, n, ph);
+            tuner_store<SmT, IN_U8, SM_NT>(st.r, lds, osc, n, ph);
         } else {
             st.store(lds);
         }
@@ -575,7 +575,7 @@ void launch_fm_chain_small(hipStream_t s, const uint8_t* d_in, int64_t s0, int64
     p.row_stride = t.row_stride; p.ntaps = t.ntaps; p.rLp = t.rLp; p.gain = t.gain; p.seam = t.seam;
     const int64_t qa0 = (q0 / 3) * 3;
     const int64_t tiles = (q1 - qa0 + A - 1) / A;
-    static_assert(sizeof(Stage<SmT, true, SM_NT>::r) == sizeof(uint4[SM_PER]) && Stage<SmT, true, SM_NT>::NV == SM_NV, "tuner_store walks the loader's vectors");
+    static_assert(sizeof(Stage<SmT, IN_U8, SM_NT>::r) == sizeof(uint4[SM_PER]) && Stage<SmT, IN_U8, SM_NT>::NV == SM_NV, "tuner_store walks the loader's vectors");
     // tuned: the phase of tile 0's first sample, 80 (q0 / 3) - 8 (-8 at the stream's start: d[-1], which the kernel zeroes)
     int ph_launch = 0;
     if (d_osc != nullptr) {
@@ -654,7 +654,7 @@ void launch_bank(hipStream_t s, const void* d_in_v, bool i16, int64_t s0, int64_
                            t.d_fplain, p, reinterpret_cast<const float2*>(d_tables), 0, 0, st);
     };
     if (i16) {
-        static_assert(StageI16<SmT, SM_NT>::NV * StageI16<SmT, SM_NT>::SPV == SmT::SPAN, "the int16 loader reads exactly the tile");
+        static_assert(Stage<SmT, IN_I16, SM_NT>::NV * Stage<SmT, IN_I16, SM_NT>::SPV == SmT::SPAN, "the int16 loader reads exactly the tile");
         if (last_tap_zero) launch(k_fm_chain_small<1, true, true, true>, 3);
         else launch(k_fm_chain_small<0, true, true, true>, 2);
         g_small_bank_i16_launches++;

@@ -25,6 +25,11 @@
 // The bank's Pipe (pipes.cpp): a block of another size than its predecessors has no seam_block, so its submission is the outputs that
 // straddle the boundary (all Cross) and then the outputs inside the block (all One).  k_tuner_bank_cross is the first part for every
 // channel in one launch: k_tuner_bank_crossfix's body over an explicit output range.  sdrhip_tuner_bank_run never takes it.
+//
+// Input formats: every kernel here takes the format as FMT (InFmt: cfloat, u8 IQ, int16 IQ); the staging and the mixing store of a
+// tile are Stage<T, FMT, NT> and tuner_store<T, FMT, NT>, one sample of the sequential-order kernels is tuner_sample<FMT>.  Every
+// launch writes the bits of the cfloat launch on the converted samples.  The one-row tuner on int16 has no kernel of its own: its
+// fused route is k_tuner_bank_c4 with ONE channel (table offset 0), a launch that counts as an int16 launch and not as a banked one.
 #include "decimate_tile.hpp"
 #include "tuner_mix.hpp"
 
@@ -34,6 +39,8 @@ static std::atomic<long long> g_tuner_bank_launches{0};
 long long tuner_bank_launch_count() { return g_tuner_bank_launches.load(); }
 static std::atomic<long long> g_tuner_bank_cross_launches{0};
 long long tuner_bank_cross_launch_count() { return g_tuner_bank_cross_launches.load(); }
+static std::atomic<long long> g_tuner_i16_launches{0};
+long long tuner_i16_launch_count() { return g_tuner_i16_launches.load(); }
 
 namespace {
 
@@ -45,7 +52,7 @@ struct BankChannels {
     int ph[kTunerBankMaxChannels];             // (k_begin D) mod period: the host's one 64-bit modulo per channel and launch
 };
 
-template <int D, int P, int R, int NT, bool U8, int TC, bool GUARD>
+template <int D, int P, int R, int NT, int FMT, int TC, bool GUARD>
 __global__ void __launch_bounds__(NT) k_tuner_bank_c4(const void* __restrict__ in, int64_t x0 /* sample index of output 0's window in `in` */,
                                                       int count, const float* __restrict__ taps /* plain */, float* __restrict__ out,
                                                       int p_eff /* GUARD: taps of the filter (multiple of TC, <= P) */,
@@ -54,7 +61,7 @@ __global__ void __launch_bounds__(NT) k_tuner_bank_c4(const void* __restrict__ i
                                                       const float2* __restrict__ osc /* every table */, BankChannels bank)
 {
     using T = Tile<D, P, R, NT>;
-    using St = Stage<T, U8, NT>;
+    using St = Stage<T, FMT, NT>;
     constexpr int NP = 4, ORD = 0;                           // the AVX "RC" order
     extern __shared__ __attribute__((aligned(16))) unsigned char tuner_bank_smem[];
     float2* lds = reinterpret_cast<float2*>(tuner_bank_smem);
@@ -77,7 +84,7 @@ __global__ void __launch_bounds__(NT) k_tuner_bank_c4(const void* __restrict__ i
         const uint32_t n = (uint32_t)bank.period[j];
         constexpr uint32_t TS = (uint32_t)T::OUTS * D;
         const uint32_t ph = ((uint32_t)bank.ph[j] + (((uint32_t)tile % n) * (TS % n)) % n + (uint32_t)(threadIdx.x * St::SPV)) % n;
-        tuner_store<T, U8, NT>(st.r, lds, osc, n, ph);
+        tuner_store<T, FMT, NT>(st.r, lds, osc, n, ph);
     }
     __syncthreads();
 
@@ -121,7 +128,7 @@ __global__ void __launch_bounds__(NT) k_tuner_bank_c4(const void* __restrict__ i
 }
 
 // Cross outputs of every channel, one thread per candidate slot of a seam and channel (k_tuner_crossfix with the channel axis)
-template <bool U8>
+template <int FMT>
 __global__ void __launch_bounds__(256) k_tuner_bank_crossfix(Geom g, const float* __restrict__ xtaps, const void* __restrict__ in,
                                                               float* __restrict__ out, int64_t first_seam, int nseams, int per_seam,
                                                               const float2* __restrict__ osc, BankChannels bank)
@@ -142,14 +149,7 @@ __global__ void __launch_bounds__(256) k_tuner_bank_crossfix(Geom g, const float
     uint32_t ph = (uint32_t)((uint64_t)v % n);
     float re = 0.0f, im = 0.0f;
     for (int j = 0; j < g.Lp; j++) {
-        float2 x;
-        if constexpr (U8) {
-            const uchar2 u = reinterpret_cast<const uchar2*>(in)[v - g.in_base + j];
-            x = tuner_u8(u.x, u.y);
-        } else {
-            x = reinterpret_cast<const float2*>(in)[v - g.in_base + j];
-        }
-        const float2 mx = tuner_mul(x, osc[ph]);
+        const float2 mx = tuner_mul(tuner_sample<FMT>(in, v - g.in_base + j), osc[ph]);
         ph = wrap_inc(ph, n);
         re = re + mx.x * xtaps[j];
         im = im + mx.y * xtaps[j];
@@ -160,7 +160,7 @@ __global__ void __launch_bounds__(256) k_tuner_bank_crossfix(Geom g, const float
 // Outputs [g.k_begin, g.k_begin + g.count) of every channel, ALL of them Cross (the straddlers of a boundary between two blocks of
 // unequal size, which no seam_block describes): k_tuner_bank_crossfix's body on an explicit range instead of a seam's candidate
 // slots.  Block b: channel b % K, outputs of block b / K.
-template <bool U8>
+template <int FMT>
 __global__ void __launch_bounds__(256) k_tuner_bank_cross(Geom g, const float* __restrict__ xtaps, const void* __restrict__ in,
                                                            float* __restrict__ out, const float2* __restrict__ osc, BankChannels bank)
 {
@@ -175,14 +175,7 @@ __global__ void __launch_bounds__(256) k_tuner_bank_cross(Geom g, const float* _
     uint32_t ph = (uint32_t)((uint64_t)v % n);
     float re = 0.0f, im = 0.0f;
     for (int j = 0; j < g.Lp; j++) {
-        float2 x;
-        if constexpr (U8) {
-            const uchar2 u = reinterpret_cast<const uchar2*>(in)[v - g.in_base + j];
-            x = tuner_u8(u.x, u.y);
-        } else {
-            x = reinterpret_cast<const float2*>(in)[v - g.in_base + j];
-        }
-        const float2 mx = tuner_mul(x, osc[ph]);
+        const float2 mx = tuner_mul(tuner_sample<FMT>(in, v - g.in_base + j), osc[ph]);
         ph = wrap_inc(ph, n);
         re = re + mx.x * xtaps[j];
         im = im + mx.y * xtaps[j];
@@ -190,7 +183,7 @@ __global__ void __launch_bounds__(256) k_tuner_bank_cross(Geom g, const float* _
     *reinterpret_cast<float2*>(out + 2 * (int64_t)t) = make_float2(re, im);
 }
 
-template <int D, int P, bool U8, int TC, bool GUARD>
+template <int D, int P, int FMT, int TC, bool GUARD>
 void launch_tuner_bank_c4(hipStream_t s, const Geom& g, const float* taps, const void* in, float* out, bool inline_cross, bool* inlined,
                           const float* d_tables, const BankChannels& bank)
 {
@@ -198,7 +191,7 @@ void launch_tuner_bank_c4(hipStream_t s, const Geom& g, const float* taps, const
     using T = Tile<D, P, R, NT>;
     // the dynamic-LDS attribute is per device: one flag per (instantiation, device); idempotent, a race only repeats the call
     static std::atomic<bool> attr_set[64];
-    auto kern = k_tuner_bank_c4<D, P, R, NT, U8, TC, GUARD>;
+    auto kern = k_tuner_bank_c4<D, P, R, NT, FMT, TC, GUARD>;
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= 64 || !attr_set[dev]) {
@@ -218,16 +211,30 @@ void launch_tuner_bank_c4(hipStream_t s, const Geom& g, const float* taps, const
                        reinterpret_cast<const float2*>(d_tables), bank);
 }
 
+// the instantiation that serves the launch's shape (tuner_fused_fits has admitted it)
+template <int FMT>
+void launch_tuner_bank_c4_shape(hipStream_t s, const Geom& g, int P, const float* taps, const void* in, float* out, bool inl, bool* inlined,
+                                const float* d_tables, const BankChannels& bank)
+{
+#define TUNER_BANK(DV, TCV, GV) launch_tuner_bank_c4<DV, 128, FMT, TCV, GV>(s, g, taps, in, out, inl, inlined, d_tables, bank)
+    if (g.D == 4) TUNER_BANK(4, 4, true);
+    else if (g.D == 16) { if (P % 8 == 0) TUNER_BANK(16, 8, true); else TUNER_BANK(16, 4, true); }
+    else if (P == 128) TUNER_BANK(8, 8, false);      // the exact-length walk for the full 128 taps
+    else if (P % 8 == 0) TUNER_BANK(8, 8, true);
+    else TUNER_BANK(8, 4, true);
+#undef TUNER_BANK
+}
+
 }  // namespace
 
 bool launch_tuner_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in,
-                       bool in_is_u8, float* d_out, int64_t out_stride, const float* d_tables, int channels, const int* offsets,
-                       const int* periods)
+                       InFmt fmt, float* d_out, int64_t out_stride, const float* d_tables, int channels, const int* offsets,
+                       const int* periods, bool counts_as_bank)
 {
     if (channels < 1 || channels > kTunerBankMaxChannels || (out_stride & 1) != 0) return false;
     if (channels > 1 && out_stride < 2 * (int64_t)g.count) return false;
     for (int j = 0; j < channels; j++)
-        if (!tuner_fused_fits(g, P, d_cross_taps != nullptr, d_in, in_is_u8, d_out, periods[j])) return false;
+        if (!tuner_fused_fits(g, P, d_cross_taps != nullptr, d_in, fmt, d_out, periods[j])) return false;
     BankChannels bank = {};
     bank.out_stride = out_stride;
     bank.channels = channels;
@@ -239,36 +246,35 @@ bool launch_tuner_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, 
     // launch-bound sizes compute their Cross outputs inside the tile kernel: launch_tuner_fused's decision
     const bool inl = g.seamBI > 0 && g.count <= 5 * (int64_t)small_launch_outputs();
     bool inlined = false;
-#define TUNER_BANK(DV, TCV, GV) do { if (in_is_u8) launch_tuner_bank_c4<DV, 128, true, TCV, GV>(s, g, d_plain_taps, d_in, d_out, inl, &inlined, d_tables, bank); \
-                                     else launch_tuner_bank_c4<DV, 128, false, TCV, GV>(s, g, d_plain_taps, d_in, d_out, inl, &inlined, d_tables, bank); } while (0)
-    if (g.D == 4) TUNER_BANK(4, 4, true);
-    else if (g.D == 16) { if (P % 8 == 0) TUNER_BANK(16, 8, true); else TUNER_BANK(16, 4, true); }
-    else if (P == 128) TUNER_BANK(8, 8, false);      // the exact-length walk for the full 128 taps
-    else if (P % 8 == 0) TUNER_BANK(8, 8, true);
-    else TUNER_BANK(8, 4, true);
-#undef TUNER_BANK
-    g_tuner_bank_launches.fetch_add(1, std::memory_order_relaxed);
+    switch (fmt) {
+    case IN_U8: launch_tuner_bank_c4_shape<IN_U8>(s, g, P, d_plain_taps, d_in, d_out, inl, &inlined, d_tables, bank); break;
+    case IN_I16: launch_tuner_bank_c4_shape<IN_I16>(s, g, P, d_plain_taps, d_in, d_out, inl, &inlined, d_tables, bank); break;
+    default: launch_tuner_bank_c4_shape<IN_CF32>(s, g, P, d_plain_taps, d_in, d_out, inl, &inlined, d_tables, bank); break;
+    }
+    if (fmt == IN_I16) g_tuner_i16_launches.fetch_add(1, std::memory_order_relaxed);
+    if (counts_as_bank) g_tuner_bank_launches.fetch_add(1, std::memory_order_relaxed);
 
     const SeamSpan sp = seam_span(g);
     if (sp.nseams > 0 && !inlined) {
         const unsigned per_channel = (unsigned)(((int64_t)sp.nseams * sp.per + 255) / 256);
         const dim3 grid(per_channel * (unsigned)channels), block(256);
-        const float2* o2 = reinterpret_cast<const float2*>(d_tables);
-        if (in_is_u8) hipLaunchKernelGGL(k_tuner_bank_crossfix<true>, grid, block, 0, s, g, d_cross_taps, d_in, d_out, sp.first, sp.nseams, sp.per, o2, bank);
-        else hipLaunchKernelGGL(k_tuner_bank_crossfix<false>, grid, block, 0, s, g, d_cross_taps, d_in, d_out, sp.first, sp.nseams, sp.per, o2, bank);
+        auto fix = fmt == IN_U8 ? k_tuner_bank_crossfix<IN_U8> : fmt == IN_I16 ? k_tuner_bank_crossfix<IN_I16> : k_tuner_bank_crossfix<IN_CF32>;
+        hipLaunchKernelGGL(fix, grid, block, 0, s, g, d_cross_taps, d_in, d_out, sp.first, sp.nseams, sp.per,
+                           reinterpret_cast<const float2*>(d_tables), bank);
     }
     return true;
 }
 
-bool launch_tuner_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_taps, const void* d_in, bool in_is_u8, float* d_out,
+bool launch_tuner_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_taps, const void* d_in, InFmt fmt, float* d_out,
                              int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods)
 {
     // launch_tuner_bank's refusals for channels and stride; one thread reads its window sample by sample: no alignment beyond the
-    // element's own
+    // element's own (a float, a u8 pair, an int16 pair)
+    static const uintptr_t kInMask[3] = {/* IN_CF32 */ 7, /* IN_U8 */ 1, /* IN_I16 */ 3};
     if (channels < 1 || channels > kTunerBankMaxChannels || (out_stride & 1) != 0) return false;
     if (channels > 1 && out_stride < 2 * (int64_t)g.count) return false;
     if (g.I != 1 || g.count <= 0 || g.k_begin < 0 || g.k_begin * g.D < g.in_base || d_cross_taps == nullptr) return false;
-    if ((reinterpret_cast<uintptr_t>(d_out) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_in) & (in_is_u8 ? 1 : 7)) != 0) return false;
+    if ((reinterpret_cast<uintptr_t>(d_out) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_in) & kInMask[fmt]) != 0) return false;
     BankChannels bank = {};
     bank.out_stride = out_stride;
     bank.channels = channels;
@@ -279,9 +285,8 @@ bool launch_tuner_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_
     }
     const unsigned per_channel = (unsigned)(((int64_t)g.count + 255) / 256);        // at most 2^23: times 32 channels fits a 1-D grid
     const dim3 grid(per_channel * (unsigned)channels), block(256);
-    const float2* o2 = reinterpret_cast<const float2*>(d_tables);
-    if (in_is_u8) hipLaunchKernelGGL(k_tuner_bank_cross<true>, grid, block, 0, s, g, d_cross_taps, d_in, d_out, o2, bank);
-    else hipLaunchKernelGGL(k_tuner_bank_cross<false>, grid, block, 0, s, g, d_cross_taps, d_in, d_out, o2, bank);
+    auto cross = fmt == IN_U8 ? k_tuner_bank_cross<IN_U8> : fmt == IN_I16 ? k_tuner_bank_cross<IN_I16> : k_tuner_bank_cross<IN_CF32>;
+    hipLaunchKernelGGL(cross, grid, block, 0, s, g, d_cross_taps, d_in, d_out, reinterpret_cast<const float2*>(d_tables), bank);
     g_tuner_bank_cross_launches.fetch_add(1, std::memory_order_relaxed);
     return true;
 }

@@ -1,10 +1,10 @@
 // small_i16.hpp -- 16-bit signed IQ in front of the tuned one-kernel FM chain (kernels_small.hip, the receiver bank's int16 launch):
-// the staging of one tile whose BOTH ends may lie outside the launch's input.  StageI16::load (tuner_i16.hpp) cuts a tile at its far
+// the staging of one tile whose BOTH ends may lie outside the launch's input.  Stage::load (decimate_tile.hpp) cuts a tile at its far
 // end only -- the tuner's tiles start at the first window -- while the chain's first tile starts one decimator output before the
-// first y, before sample 0 at the stream's start, and its last tile runs past the receptive field.  The raw vectors land in StageI16's
-// register layout, so tuner_store_i16 (convert, then mix) takes them as they are.
+// first y, before sample 0 at the stream's start, and its last tile runs past the receptive field.  The raw vectors land in the int16
+// Stage's register layout, so tuner_store (tuner_mix.hpp: convert, then mix) takes them as they are.
 #pragma once
-#include "tuner_i16.hpp"
+#include "tuner_mix.hpp"
 
 namespace sdrhip {
 namespace {
@@ -14,9 +14,9 @@ namespace {
 // vectors where all 4 samples exist, else sample by sample (one 32-bit word each); samples outside [0, n_in) read as int16 0 = +0.0f.
 // No byte outside [in, in + 4 n_in) is read.
 template <class T, int NT>
-__device__ __forceinline__ void small_load_i16(StageI16<T, NT>& st, const void* __restrict__ in, int64_t rel0, int64_t n_in)
+__device__ __forceinline__ void small_load_i16(Stage<T, IN_I16, NT>& st, const void* __restrict__ in, int64_t rel0, int64_t n_in)
 {
-    using St = StageI16<T, NT>;
+    using St = Stage<T, IN_I16, NT>;
     auto& r = st.r;
     constexpr int SPV = St::SPV, NV = St::NV, PER = St::PER;
     const int tid = threadIdx.x;

@@ -4,8 +4,8 @@
 // taps, aligned tile starts).  Two-pass: k_tuner_mix writes the mixed samples of a bounded chunk of the launch into a leased
 // scratch buffer and the stock decimator (fir_run, every order and factor) runs on it; chunks overlap by numCoeffs - factor
 // samples, which are mixed twice.  Both give sdrhip_decimator_run's bits on the mixed stream.
-// Input formats (InFmt): cfloat and u8 IQ take the kernels of kernels_tuner.hip; int16 IQ (sdrhip_tuner_run_i16) takes those of
-// kernels_tuner_i16.hip -- its fused route is the tuner bank's int16 tile kernel with one channel, its two-pass route an int16 mix.
+// Input formats (InFmt): every kernel-side entry point takes the format.  int16 IQ (sdrhip_tuner_run_i16) has no one-row tile kernel:
+// launch_tuner_fused hands it to the tuner bank's tile kernel with one channel; its two-pass route is k_tuner_mix on int16.
 #include <math.h>
 
 #include <atomic>
@@ -93,8 +93,7 @@ static int tuner_two_pass(const TunerDesc* t, hipStream_t s, const void* d_in, I
             const int64_t ke = kb + cnt_max < k_end ? kb + cnt_max : k_end;
             const int64_t a0 = kb * D, nin = (ke - kb - 1) * D + Lp;
             const char* src = static_cast<const char*>(d_in) + esz * (a0 - g.in_base);
-            if (fmt == IN_I16) launch_tuner_mix_i16(s, src, work, nin, t->d_osc, t->period, (int)(a0 % t->period));
-            else launch_tuner_mix(s, src, fmt == IN_U8, work, nin, t->d_osc, t->period, (int)(a0 % t->period));
+            launch_tuner_mix(s, src, fmt, work, nin, t->d_osc, t->period, (int)(a0 % t->period));
             rc = fir_run(&t->fir, s, work, false, a0, d_out + 2 * (kb - g.k_begin), kb, ke, seam_block);
         }
         if (rc == SDRHIP_OK) e = hipGetLastError();
@@ -132,11 +131,7 @@ int tuner_run(const TunerDesc* t, hipStream_t s, const void* d_in, InFmt fmt, in
     g.seamBI = seam_block;
     const int route = t->route;
     if (route != 2) {
-        // int16 input: the bank's int16 tile kernel with one channel (its table at offset 0), kernels_tuner_i16.hip
-        const int off0 = 0;
-        const bool fused = d->corder != CO_L4 ? false
-                         : fmt == IN_I16 ? launch_tuner_bank_i16(s, g, d->d_plain, d->Lp, d->d_cross, d_in, d_out, 0, t->d_osc, 1, &off0, &t->period, false)
-                                         : launch_tuner_fused(s, g, d->d_plain, d->Lp, d->d_cross, d_in, fmt == IN_U8, d_out, t->d_osc, t->period);
+        const bool fused = d->corder == CO_L4 && launch_tuner_fused(s, g, d->d_plain, d->Lp, d->d_cross, d_in, fmt, d_out, t->d_osc, t->period);
         if (fused) {
             SDRHIP_CHECK_HIP(hipGetLastError());
             return SDRHIP_OK;

@@ -24,20 +24,16 @@ static_assert(SDRHIP_TUNER_BANK_MAX_CHANNELS == kTunerBankMaxChannels, "the head
 // the rectangle -- more than 2^24 samples per launch -- goes channel by channel.  The bound is in INPUT SAMPLES of the launch,
 // count * factor: a launch of the other factors or of fewer taps reads the same samples with no more arithmetic per sample than the
 // measured shape, and a launch shorter than one block is no less launch-bound than one block, so neither is held to be outside.
-static const int kBankAutoMinChannels = 2;
-static const int64_t kBankAutoMaxSamples = (int64_t)1 << 24;
-
-static bool bank_auto(int channels, int64_t samples)
-{
-    return channels >= kBankAutoMinChannels && samples <= kBankAutoMaxSamples;
-}
-
-// auto for int16 input, read from `tools/tuner_bank_bench.py --i16` (profiles/tuner_i16_bench.txt) by the same criterion over the same
+//
+// int16 input, read from `tools/tuner_bank_bench.py --i16` (profiles/tuner_i16_bench.txt) by the same criterion over the same
 // rectangle: at EVERY point with K >= 2 the banked int16 launch's slowest round is below the K run_i16 calls' fastest (0.52 .. 0.03 of
 // their time at one block, 0.90 .. 0.78 at 2^24 samples), so the sweep confirms the u8 / cfloat rectangle and the bounds are again its
 // edges, not crossovers; nothing beyond 2^24 samples per launch is measured and the rule is not widened.  One channel goes to its tuner,
 // which for int16 launches the same kernel with one channel: level by construction, and measured so (0.995 .. 1.001).
-static bool bank_auto_i16(int channels, int64_t samples)
+static const int kBankAutoMinChannels = 2;
+static const int64_t kBankAutoMaxSamples = (int64_t)1 << 24;
+
+static bool bank_auto(int channels, int64_t samples)
 {
     return channels >= kBankAutoMinChannels && samples <= kBankAutoMaxSamples;
 }
@@ -85,21 +81,16 @@ int tuner_bank_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, InFm
     g.seamBI = seam_block;
     const int route = b->route;
     // the Cross taps are the prepared plain taps, on the device once the descriptor is (FirDesc::ensure_device)
-    const bool fits = d->corder == CO_L4 && (fmt == IN_I16 ? tuner_i16_fused_fits(g, d->Lp, true, d_in, d_out, 1)
-                                                           : tuner_fused_fits(g, d->Lp, true, d_in, fmt == IN_U8, d_out, 1));
+    const bool fits = d->corder == CO_L4 && tuner_fused_fits(g, d->Lp, true, d_in, fmt, d_out, 1);
     if (route == 1 && !fits) {
         set_error("sdrhip_tuner_bank_run: the banked launch serves the AVX order, factors 4 / 8 / 16, up to 128 prepared taps, seam_block >= 0 "
                   "and a 16-byte aligned first window; this launch is none of that (route 0 or 2 runs it)");
         return SDRHIP_ERR_ARG;
     }
-    const bool banked_by_rule = fmt == IN_I16 ? bank_auto_i16(K, (int64_t)g.count * g.D) : bank_auto(K, (int64_t)g.count * g.D);
-    if (fits && (route == 1 || (route == 0 && banked_by_rule))) {
+    if (fits && (route == 1 || (route == 0 && bank_auto(K, (int64_t)g.count * g.D)))) {
         int rc = b->ensure_device();
         if (rc != SDRHIP_OK) return rc;
-        const bool launched = fmt == IN_I16
-            ? launch_tuner_bank_i16(s, g, d->d_plain, d->Lp, d->d_cross, d_in, d_out, out_stride, b->d_tables, K, b->off, b->period, true)
-            : launch_tuner_bank(s, g, d->d_plain, d->Lp, d->d_cross, d_in, fmt == IN_U8, d_out, out_stride, b->d_tables, K, b->off, b->period);
-        if (launched) {
+        if (launch_tuner_bank(s, g, d->d_plain, d->Lp, d->d_cross, d_in, fmt, d_out, out_stride, b->d_tables, K, b->off, b->period, true)) {
             SDRHIP_CHECK_HIP(hipGetLastError());
             return SDRHIP_OK;
         }
@@ -135,10 +126,7 @@ int tuner_bank_cross_run(const TunerBankDesc* b, hipStream_t s, const void* d_in
     g.D = d->factor;
     g.Lp = d->Lp;
     g.seamBI = -1;
-    const bool launched = fmt == IN_I16
-        ? launch_tuner_bank_cross_i16(s, g, d->d_cross, d_in, d_out, out_stride, b->d_tables, (int)b->ch.size(), b->off, b->period)
-        : launch_tuner_bank_cross(s, g, d->d_cross, d_in, fmt == IN_U8, d_out, out_stride, b->d_tables, (int)b->ch.size(), b->off, b->period);
-    if (!launched) {
+    if (!launch_tuner_bank_cross(s, g, d->d_cross, d_in, fmt, d_out, out_stride, b->d_tables, (int)b->ch.size(), b->off, b->period)) {
         set_error("tuner_bank_cross_run: the all-Cross launch refused its channels, stride or pointers");
         return SDRHIP_ERR_ARG;
     }
@@ -225,8 +213,8 @@ int sdrhip_tuner_bank_run_i16(const sdrhip_tuner_bank* b, void* stream, const in
     return tuner_bank_run(b, (hipStream_t)stream, d_in_iq, IN_I16, in_base, d_out, out_stride, k_begin, k_end, seam_block);
 }
 
-// the int16 kernels (kernels_tuner_i16.hip) keep counters of their own: a banked launch is a banked launch whatever it reads
-long long sdrhip_debug_tuner_bank_launches(void) { return tuner_bank_launch_count() + tuner_i16_bank_launch_count(); }
-long long sdrhip_debug_tuner_bank_cross_launches(void) { return tuner_bank_cross_launch_count() + tuner_i16_bank_cross_launch_count(); }
+// a banked launch is a banked launch whatever it reads
+long long sdrhip_debug_tuner_bank_launches(void) { return tuner_bank_launch_count(); }
+long long sdrhip_debug_tuner_bank_cross_launches(void) { return tuner_bank_cross_launch_count(); }
 
 }  // extern "C"
