@@ -43,6 +43,28 @@
  * block's first "One".  seam_block = 0 means one
  * contiguous buffer: every output is "One" (what a single FFI call computes).
  *
+ * Stream contract of layer (2) (tests/test_gpu_stream_order.py runs every family below behind a gate on a non-blocking stream).
+ * ORDERED ON `stream`: every kernel, memset and copy a `_run` call makes on the caller's data -- the whole launch set: tile kernels
+ * and their seam fix-up launches, the settle and repair launches of dcBlocker / agc, the mix + decimate pairs of the tuner's two-pass
+ * route, hipFFT's transforms, the layers and finalise launches of a reduction -- is queued on `stream` in call order.  The call
+ * reads d_in and workspaces, and writes d_out, d_final and states, only there: the caller may queue the producer of d_in before the
+ * call and a consumer of d_out (or an overwrite of d_in) after it on the same stream, with no host synchronisation in between.
+ * Scratch a descriptor owns and shares between calls (the tuner's leased lanes, the spectrum operator's work buffer) is handed from
+ * one stream to the next with an event or a drain; a caller never orders it.
+ * A FIRST RUN of a descriptor uploads its taps, tables, window and twiddles with blocking copies on the null stream (finished when
+ * the call returns, before the first kernel it queues can start) and may allocate; it never waits for `stream`, but an allocation
+ * may wait for the whole device.  The operators without a descriptor (convert, scale, fmDemod, amDemod, dcBlocker, agc and all
+ * their row forms) have no first run.
+ * MAY BLOCK THE HOST after the first run: (a) sdrhip_spectrum_run_device on the hipFFT route, and sdrhip_spectrum_reduce_run_device
+ * on the hipFFT route or with a group of more than 32 rows, when `stream` is not the stream of the object's last such run: the call
+ * waits on the host until that last stream has drained (one work buffer per object), and also when it needs a transform plan for a
+ * batch size the object has not kept; (b) a tuner two-pass run (and so a tuner bank's or FM bank's channel-by-channel route through
+ * it) whose chunk needs more scratch than its lane holds: it waits for the lane's last borrower and reallocates; (c) a run of a
+ * shape that needs a larger internal buffer than any run before it.  Every other `_run` call -- the FIR stage operators and their
+ * row forms, convert, scale, fmDemod, amDemod, dcBlocker, agc and their row forms, the tuner's fused route and its two-pass route at
+ * a scratch size it has seen, the tuner bank, the FM chain without overlap mode, the FM bank, the spectrum operator's one-kernel
+ * route with groups of at most 32 rows -- returns without having waited for `stream` or for any other stream.
+ *
  * Errors: drop-in symbols cannot report (void returns): on a failure they call the
  * handler of sdrhip_set_error_handler and return, or -- without one -- print to stderr and abort().  sdrhip_* return SDRHIP_OK (0) or a negative code;
  * sdrhip_last_error() returns a thread-local message.
