@@ -526,6 +526,77 @@ long long sdrhip_debug_rows_launches(void);
 int sdrhip_am_demod_run_rows(void *stream, const float *d_in_iq, int64_t in_stride, float *d_out, int64_t out_stride,
                              int rows, int64_t n);
 
+/* ---- AM receiver bank: every channel's envelope (and dcBlocker) from one capture ---- */
+/* The AM receiver of the reference's Readme (tuner, decimator, `magnitude`, dcBlocker) for the K channels of a tuner bank.
+ * Definition: channel j's row is d_out + j * out_stride floats and holds k_end - k_begin floats; they equal, bit for bit, what
+ * sdrhip_tuner_bank_run / _run_u8 / _run_i16 writes into complex rows for the same (d_in, in_base, k_begin, k_end, seam_block), put
+ * through sdrhip_am_demod_run_rows and then, with dc_block = 1, through sdrhip_dc_blocker_run_rows from the state d_dc_state, with a
+ * workspace and the default run-in, its final state written back to d_dc_state -- on every route, for every seam_block, in_base, cut
+ * into launches and out_stride.  Nothing new is argued: the (*) parity and the One / Cross rule are the tuner's, `magnitude` is
+ * amDemod's, dcBlocker is dcBlocker.  Floats of d_out outside the K rows' [0, k_end - k_begin) are not touched.
+ * d_dc_state: 2 K device floats, channel j's (lastSample, lastOutput) at [2j, 2j + 2), read and written; NULL if and only if
+ * dc_block = 0.  THE STATE BELONGS TO OUTPUT k_begin: it is dcBlocker's state in front of that output, and after the run it is the
+ * state in front of output k_end.  Consecutive runs over consecutive ranges [k0, k1), [k1, k2), ... that reuse one state array, on one
+ * stream, are ONE stream and give the bits of one run over [k0, kn); a stream starts from zeros (`func 0 0`, Filter.hs:731).  Two
+ * streams (two host threads on one bank) take two state arrays and two workspaces.
+ * Create: the tuner bank is BORROWED and must outlive the AM bank; SDRHIP_ERR_ARG (and *b = NULL) for a null bank and a dc_block
+ * outside 0 / 1.
+ * Workspace: sdrhip_am_bank_workspace_bytes(b, count) bytes for a run of count = k_end - k_begin outputs, 16-byte aligned, used
+ * during the run only.  It is what route 2 needs (the complex rows, the envelope rows and dcBlocker's workspace) and is asked for on
+ * routes 0 and 2; route 1 asks for the envelope rows and dcBlocker's workspace with dc_block = 1 (a workspace of the full size
+ * serves), and for NO workspace with dc_block = 0: d_workspace may then be NULL.
+ * Run: SDRHIP_ERR_ARG before any device work, with nothing written, for whatever sdrhip_tuner_bank_run* refuses (its even-stride rule
+ * aside: any out_stride >= k_end - k_begin is legal, odd ones included, and any with one channel), out_stride < k_end - k_begin with
+ * more than one channel, a null d_dc_state with dc_block = 1 or a non-null one with dc_block = 0, a workspace that is null, shorter
+ * than the route asks for or not 16-byte aligned, a d_out off a float's alignment, and route 1 forced on a launch the tuner bank's
+ * banked launch does not serve.  An empty range is SDRHIP_OK and leaves the state as it is.  Asynchronous on `stream`; after the first
+ * run a run makes no allocation, no host synchronisation and no host-to-device copy on route 1.  An AM bank is immutable after create
+ * (but for set_route) and may be shared by host threads.
+ * Routes (same bits).  1 = fused: ONE launch of the tuner bank's tile kernel in its envelope form for all channels -- the magnitude of
+ * each finished output is what the kernel stores, so no complex row is written or read back -- one envelope fix-up launch for all
+ * channels where the tuner bank takes one, and with dc_block = 1 one sdrhip_dc_blocker_run_rows launch set from the envelope rows in
+ * the workspace into d_out (that operator refuses d_in == d_out); with dc_block = 0 the tile launch writes d_out itself.  It fits
+ * exactly where the tuner bank's banked launch fits (AVX order, factor 4 / 8 / 16, up to 128 prepared taps, seam_block >= 0, a 16-byte
+ * aligned first window; d_out needs a float's alignment only) and is SDRHIP_ERR_ARG elsewhere.  2 = composed: the three calls of the
+ * definition, the tuner bank on ITS route setting.  0 = auto (default): route 1 where it fits AND the launch lies in the part of the measured
+ * rectangle where route 1's slowest round was below route 2's fastest (tools/am_bank_bench.py, profiles/am_bank_bench.txt: 1 / 2 / 8 / 32
+ * channels x launches of 8192, 2^17, 2^20 and 2^24 input samples, 128 taps / 8, u8, cfloat and int16 input, dc_block off and on, the two
+ * routes alternating in one process, 7 rounds); everything else, and everything outside that rectangle, is route 2.  The rule, with
+ * n = (k_end - k_begin) * factor the input samples of the launch, for the three input types alike:
+ *     dc_block = 0:  fused  iff  n <= 2^24
+ *     dc_block = 1:  fused  iff  n <= 2^24  and  ( channels >= 8  or  channels == 1 and n >= 1048456  or  channels == 2 and n >= 16777096 )
+ * Without dcBlocker route 1 is ahead at all 48 measured points, one channel included (0.75 .. 0.91 of route 2's time: 9.2 against
+ * 11.5 us for 8 channels at 8192 samples of u8, 921 against 1051 us for 32 channels at 2^24).  With dcBlocker its walk is most of
+ * either route (76.9 against 79.3 us for 8 channels at 8192 samples) and route 1 is ahead at all 24 points with 8 and 32 channels
+ * (0.89 .. 0.99) but NOT with 1 and 2 channels at 8192 and 2^17 samples: one channel at 8192 samples is BEHIND (43.9 against 37.9 us
+ * u8, 41.8 against 37.5 cfloat, 44.2 against 39.6 int16), two channels are 1.01 .. 1.03, at 2^17 the spreads overlap, and two
+ * channels at 2^20 are ahead for int16 alone.  One channel at the 2^20 and 2^24 launches and two channels at the 2^24 launch are ahead
+ * for every input type, by 0.5 .. 1.9 %, and the rule takes them: 1048456 and 16777096 are those measured launches (131057 and 2097137
+ * outputs x 8 samples).  2 < channels < 8 with dcBlocker, and anything beyond 2^24 samples per launch, is not measured and is route 2.
+ * Under auto a launch that the envelope kernel turns down after the predicate admitted it runs composed (route 1 forced: an error). */
+typedef struct sdrhip_am_bank sdrhip_am_bank;
+int sdrhip_am_bank_create(sdrhip_am_bank **b, const sdrhip_tuner_bank *tuner_bank, int dc_block);
+void sdrhip_am_bank_destroy(sdrhip_am_bank *b);
+int sdrhip_am_bank_channels(const sdrhip_am_bank *b);
+int sdrhip_am_bank_set_route(sdrhip_am_bank *b, int route);          /* 0 auto, 1 fused, 2 composed */
+size_t sdrhip_am_bank_workspace_bytes(const sdrhip_am_bank *b, int64_t count);   /* 0 for a null bank or a count outside 1 .. 2^31 - 2 */
+int sdrhip_am_bank_run(const sdrhip_am_bank *b, void *stream, const float *d_in, int64_t in_base, float *d_out, int64_t out_stride,
+                       int64_t k_begin, int64_t k_end, int64_t seam_block, float *d_dc_state, void *d_workspace,
+                       size_t workspace_bytes);
+int sdrhip_am_bank_run_u8(const sdrhip_am_bank *b, void *stream, const uint8_t *d_in_iq, int64_t in_base, float *d_out,
+                          int64_t out_stride, int64_t k_begin, int64_t k_end, int64_t seam_block, float *d_dc_state,
+                          void *d_workspace, size_t workspace_bytes);
+int sdrhip_am_bank_run_i16(const sdrhip_am_bank *b, void *stream, const int16_t *d_in_iq, int64_t in_base, float *d_out,
+                           int64_t out_stride, int64_t k_begin, int64_t k_end, int64_t seam_block, float *d_dc_state,
+                           void *d_workspace, size_t workspace_bytes);
+/* envelope tile launches (route 1: exactly one per run; an int16 one also counts in sdrhip_debug_tuner_i16_launches, none counts in
+ * sdrhip_debug_tuner_bank_launches or sdrhip_debug_am_demod_launches) and envelope fix-up launches (at most one per run), process-wide */
+long long sdrhip_debug_am_bank_launches(void);
+long long sdrhip_debug_am_bank_fixup_launches(void);
+/* launches of the all-Cross envelope kernel of the bank's Pipe (sdrhip_pipe_am_bank: the boundary part of a ragged push), process-wide;
+ * sdrhip_am_bank_run never takes it */
+long long sdrhip_debug_am_bank_cross_launches(void);
+
 /* The FIR operators over rows: the filter, decimator and resampler stages behind a bank (second decimator per channel, resampler
  * and audio filter per station) in one launch set instead of one call per row.  in_base, k_begin, k_end, seam_block and out_block
  * mean what they mean to sdrhip_filter_run / sdrhip_decimator_run / sdrhip_resampler_run and are the same for every row; row r's
@@ -1106,6 +1177,31 @@ uint8_t *sdrhip_pipe_input_buffer_u8(sdrhip_pipe *p, int n_samples);
  * int16; restore refuses an int16 state on a cfloat or u8 pipe and the reverse, the pipe unchanged.
  * Create: SDRHIP_ERR_ARG (and *p = NULL) before any device work for a null argument and block_size_out <= 0. */
 int sdrhip_pipe_tuner_bank_i16(sdrhip_pipe **p, const sdrhip_tuner_bank *b, int block_size_out);
+
+/* The AM bank (sdrhip_am_bank_*) on host blocks: cfloat (input_type 0, sdrhip_pipe_push / _input_buffer), u8 IQ (1, _push_u8 /
+ * _input_buffer_u8) or int16 IQ (2, _push_i16 / _input_buffer_i16) blocks in, every channel's audio out in blocks of exactly
+ * block_size_out FLOATS through sdrhip_pipe_pop_rows / sdrhip_pipe_rows (sdrhip_pipe_pop with one channel).
+ * Definition: channel j's blocks are sdrhip_pipe_tuner_bank's blocks of the same pushes, put through `magnitude` (amDemod) and, when
+ * the bank was created with dc_block = 1, through dcBlocker from (0, 0) (`func 0 0`, Filter.hs:731) over the whole stream: both are
+ * independent of the block sizes.  Bit for bit, for every sequence of block sizes, coalesced or adaptive.
+ * Machinery: sdrhip_pipe_tuner_bank's, with one float per output -- the [carried tail | staged] copy, the 16-byte alignment of the
+ * first window in device memory, equal blocks as ONE envelope run with the block size as seam_block (one envelope tile launch,
+ * sdrhip_debug_am_bank_launches), a block of another size as the all-Cross envelope launch over the outputs that straddle the
+ * boundary (sdrhip_debug_am_bank_cross_launches) plus one run with seam_block 0.  The envelope launches are the AM bank's fused route
+ * wherever it fits, whatever the bank's route setting and auto rule (those belong to sdrhip_am_bank_run); a bank of another order or
+ * factor goes through the tuner bank and amDemod's rows form.  The input is NEVER read in place, whatever the row count (a stated choice:
+ * the FM bank stream's sweep found no in-place region): up to 512 KiB a submission is one copy and its launches on one stream.
+ * dcBlocker runs behind the envelope on the device: the K state pairs live in device memory, zero at create, and there is no host
+ * synchronisation between pushes.  ORDERING: dcBlocker makes consecutive submissions depend on each other, so every launch of a pipe
+ * with dc_block goes to ONE compute stream (the engine's first) and is ordered behind the previous submission's by that stream; without
+ * dc_block the submissions stay as independent as sdrhip_pipe_tuner_bank's (a stream per slot).
+ * sdrhip_pipe_set_coalesce / _set_adaptive, sdrhip_pipe_flush / _poll as for sdrhip_pipe_tuner_bank; the push call of another input
+ * type is SDRHIP_ERR_ARG.  Save / restore: the rows state of sdrhip_pipe_tuner_bank plus dc_block and the 2 K dcBlocker floats (save
+ * flushes, then reads them back, as the dcBlocker Pipe's save); restore refuses another kind, row count, input type, block_size_out,
+ * factor, tap count or dc_block and a truncated state, with the pipe unchanged.  The kind number is a new one at the end: states of
+ * every other kind keep their bytes.  SDRHIP_ERR_ARG (and *p = NULL) before any device work for a null bank, block_size_out <= 0 and
+ * an input_type outside 0 .. 2.  The AM bank (and its tuner bank) is borrowed and must outlive the pipe. */
+int sdrhip_pipe_am_bank(sdrhip_pipe **p, const sdrhip_am_bank *b, int block_size_out, int input_type);
 int sdrhip_pipe_push_i16(sdrhip_pipe *p, const int16_t *iq, int n_samples);
 int16_t *sdrhip_pipe_input_buffer_i16(sdrhip_pipe *p, int n_samples);
 int sdrhip_pipe_pop_rows(sdrhip_pipe *p, float *out, int64_t row_stride, int max_blocks);

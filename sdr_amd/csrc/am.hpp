@@ -11,4 +11,17 @@ void launch_am_demod_rows(hipStream_t s, int rows, const float* d_in_iq, int64_t
                           int64_t n);
 long long am_demod_launch_count();   // diagnostics: kernel launches so far
 
+// Data.Complex.magnitude at Float: exponent 0 = 0, otherwise frexp's exponent (denormals normalised); scaleFloat = ldexpf with one
+// rounding; sqrtf is correctly rounded (hipcc's default).  One copy for kernels_am.hip and the envelope form of the tuner bank's
+// kernels (kernels_tuner_bank.hip); kernels_agc.hip keeps its own.
+__device__ __forceinline__ float am_magnitude(float re, float im)
+{
+    int er, ei;
+    (void)frexpf(re, &er);
+    (void)frexpf(im, &ei);
+    const int k = er > ei ? er : ei;
+    const float a = ldexpf(re, -k), b = ldexpf(im, -k);
+    return ldexpf(sqrtf(a * a + b * b), k);
+}
+
 }  // namespace sdrhip

@@ -125,8 +125,24 @@ int tuner_bank_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, InFm
 int tuner_bank_cross_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out,
                          int64_t out_stride, int64_t k_begin, int64_t k_end);
 
+// The AM bank (include/sdr_hip.h, am_bank.cpp): a BORROWED tuner bank, the envelope of each of its rows and, with dc_block, dcBlocker.
+struct AmBankDesc {
+    const TunerBankDesc* tb = nullptr;
+    int dc_block = 0;
+    mutable int route = 0;                     // 0 = auto, 1 = fused, 2 = composed
+};
+// For the bank's Pipe (pipes.cpp), which owns its scratch, runs dcBlocker itself and has no route setting: the envelope rows alone,
+// d_env + j * env_stride floats.  am_bank_envelope: outputs [k_begin, k_end) by the fused launch set where it fits (seam_block >= 0),
+// else by the tuner bank into d_iq (channels rows of 2 * row_floats floats, 16-byte aligned; null = no fall-back: SDRHIP_ERR_ARG) and
+// amDemod's rows form.  am_bank_envelope_cross: every output Cross, one launch (k_tuner_bank_cross in its envelope form).
+int am_bank_envelope(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_env, int64_t env_stride,
+                     int64_t k_begin, int64_t k_end, int64_t seam_block, float* d_iq, int64_t row_floats);
+int am_bank_envelope_cross(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_env,
+                           int64_t env_stride, int64_t k_begin, int64_t k_end);
+
 }  // namespace sdrhip
 
+struct sdrhip_am_bank : sdrhip::AmBankDesc {};
 struct sdrhip_filter : sdrhip::FirDesc {};
 struct sdrhip_decimator : sdrhip::FirDesc {};
 struct sdrhip_resampler : sdrhip::ResampDesc {};

@@ -383,6 +383,23 @@ constexpr int kTunerBankMaxChannels = 32;
 bool launch_tuner_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in,
                        InFmt fmt, float* d_out, int64_t out_stride, const float* d_tables, int channels, const int* offsets,
                        const int* periods, bool counts_as_bank);
+// What a kernel of the bank stores per finished output (`int OUT` template argument beside FMT): the complex value, or its
+// Data.Complex magnitude as one float (am.hpp: am_magnitude) -- the AM bank's envelope form.
+enum OutKind : int { OUT_IQ = 0, OUT_ENV = 1 };
+// launch_tuner_bank's launch set in the envelope form (am_bank.cpp): row j is g.count FLOATS at d_out + j * out_stride, any
+// out_stride >= g.count (odd ones included) when there is more than one channel, d_out at any float address.  Shapes and input
+// alignment as launch_tuner_bank; false = not this shape, nothing launched.  Counts in am_bank_launch_count (int16 input also in
+// tuner_i16_launch_count) and in no other counter; its fix-up launch counts in am_bank_fixup_launch_count.
+bool launch_am_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in,
+                    InFmt fmt, float* d_out, int64_t out_stride, const float* d_tables, int channels, const int* offsets,
+                    const int* periods);
+// launch_tuner_bank_cross in the envelope form: the Cross part of a ragged push of the AM bank's Pipe (pipes.cpp).  Float rows, any
+// out_stride >= g.count with more than one channel, d_out at any float address; false = refused, nothing launched.
+bool launch_am_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_taps, const void* d_in, InFmt fmt, float* d_out,
+                          int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods);
+long long am_bank_cross_launch_count();   // diagnostics: launches of the all-Cross envelope kernel
+long long am_bank_launch_count();         // diagnostics: envelope tile launches, every format
+long long am_bank_fixup_launch_count();   // diagnostics: envelope fix-up launches
 long long tuner_bank_launch_count();    // diagnostics: banked launches, every format
 long long tuner_i16_launch_count();     // diagnostics: int16 launches of the tile kernel, bank or one-row
 // Outputs [g.k_begin, g.k_begin + g.count) of every channel in the reference's sequential order, all of them (g.seamBI is not read):

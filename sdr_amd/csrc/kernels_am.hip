@@ -3,8 +3,8 @@
 //     out[i] = magnitude (in[2i] :+ in[2i+1])
 //
 // `magnitude` is GHC base's Data.Complex.magnitude at Float, the function agc steps with (kernels_agc.hip: agc_magnitude, restated
-// here so that file's code stays as it is): scale both parts by 2^-k, k the larger frexp exponent, square, add, sqrt, scale
-// back.  Not sqrtf(re*re + im*im) and not hypotf: they differ where a square under- or overflows, and a correctly rounded hypot
+// as am_magnitude in am.hpp so that file's code stays as it is): scale both parts by 2^-k, k the larger frexp exponent, square, add,
+// sqrt, scale back.  Not sqrtf(re*re + im*im) and not hypotf: they differ where a square under- or overflows, and a correctly rounded hypot
 // differs on about one ordinary sample in six.  The build's -ffp-contract=off keeps a*a + b*b unfused.
 //
 // Non-finite input: frexpf's exponent of Inf and NaN is 0 on the device (v_frexp_exp_i32_f32) as in the model, so k is the finite
@@ -19,17 +19,7 @@
 
 namespace sdrhip {
 
-// Data.Complex.magnitude at Float: exponent 0 = 0, otherwise frexp's exponent (denormals normalised); scaleFloat = ldexpf with one
-// rounding; sqrtf is correctly rounded (hipcc's default).
-__device__ __forceinline__ float am_magnitude(float re, float im)
-{
-    int er, ei;
-    (void)frexpf(re, &er);
-    (void)frexpf(im, &ei);
-    const int k = er > ei ? er : ei;
-    const float a = ldexpf(re, -k), b = ldexpf(im, -k);
-    return ldexpf(sqrtf(a * a + b * b), k);
-}
+// am_magnitude (Data.Complex.magnitude at Float): am.hpp, shared with the envelope form of the tuner bank's kernels.
 
 // LA / SA = access width the row starts allow on the load / store side: 2 = 16-byte, 1 = 8-byte, 0 = 4-byte (any float pointer).
 // Quad q of a row is its input floats [8q, 8q + 8) and output floats [4q, 4q + 4): a multiple of 16 bytes from the row start on

@@ -30,6 +30,14 @@
 // tile are Stage<T, FMT, NT> and tuner_store<T, FMT, NT>, one sample of the sequential-order kernels is tuner_sample<FMT>.  Every
 // launch writes the bits of the cfloat launch on the converted samples.  The one-row tuner on int16 has no kernel of its own: its
 // fused route is k_tuner_bank_c4 with ONE channel (table offset 0), a launch that counts as an int16 launch and not as a banked one.
+//
+// Output kinds: k_tuner_bank_c4, k_tuner_bank_crossfix and k_tuner_bank_cross take OUT beside FMT.  OUT_IQ stores the finished (re, im), as above.  OUT_ENV
+// (the AM bank, am_bank.cpp) stores am_magnitude(re, im) (am.hpp: Data.Complex.magnitude at Float) of the SAME finished output, one
+// float per output, into float rows out_stride floats apart: staging, mix, MAC walk, fold and Cross outputs are untouched, so the
+// value under the magnitude is the OUT_IQ launch's bit for bit.  Any out_stride >= count, any float-aligned row: a thread's pair is one
+// 8-byte store where row pointer + output index is 8-byte aligned and both outputs exist, 4-byte stores otherwise (the two
+// sequential-order kernels hold one output a thread: 4-byte stores).
+#include "am.hpp"
 #include "decimate_tile.hpp"
 #include "tuner_mix.hpp"
 
@@ -41,6 +49,12 @@ static std::atomic<long long> g_tuner_bank_cross_launches{0};
 long long tuner_bank_cross_launch_count() { return g_tuner_bank_cross_launches.load(); }
 static std::atomic<long long> g_tuner_i16_launches{0};
 long long tuner_i16_launch_count() { return g_tuner_i16_launches.load(); }
+static std::atomic<long long> g_am_bank_launches{0};
+long long am_bank_launch_count() { return g_am_bank_launches.load(); }
+static std::atomic<long long> g_am_bank_fixup_launches{0};
+long long am_bank_fixup_launch_count() { return g_am_bank_fixup_launches.load(); }
+static std::atomic<long long> g_am_bank_cross_launches{0};
+long long am_bank_cross_launch_count() { return g_am_bank_cross_launches.load(); }
 
 namespace {
 
@@ -52,7 +66,7 @@ struct BankChannels {
     int ph[kTunerBankMaxChannels];             // (k_begin D) mod period: the host's one 64-bit modulo per channel and launch
 };
 
-template <int D, int P, int R, int NT, int FMT, int TC, bool GUARD>
+template <int D, int P, int R, int NT, int FMT, int OUT, int TC, bool GUARD>
 __global__ void __launch_bounds__(NT) k_tuner_bank_c4(const void* __restrict__ in, int64_t x0 /* sample index of output 0's window in `in` */,
                                                       int count, const float* __restrict__ taps /* plain */, float* __restrict__ out,
                                                       int p_eff /* GUARD: taps of the filter (multiple of TC, <= P) */,
@@ -115,6 +129,22 @@ __global__ void __launch_bounds__(NT) k_tuner_bank_c4(const void* __restrict__ i
         }
         if (any) inline_cross_outputs<D, R, T, TC, GUARD>(win, taps, plen, cross, res);
     }
+    if constexpr (OUT == OUT_ENV) {
+        // one float per output: the pair as ONE 8-byte store where the row's pointer plus the output index is 8-byte aligned (the
+        // ROW's pointer decides again: an odd stride or a launch cut at an odd output moves it) and both lie inside count
+        float env[R];
+#pragma unroll
+        for (int r = 0; r < R; r++) env[r] = am_magnitude(res[r].x, res[r].y);
+        float* dst = out + o;
+        if (R == 2 && o + R <= count && (reinterpret_cast<uintptr_t>(dst) & 7) == 0) {
+            *reinterpret_cast<float2*>(dst) = make_float2(env[0], env[R - 1]);
+        } else {
+#pragma unroll
+            for (int r = 0; r < R; r++)
+                if (o + r < count) dst[r] = env[r];
+        }
+        return;
+    }
     // the ROW's pointer decides: an odd row of a stride that is 2 (mod 4), or a launch cut at an odd output, takes the float2 stores
     if (R % 2 == 0 && o + R <= count && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
         float4* dst = reinterpret_cast<float4*>(out + 2 * (int64_t)o);
@@ -128,7 +158,7 @@ __global__ void __launch_bounds__(NT) k_tuner_bank_c4(const void* __restrict__ i
 }
 
 // Cross outputs of every channel, one thread per candidate slot of a seam and channel (k_tuner_crossfix with the channel axis)
-template <int FMT>
+template <int FMT, int OUT>
 __global__ void __launch_bounds__(256) k_tuner_bank_crossfix(Geom g, const float* __restrict__ xtaps, const void* __restrict__ in,
                                                               float* __restrict__ out, int64_t first_seam, int nseams, int per_seam,
                                                               const float2* __restrict__ osc, BankChannels bank)
@@ -154,13 +184,14 @@ __global__ void __launch_bounds__(256) k_tuner_bank_crossfix(Geom g, const float
         re = re + mx.x * xtaps[j];
         im = im + mx.y * xtaps[j];
     }
-    *reinterpret_cast<float2*>(out + 2 * (m - g.k_begin)) = make_float2(re, im);
+    if constexpr (OUT == OUT_ENV) out[m - g.k_begin] = am_magnitude(re, im);
+    else *reinterpret_cast<float2*>(out + 2 * (m - g.k_begin)) = make_float2(re, im);
 }
 
 // Outputs [g.k_begin, g.k_begin + g.count) of every channel, ALL of them Cross (the straddlers of a boundary between two blocks of
 // unequal size, which no seam_block describes): k_tuner_bank_crossfix's body on an explicit range instead of a seam's candidate
 // slots.  Block b: channel b % K, outputs of block b / K.
-template <int FMT>
+template <int FMT, int OUT>
 __global__ void __launch_bounds__(256) k_tuner_bank_cross(Geom g, const float* __restrict__ xtaps, const void* __restrict__ in,
                                                            float* __restrict__ out, const float2* __restrict__ osc, BankChannels bank)
 {
@@ -180,10 +211,11 @@ __global__ void __launch_bounds__(256) k_tuner_bank_cross(Geom g, const float* _
         re = re + mx.x * xtaps[j];
         im = im + mx.y * xtaps[j];
     }
-    *reinterpret_cast<float2*>(out + 2 * (int64_t)t) = make_float2(re, im);
+    if constexpr (OUT == OUT_ENV) out[t] = am_magnitude(re, im);
+    else *reinterpret_cast<float2*>(out + 2 * (int64_t)t) = make_float2(re, im);
 }
 
-template <int D, int P, int FMT, int TC, bool GUARD>
+template <int D, int P, int FMT, int OUT, int TC, bool GUARD>
 void launch_tuner_bank_c4(hipStream_t s, const Geom& g, const float* taps, const void* in, float* out, bool inline_cross, bool* inlined,
                           const float* d_tables, const BankChannels& bank)
 {
@@ -191,7 +223,7 @@ void launch_tuner_bank_c4(hipStream_t s, const Geom& g, const float* taps, const
     using T = Tile<D, P, R, NT>;
     // the dynamic-LDS attribute is per device: one flag per (instantiation, device); idempotent, a race only repeats the call
     static std::atomic<bool> attr_set[64];
-    auto kern = k_tuner_bank_c4<D, P, R, NT, FMT, TC, GUARD>;
+    auto kern = k_tuner_bank_c4<D, P, R, NT, FMT, OUT, TC, GUARD>;
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= 64 || !attr_set[dev]) {
@@ -212,11 +244,11 @@ void launch_tuner_bank_c4(hipStream_t s, const Geom& g, const float* taps, const
 }
 
 // the instantiation that serves the launch's shape (tuner_fused_fits has admitted it)
-template <int FMT>
+template <int FMT, int OUT>
 void launch_tuner_bank_c4_shape(hipStream_t s, const Geom& g, int P, const float* taps, const void* in, float* out, bool inl, bool* inlined,
                                 const float* d_tables, const BankChannels& bank)
 {
-#define TUNER_BANK(DV, TCV, GV) launch_tuner_bank_c4<DV, 128, FMT, TCV, GV>(s, g, taps, in, out, inl, inlined, d_tables, bank)
+#define TUNER_BANK(DV, TCV, GV) launch_tuner_bank_c4<DV, 128, FMT, OUT, TCV, GV>(s, g, taps, in, out, inl, inlined, d_tables, bank)
     if (g.D == 4) TUNER_BANK(4, 4, true);
     else if (g.D == 16) { if (P % 8 == 0) TUNER_BANK(16, 8, true); else TUNER_BANK(16, 4, true); }
     else if (P == 128) TUNER_BANK(8, 8, false);      // the exact-length walk for the full 128 taps
@@ -225,16 +257,21 @@ void launch_tuner_bank_c4_shape(hipStream_t s, const Geom& g, int P, const float
 #undef TUNER_BANK
 }
 
-}  // namespace
-
-bool launch_tuner_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in,
-                       InFmt fmt, float* d_out, int64_t out_stride, const float* d_tables, int channels, const int* offsets,
-                       const int* periods, bool counts_as_bank)
+// launch_tuner_bank (OUT_IQ: out_stride in floats of complex rows) and launch_am_bank (OUT_ENV: one float per output)
+template <int OUT>
+bool launch_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in, InFmt fmt,
+                 float* d_out, int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods,
+                 bool counts_as_bank)
 {
-    if (channels < 1 || channels > kTunerBankMaxChannels || (out_stride & 1) != 0) return false;
-    if (channels > 1 && out_stride < 2 * (int64_t)g.count) return false;
+    constexpr int64_t FPO = OUT == OUT_ENV ? 1 : 2;         // floats per output
+    if (channels < 1 || channels > kTunerBankMaxChannels) return false;
+    if (OUT == OUT_IQ && (out_stride & 1) != 0) return false;
+    if (channels > 1 && out_stride < FPO * (int64_t)g.count) return false;
+    // tuner_fused_fits reads d_out for the 8-byte alignment of complex rows alone; envelope rows are floats at any float address
+    if (OUT == OUT_ENV && (reinterpret_cast<uintptr_t>(d_out) & 3) != 0) return false;
+    const void* fit_out = OUT == OUT_ENV ? nullptr : d_out;
     for (int j = 0; j < channels; j++)
-        if (!tuner_fused_fits(g, P, d_cross_taps != nullptr, d_in, fmt, d_out, periods[j])) return false;
+        if (!tuner_fused_fits(g, P, d_cross_taps != nullptr, d_in, fmt, fit_out, periods[j])) return false;
     BankChannels bank = {};
     bank.out_stride = out_stride;
     bank.channels = channels;
@@ -247,34 +284,60 @@ bool launch_tuner_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, 
     const bool inl = g.seamBI > 0 && g.count <= 5 * (int64_t)small_launch_outputs();
     bool inlined = false;
     switch (fmt) {
-    case IN_U8: launch_tuner_bank_c4_shape<IN_U8>(s, g, P, d_plain_taps, d_in, d_out, inl, &inlined, d_tables, bank); break;
-    case IN_I16: launch_tuner_bank_c4_shape<IN_I16>(s, g, P, d_plain_taps, d_in, d_out, inl, &inlined, d_tables, bank); break;
-    default: launch_tuner_bank_c4_shape<IN_CF32>(s, g, P, d_plain_taps, d_in, d_out, inl, &inlined, d_tables, bank); break;
+    case IN_U8: launch_tuner_bank_c4_shape<IN_U8, OUT>(s, g, P, d_plain_taps, d_in, d_out, inl, &inlined, d_tables, bank); break;
+    case IN_I16: launch_tuner_bank_c4_shape<IN_I16, OUT>(s, g, P, d_plain_taps, d_in, d_out, inl, &inlined, d_tables, bank); break;
+    default: launch_tuner_bank_c4_shape<IN_CF32, OUT>(s, g, P, d_plain_taps, d_in, d_out, inl, &inlined, d_tables, bank); break;
     }
     if (fmt == IN_I16) g_tuner_i16_launches.fetch_add(1, std::memory_order_relaxed);
-    if (counts_as_bank) g_tuner_bank_launches.fetch_add(1, std::memory_order_relaxed);
+    if (OUT == OUT_ENV) g_am_bank_launches.fetch_add(1, std::memory_order_relaxed);
+    else if (counts_as_bank) g_tuner_bank_launches.fetch_add(1, std::memory_order_relaxed);
 
     const SeamSpan sp = seam_span(g);
     if (sp.nseams > 0 && !inlined) {
         const unsigned per_channel = (unsigned)(((int64_t)sp.nseams * sp.per + 255) / 256);
         const dim3 grid(per_channel * (unsigned)channels), block(256);
-        auto fix = fmt == IN_U8 ? k_tuner_bank_crossfix<IN_U8> : fmt == IN_I16 ? k_tuner_bank_crossfix<IN_I16> : k_tuner_bank_crossfix<IN_CF32>;
+        auto fix = fmt == IN_U8 ? k_tuner_bank_crossfix<IN_U8, OUT> : fmt == IN_I16 ? k_tuner_bank_crossfix<IN_I16, OUT>
+                                                                                    : k_tuner_bank_crossfix<IN_CF32, OUT>;
         hipLaunchKernelGGL(fix, grid, block, 0, s, g, d_cross_taps, d_in, d_out, sp.first, sp.nseams, sp.per,
                            reinterpret_cast<const float2*>(d_tables), bank);
+        if (OUT == OUT_ENV) g_am_bank_fixup_launches.fetch_add(1, std::memory_order_relaxed);
     }
     return true;
 }
 
-bool launch_tuner_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_taps, const void* d_in, InFmt fmt, float* d_out,
-                             int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods)
+}  // namespace
+
+bool launch_tuner_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in,
+                       InFmt fmt, float* d_out, int64_t out_stride, const float* d_tables, int channels, const int* offsets,
+                       const int* periods, bool counts_as_bank)
+{
+    return launch_bank<OUT_IQ>(s, g, d_plain_taps, P, d_cross_taps, d_in, fmt, d_out, out_stride, d_tables, channels, offsets, periods,
+                               counts_as_bank);
+}
+
+bool launch_am_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in,
+                    InFmt fmt, float* d_out, int64_t out_stride, const float* d_tables, int channels, const int* offsets,
+                    const int* periods)
+{
+    return launch_bank<OUT_ENV>(s, g, d_plain_taps, P, d_cross_taps, d_in, fmt, d_out, out_stride, d_tables, channels, offsets, periods,
+                                false);
+}
+
+namespace {
+// launch_tuner_bank_cross (OUT_IQ) and launch_am_bank_cross (OUT_ENV: float rows, any out_stride >= g.count, 4-byte stores)
+template <int OUT>
+bool launch_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_taps, const void* d_in, InFmt fmt, float* d_out,
+                       int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods)
 {
     // launch_tuner_bank's refusals for channels and stride; one thread reads its window sample by sample: no alignment beyond the
     // element's own (a float, a u8 pair, an int16 pair)
     static const uintptr_t kInMask[3] = {/* IN_CF32 */ 7, /* IN_U8 */ 1, /* IN_I16 */ 3};
-    if (channels < 1 || channels > kTunerBankMaxChannels || (out_stride & 1) != 0) return false;
-    if (channels > 1 && out_stride < 2 * (int64_t)g.count) return false;
+    constexpr int64_t FPO = OUT == OUT_ENV ? 1 : 2;         // floats per output
+    if (channels < 1 || channels > kTunerBankMaxChannels) return false;
+    if (OUT == OUT_IQ && (out_stride & 1) != 0) return false;
+    if (channels > 1 && out_stride < FPO * (int64_t)g.count) return false;
     if (g.I != 1 || g.count <= 0 || g.k_begin < 0 || g.k_begin * g.D < g.in_base || d_cross_taps == nullptr) return false;
-    if ((reinterpret_cast<uintptr_t>(d_out) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_in) & kInMask[fmt]) != 0) return false;
+    if ((reinterpret_cast<uintptr_t>(d_out) & (OUT == OUT_ENV ? 3 : 7)) != 0 || (reinterpret_cast<uintptr_t>(d_in) & kInMask[fmt]) != 0) return false;
     BankChannels bank = {};
     bank.out_stride = out_stride;
     bank.channels = channels;
@@ -285,10 +348,23 @@ bool launch_tuner_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_
     }
     const unsigned per_channel = (unsigned)(((int64_t)g.count + 255) / 256);        // at most 2^23: times 32 channels fits a 1-D grid
     const dim3 grid(per_channel * (unsigned)channels), block(256);
-    auto cross = fmt == IN_U8 ? k_tuner_bank_cross<IN_U8> : fmt == IN_I16 ? k_tuner_bank_cross<IN_I16> : k_tuner_bank_cross<IN_CF32>;
+    auto cross = fmt == IN_U8 ? k_tuner_bank_cross<IN_U8, OUT> : fmt == IN_I16 ? k_tuner_bank_cross<IN_I16, OUT> : k_tuner_bank_cross<IN_CF32, OUT>;
     hipLaunchKernelGGL(cross, grid, block, 0, s, g, d_cross_taps, d_in, d_out, reinterpret_cast<const float2*>(d_tables), bank);
-    g_tuner_bank_cross_launches.fetch_add(1, std::memory_order_relaxed);
+    (OUT == OUT_ENV ? g_am_bank_cross_launches : g_tuner_bank_cross_launches).fetch_add(1, std::memory_order_relaxed);
     return true;
+}
+}  // namespace
+
+bool launch_tuner_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_taps, const void* d_in, InFmt fmt, float* d_out,
+                             int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods)
+{
+    return launch_bank_cross<OUT_IQ>(s, g, d_cross_taps, d_in, fmt, d_out, out_stride, d_tables, channels, offsets, periods);
+}
+
+bool launch_am_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_taps, const void* d_in, InFmt fmt, float* d_out,
+                          int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods)
+{
+    return launch_bank_cross<OUT_ENV>(s, g, d_cross_taps, d_in, fmt, d_out, out_stride, d_tables, channels, offsets, periods);
 }
 
 }  // namespace sdrhip

@@ -36,7 +36,7 @@
 
 using namespace sdrhip;
 
-enum PipeKind { PK_FILTER, PK_DECIMATOR, PK_RESAMPLER, PK_DEMOD, PK_DCBLOCK, PK_AGC, PK_TUNER, PK_TUNER_BANK, PK_AM };   // saved states hold the number: new kinds go at the end
+enum PipeKind { PK_FILTER, PK_DECIMATOR, PK_RESAMPLER, PK_DEMOD, PK_DCBLOCK, PK_AGC, PK_TUNER, PK_TUNER_BANK, PK_AM, PK_AM_BANK };   // saved states hold the number: new kinds go at the end
 
 struct sdrhip_pipe {
     PipeKind kind;
@@ -48,6 +48,13 @@ struct sdrhip_pipe {
     // per element), and stay in that type up to the kernels' loaders
     const TunerBankDesc* bank = nullptr;
     InFmt fmt = IN_CF32;
+    // PK_AM_BANK: the AM bank's Pipe -- the tuner bank's Pipe with ONE float per output (the envelope; bank = the AM bank's tuner bank)
+    // and, with am_dc, dcBlocker behind it on the device: its K state pairs live in dc_state, the envelope rows and dcBlocker's
+    // workspace in dc_ws, and EVERY submission goes to compute stream 0, so each is ordered behind its predecessor by the stream.
+    // am_iq[slot]: complex rows of a submission the fused launch does not serve (another order or factor), one buffer per slot because
+    // without am_dc the slots' submissions run on streams of their own.
+    bool am_dc = false;
+    DevBuf am_iq[HostStream::kMaxSlots];
     int block_out = 0;
     bool cplx_in = false, cplx_out = false;
     int I = 1, D = 1, Lp = 1;
@@ -184,8 +191,13 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
     // tile over the link (the reason the FM bank's stream gives, chain.cpp).  Up to the direct bound such a submission is ONE copy
     // into device memory on the slot's own stream and the launch behind it.
     const int rows = p->rows();
-    const HostStream::Route route = !direct ? HostStream::kCopyEngines : rows > 1 ? HostStream::kSlotStream : HostStream::kInPlace;
-    if (p->kind == PK_TUNER_BANK && route != HostStream::kInPlace) {
+    // The AM bank's Pipe never reads in place, whatever the row count (a stated choice: the FM bank stream's sweep found no in-place
+    // region), and with dcBlocker all its launches share compute stream 0: a submission's dcBlocker starts from the state its
+    // predecessor's left on the device
+    const bool am = p->kind == PK_AM_BANK;
+    if (am && p->am_dc) cs = e.compute[0];
+    const HostStream::Route route = !direct ? HostStream::kCopyEngines : (rows > 1 || am) ? HostStream::kSlotStream : HostStream::kInPlace;
+    if ((p->kind == PK_TUNER_BANK || am) && route != HostStream::kInPlace) {
         // the copy may land anywhere in the slot's device buffer: put the banked launch's first window on a 16-byte boundary there,
         // which the staging buffer cannot promise once a block had an odd size
         const int64_t k0 = uniform_seam > 0 ? m_done : m_split;
@@ -196,6 +208,41 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
     int rc = e.submit(route, cs, first, (size_t)(tail + n) * ein, rows * row_floats, [&](hipStream_t s, const void* d_in, void* d_out) {
         const float* din = (const float*)d_in;
         float* dout = (float*)d_out;
+        if (p->kind == PK_AM_BANK) {
+            // every row [cross | one] as ENVELOPES, one float per output: the fused launch set where it fits (dev_skew has aligned the
+            // first window), else tuner bank + amDemod rows through the slot's complex scratch
+            const int K = rows;
+            const int64_t count = m_end - m_done, np = (count + 3) & ~(int64_t)3;
+            int r;
+            float* env = dout;
+            int64_t env_stride = row_floats;
+            if (p->am_dc) {
+                const size_t need = (size_t)K * (size_t)np * sizeof(float) + dc_blocker_rows_workspace_bytes(K, count);
+                if (need > p->dc_ws.cap) SDRHIP_CHECK_HIP(hipStreamSynchronize(s));            // growing frees the old buffer
+                if ((r = p->dc_ws.ensure(need)) != SDRHIP_OK) return r;
+                env = (float*)p->dc_ws.p;
+                env_stride = np;
+            }
+            // (the complex scratch is kept ready for every submission: whether the fused launch takes one is the launcher's decision)
+            DevBuf& b = p->am_iq[si];
+            const size_t iq_bytes = (size_t)K * 2 * (size_t)np * sizeof(float);
+            if (iq_bytes > b.cap) SDRHIP_CHECK_HIP(hipStreamSynchronize(s));
+            if ((r = b.ensure(iq_bytes)) != SDRHIP_OK) return r;
+            float* iq = (float*)b.p;
+            if (uniform_seam > 0) {
+                r = am_bank_envelope(p->bank, s, d_in, p->fmt, in_base, env, env_stride, m_done, m_end, uniform_seam, iq, np);
+            } else {
+                const int64_t ncross = m_split - m_done;
+                r = SDRHIP_OK;
+                if (ncross > 0) r = am_bank_envelope_cross(p->bank, s, d_in, p->fmt, in_base, env, env_stride, m_done, m_split);
+                if (r == SDRHIP_OK) r = am_bank_envelope(p->bank, s, d_in, p->fmt, in_base, env + ncross, env_stride, m_split, m_end, 0, iq, np);
+            }
+            if (r != SDRHIP_OK || !p->am_dc) return r;
+            launch_dc_blocker_rows(s, K, count, env, np, dout, row_floats, (const float*)p->dc_state.p, (float*)p->dc_state.p,
+                                   env + (size_t)K * (size_t)np, 0);
+            SDRHIP_CHECK_HIP(hipGetLastError());
+            return SDRHIP_OK;
+        }
         if (p->kind == PK_TUNER_BANK) {
             // every row [cross | one], row_floats apart: the bank's own rule picks the banked launch or channel by channel
             if (uniform_seam > 0) return tuner_bank_run(p->bank, s, d_in, p->fmt, in_base, dout, row_floats, m_done, m_end, uniform_seam);
@@ -356,6 +403,32 @@ int sdrhip_pipe_tuner_bank_i16(sdrhip_pipe** pp, const sdrhip_tuner_bank* b, int
     if (rc != SDRHIP_OK) return rc;
     (*pp)->bank = b;
     if (b->ch.size() > 1) (*pp)->eng.set_rows((int)b->ch.size());
+    return SDRHIP_OK;
+}
+
+int sdrhip_pipe_am_bank(sdrhip_pipe** pp, const sdrhip_am_bank* a, int block_size_out, int input_type)
+{
+    // (all of it before pipe_new, whose engine creates streams: a refused create has done no device work)
+    SDRHIP_REQUIRE(pp != nullptr, "sdrhip_pipe_am_bank");
+    *pp = nullptr;
+    SDRHIP_REQUIRE(a != nullptr, "sdrhip_pipe_am_bank: null bank");
+    SDRHIP_REQUIRE(block_size_out > 0, "sdrhip_pipe_am_bank: block_size_out > 0");
+    SDRHIP_REQUIRE(input_type >= 0 && input_type <= 2, "sdrhip_pipe_am_bank: input_type is 0 (cfloat blocks), 1 (u8 IQ) or 2 (int16 IQ)");
+    const TunerBankDesc* b = a->tb;
+    const FirDesc* f = &b->ch[0]->fir;
+    const int K = (int)b->ch.size();
+    int rc = pipe_new(pp, PK_AM_BANK, f, nullptr, block_size_out, true, false, 1, f->factor, f->Lp, (InFmt)input_type);
+    if (rc != SDRHIP_OK) return rc;
+    sdrhip_pipe* p = *pp;
+    p->bank = b;
+    p->am_dc = a->dc_block != 0;
+    if (K > 1) p->eng.set_rows(K);
+    if (p->am_dc) {
+        const size_t bytes = (size_t)K * 2 * sizeof(float);
+        if ((rc = p->dc_state.ensure(bytes < 16 ? 16 : bytes)) != SDRHIP_OK) { delete p; *pp = nullptr; return rc; }
+        hipError_t e = hipMemsetAsync(p->dc_state.p, 0, bytes, p->eng.compute[0]);   // every channel: func 0 0, Filter.hs:731
+        if (e != hipSuccess) { set_error("sdrhip_pipe_am_bank: %s", hipGetErrorString(e)); delete p; *pp = nullptr; return SDRHIP_ERR_HIP; }
+    }
     return SDRHIP_OK;
 }
 
@@ -620,6 +693,14 @@ struct PipeStateRows {
     int32_t rows, input_u8;
 };
 static uint32_t pipe_state_version(const sdrhip_pipe* p) { return p->rows() > 1 || p->fmt != IN_CF32 ? 2u : 1u; }
+// The AM bank's Pipe appends, behind everything else: dc_block, the number of dcBlocker floats (2 K or 0), and those floats.
+struct PipeStateAm {
+    int32_t dc_block, n_floats;
+};
+static size_t pipe_state_am_bytes(const sdrhip_pipe* p)
+{
+    return p->kind != PK_AM_BANK ? 0 : sizeof(PipeStateAm) + (p->am_dc ? (size_t)p->rows() * 2 * sizeof(float) : 0);
+}
 static size_t pipe_state_header_bytes(const sdrhip_pipe* p) { return sizeof(PipeStateHeader) + (pipe_state_version(p) == 2 ? sizeof(PipeStateRows) : 0); }
 }  // namespace
 
@@ -630,7 +711,8 @@ size_t sdrhip_pipe_state_bytes(sdrhip_pipe* p)
     // slot is harvested into the fifo), so the size returned is what the save that follows needs -- whatever the ratio of
     // the stage and the size of the blocks in flight.  0 = the drain failed (sdrhip_last_error).
     if (sdrhip_pipe_flush(p) < 0) return 0;
-    return pipe_state_header_bytes(p) + p->eng.state_bytes(p->eng.hist_n, (int64_t)p->eng.pending()) + p->demod_blocks.size() * sizeof(int32_t);
+    return pipe_state_header_bytes(p) + p->eng.state_bytes(p->eng.hist_n, (int64_t)p->eng.pending()) + p->demod_blocks.size() * sizeof(int32_t) +
+           pipe_state_am_bytes(p);
 }
 
 int sdrhip_pipe_save(sdrhip_pipe* p, void* buf, size_t capacity, size_t* used)
@@ -655,7 +737,8 @@ int sdrhip_pipe_save(sdrhip_pipe* p, void* buf, size_t capacity, size_t* used)
         SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));
         SDRHIP_CHECK_HIP(hipMemcpy(h.dc, p->dc_state.p, 16, hipMemcpyDeviceToHost));
     }
-    const size_t need = pipe_state_header_bytes(p) + p->eng.state_bytes(h.hist_n, h.pending) + (size_t)h.n_blocks * sizeof(int32_t);
+    const size_t need = pipe_state_header_bytes(p) + p->eng.state_bytes(h.hist_n, h.pending) + (size_t)h.n_blocks * sizeof(int32_t) +
+                        pipe_state_am_bytes(p);
     if (capacity < need) {
         set_error("sdrhip_pipe_save: %zu bytes needed, %zu given", need, capacity);
         return SDRHIP_ERR_ARG;
@@ -667,6 +750,16 @@ int sdrhip_pipe_save(sdrhip_pipe* p, void* buf, size_t capacity, size_t* used)
     }
     unsigned char* o = p->eng.save((unsigned char*)buf + pipe_state_header_bytes(p));
     for (int len : p->demod_blocks) { const int32_t v = len; memcpy(o, &v, sizeof v); o += sizeof v; }
+    if (p->kind == PK_AM_BANK) {
+        // the flush above has harvested every submission, so the dcBlocker floats on the device are the stream's (as the dcBlocker Pipe's save)
+        const PipeStateAm x = {p->am_dc ? 1 : 0, p->am_dc ? 2 * p->rows() : 0};
+        memcpy(o, &x, sizeof x);
+        o += sizeof x;
+        if (p->am_dc) {
+            SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));
+            SDRHIP_CHECK_HIP(hipMemcpy(o, p->dc_state.p, (size_t)x.n_floats * sizeof(float), hipMemcpyDeviceToHost));
+        }
+    }
     *used = need;
     return SDRHIP_OK;
 }
@@ -692,7 +785,8 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
                    "sdrhip_pipe_restore: the state belongs to a pipe of another kind or geometry");
     SDRHIP_REQUIRE(h.hist_n >= 0 && h.hist_n <= h.head_cap && h.pending >= 0 && h.n_blocks >= 0 && h.E_prev >= h.hist_n && h.m_done >= 0,
                    "sdrhip_pipe_restore: inconsistent state");
-    if (p->kind == PK_FILTER || p->kind == PK_DECIMATOR || p->kind == PK_RESAMPLER || p->kind == PK_TUNER || p->kind == PK_TUNER_BANK) {
+    if (p->kind == PK_FILTER || p->kind == PK_DECIMATOR || p->kind == PK_RESAMPLER || p->kind == PK_TUNER || p->kind == PK_TUNER_BANK ||
+        p->kind == PK_AM_BANK) {
         // the next pending output must start inside what the pipe has seen, every output computable from those elements must be
         // done at most once, and the history must reach back to its first input (3 elements of alignment slack, 7 of u8, fir_submit):
         // otherwise the kernels would be sent in front of the staging buffer
@@ -703,8 +797,14 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
         SDRHIP_REQUIRE(h.m_done <= m_max && first_in <= h.E_prev + (p->Lp + p->D) / p->I + 1 && h.hist_n >= h.E_prev - keep_from,
                        "sdrhip_pipe_restore: the position and the history of the state do not belong together");
     }
-    SDRHIP_REQUIRE(bytes >= pipe_state_header_bytes(p) + p->eng.state_bytes(h.hist_n, h.pending) + (size_t)h.n_blocks * sizeof(int32_t),
-                   "sdrhip_pipe_restore: truncated state");
+    const size_t am_at = pipe_state_header_bytes(p) + p->eng.state_bytes(h.hist_n, h.pending) + (size_t)h.n_blocks * sizeof(int32_t);
+    SDRHIP_REQUIRE(bytes >= am_at + pipe_state_am_bytes(p), "sdrhip_pipe_restore: truncated state");
+    if (p->kind == PK_AM_BANK) {
+        PipeStateAm x;
+        memcpy(&x, (const unsigned char*)buf + am_at, sizeof x);
+        SDRHIP_REQUIRE(x.dc_block == (p->am_dc ? 1 : 0) && x.n_floats == (p->am_dc ? 2 * p->rows() : 0),
+                       "sdrhip_pipe_restore: the state belongs to an AM bank pipe of another dc_block");
+    }
     const unsigned char* in = p->eng.restore((const unsigned char*)buf + pipe_state_header_bytes(p), h.hist_n, h.pending);
     p->E_prev = h.E_prev;
     p->m_done = h.m_done;
@@ -714,6 +814,10 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
     p->last_im = h.last_im;
     p->demod_blocks.clear();
     for (int i = 0; i < h.n_blocks; i++) { int32_t v; memcpy(&v, in, sizeof v); in += sizeof v; p->demod_blocks.push_back(v); }
+    if (p->kind == PK_AM_BANK && p->am_dc) {
+        SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));       // the create call's memset
+        SDRHIP_CHECK_HIP(hipMemcpy(p->dc_state.p, in + sizeof(PipeStateAm), (size_t)p->rows() * 2 * sizeof(float), hipMemcpyHostToDevice));
+    }
     if (p->has_dev_state()) {
         SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));       // the create call's memset
         SDRHIP_CHECK_HIP(hipMemcpy(p->dc_state.p, h.dc, 16, hipMemcpyHostToDevice));

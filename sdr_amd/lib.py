@@ -124,6 +124,21 @@ lib.sdrhip_debug_tuner_bank_launches.argtypes = []
 lib.sdrhip_debug_tuner_bank_launches.restype = C.c_longlong
 lib.sdrhip_debug_tuner_bank_cross_launches.argtypes = []
 lib.sdrhip_debug_tuner_bank_cross_launches.restype = C.c_longlong
+lib.sdrhip_am_bank_create.argtypes = [C.POINTER(_vp), _vp, C.c_int]
+lib.sdrhip_am_bank_destroy.argtypes = [_vp]
+lib.sdrhip_am_bank_destroy.restype = None
+lib.sdrhip_am_bank_channels.argtypes = [_vp]
+lib.sdrhip_am_bank_set_route.argtypes = [_vp, C.c_int]
+lib.sdrhip_am_bank_workspace_bytes.argtypes = [_vp, _i64]
+lib.sdrhip_am_bank_workspace_bytes.restype = C.c_size_t
+for _n in ("sdrhip_am_bank_run", "sdrhip_am_bank_run_u8", "sdrhip_am_bank_run_i16"):
+    getattr(lib, _n).argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, C.c_size_t]
+lib.sdrhip_debug_am_bank_launches.argtypes = []
+lib.sdrhip_debug_am_bank_launches.restype = C.c_longlong
+lib.sdrhip_debug_am_bank_fixup_launches.argtypes = []
+lib.sdrhip_debug_am_bank_fixup_launches.restype = C.c_longlong
+lib.sdrhip_debug_am_bank_cross_launches.argtypes = []
+lib.sdrhip_debug_am_bank_cross_launches.restype = C.c_longlong
 
 lib.sdrhip_resampler_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.c_int]
 lib.sdrhip_resampler_num_coeffs.argtypes = [_vp]
@@ -332,6 +347,7 @@ lib.sdrhip_pipe_push_u8.argtypes = [_vp, _u8p, C.c_int]
 lib.sdrhip_pipe_input_buffer_u8.argtypes = [_vp, C.c_int]
 lib.sdrhip_pipe_input_buffer_u8.restype = _vp
 lib.sdrhip_pipe_tuner_bank_i16.argtypes = [C.POINTER(_vp), _vp, C.c_int]
+lib.sdrhip_pipe_am_bank.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int]
 lib.sdrhip_pipe_push_i16.argtypes = [_vp, _i16p, C.c_int]
 lib.sdrhip_pipe_input_buffer_i16.argtypes = [_vp, C.c_int]
 lib.sdrhip_pipe_input_buffer_i16.restype = _vp
@@ -958,6 +974,69 @@ class TunerBank(_Handle):
               "sdrhip_tuner_bank_run_i16")
 
 
+def am_bank_launches():
+    """Envelope tile launches of the AM bank's fused route so far (sdrhip_debug_am_bank_launches)."""
+    return int(lib.sdrhip_debug_am_bank_launches())
+
+
+def am_bank_fixup_launches():
+    """Envelope fix-up launches of the AM bank's fused route so far (sdrhip_debug_am_bank_fixup_launches)."""
+    return int(lib.sdrhip_debug_am_bank_fixup_launches())
+
+
+def am_bank_cross_launches():
+    """Launches of the all-Cross envelope kernel of the AM bank's Pipe so far (sdrhip_debug_am_bank_cross_launches)."""
+    return int(lib.sdrhip_debug_am_bank_cross_launches())
+
+
+class AmBank(_Handle):
+    """The AM receiver for every channel of a TunerBank: row j of a run is the envelope (Data.Complex magnitude) of the bank's complex
+    row j and, with dc_block, dcBlocker of that from the state in dc_state (2 K device floats, read and written; it belongs to output
+    k_begin, so consecutive runs over consecutive ranges on one state array are one stream).  Bit for bit TunerBank.run ->
+    am_demod_run_rows -> dc_blocker_run_rows on every route (sdr_hip.h, sdrhip_am_bank_*).  The tuner bank is borrowed: the object
+    keeps a reference to it."""
+    _destroy = lib.sdrhip_am_bank_destroy
+    ROUTE_AUTO, ROUTE_FUSED, ROUTE_COMPOSED = 0, 1, 2
+
+    def __init__(self, tuner_bank, dc_block=True):
+        super().__init__()
+        self.tuner_bank = tuner_bank
+        self.dc_block = bool(dc_block)
+        check(lib.sdrhip_am_bank_create(C.byref(self.h), tuner_bank.h, int(self.dc_block)), "sdrhip_am_bank_create")
+
+    @property
+    def channels(self):
+        return check(lib.sdrhip_am_bank_channels(self.h), "sdrhip_am_bank_channels")
+
+    def set_route(self, route):
+        """0 = auto (sdr_hip.h), 1 = fused: the envelope form of the banked launch (a launch it does not serve is an error),
+        2 = composed: the three calls of the definition."""
+        check(lib.sdrhip_am_bank_set_route(self.h, int(route)), "sdrhip_am_bank_set_route")
+
+    def workspace_bytes(self, count):
+        return int(lib.sdrhip_am_bank_workspace_bytes(self.h, int(count)))
+
+    def _run(self, fn, name, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block, dc_state, workspace, workspace_bytes, stream):
+        check(fn(self.h, stream, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block, dc_state, workspace, workspace_bytes), name)
+
+    def run(self, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block=0, dc_state=None, workspace=None, workspace_bytes=0,
+            stream=None):
+        """cfloat input; channel j's floats [k_begin, k_end) -> d_out + 4 * j * out_stride bytes.  Pointers are device addresses."""
+        self._run(lib.sdrhip_am_bank_run, "sdrhip_am_bank_run", d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block, dc_state,
+                  workspace, workspace_bytes, stream)
+
+    def run_u8(self, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block=0, dc_state=None, workspace=None, workspace_bytes=0,
+               stream=None):
+        self._run(lib.sdrhip_am_bank_run_u8, "sdrhip_am_bank_run_u8", d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block,
+                  dc_state, workspace, workspace_bytes, stream)
+
+    def run_i16(self, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block=0, dc_state=None, workspace=None, workspace_bytes=0,
+                stream=None):
+        """interleaved int16 IQ input (4 bytes per sample); rows as run."""
+        self._run(lib.sdrhip_am_bank_run_i16, "sdrhip_am_bank_run_i16", d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block,
+                  dc_state, workspace, workspace_bytes, stream)
+
+
 class FmChain(_Handle):
     """The FM receiver of examples/fm/fm.hs:34-41 as one device-resident object."""
     _destroy = lib.sdrhip_fm_chain_destroy
@@ -1435,6 +1514,12 @@ class Pipe(_Handle):
         elif kind == "tuner_bank":
             check(lib.sdrhip_pipe_tuner_bank(C.byref(self.h), desc.h, block_size_out, int(input_u8)), "sdrhip_pipe_tuner_bank")
             self.input_u8 = bool(input_u8)
+        elif kind == "am_bank":
+            if input_u8 and input_i16:
+                raise ValueError("Pipe.am_bank: input_u8 and input_i16 exclude each other")
+            check(lib.sdrhip_pipe_am_bank(C.byref(self.h), desc.h, block_size_out, 2 if input_i16 else int(bool(input_u8))), "sdrhip_pipe_am_bank")
+            self.input_u8, self.input_i16 = bool(input_u8), bool(input_i16)
+            self.complex_in = True
         elif kind == "fm_demod":
             check(lib.sdrhip_pipe_fm_demod(C.byref(self.h)), "sdrhip_pipe_fm_demod")
         elif kind == "am_demod":
@@ -1461,6 +1546,12 @@ class Pipe(_Handle):
         return Pipe("tuner_bank", bank, block_size_out, input_u8=input_u8, input_i16=input_i16)
 
     @staticmethod
+    def am_bank(am_bank, block_size_out, input_u8=False, input_i16=False):
+        """The AM bank on host blocks: cfloat, u8 IQ or int16 IQ blocks in, every channel's audio (the envelope; with the bank's
+        dc_block, dcBlocker of it, its state kept on the device) in blocks of block_size_out floats out."""
+        return Pipe("am_bank", am_bank, block_size_out, input_u8=input_u8, input_i16=input_i16)
+
+    @staticmethod
     def am_demod():
         """The AM envelope detector on host blocks: interleaved complex float32 blocks in, float blocks of the same length out."""
         return Pipe("am_demod")
@@ -1484,6 +1575,8 @@ class Pipe(_Handle):
                 raise SdrHipError(f"{call}: this pipe takes int16 IQ blocks, not {getattr(block, 'dtype', type(block).__name__)}")
             return
         is_u8 = getattr(block, "dtype", None) == np.uint8
+        if getattr(block, "dtype", None) == np.int16:
+            raise SdrHipError(f"{call}: this pipe takes {'uint8 IQ' if self.input_u8 else 'float32'} blocks, not int16")
         if is_u8 != self.input_u8:
             raise SdrHipError(f"{call}: this pipe takes {'uint8 IQ' if self.input_u8 else 'float32'} blocks, not "
                               f"{getattr(block, 'dtype', type(block).__name__)}")
@@ -1548,7 +1641,7 @@ class Pipe(_Handle):
         return self._pop(check(lib.sdrhip_pipe_restore(self.h, state, len(state)), "sdrhip_pipe_restore"))
 
     def _pop(self, ready):
-        if self.kind == "tuner_bank":
+        if self.kind in ("tuner_bank", "am_bank"):
             if ready <= 0:
                 return []
             got = self.pop_rows(ready)
