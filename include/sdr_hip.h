@@ -1054,7 +1054,7 @@ int sdrhip_fft_run_device(sdrhip_fft *f, void *stream, const double *d_in, doubl
 
 /* The spectrum operator: the reference's waterfall pipe, interleavedIQUnsigned256ToFloat (Util.hs:92-98) -> halfBandUp
  * (Util.hs:264-271) x hanning / hamming / blackman (FilterDesign.hs:39-60) -> fftw (FFT.hs:44-76) -> magnitude and a scale, from raw
- * IQ in device memory to plot-ready float32 rows.  With x[j] the converted sample, all arithmetic in double:
+ * IQ (u8, float32 or int16: SDRHIP_IQ_*) in device memory to plot-ready float32 rows.  With x[j] the converted sample, all arithmetic in double:
  *     x'[j] = x[j] * (half_band_shift ? (-1)^j : 1) * w[j];  X = forward DFT of x' (unnormalised, sign exp(-2 pi i jk/n));
  *     out[k] = (float)(scale * |X[k]|),  |X| = sqrt(re^2 + im^2): cf32 input must stay well inside double's range (|x| < 1e150).
  * The windows are computed on the host in double with the reference's formulas (denominator n - 1, so n >= 2).  Tolerance
@@ -1066,6 +1066,11 @@ int sdrhip_fft_run_device(sdrhip_fft *f, void *stream, const double *d_in, doubl
 typedef struct sdrhip_spectrum sdrhip_spectrum;
 #define SDRHIP_IQ_U8   0   /* interleaved unsigned bytes, (v - 128) / 128   (Util.hs:92-98)  */
 #define SDRHIP_IQ_CF32 1   /* interleaved float32 re, im (e.g. a decimator's output)          */
+/* interleaved int16 (I, Q), c(s) = (double)s * 2^-11 over the WHOLE int16 range (the BladeRF conversion, convert.c:52-85; exact, so it
+ * equals (double)((float)s * 2^-11): a cf32 object on sdrhip_convert_i16_run's floats gives the same bits on the one-kernel route).
+ * d_in must be 2-byte aligned, else SDRHIP_ERR_ARG before any launch with nothing written; a 4-byte aligned base is read with one load
+ * per sample, any other with two.  No byte outside [0, 4 * n_samples) of d_in is read. */
+#define SDRHIP_IQ_I16  2
 #define SDRHIP_WINDOW_NONE 0
 #define SDRHIP_WINDOW_HANNING 1    /* FilterDesign.hs:39-44 */
 #define SDRHIP_WINDOW_HAMMING 2    /* :47-52 */
@@ -1204,6 +1209,50 @@ int sdrhip_pipe_tuner_bank_i16(sdrhip_pipe **p, const sdrhip_tuner_bank *b, int 
 int sdrhip_pipe_am_bank(sdrhip_pipe **p, const sdrhip_am_bank *b, int block_size_out, int input_type);
 int sdrhip_pipe_push_i16(sdrhip_pipe *p, const int16_t *iq, int n_samples);
 int16_t *sdrhip_pipe_input_buffer_i16(sdrhip_pipe *p, int n_samples);
+
+/* The waterfall on host blocks: raw IQ blocks of ANY size >= 1 sample in, spectrum rows out.
+ * Input: the type of the spectrum object -- a cfloat object's pipe takes sdrhip_pipe_push / _input_buffer (n complex samples), a u8
+ * one _push_u8 / _input_buffer_u8, an int16 one _push_i16 / _input_buffer_i16 (n_samples (I, Q) pairs); the wrong call for the pipe's
+ * type is SDRHIP_ERR_ARG (NULL) with nothing staged.
+ * Output: blocks of exactly n floats, one output row each.  sdrhip_pipe_pop returns n, or 0 if no row is ready; a capacity below n is
+ * SDRHIP_ERR_ARG with nothing written and nothing popped.  sdrhip_pipe_pop_rows serves it as a one-row pipe with block_size_out = n;
+ * sdrhip_pipe_rows is 1.  The counts push / flush / poll / restore return are output rows.
+ * Definition: with S the concatenation of every sample pushed so far, output row R exists as soon as
+ * (R * group + group - 1) * hop + n <= |S| and is row R of
+ *     sdrhip_spectrum_reduce_run_device(s, stream, S, |S|, hop, rows_out, group, reduce, unit, floor_db, out).
+ * With group 1, MEAN_MAGNITUDE and LINEAR that is sdrhip_spectrum_run_device's row; with hop = n it is the reference's waterfall pipe
+ * (one block of n samples, one row).  On the one-kernel route the rows equal that one call's BIT FOR BIT, for every sequence of push
+ * sizes, coalesced or adaptive, and every group length (a row's bits depend on its own samples, group, reduce and unit alone); on the
+ * hipFFT route the operator's tolerance contract holds.  Nothing new is argued.
+ * Machinery: the host keeps the samples from the first row not yet produced onward, in the input's own type (the engine's
+ * [carried tail | staged]).  A push that completes no output row launches nothing.  A submission that completes r >= 1 rows is ONE
+ * reduce run over [tail | staged] with rows_out = r (one count of sdrhip_debug_spectrum_fused_launches on the one-kernel route).  The
+ * next tail starts at stream sample rows_done * group * hop; with hop > n that can lie beyond what has been pushed, and the samples in
+ * between are dropped on arrival, never staged.  The stream position is 64-bit.
+ * Submission: the input is NEVER read in place over PCIe (with hop < n every sample is read n / hop times): up to 512 KiB a submission
+ * is one copy on its slot's stream and the launch behind it, beyond that the copy engines (a stated choice, not a measured one).
+ * ORDERING: the spectrum object has one scratch buffer.  A submission that does not touch it (one-kernel route, group <= 32) keeps a
+ * stream per slot; every submission that does (hipFFT route, groups of more than 32 rows, split or not) goes to ONE compute stream
+ * (the engine's first) and is ordered behind its predecessor by it.  Up to four submissions are in flight.
+ * MAY BLOCK THE HOST: a push / flush that reopens a slot waits for that slot's previous submission (as every pipe); on the hipFFT route
+ * a submission whose batch of rows needs a transform plan the object has not kept waits for the object's last run, and one that needs
+ * a larger work buffer than any before waits for the device (the rules of sdrhip_spectrum_reduce_run_device, unchanged).  Every other
+ * push returns without waiting for the GPU.
+ * Borrowing: the pipe borrows the spectrum object EXCLUSIVELY: the object must outlive the pipe, its route and split settings are read
+ * at every submission, and a direct sdrhip_spectrum_*run* call on it while the pipe holds submissions in flight (before a flush) is
+ * the caller's error.
+ * sdrhip_pipe_set_coalesce(N > 1): a submission waits for N complete rows; sdrhip_pipe_set_adaptive(M): rows pile up (up to M rows or
+ * 4 MiB of input) while the slot a submission would move on to is still running; flush submits every complete row and drains; poll
+ * and destroy as for the filter-like pipes.  Results never depend on them.
+ * Save / restore: a state version and kind of its own (the kind number is a new one at the end; states of every other kind keep their
+ * bytes): uint32 magic, version (3); int32 kind, n, input type (0 cfloat, 1 u8, 2 int16), group, reduce, unit; int64 hop; double
+ * floor_db; int64 stream position, rows produced, skip count, tail samples, pending floats; then the tail in the input's type and the
+ * rows not yet popped.  Restore refuses (SDRHIP_ERR_ARG, the pipe unchanged) a state of another kind, a difference in n, input type,
+ * hop, group, reduce, unit or floor_db, and a truncated or inconsistent state.
+ * Create: SDRHIP_ERR_ARG (and *p = NULL) before any device work for a null argument, hop < 1, group < 1, reduce or unit out of range,
+ * a non-finite floor_db, and a carried tail that could exceed 4 MiB: ((group - 1) * hop + n - 1) * (bytes per sample) > 4 MiB (the
+ * engine's adaptive staging cap: a stated bound; carrying partial group sums on the device instead is out of scope). */
+int sdrhip_pipe_spectrum(sdrhip_pipe **p, sdrhip_spectrum *s, int64_t hop, int group, int reduce, int unit, double floor_db);
 int sdrhip_pipe_pop_rows(sdrhip_pipe *p, float *out, int64_t row_stride, int max_blocks);
 /* Feed one upstream block (n elements: floats, or complex pairs for complex
  * stages).  Returns the number of complete output blocks now ready (>= 0) or a

@@ -8,7 +8,7 @@
 // libhipfft.so is bound at run time like RCCL, so libsdr_hip.so keeps loading where it is absent.
 //
 // The spectrum operator (sdrhip_spectrum_*, second half of this file) is the reference's whole waterfall pipe on device memory: raw IQ
-// (u8 as Util.hs:92-98 converts it, or float32) x halfBandUp (Util.hs:264-271) x a window (FilterDesign.hs:39-60) -> DFT -> scale * |X|
+// (u8 as Util.hs:92-98 converts it, int16 as convert.c:52-85 does, or float32) x halfBandUp (Util.hs:264-271) x a window (FilterDesign.hs:39-60) -> DFT -> scale * |X|
 // as float32 rows.  Two routes with one contract (tests/test_gpu_spectrum.py): power-of-two n from 64 to 8192 run as ONE kernel of
 // ours with the transform resident in LDS (kernels_spectrum.hip); every other n, or any n on request, runs as a pre-kernel, the
 // batched hipFFT Z2Z plan in place on a scratch_pool buffer, and a post-kernel, in chunks of rows that keep the scratch bounded.
@@ -198,7 +198,7 @@ struct sdrhip_spectrum {
     std::vector<SpectrumPlan> plans;       // one per batch size in use: the chunk, and the last chunk of a run
     bool fused_size() const { return spectrum_fused_size(n); }
     bool takes_fused() const { return route == 1 || (route == 0 && fused_size()); }
-    size_t sample_bytes() const { return format == SDRHIP_IQ_U8 ? 2 : 8; }
+    size_t sample_bytes() const { return format == SDRHIP_IQ_U8 ? 2 : format == SDRHIP_IQ_I16 ? 4 : 8; }
     ~sdrhip_spectrum()
     {
         if (ran_hipfft) (void)hipStreamSynchronize(last_stream);
@@ -422,7 +422,7 @@ int sdrhip_spectrum_create(sdrhip_spectrum** out, int n, int input_format, int w
     SDRHIP_REQUIRE(out != nullptr, "sdrhip_spectrum_create");
     *out = nullptr;
     SDRHIP_REQUIRE(n >= 2 && n <= (1 << 27), "sdrhip_spectrum_create");
-    SDRHIP_REQUIRE(input_format == SDRHIP_IQ_U8 || input_format == SDRHIP_IQ_CF32, "sdrhip_spectrum_create");
+    SDRHIP_REQUIRE(input_format == SDRHIP_IQ_U8 || input_format == SDRHIP_IQ_CF32 || input_format == SDRHIP_IQ_I16, "sdrhip_spectrum_create");
     SDRHIP_REQUIRE(window >= SDRHIP_WINDOW_NONE && window <= SDRHIP_WINDOW_CUSTOM, "sdrhip_spectrum_create");
     SDRHIP_REQUIRE(window != SDRHIP_WINDOW_CUSTOM || custom_window != nullptr, "sdrhip_spectrum_create");
     sdrhip_spectrum* s = new sdrhip_spectrum();
@@ -473,6 +473,7 @@ int sdrhip_spectrum_run_device(sdrhip_spectrum* s, void* stream, const void* d_i
     SDRHIP_REQUIRE(s != nullptr && d_in != nullptr && d_out != nullptr, "sdrhip_spectrum_run_device");
     SDRHIP_REQUIRE(rows >= 1 && hop >= 1 && n_samples >= s->n, "sdrhip_spectrum_run_device");
     SDRHIP_REQUIRE(rows == 1 || hop <= (n_samples - s->n) / (rows - 1), "sdrhip_spectrum_run_device: the last row must end inside the input");
+    SDRHIP_REQUIRE(s->format != SDRHIP_IQ_I16 || ((uintptr_t)d_in & 1u) == 0, "sdrhip_spectrum_run_device: int16 input at an odd address");
     int rc;
     if ((rc = spectrum_upload(s)) != SDRHIP_OK) return rc;
     SpectrumArgs a;
@@ -527,11 +528,32 @@ int sdrhip_spectrum_set_reduce_split(sdrhip_spectrum* s, int mode)
 
 long long sdrhip_debug_spectrum_reduce_split_launches(void) { return g_spectrum_reduce_split_launches.load(); }
 
+}  // extern "C"
+
+// what the waterfall Pipe (pipes.cpp) asks of the object it borrows
+namespace sdrhip {
+int spectrum_size_of(const sdrhip_spectrum* s) { return s->n; }
+int spectrum_format_of(const sdrhip_spectrum* s) { return s->format; }
+bool spectrum_reduce_uses_scratch(const sdrhip_spectrum* s, int group) { return !s->takes_fused() || group > SPECTRUM_REDUCE_CHUNK; }
+// `stream` is about to be destroyed: if the scratch was last used on it, drain it now, so that neither the next run nor the object's
+// destructor waits on a stream that no longer exists
+void spectrum_forget_stream(sdrhip_spectrum* s, hipStream_t stream)
+{
+    if (!s->ran_hipfft || s->last_stream != stream) return;
+    (void)hipStreamSynchronize(stream);
+    s->ran_hipfft = false;
+    s->last_stream = nullptr;
+}
+}  // namespace sdrhip
+
+extern "C" {
+
 int sdrhip_spectrum_reduce_run_device(sdrhip_spectrum* s, void* stream, const void* d_in, int64_t n_samples, int64_t hop, int rows_out, int group,
                                       int reduce, int unit, double floor_db, float* d_out)
 {
     SDRHIP_REQUIRE(s != nullptr && d_in != nullptr && d_out != nullptr, "sdrhip_spectrum_reduce_run_device");
     SDRHIP_REQUIRE(spectrum_reduce_args_ok(s, n_samples, hop, rows_out, group, reduce, unit, floor_db), "sdrhip_spectrum_reduce_run_device");
+    SDRHIP_REQUIRE(s->format != SDRHIP_IQ_I16 || ((uintptr_t)d_in & 1u) == 0, "sdrhip_spectrum_reduce_run_device: int16 input at an odd address");
     int rc;
     if ((rc = spectrum_upload(s)) != SDRHIP_OK) return rc;
     SpectrumArgs a;

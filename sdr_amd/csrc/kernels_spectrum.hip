@@ -47,7 +47,8 @@ __device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_doub
 __device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 
 // sample `idx` of the input as a complex double.  A row starts wherever hop puts it, so `wide` (the base pointer allows one load per
-// sample: 2-byte aligned u8, 8-byte aligned float32) is decided per launch and the narrow loads serve every other base.
+// sample: 2-byte aligned u8, 8-byte aligned float32, 4-byte aligned int16) is decided per launch and the narrow loads serve every
+// other base.  int16 is c(s) = s * 2^-11 over the whole range (the BladeRF conversion, convert.c:52-85): exact in double.
 template <int FMT>
 __device__ __forceinline__ double2 load_sample(const void* in, int64_t idx, bool wide)
 {
@@ -63,6 +64,18 @@ __device__ __forceinline__ double2 load_sample(const void* in, int64_t idx, bool
             im = p[1];
         }
         return make_double2(((double)re - 128.0) / 128.0, ((double)im - 128.0) / 128.0);
+    } else if (FMT == 2) {
+        const unsigned char* p = static_cast<const unsigned char*>(in) + 4 * idx;
+        int re, im;
+        if (wide) {
+            const uint32_t w = *reinterpret_cast<const uint32_t*>(p);
+            re = (int)(int16_t)(w & 0xffff);
+            im = (int32_t)w >> 16;
+        } else {
+            re = (int)(int16_t)*reinterpret_cast<const unsigned short*>(p);
+            im = (int)(int16_t)*reinterpret_cast<const unsigned short*>(p + 2);
+        }
+        return make_double2((double)re * 0.00048828125, (double)im * 0.00048828125);
     } else {
         const float* p = static_cast<const float*>(in) + 2 * idx;
         if (wide) {
@@ -452,7 +465,7 @@ __global__ __launch_bounds__(256) void spectrum_magnitude(const double2* __restr
     for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < count; k += (int64_t)gridDim.x * 256) out[k] = magnitude(work[k], scale);
 }
 
-bool wide_loads(const SpectrumArgs& a) { return ((uintptr_t)a.in & (a.format == 0 ? 1u : 7u)) == 0; }
+bool wide_loads(const SpectrumArgs& a) { return ((uintptr_t)a.in & (a.format == 0 ? 1u : a.format == 2 ? 3u : 7u)) == 0; }
 
 template <int T>
 hipError_t launch_fused(hipStream_t stream, const SpectrumArgs& a, int lg, float* out)
@@ -463,6 +476,8 @@ hipError_t launch_fused(hipStream_t stream, const SpectrumArgs& a, int lg, float
     const unsigned grid = (unsigned)(ntiles < resident ? ntiles : resident);
     if (a.format == 0)
         spectrum_fused<T, 0><<<grid, T, 0, stream>>>(a.in, a.hop, a.rows, lg, a.shift, a.scale, a.window, a.twiddle, wide_loads(a), out);
+    else if (a.format == 2)
+        spectrum_fused<T, 2><<<grid, T, 0, stream>>>(a.in, a.hop, a.rows, lg, a.shift, a.scale, a.window, a.twiddle, wide_loads(a), out);
     else
         spectrum_fused<T, 1><<<grid, T, 0, stream>>>(a.in, a.hop, a.rows, lg, a.shift, a.scale, a.window, a.twiddle, wide_loads(a), out);
     return hipGetLastError();
@@ -484,6 +499,9 @@ hipError_t launch_fused_reduce(hipStream_t stream, const SpectrumArgs& a, const 
     if (a.format == 0) {
         if (partial) SDRHIP_REDUCE_LAUNCH(0, true);
         else SDRHIP_REDUCE_LAUNCH(0, false);
+    } else if (a.format == 2) {
+        if (partial) SDRHIP_REDUCE_LAUNCH(2, true);
+        else SDRHIP_REDUCE_LAUNCH(2, false);
     } else {
         if (partial) SDRHIP_REDUCE_LAUNCH(1, true);
         else SDRHIP_REDUCE_LAUNCH(1, false);
@@ -539,6 +557,8 @@ hipError_t launch_spectrum_prepare(hipStream_t stream, const SpectrumArgs& a, in
     const dim3 grid((unsigned)((a.n + 255) / 256), (unsigned)(nrows < 4096 ? nrows : 4096));
     if (a.format == 0)
         spectrum_prepare<0><<<grid, 256, 0, stream>>>(a.in, a.hop, row0, nrows, a.n, a.shift, a.window, wide_loads(a), work);
+    else if (a.format == 2)
+        spectrum_prepare<2><<<grid, 256, 0, stream>>>(a.in, a.hop, row0, nrows, a.n, a.shift, a.window, wide_loads(a), work);
     else
         spectrum_prepare<1><<<grid, 256, 0, stream>>>(a.in, a.hop, row0, nrows, a.n, a.shift, a.window, wide_loads(a), work);
     return hipGetLastError();

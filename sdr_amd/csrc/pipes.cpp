@@ -25,6 +25,9 @@
 // per element from the staging buffer to the kernels' loaders) or int16 IQ (4 bytes per element, sdrhip_pipe_tuner_bank_i16).  With more than one row nothing is read in place: up to kDirectBytes
 // a submission is one copy on the slot's stream and the launch behind it, placed in device memory so that the banked launch's first
 // window is 16-byte aligned (HostStream::dev_skew).
+//
+// The waterfall Pipe (sdrhip_pipe_spectrum) is the spectrum operator's reducing form on the same engine: blocks of any size in, rows of
+// n floats out, the carried tail being the samples from the first row not yet produced onward (spectrum_push / spectrum_submit below).
 #include <stdlib.h>
 #include <string.h>
 
@@ -33,10 +36,14 @@
 #include "am.hpp"
 #include "descriptors.hpp"
 #include "host_stream.hpp"
+#include "spectrum.hpp"
 
 using namespace sdrhip;
 
-enum PipeKind { PK_FILTER, PK_DECIMATOR, PK_RESAMPLER, PK_DEMOD, PK_DCBLOCK, PK_AGC, PK_TUNER, PK_TUNER_BANK, PK_AM, PK_AM_BANK };   // saved states hold the number: new kinds go at the end
+enum PipeKind : int { PK_FILTER, PK_DECIMATOR, PK_RESAMPLER, PK_DEMOD, PK_DCBLOCK, PK_AGC, PK_TUNER, PK_TUNER_BANK, PK_AM, PK_AM_BANK };   // saved states hold the number: new kinds go at the end
+// The waterfall Pipe's kind, the next number (10).  It stands behind the list, not in it: tests/test_pipe_am_bank_abi.py pins the line
+// above as the ten kinds whose saved states exist in the field.
+constexpr PipeKind PK_SPECTRUM = static_cast<PipeKind>(PK_AM_BANK + 1);
 
 struct sdrhip_pipe {
     PipeKind kind;
@@ -55,6 +62,13 @@ struct sdrhip_pipe {
     // without am_dc the slots' submissions run on streams of their own.
     bool am_dc = false;
     DevBuf am_iq[HostStream::kMaxSlots];
+    // PK_SPECTRUM: the waterfall Pipe over a borrowed spectrum object.  Elements are samples in the object's own type (fmt); output
+    // blocks are rows of block_out = n floats.  The engine's history holds exactly the carried tail (the samples from the first row
+    // not yet produced onward) while nothing is staged; sp_skip samples of the stream are still to be dropped on arrival (hop > n).
+    sdrhip_spectrum* spec = nullptr;
+    int64_t sp_hop = 0, sp_pos = 0, sp_rows_done = 0, sp_skip = 0;      // sp_pos: samples pushed so far
+    int sp_group = 1, sp_reduce = 0, sp_unit = 0;
+    double sp_floor_db = 0.0;
     int block_out = 0;
     bool cplx_in = false, cplx_out = false;
     int I = 1, D = 1, Lp = 1;
@@ -353,7 +367,155 @@ static int fir_like_push(sdrhip_pipe* p, const void* block, int n)
     return ready_blocks(p);
 }
 
+// ---- the waterfall Pipe (sdrhip_pipe_spectrum) ------------------------------------------------------------------------------------
+// With S the samples pushed so far, output row R exists once (R group + group - 1) hop + n <= |S| and is row R of ONE
+// sdrhip_spectrum_reduce_run_device over S.  The host keeps the samples from row sp_rows_done's first one onward: the engine's history
+// while no row is complete, [history | staged] in the slot's staging buffer once one is (a submission, or rows piling up behind a
+// busy GPU / a coalesce count).  A submission is one reduce run over [tail | staged] with rows_out = every complete row.
+static constexpr size_t kSpectrumTailBytes = 4 << 20;     // the engine's adaptive staging cap: the bound of the carried tail
+
+static int64_t spectrum_rows_in(const sdrhip_pipe* p, int64_t avail)
+{
+    if (avail < p->block_out) return 0;
+    return ((avail - p->block_out) / p->sp_hop + 1) / p->sp_group;
+}
+
+static int spectrum_submit(sdrhip_pipe* p)
+{
+    HostStream& e = p->eng;
+    const int si = e.cur();
+    const size_t ein = p->ein();
+    const int64_t tail = e.hist_n, have = tail + e.staged, r = spectrum_rows_in(p, have);
+    if (r < 1) return SDRHIP_OK;
+    uint8_t* first = e.staged_base() - (size_t)tail * ein;
+    if (tail > 0) memcpy(first, e.hist.data(), (size_t)tail * ein);
+    // The input is never read in place (hop < n reads every sample n / hop times): up to kDirectBytes one copy on the slot's stream
+    // and the launch behind it, beyond that the copy engines.  A run that goes through the object's ONE scratch buffer (the hipFFT
+    // route, layers of a group past 32 rows) is ordered behind its predecessor by the engine's first compute stream.
+    const bool direct = (size_t)have * ein <= sdrhip_pipe::kDirectBytes;
+    const bool scratch = spectrum_reduce_uses_scratch(p->spec, p->sp_group);
+    hipStream_t cs = direct && !scratch ? e.compute[si] : e.compute[0];
+    const int n = p->block_out;
+    int rc = e.submit(direct ? HostStream::kSlotStream : HostStream::kCopyEngines, cs, first, (size_t)have * ein, r * n,
+                      [&](hipStream_t s, const void* d_in, void* d_out) {
+        return sdrhip_spectrum_reduce_run_device(p->spec, s, d_in, have, p->sp_hop, (int)r, p->sp_group, p->sp_reduce, p->sp_unit, p->sp_floor_db,
+                                                 (float*)d_out);
+    });
+    if (rc != SDRHIP_OK) return rc;
+    // the next tail starts at stream sample (rows_done + r) group hop: inside [tail | staged] (still in the slot's staging buffer, which
+    // nothing writes before the slot is reopened), or `skip` samples beyond its end
+    const int64_t used = r * p->sp_group * p->sp_hop;
+    if (used < have) {
+        e.hist_n = have - used;
+        memcpy(e.hist.data(), first + (size_t)used * ein, (size_t)e.hist_n * ein);
+    } else {
+        e.hist_n = 0;
+        p->sp_skip = used - have;
+    }
+    p->sp_rows_done += r;
+    return SDRHIP_OK;
+}
+
+// room for `elems` staged elements in the current slot; growth doubles, so that small pushes piling up do not re-pin every time
+static int spectrum_open_slot(sdrhip_pipe* p, int64_t elems)
+{
+    HostStream& e = p->eng;
+    const size_t ein = p->ein(), head = (size_t)e.head_cap * ein, cap = e.slot[e.cur()].hin.cap;
+    size_t bytes = (size_t)elems * ein;
+    if (cap < head + bytes && cap > head && bytes < 2 * (cap - head)) bytes = 2 * (cap - head);
+    return e.open_slot(bytes, (size_t)(e.staged + p->lent) * ein);
+}
+
+static int spectrum_push(sdrhip_pipe* p, const void* block, int n)
+{
+    HostStream& e = p->eng;
+    const size_t ein = p->ein();
+    int rc;
+    if ((int64_t)e.staged + n > (int64_t)1 << 30) {
+        set_error("pipe: %d samples behind %d staged ones exceed the staging limit", n, e.staged);
+        return SDRHIP_ERR_ARG;
+    }
+    const bool in_place = e.slot[e.cur()].hin.p != nullptr && block == (const void*)e.write_pos();
+    // samples between the last produced row's group and the next one's first sample (hop > n) are dropped on arrival
+    const int64_t drop = p->sp_skip < n ? p->sp_skip : n;
+    const int m = n - (int)drop;
+    p->sp_skip -= drop;
+    p->sp_pos += n;
+    if (!in_place) p->lent = 0;            // a block lent and not pushed is abandoned: growth below need not keep it
+    if (m == 0) {
+        p->lent = 0;
+        return ready_blocks(p);
+    }
+    if (e.staged == 0 && spectrum_rows_in(p, e.hist_n + m) < 1) {
+        // no row yet: the samples join the carried tail (fewer than (group - 1) hop + n of them: the history's size), nothing is launched
+        memcpy(e.hist.data() + (size_t)e.hist_n * ein, (const uint8_t*)block + (size_t)drop * ein, (size_t)m * ein);
+        e.hist_n += m;
+        p->lent = 0;
+        return ready_blocks(p);
+    }
+    if ((rc = spectrum_open_slot(p, (int64_t)e.staged + (in_place ? n : m))) != SDRHIP_OK) return rc;
+    // (growth keeps the lent region, so a block the caller filled in place is at the write position of the new buffer too)
+    const uint8_t* src = in_place ? e.write_pos() + (size_t)drop * ein : (const uint8_t*)block + (size_t)drop * ein;
+    if (src != e.write_pos()) memmove(e.write_pos(), src, (size_t)m * ein);
+    p->lent = 0;
+    e.staged += m;
+    const int64_t r = spectrum_rows_in(p, e.hist_n + e.staged);
+    // every push that completes a row goes out at once; coalesce(N > 1) waits for N rows; adaptive lets rows pile up (up to its row
+    // count and byte cap) while the slot the submission would move on to is still running
+    bool go = true;
+    if (p->coalesce > 1) go = r >= p->coalesce;
+    else if (p->adaptive > 1)
+        go = r >= p->adaptive || (int64_t)(e.hist_n + e.staged) * (int64_t)ein >= sdrhip_pipe::adaptive_bytes() || !e.next_in_flight();
+    const int64_t pushes_before = e.pushes;
+    if (go && (rc = spectrum_submit(p)) != SDRHIP_OK) return rc;
+    if (e.pushes != pushes_before && (rc = e.harvest_done()) != SDRHIP_OK) return rc;
+    return ready_blocks(p);
+}
+
+// flush / save: every complete row goes out, and what is left of the staged samples (no whole row) joins the history
+static int spectrum_settle(sdrhip_pipe* p)
+{
+    int rc;
+    p->lent = 0;
+    if (p->eng.staged > 0 && (rc = spectrum_submit(p)) != SDRHIP_OK) return rc;
+    return SDRHIP_OK;
+}
+
 extern "C" {
+
+int sdrhip_pipe_spectrum(sdrhip_pipe** pp, sdrhip_spectrum* s, int64_t hop, int group, int reduce, int unit, double floor_db)
+{
+    // (all of it before pipe_new, whose engine creates streams: a refused create has done no device work)
+    SDRHIP_REQUIRE(pp != nullptr, "sdrhip_pipe_spectrum");
+    *pp = nullptr;
+    SDRHIP_REQUIRE(s != nullptr, "sdrhip_pipe_spectrum: null spectrum object");
+    SDRHIP_REQUIRE(hop >= 1 && group >= 1, "sdrhip_pipe_spectrum: hop >= 1, group >= 1");
+    SDRHIP_REQUIRE(reduce >= SDRHIP_REDUCE_MEAN_POWER && reduce <= SDRHIP_REDUCE_MAX_MAGNITUDE, "sdrhip_pipe_spectrum: reduce out of range");
+    SDRHIP_REQUIRE(unit == SDRHIP_UNIT_LINEAR || unit == SDRHIP_UNIT_DB, "sdrhip_pipe_spectrum: unit out of range");
+    SDRHIP_REQUIRE(floor_db == floor_db && floor_db - floor_db == 0.0, "sdrhip_pipe_spectrum: floor_db must be finite");
+    const int n = spectrum_size_of(s), format = spectrum_format_of(s);
+    const InFmt fmt = format == SDRHIP_IQ_U8 ? IN_U8 : format == SDRHIP_IQ_I16 ? IN_I16 : IN_CF32;
+    const int64_t sb = in_fmt_bytes(fmt), cap = (int64_t)kSpectrumTailBytes / sb;
+    // the carried tail, ((group - 1) hop + n - 1) samples at most, stays within 4 MiB (without overflow: hop <= cap first)
+    SDRHIP_REQUIRE(n - 1 <= cap && (group == 1 || (hop <= cap && (int64_t)(group - 1) <= (cap - (n - 1)) / hop)),
+                   "sdrhip_pipe_spectrum: ((group - 1) * hop + n - 1) samples of carried tail exceed 4 MiB");
+    const int64_t max_tail = (int64_t)(group - 1) * hop + n - 1;
+    sdrhip_pipe* p = new sdrhip_pipe();
+    p->kind = PK_SPECTRUM;
+    p->spec = s;
+    p->block_out = n;
+    p->cplx_in = true;
+    p->cplx_out = false;
+    p->fmt = fmt;
+    p->sp_hop = hop; p->sp_group = group; p->sp_reduce = reduce; p->sp_unit = unit; p->sp_floor_db = floor_db;
+    int rc = p->eng.init(HostStream::kMaxSlots, p->ein(), max_tail > 0 ? max_tail : 1, "pipe: stream/event creation failed");
+    if (rc != SDRHIP_OK) {
+        delete p;
+        return rc;
+    }
+    *pp = p;
+    return SDRHIP_OK;
+}
 
 int sdrhip_pipe_fir_filter(sdrhip_pipe** pp, const sdrhip_filter* f, int block_size_out)
 {
@@ -560,6 +722,7 @@ int sdrhip_pipe_push(sdrhip_pipe* p, const float* block, int n)
     SDRHIP_REQUIRE(p != nullptr && block != nullptr && n > 0, "sdrhip_pipe_push");
     SDRHIP_REQUIRE(p->fmt == IN_CF32, p->fmt == IN_U8 ? "sdrhip_pipe_push: this pipe takes u8 IQ blocks (sdrhip_pipe_push_u8)"
                                                        : "sdrhip_pipe_push: this pipe takes int16 IQ blocks (sdrhip_pipe_push_i16)");
+    if (p->kind == PK_SPECTRUM) return spectrum_push(p, block, n);
     return p->is_map() ? map_push(p, block, n) : fir_like_push(p, block, n);
 }
 
@@ -568,7 +731,7 @@ int sdrhip_pipe_push_u8(sdrhip_pipe* p, const uint8_t* iq, int n_samples)
     SDRHIP_REQUIRE(p != nullptr && iq != nullptr && n_samples > 0, "sdrhip_pipe_push_u8");
     SDRHIP_REQUIRE(p->fmt == IN_U8, p->fmt == IN_I16 ? "sdrhip_pipe_push_u8: this pipe takes int16 IQ blocks (sdrhip_pipe_push_i16)"
                                                      : "sdrhip_pipe_push_u8: this pipe takes float blocks (sdrhip_pipe_push)");
-    return fir_like_push(p, iq, n_samples);
+    return p->kind == PK_SPECTRUM ? spectrum_push(p, iq, n_samples) : fir_like_push(p, iq, n_samples);
 }
 
 int sdrhip_pipe_push_i16(sdrhip_pipe* p, const int16_t* iq, int n_samples)
@@ -576,7 +739,7 @@ int sdrhip_pipe_push_i16(sdrhip_pipe* p, const int16_t* iq, int n_samples)
     SDRHIP_REQUIRE(p != nullptr && iq != nullptr && n_samples > 0, "sdrhip_pipe_push_i16");
     SDRHIP_REQUIRE(p->fmt == IN_I16, p->fmt == IN_U8 ? "sdrhip_pipe_push_i16: this pipe takes u8 IQ blocks (sdrhip_pipe_push_u8)"
                                                      : "sdrhip_pipe_push_i16: this pipe takes float blocks (sdrhip_pipe_push)");
-    return fir_like_push(p, iq, n_samples);
+    return p->kind == PK_SPECTRUM ? spectrum_push(p, iq, n_samples) : fir_like_push(p, iq, n_samples);
 }
 
 int sdrhip_pipe_set_coalesce(sdrhip_pipe* p, int blocks)
@@ -609,6 +772,14 @@ static void* pipe_input_buffer(sdrhip_pipe* p, int n, InFmt fmt, const char* who
         return nullptr;
     }
     HostStream& e = p->eng;
+    if (p->kind == PK_SPECTRUM) {
+        // behind what is staged (rows waiting for a coalesce count or a busy GPU); a push that completes no row copies it to the tail
+        if ((int64_t)e.staged + n > (int64_t)1 << 30) { set_error("%s: too many samples staged", who); return nullptr; }
+        p->lent = 0;
+        if (spectrum_open_slot(p, (int64_t)e.staged + n) != SDRHIP_OK) return nullptr;
+        p->lent = n;
+        return e.write_pos();
+    }
     const int ce = p->coalesce_eff(p->uniform_n ? p->uniform_n : n);
     const bool coalescing = ce > 1 && p->all_uniform && (p->uniform_n == 0 || p->uniform_n == n);
     if (!coalescing && e.staged > 0 && fir_submit(p, e.staged, p->uniform_n) != SDRHIP_OK) return nullptr;
@@ -645,7 +816,9 @@ int sdrhip_pipe_flush(sdrhip_pipe* p)
 {
     SDRHIP_REQUIRE(p != nullptr, "sdrhip_pipe_flush");
     int rc;
-    if (p->eng.staged > 0 && (rc = p->is_map() ? map_submit(p) : fir_submit(p, p->eng.staged, p->uniform_n)) != SDRHIP_OK) return rc;
+    if (p->kind == PK_SPECTRUM) {
+        if ((rc = spectrum_settle(p)) != SDRHIP_OK) return rc;
+    } else if (p->eng.staged > 0 && (rc = p->is_map() ? map_submit(p) : fir_submit(p, p->eng.staged, p->uniform_n)) != SDRHIP_OK) return rc;
     if ((rc = p->eng.flush()) != SDRHIP_OK) return rc;
     return ready_blocks(p);
 }
@@ -702,6 +875,17 @@ static size_t pipe_state_am_bytes(const sdrhip_pipe* p)
     return p->kind != PK_AM_BANK ? 0 : sizeof(PipeStateAm) + (p->am_dc ? (size_t)p->rows() * 2 * sizeof(float) : 0);
 }
 static size_t pipe_state_header_bytes(const sdrhip_pipe* p) { return sizeof(PipeStateHeader) + (pipe_state_version(p) == 2 ? sizeof(PipeStateRows) : 0); }
+// Version 3: the waterfall Pipe.  This header, the carried tail (tail_n samples in the input's own type), the rows not yet popped
+// (pending floats).  pos = samples pushed so far; the tail starts at stream sample rows_done * group * hop = pos - tail_n (skip == 0)
+// or lies skip samples beyond pos (tail_n == 0).
+struct PipeStateSpectrum {
+    uint32_t magic, version;
+    int32_t kind, n, input_type, group, reduce, unit;
+    int64_t hop;
+    double floor_db;
+    int64_t pos, rows_done, skip, tail_n, pending;
+};
+constexpr uint32_t kPipeSpectrumVersion = 3;
 }  // namespace
 
 size_t sdrhip_pipe_state_bytes(sdrhip_pipe* p)
@@ -711,6 +895,7 @@ size_t sdrhip_pipe_state_bytes(sdrhip_pipe* p)
     // slot is harvested into the fifo), so the size returned is what the save that follows needs -- whatever the ratio of
     // the stage and the size of the blocks in flight.  0 = the drain failed (sdrhip_last_error).
     if (sdrhip_pipe_flush(p) < 0) return 0;
+    if (p->kind == PK_SPECTRUM) return sizeof(PipeStateSpectrum) + p->eng.state_bytes(p->eng.hist_n, (int64_t)p->eng.pending());
     return pipe_state_header_bytes(p) + p->eng.state_bytes(p->eng.hist_n, (int64_t)p->eng.pending()) + p->demod_blocks.size() * sizeof(int32_t) +
            pipe_state_am_bytes(p);
 }
@@ -720,6 +905,25 @@ int sdrhip_pipe_save(sdrhip_pipe* p, void* buf, size_t capacity, size_t* used)
     SDRHIP_REQUIRE(p != nullptr && buf != nullptr && used != nullptr, "sdrhip_pipe_save");
     int rc = sdrhip_pipe_flush(p);
     if (rc < 0) return rc;
+    if (p->kind == PK_SPECTRUM) {
+        PipeStateSpectrum x;
+        memset(&x, 0, sizeof x);
+        x.magic = kPipeMagic;
+        x.version = kPipeSpectrumVersion;
+        x.kind = (int32_t)p->kind;
+        x.n = p->block_out; x.input_type = (int32_t)p->fmt; x.group = p->sp_group; x.reduce = p->sp_reduce; x.unit = p->sp_unit;
+        x.hop = p->sp_hop; x.floor_db = p->sp_floor_db;
+        x.pos = p->sp_pos; x.rows_done = p->sp_rows_done; x.skip = p->sp_skip; x.tail_n = p->eng.hist_n; x.pending = (int64_t)p->eng.pending();
+        const size_t need = sizeof x + p->eng.state_bytes(x.tail_n, x.pending);
+        if (capacity < need) {
+            set_error("sdrhip_pipe_save: %zu bytes needed, %zu given", need, capacity);
+            return SDRHIP_ERR_ARG;
+        }
+        memcpy(buf, &x, sizeof x);
+        (void)p->eng.save((unsigned char*)buf + sizeof x);
+        *used = need;
+        return SDRHIP_OK;
+    }
     PipeStateHeader h;
     memset(&h, 0, sizeof h);
     h.magic = kPipeMagic;
@@ -766,6 +970,31 @@ int sdrhip_pipe_save(sdrhip_pipe* p, void* buf, size_t capacity, size_t* used)
 
 int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
 {
+    if (p != nullptr && p->kind == PK_SPECTRUM) {
+        SDRHIP_REQUIRE(buf != nullptr && bytes >= 3 * sizeof(int32_t), "sdrhip_pipe_restore");
+        SDRHIP_REQUIRE(p->eng.pushes == 0 && p->sp_pos == 0 && p->eng.staged == 0 && p->eng.pending() == 0,
+                       "sdrhip_pipe_restore: only into a pipe that has not been pushed to");
+        PipeStateSpectrum x;
+        memset(&x, 0, sizeof x);
+        memcpy(&x, buf, bytes < sizeof x ? bytes : sizeof x);
+        SDRHIP_REQUIRE(x.magic == kPipeMagic, "sdrhip_pipe_restore: not a pipe state");
+        SDRHIP_REQUIRE(x.version == kPipeSpectrumVersion && x.kind == (int32_t)PK_SPECTRUM, "sdrhip_pipe_restore: the state belongs to a pipe of another kind");
+        SDRHIP_REQUIRE(bytes >= sizeof x, "sdrhip_pipe_restore: truncated state");
+        SDRHIP_REQUIRE(x.n == p->block_out && x.input_type == (int32_t)p->fmt && x.hop == p->sp_hop && x.group == p->sp_group && x.reduce == p->sp_reduce &&
+                           x.unit == p->sp_unit && memcmp(&x.floor_db, &p->sp_floor_db, sizeof(double)) == 0,
+                       "sdrhip_pipe_restore: the state belongs to a waterfall pipe of other parameters");
+        // the tail holds no whole row and starts where row rows_done does
+        const __int128 start = (__int128)x.rows_done * p->sp_group * p->sp_hop;
+        SDRHIP_REQUIRE(x.pos >= 0 && x.rows_done >= 0 && x.skip >= 0 && x.tail_n >= 0 && x.pending >= 0 && x.pending % p->block_out == 0 &&
+                           x.tail_n <= p->eng.head_cap && (x.skip == 0 || x.tail_n == 0) && start == (__int128)x.pos - x.tail_n + x.skip &&
+                           spectrum_rows_in(p, x.tail_n) == 0,
+                       "sdrhip_pipe_restore: inconsistent state");
+        SDRHIP_REQUIRE(x.pending <= (int64_t)((bytes - sizeof x) / sizeof(float)) &&
+                           bytes - sizeof x >= p->eng.state_bytes(x.tail_n, x.pending), "sdrhip_pipe_restore: truncated state");
+        (void)p->eng.restore((const unsigned char*)buf + sizeof x, x.tail_n, x.pending);
+        p->sp_pos = x.pos; p->sp_rows_done = x.rows_done; p->sp_skip = x.skip;
+        return ready_blocks(p);
+    }
     SDRHIP_REQUIRE(p != nullptr && buf != nullptr && bytes >= sizeof(PipeStateHeader), "sdrhip_pipe_restore");
     SDRHIP_REQUIRE(p->eng.pushes == 0 && p->E_prev == 0 && p->eng.staged == 0 && p->eng.pending() == 0,
                    "sdrhip_pipe_restore: only into a pipe that has not been pushed to");
@@ -825,6 +1054,13 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
     return ready_blocks(p);
 }
 
-void sdrhip_pipe_destroy(sdrhip_pipe* p) { delete p; }
+void sdrhip_pipe_destroy(sdrhip_pipe* p)
+{
+    // the borrowed spectrum object outlives the pipe's streams: it must not remember one of them as its scratch's last user
+    if (p != nullptr && p->kind == PK_SPECTRUM)
+        for (hipStream_t st : p->eng.compute)
+            if (st) spectrum_forget_stream(p->spec, st);
+    delete p;
+}
 
 }  // extern "C"

@@ -7,7 +7,7 @@ namespace sdrhip {
 
 // what the kernels need to know about one sdrhip_spectrum_run_device call
 struct SpectrumArgs {
-    const void* in;         // raw IQ: interleaved u8 (format 0) or float32 (format 1)
+    const void* in;         // raw IQ: interleaved u8 (format 0), float32 (format 1) or int16 (format 2)
     int format;
     int64_t hop;            // samples between row starts
     int64_t rows;
@@ -52,4 +52,14 @@ hipError_t launch_spectrum_reduce_finalise(hipStream_t stream, const double* par
 hipError_t launch_spectrum_accumulate(hipStream_t stream, const double2* work, int64_t b0, int64_t nrows, int n, double scale, const SpectrumReduce& f,
                                       double* chunk, double* total, float* out);
 
+}  // namespace sdrhip
+
+// what the waterfall Pipe (sdrhip_pipe_spectrum, pipes.cpp) asks of the object it borrows (fft.cpp): its size, its SDRHIP_IQ_*
+// format, and whether a reduce run of this group length goes through the object's one scratch buffer (the hipFFT route, or layers)
+struct sdrhip_spectrum;
+namespace sdrhip {
+int spectrum_size_of(const sdrhip_spectrum* s);
+int spectrum_format_of(const sdrhip_spectrum* s);
+bool spectrum_reduce_uses_scratch(const sdrhip_spectrum* s, int group);
+void spectrum_forget_stream(sdrhip_spectrum* s, hipStream_t stream);      // before `stream` is destroyed
 }  // namespace sdrhip

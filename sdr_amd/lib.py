@@ -352,6 +352,7 @@ lib.sdrhip_pipe_push_i16.argtypes = [_vp, _i16p, C.c_int]
 lib.sdrhip_pipe_input_buffer_i16.argtypes = [_vp, C.c_int]
 lib.sdrhip_pipe_input_buffer_i16.restype = _vp
 lib.sdrhip_pipe_pop_rows.argtypes = [_vp, _f32p, _i64, C.c_int]
+lib.sdrhip_pipe_spectrum.argtypes = [C.POINTER(_vp), _vp, _i64, C.c_int, C.c_int, C.c_int, C.c_double]
 lib.sdrhip_pipe_set_coalesce.argtypes = [_vp, C.c_int]
 lib.sdrhip_pipe_set_adaptive.argtypes = [_vp, C.c_int]
 lib.sdrhip_pipe_input_buffer.argtypes = [_vp, C.c_int]
@@ -1211,7 +1212,7 @@ class Fft(_Handle):
         return out if self.batch > 1 else out[0]
 
 
-IQ_U8, IQ_CF32 = 0, 1
+IQ_U8, IQ_CF32, IQ_I16 = 0, 1, 2
 WINDOW_NONE, WINDOW_HANNING, WINDOW_HAMMING, WINDOW_BLACKMAN, WINDOW_CUSTOM = 0, 1, 2, 3, 4
 SPECTRUM_ROUTE_AUTO, SPECTRUM_ROUTE_FUSED, SPECTRUM_ROUTE_HIPFFT = 0, 1, 2
 REDUCE_MEAN_POWER, REDUCE_MEAN_MAGNITUDE, REDUCE_MAX_MAGNITUDE = 0, 1, 2
@@ -1220,7 +1221,7 @@ REDUCE_SPLIT_AUTO, REDUCE_SPLIT_NEVER, REDUCE_SPLIT_ALWAYS = 0, 1, 2
 
 
 class Spectrum(_Handle):
-    """The reference's waterfall pipe as one operator: raw IQ (u8 or interleaved float32) x halfBandUp x window -> DFT ->
+    """The reference's waterfall pipe as one operator: raw IQ (u8, interleaved float32 or interleaved int16) x halfBandUp x window -> DFT ->
     scale * |X| as float32 rows (sdr_hip.h, sdrhip_spectrum_*).  Row r covers samples [r*hop, r*hop + n)."""
     _destroy = lib.sdrhip_spectrum_destroy
 
@@ -1235,6 +1236,10 @@ class Spectrum(_Handle):
         check(lib.sdrhip_spectrum_create(C.byref(self.h), n, input_format, window, cw.ctypes.data_as(_f64p) if cw is not None else None,
                                          int(bool(half_band_shift)), float(scale)), "sdrhip_spectrum_create")
         self.n, self.input_format = n, input_format
+
+    def _host_dtype(self):
+        import numpy as np
+        return {IQ_U8: np.uint8, IQ_I16: np.int16}.get(self.input_format, np.float32)
 
     def window(self):
         import numpy as np
@@ -1257,9 +1262,9 @@ class Spectrum(_Handle):
         return rows
 
     def run(self, iq, hop=None, rows=None):
-        """iq: a host array of interleaved samples (uint8 or float32, by input_format) -> rows x n float32."""
+        """iq: a host array of interleaved samples (uint8, float32 or int16, by input_format) -> rows x n float32."""
         import numpy as np
-        a = np.ascontiguousarray(iq, dtype=np.uint8 if self.input_format == IQ_U8 else np.float32).reshape(-1)
+        a = np.ascontiguousarray(iq, dtype=self._host_dtype()).reshape(-1)
         n_samples = a.size // 2
         hop = self.n if hop is None else int(hop)
         rows = self.rows_of(n_samples, hop) if rows is None else int(rows)
@@ -1283,7 +1288,7 @@ class Spectrum(_Handle):
     def reduce(self, iq, group, reduce=REDUCE_MEAN_POWER, unit=UNIT_LINEAR, floor_db=-200.0, hop=None, rows_out=None):
         """iq: a host array of interleaved samples -> rows_out x n float32 (see reduce_device)."""
         import numpy as np
-        a = np.ascontiguousarray(iq, dtype=np.uint8 if self.input_format == IQ_U8 else np.float32).reshape(-1)
+        a = np.ascontiguousarray(iq, dtype=self._host_dtype()).reshape(-1)
         n_samples = a.size // 2
         hop = self.n if hop is None else int(hop)
         rows_out = self.rows_of(n_samples, hop) // int(group) if rows_out is None else int(rows_out)
@@ -1490,7 +1495,7 @@ class Pipe(_Handle):
     Tuner(factor, coeffs, tables[j], order) yields."""
     _destroy = lib.sdrhip_pipe_destroy
 
-    def __init__(self, kind, desc=None, block_size_out=8192, mu=None, reference=None, input_u8=False, input_i16=False):
+    def __init__(self, kind, desc=None, block_size_out=8192, mu=None, reference=None, input_u8=False, input_i16=False, spectrum_args=None):
         super().__init__()
         self.desc = desc  # keep the descriptor alive
         self.block_size_out = block_size_out
@@ -1519,6 +1524,12 @@ class Pipe(_Handle):
                 raise ValueError("Pipe.am_bank: input_u8 and input_i16 exclude each other")
             check(lib.sdrhip_pipe_am_bank(C.byref(self.h), desc.h, block_size_out, 2 if input_i16 else int(bool(input_u8))), "sdrhip_pipe_am_bank")
             self.input_u8, self.input_i16 = bool(input_u8), bool(input_i16)
+            self.complex_in = True
+        elif kind == "spectrum":
+            hop, group, reduce, unit, floor_db = spectrum_args
+            check(lib.sdrhip_pipe_spectrum(C.byref(self.h), desc.h, int(hop), int(group), int(reduce), int(unit), float(floor_db)),
+                  "sdrhip_pipe_spectrum")
+            self.input_u8, self.input_i16 = desc.input_format == IQ_U8, desc.input_format == IQ_I16
             self.complex_in = True
         elif kind == "fm_demod":
             check(lib.sdrhip_pipe_fm_demod(C.byref(self.h)), "sdrhip_pipe_fm_demod")
@@ -1550,6 +1561,13 @@ class Pipe(_Handle):
         """The AM bank on host blocks: cfloat, u8 IQ or int16 IQ blocks in, every channel's audio (the envelope; with the bank's
         dc_block, dcBlocker of it, its state kept on the device) in blocks of block_size_out floats out."""
         return Pipe("am_bank", am_bank, block_size_out, input_u8=input_u8, input_i16=input_i16)
+
+    @staticmethod
+    def spectrum(spectrum, hop=None, group=1, reduce=REDUCE_MEAN_MAGNITUDE, unit=UNIT_LINEAR, floor_db=-200.0):
+        """The waterfall on host blocks (sdrhip_pipe_spectrum): blocks of any size in the Spectrum's own input type in (uint8, float32 or
+        int16 arrays; an array of another dtype is refused), rows of n float32 out -- output row R reducing input rows R*group ..
+        R*group+group-1 of the whole stream, as Spectrum.reduce_device over the concatenated pushes.  hop defaults to n."""
+        return Pipe("spectrum", spectrum, spectrum.n, spectrum_args=(spectrum.n if hop is None else hop, group, reduce, unit, floor_db))
 
     @staticmethod
     def am_demod():
