@@ -1089,6 +1089,17 @@ int  sdrhip_spectrum_run_device(sdrhip_spectrum *s, void *stream, const void *d_
 int  sdrhip_spectrum_run(sdrhip_spectrum *s, const void *in, int64_t n_samples, int64_t hop, int rows, float *out);
 int  sdrhip_spectrum_set_route(sdrhip_spectrum *s, int route);   /* 0 = auto, 1 = the one-kernel route, 2 = hipFFT route */
 long long sdrhip_debug_spectrum_fused_launches(void);            /* process-wide, for tests that assert the route */
+/* process-wide: hipFFT transforms (one per chunk of rows that fits the scratch buffer) the operator has issued, from
+ * sdrhip_spectrum_run_device and sdrhip_spectrum_reduce_run_device alike: tests of the chunking assert that it happened */
+long long sdrhip_debug_spectrum_hipfft_batches(void);
+/* Input addresses: u8 input may start at any address.  float32 input must be 4-byte aligned, else SDRHIP_ERR_ARG before any launch
+ * with nothing written (an 8-byte aligned base is read with one load per sample, any other with two); int16 as stated at
+ * SDRHIP_IQ_I16.  No byte outside the n_samples samples of d_in is read.
+ * Non-finite float32 input (u8 and int16 cannot produce any): a NaN or an Inf in a sample makes EVERY bin of every row that holds
+ * the sample non-finite -- NaN in every bin for a NaN sample, also where the window is 0 there (0 * NaN is NaN) -- and leaves every
+ * other row's bits alone.  In the reducing form below such a row poisons its output row in every reduce and unit: all bins NaN for a
+ * NaN sample, all bins non-finite for an Inf; the max hold does not drop the row and the dB floor does not hide it.  Which NaN
+ * (sign, payload) is unspecified.  Both routes behave so. */
 
 /* The operator's rows reduced on the device: output row R is made of the `group` consecutive input rows R*group .. R*group + group - 1
  * (input row r = samples [r*hop, r*hop + n), as above), which never reach memory.  With m_r[k] = scale * |X_r[k]|, exactly the double
@@ -1118,6 +1129,9 @@ int  sdrhip_spectrum_set_reduce_split(sdrhip_spectrum *s, int mode);   /* 0 = au
 /* process-wide: reduce calls that spread a group over workgroups.  Every reduce call on the one-kernel route also counts once in
  * sdrhip_debug_spectrum_fused_launches. */
 long long sdrhip_debug_spectrum_reduce_split_launches(void);
+/* process-wide: launches of the layered kernel, one per (slice of output rows, slice of chunks) that the bounded scratch buffer cuts
+ * a reduce call of more than 32 rows per group into: tests of the slicing assert that it happened */
+long long sdrhip_debug_spectrum_reduce_layer_launches(void);
 
 /* ------------------------------------------------------------------------ */
 /* (3) Pipe operators on host blocks                                        */

@@ -175,6 +175,8 @@ namespace {
 
 std::atomic<long long> g_spectrum_fused_launches{0};
 std::atomic<long long> g_spectrum_reduce_split_launches{0};
+std::atomic<long long> g_spectrum_hipfft_batches{0};               // ExecZ2Z calls of the operator: one per chunk / batch of rows
+std::atomic<long long> g_spectrum_reduce_layer_launches{0};        // layered spectrum_fused_reduce launches: one per (row slice, chunk slice)
 
 constexpr size_t SPECTRUM_SCRATCH_BYTES = (size_t)64 << 20;      // the hipFFT route's intermediate: at most this, or one row
 
@@ -297,6 +299,7 @@ int spectrum_run_hipfft(sdrhip_spectrum* s, hipStream_t stream, const SpectrumAr
         SDRHIP_CHECK_HIP(launch_spectrum_prepare(stream, a, row0, nrows, work));
         SDRHIP_CHECK_FFT(h->SetStream(plan, stream));
         SDRHIP_CHECK_FFT(h->ExecZ2Z(plan, reinterpret_cast<hipfftDoubleComplex*>(work), reinterpret_cast<hipfftDoubleComplex*>(work), HIPFFT_FORWARD));
+        g_spectrum_hipfft_batches.fetch_add(1);
         SDRHIP_CHECK_HIP(launch_spectrum_magnitude(stream, work, nrows * s->n, s->scale, d_out + row0 * s->n));
     }
     return SDRHIP_OK;
@@ -355,6 +358,7 @@ int spectrum_reduce_fused(sdrhip_spectrum* s, hipStream_t stream, const Spectrum
             int per_item = c1 - c0;                     // not split: a tile's chunks stay with one workgroup
             if (split) per_item = (int)ceil_div(c1 - c0, ceil_div(SPECTRUM_SPLIT_ITEMS, tiles));
             SDRHIP_CHECK_HIP(launch_spectrum_fused_reduce(stream, b, f, c0, c1, per_item, partial, nullptr));
+            g_spectrum_reduce_layer_launches.fetch_add(1);
             SDRHIP_CHECK_HIP(launch_spectrum_reduce_finalise(stream, partial, c1 - c0, b.rows * n, total, c0 == 0, c1 == nchunks, f, d_out + r0 * n));
         }
     }
@@ -394,6 +398,7 @@ int spectrum_reduce_hipfft(sdrhip_spectrum* s, hipStream_t stream, const Spectru
             SDRHIP_CHECK_HIP(launch_spectrum_prepare(stream, a, r0 * f.group + b0, nrows, work));
             SDRHIP_CHECK_FFT(h->SetStream(plan, stream));
             SDRHIP_CHECK_FFT(h->ExecZ2Z(plan, reinterpret_cast<hipfftDoubleComplex*>(work), reinterpret_cast<hipfftDoubleComplex*>(work), HIPFFT_FORWARD));
+        g_spectrum_hipfft_batches.fetch_add(1);
             SDRHIP_CHECK_HIP(launch_spectrum_accumulate(stream, work, b0, nrows, n, s->scale, f, chunk, total, d_out + r0 * n));
         }
     }
@@ -467,6 +472,8 @@ int sdrhip_spectrum_set_route(sdrhip_spectrum* s, int route)
 }
 
 long long sdrhip_debug_spectrum_fused_launches(void) { return g_spectrum_fused_launches.load(); }
+long long sdrhip_debug_spectrum_hipfft_batches(void) { return g_spectrum_hipfft_batches.load(); }
+long long sdrhip_debug_spectrum_reduce_layer_launches(void) { return g_spectrum_reduce_layer_launches.load(); }
 
 int sdrhip_spectrum_run_device(sdrhip_spectrum* s, void* stream, const void* d_in, int64_t n_samples, int64_t hop, int rows, float* d_out)
 {
@@ -474,6 +481,7 @@ int sdrhip_spectrum_run_device(sdrhip_spectrum* s, void* stream, const void* d_i
     SDRHIP_REQUIRE(rows >= 1 && hop >= 1 && n_samples >= s->n, "sdrhip_spectrum_run_device");
     SDRHIP_REQUIRE(rows == 1 || hop <= (n_samples - s->n) / (rows - 1), "sdrhip_spectrum_run_device: the last row must end inside the input");
     SDRHIP_REQUIRE(s->format != SDRHIP_IQ_I16 || ((uintptr_t)d_in & 1u) == 0, "sdrhip_spectrum_run_device: int16 input at an odd address");
+    SDRHIP_REQUIRE(s->format != SDRHIP_IQ_CF32 || ((uintptr_t)d_in & 3u) == 0, "sdrhip_spectrum_run_device: float32 input at an address that is not a multiple of 4");
     int rc;
     if ((rc = spectrum_upload(s)) != SDRHIP_OK) return rc;
     SpectrumArgs a;
@@ -554,6 +562,8 @@ int sdrhip_spectrum_reduce_run_device(sdrhip_spectrum* s, void* stream, const vo
     SDRHIP_REQUIRE(s != nullptr && d_in != nullptr && d_out != nullptr, "sdrhip_spectrum_reduce_run_device");
     SDRHIP_REQUIRE(spectrum_reduce_args_ok(s, n_samples, hop, rows_out, group, reduce, unit, floor_db), "sdrhip_spectrum_reduce_run_device");
     SDRHIP_REQUIRE(s->format != SDRHIP_IQ_I16 || ((uintptr_t)d_in & 1u) == 0, "sdrhip_spectrum_reduce_run_device: int16 input at an odd address");
+    SDRHIP_REQUIRE(s->format != SDRHIP_IQ_CF32 || ((uintptr_t)d_in & 3u) == 0,
+                   "sdrhip_spectrum_reduce_run_device: float32 input at an address that is not a multiple of 4");
     int rc;
     if ((rc = spectrum_upload(s)) != SDRHIP_OK) return rc;
     SpectrumArgs a;

@@ -248,15 +248,17 @@ __global__ __launch_bounds__(T) void spectrum_fused(const void* __restrict__ in,
 }
 
 // ---- the reducing form (sdrhip_spectrum_reduce_*) -------------------------------------------------------------------------------
-// one value into an accumulator / a chunk's accumulator into the total / the total into the output float
+// one value into an accumulator / a chunk's accumulator into the total / the total into the output float.  A non-finite magnitude
+// (cf32 input that holds a NaN or an Inf) poisons its bin in every reduce and unit, as numpy's max and maximum do in the model: the max
+// hold takes a NaN and keeps one (a plain `m > acc ? m : acc` would drop the row), and the floor clamp lets a NaN through.
 __device__ __forceinline__ double reduce_add(double acc, double m, int reduce)
 {
-    if (reduce == 2) return m > acc ? m : acc;
+    if (reduce == 2) return (m > acc || m != m) ? m : acc;
     return acc + (reduce == 0 ? m * m : m);
 }
 __device__ __forceinline__ double reduce_fold(double total, double acc, int reduce)
 {
-    if (reduce == 2) return acc > total ? acc : total;
+    if (reduce == 2) return (acc > total || acc != acc) ? acc : total;
     return total + acc;
 }
 __device__ __forceinline__ float reduce_finish(double v, const SpectrumReduce& f)
@@ -264,7 +266,7 @@ __device__ __forceinline__ float reduce_finish(double v, const SpectrumReduce& f
     if (f.reduce != 2) v = v / (double)f.group;
     if (f.unit == 1) {
         const double d = (f.reduce == 0 ? 10.0 : 20.0) * log10(v);
-        v = d > f.floor_db ? d : f.floor_db;         // log10(0) = -inf: the floor
+        v = d < f.floor_db ? f.floor_db : d;         // log10(0) = -inf: the floor; a NaN stays a NaN
     }
     return (float)v;
 }

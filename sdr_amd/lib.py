@@ -251,11 +251,15 @@ lib.sdrhip_spectrum_run.argtypes = [_vp, _vp, _i64, _i64, C.c_int, _vp]
 lib.sdrhip_spectrum_set_route.argtypes = [_vp, C.c_int]
 lib.sdrhip_debug_spectrum_fused_launches.argtypes = []
 lib.sdrhip_debug_spectrum_fused_launches.restype = C.c_longlong
+lib.sdrhip_debug_spectrum_hipfft_batches.argtypes = []
+lib.sdrhip_debug_spectrum_hipfft_batches.restype = C.c_longlong
 lib.sdrhip_spectrum_reduce_run_device.argtypes = [_vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _vp]
 lib.sdrhip_spectrum_reduce_run.argtypes = [_vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _vp]
 lib.sdrhip_spectrum_set_reduce_split.argtypes = [_vp, C.c_int]
 lib.sdrhip_debug_spectrum_reduce_split_launches.argtypes = []
 lib.sdrhip_debug_spectrum_reduce_split_launches.restype = C.c_longlong
+lib.sdrhip_debug_spectrum_reduce_layer_launches.argtypes = []
+lib.sdrhip_debug_spectrum_reduce_layer_launches.restype = C.c_longlong
 lib.sdrhip_filter_one.argtypes = [_vp, C.c_int, _f32p, _f32p]
 lib.sdrhip_filter_cross.argtypes = [_vp, C.c_int, _f32p, C.c_int, _f32p, C.c_int, _f32p]
 lib.sdrhip_decimator_one.argtypes = [_vp, C.c_int, _f32p, _f32p]
@@ -1304,6 +1308,14 @@ def spectrum_fused_launches():
 
 def spectrum_reduce_split_launches():
     return int(lib.sdrhip_debug_spectrum_reduce_split_launches())
+
+
+def spectrum_hipfft_batches():
+    return int(lib.sdrhip_debug_spectrum_hipfft_batches())
+
+
+def spectrum_reduce_layer_launches():
+    return int(lib.sdrhip_debug_spectrum_reduce_layer_launches())
 
 
 TRANSPORT_RCCL, TRANSPORT_PEER_COPY = 1, 2

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 SPECTRUM_FUNCTIONS = ["sdrhip_spectrum_create", "sdrhip_spectrum_destroy", "sdrhip_spectrum_size", "sdrhip_spectrum_window",
                       "sdrhip_spectrum_run_device", "sdrhip_spectrum_run", "sdrhip_spectrum_set_route",
-                      "sdrhip_debug_spectrum_fused_launches"]
+                      "sdrhip_debug_spectrum_fused_launches", "sdrhip_debug_spectrum_hipfft_batches"]
 
 
 @pytest.mark.parametrize("n", [8, 64])
@@ -67,6 +67,7 @@ def test_header_declares_and_binding_binds_the_operator():
         assert hasattr(product, name), f"{name} is not exported"
         assert getattr(L.lib, name).argtypes is not None, f"{name} is not bound in sdr_amd/lib.py"
     assert L.lib.sdrhip_debug_spectrum_fused_launches.restype is C.c_longlong
+    assert L.lib.sdrhip_debug_spectrum_hipfft_batches.restype is C.c_longlong and L.spectrum_hipfft_batches() >= 0
     assert hasattr(L, "Spectrum") and hasattr(L.Spectrum, "run") and hasattr(L.Spectrum, "run_device")
     assert (L.IQ_U8, L.IQ_CF32) == (M.IQ_U8, M.IQ_CF32)
     assert (L.WINDOW_NONE, L.WINDOW_HANNING, L.WINDOW_HAMMING, L.WINDOW_BLACKMAN, L.WINDOW_CUSTOM) == (0, 1, 2, 3, 4)

@@ -13,7 +13,7 @@ import spectrum_reduce_model as R
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 REDUCE_FUNCTIONS = ["sdrhip_spectrum_reduce_run_device", "sdrhip_spectrum_reduce_run", "sdrhip_spectrum_set_reduce_split",
-                    "sdrhip_debug_spectrum_reduce_split_launches"]
+                    "sdrhip_debug_spectrum_reduce_split_launches", "sdrhip_debug_spectrum_reduce_layer_launches"]
 
 
 def test_group_of_one_mean_magnitude_is_the_operator():
@@ -91,6 +91,7 @@ def test_header_declares_and_library_exports_the_reduce_entry_points():
         assert getattr(L.lib, name).argtypes is not None, f"{name} is not bound in sdr_amd/lib.py"
     assert L.lib.sdrhip_debug_spectrum_reduce_split_launches.restype is C.c_longlong
     assert L.spectrum_reduce_split_launches() >= 0
+    assert L.lib.sdrhip_debug_spectrum_reduce_layer_launches.restype is C.c_longlong and L.spectrum_reduce_layer_launches() >= 0
     for method in ("reduce", "reduce_device", "set_reduce_split"):
         assert hasattr(L.Spectrum, method), method
     assert (L.REDUCE_MEAN_POWER, L.REDUCE_MEAN_MAGNITUDE, L.REDUCE_MAX_MAGNITUDE) == (R.MEAN_POWER, R.MEAN_MAGNITUDE, R.MAX_MAGNITUDE)

@@ -1,8 +1,9 @@
 """Reduced spectrum rows: the reducing call against what the library offered before it.
 
-    python tools/spectrum_reduce_bench.py [--samples 16777216] [--rounds 7] [--iters 10] [--out FILE]
+    python tools/spectrum_reduce_bench.py [--samples 16777216] [--rounds 7] [--iters 10] [--reduce 0|1|2] [--out FILE]
 
-For n in {1024, 8192}, hop = n, u8 input, and group in {16, 1024, all rows} (a batch of `samples / n` input rows), mean power in dB:
+For n in {1024, 8192}, hop = n, u8 input, and group in {16, 1024, all rows} (a batch of `samples / n` input rows), mean power (or with
+--reduce 1 / 2 the mean magnitude / the max hold), linear:
 
   reduce    Spectrum.reduce_device: one call, rows_out x n float32 out                        (the new code)
   rows+torch  Spectrum.run_device into a full rows x n float32 buffer, then torch on the same stream: square, mean over the group axis
@@ -29,6 +30,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--sizes", type=int, nargs="*", default=[1024, 8192])
+    ap.add_argument("--reduce", type=int, default=0, choices=[0, 1, 2], help="0 mean power, 1 mean magnitude, 2 max hold")
     ap.add_argument("--out", default=None, help="also write the table to this file")
     args = ap.parse_args()
 
@@ -42,7 +44,7 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    emit(f"# {L.device_name()}  u8 samples per call {args.samples}  hop = n  mean power  rounds {args.rounds} x {args.iters} calls")
+    emit(f"# {L.device_name()}  u8 samples per call {args.samples}  hop = n  {('mean power', 'mean magnitude', 'max hold')[args.reduce]}  rounds {args.rounds} x {args.iters} calls")
     emit("| n | group | rows_out | way | ms per call (median, min .. max) | input rows/s | max rel. diff vs rows+torch |")
     emit("|---|---|---|---|---|---|---|")
     rng = np.random.default_rng(1)
@@ -65,13 +67,14 @@ def main():
             result = {}
 
             def reduce_call(way):
-                spec[way].reduce_device(d_in.data_ptr(), rows * n, d_red.data_ptr(), group, L.REDUCE_MEAN_POWER, L.UNIT_LINEAR, hop=n, rows_out=rows_out,
+                spec[way].reduce_device(d_in.data_ptr(), rows * n, d_red.data_ptr(), group, args.reduce, L.UNIT_LINEAR, hop=n, rows_out=rows_out,
                                         stream=stream)
                 result[way] = d_red
 
             def parent_call(way):
                 spec["reduce"].run_device(d_in.data_ptr(), rows * n, d_rows.data_ptr(), hop=n, rows=rows, stream=stream)
-                result[way] = torch.square(d_rows.view(rows_out, group, n)).mean(dim=1)
+                r = d_rows.view(rows_out, group, n)
+                result[way] = torch.square(r).mean(dim=1) if args.reduce == 0 else r.mean(dim=1) if args.reduce == 1 else r.amax(dim=1)
 
             ways = [("reduce", reduce_call), ("rows+torch", parent_call)]
             if rows_out == 1:
