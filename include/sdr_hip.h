@@ -597,6 +597,78 @@ long long sdrhip_debug_am_bank_fixup_launches(void);
  * sdrhip_am_bank_run never takes it */
 long long sdrhip_debug_am_bank_cross_launches(void);
 
+/* ---- narrow-band FM demodulator bank: fmDemod of every channel of one capture ---- */
+/* The tuner bank with fmDemod (Demod.hs:21-46) as its output form: NOAA weather channels, marine VHF, PMR, 2 m.  "nfm" names the
+ * use; the object fixes no bandwidth (that is the tuner bank's decimator) and has no audio stages behind the demodulator.
+ * Definition: channel j's row is d_out + j * out_stride floats and holds k_end - k_begin floats; they equal, bit for bit, what
+ * sdrhip_tuner_bank_run / _run_u8 / _run_i16 writes into complex rows for the same (d_in, in_base, k_begin, k_end, seam_block), put
+ * through sdrhip_fm_demod_run_rows with d_last_iq = d_state and d_last_out = d_final -- on every route, for every seam_block,
+ * in_base, cut into launches and out_stride.  Output k is phase(y[k] * conjugate y[k - 1]) of channel j's decimated outputs y.
+ * Floats of d_out outside the K rows' [0, k_end - k_begin) are not touched.
+ * d_state: K (re, im) pairs of device floats, channel j's decimated output k_begin - 1 at [2j, 2j + 2), read only; NULL = zeros, the
+ * start of a stream (Demod.hs:41).  d_final: K pairs that receive every channel's decimated output k_end - 1; NULL = not wanted.
+ * THE TWO MUST NOT OVERLAP (the first workgroup of a launch reads one while the last writes the other).  Consecutive runs over
+ * consecutive ranges [k0, k1), [k1, k2), ... that swap two state arrays between runs, on one stream, are ONE stream and give the bits
+ * of one run over [k0, kn).  Two streams (two host threads on one bank) take two pairs of state arrays and two workspaces.
+ * Create: the tuner bank is BORROWED and must outlive the bank; SDRHIP_ERR_ARG (and *b = NULL) for a null tuner bank.
+ * Workspace: sdrhip_nfm_bank_workspace_bytes(b, count) bytes for a run of count = k_end - k_begin outputs, 16-byte aligned, used
+ * during the run only: route 2's complex rows.  Routes 0 and 2 ask for it; route 1 asks for none (d_workspace may be NULL).
+ * Run: SDRHIP_ERR_ARG before any device work, with nothing written, for a null bank, a range outside 0 <= k_begin <= k_end (or of
+ * 2^31 - 1 outputs and more), a first window before d_in, seam_block in (0, numCoeffs), out_stride < k_end - k_begin with more than
+ * one channel, a d_out (or a state array) off a float's alignment, an int16 input at an address that is no multiple of 4,
+ * overlapping state arrays, a workspace that is null, short or not 16-byte aligned on routes 0 and 2, and route 1 forced on a launch
+ * it does not serve.  An empty range is SDRHIP_OK and copies d_state (or zeros) to d_final, on every route, as
+ * sdrhip_fm_demod_run_rows does.  Asynchronous on `stream`; after the first run a run makes no allocation, no host synchronisation and
+ * no host-to-device copy on route 1.  A bank is immutable after create (but for set_route) and may be shared by host threads.
+ * Routes (same bits).  1 = fused: exactly ONE launch of the tuner bank's tile kernel in its fmDemod form, for all channels and
+ * nothing else -- no complex row is written or read back, no workspace.  Tiles overlap by one thread's pair of outputs so that no
+ * workgroup waits on another (2 of 512 outputs are computed twice), and Cross outputs are ALWAYS computed in the tile, for any
+ * numCoeffs <= seam_block < 2^30.  It fits where the tuner bank's banked launch fits (AVX order, factor 4 / 8 / 16, up to 128 prepared
+ * taps, seam_block >= 0, a 16-byte aligned first window; d_out needs a float's alignment only) with seam_block < 2^30, and is
+ * SDRHIP_ERR_ARG elsewhere.  2 = composed: the two calls of the definition, the tuner bank on ITS route setting.  0 = auto (default).
+ * Route 1 where it fits AND the launch lies in the part of the measured sweep where route 1's slowest round was below route 2's
+ * fastest for all three input types (tools/nfm_bank_bench.py, profiles/nfm_bank_bench.txt: 1 / 2 / 8 / 32 channels x launches of 8192,
+ * 2^17, 2^20 and 2^24 input samples, u8 / cfloat / int16, factors 8 and 16, seam_block 0 and 8192, the two routes alternating in one
+ * process, 7 rounds); everything else is route 2.  With n = (k_end - k_begin - 1) * factor + numCoeffs the launch's input samples:
+ *     factor 8,  seam_block 0:        fused  iff  n <= 2^24
+ *     factor 8,  seam_block >= 8192:  fused  iff  n <= 2^20  or  ( channels == 1 and n <= 2^24 )
+ *     factor 16, seam_block 0:        fused  iff  n <= 2^24 (channels <= 2),  n <= 2^17 (3 .. 8),  n <= 8192 (9 .. 32)
+ *     factor 16, seam_block >= 8192:  fused  iff  n >= 2^17  and  n <= 2^24 (1 channel),  2^20 (2 .. 8),  2^17 (9 .. 32)
+ * Factor 8 without seams is ahead at all 48 points (0.63 .. 0.97 of route 2's time: 10.0 against 11.2 us for one channel at 8192
+ * samples of u8, 977 against 1045 us for 32 channels at 2^24).  Route 1 is NOT ahead, and auto is route 2: at 2^24 samples with
+ * seams and more than one channel (factor 8: 1.06 .. 1.31; factor 16: 1.01 .. 1.49 -- every output pays the in-tile seam test's
+ * modulo and whole waves recompute the Cross outputs that route 2's fix-up launch gives one thread each); at factor 16 without seams
+ * with 8 channels from 2^20 on and 32 channels from 2^17 on (1.01 .. 1.11 for at least one input type; 32 channels at 2^20 are
+ * ahead by 1 .. 2 % between two points that are not, and stay on route 2); at factor 16 with seam_block 8192 at 8192 samples (1.07
+ * .. 1.14: 19.6 against 18.0 us) and with 32 channels at 2^20 (1.09 .. 1.20).  A channel count between two measured ones is fused
+ * only where both neighbours are.  NOT MEASURED, hence route 2: 0 < seam_block < 8192 (more seams a tile, up to every output Cross),
+ * factor 4, more than 2^24 samples a launch; seam_block > 8192 is held to the seam-8192 rows and other tap counts to the rule,
+ * unmeasured.  As a reference point the sweep times the AM bank's envelope launch set at the same shapes: the fmDemod form takes
+ * 0.90 .. 1.26 of its time at factor 8 without seams (fmDemod is ~100 VALU instructions an output where the magnitude is a few),
+ * 0.45 .. 1.58 with seams (the envelope form's fix-up launch against Cross outputs in the tile).  Under auto a launch that the kernel
+ * turns down after the predicate admitted it runs composed (route 1 forced: an error). */
+typedef struct sdrhip_nfm_bank sdrhip_nfm_bank;
+int sdrhip_nfm_bank_create(sdrhip_nfm_bank **b, const sdrhip_tuner_bank *tuner_bank);
+void sdrhip_nfm_bank_destroy(sdrhip_nfm_bank *b);
+int sdrhip_nfm_bank_channels(const sdrhip_nfm_bank *b);
+int sdrhip_nfm_bank_set_route(sdrhip_nfm_bank *b, int route);          /* 0 auto, 1 fused, 2 composed */
+size_t sdrhip_nfm_bank_workspace_bytes(const sdrhip_nfm_bank *b, int64_t count);   /* 0 for a null bank or a count outside 1 .. 2^31 - 2 */
+int sdrhip_nfm_bank_run(const sdrhip_nfm_bank *b, void *stream, const float *d_in, int64_t in_base, float *d_out, int64_t out_stride,
+                        int64_t k_begin, int64_t k_end, int64_t seam_block, const float *d_state, float *d_final, void *d_workspace,
+                        size_t workspace_bytes);
+int sdrhip_nfm_bank_run_u8(const sdrhip_nfm_bank *b, void *stream, const uint8_t *d_in_iq, int64_t in_base, float *d_out,
+                           int64_t out_stride, int64_t k_begin, int64_t k_end, int64_t seam_block, const float *d_state, float *d_final,
+                           void *d_workspace, size_t workspace_bytes);
+int sdrhip_nfm_bank_run_i16(const sdrhip_nfm_bank *b, void *stream, const int16_t *d_in_iq, int64_t in_base, float *d_out,
+                            int64_t out_stride, int64_t k_begin, int64_t k_end, int64_t seam_block, const float *d_state, float *d_final,
+                            void *d_workspace, size_t workspace_bytes);
+/* fmDemod-form tile launches (route 1: exactly one per run; an int16 one also counts in sdrhip_debug_tuner_i16_launches, none counts in
+ * sdrhip_debug_tuner_bank_launches, sdrhip_debug_am_bank_launches or sdrhip_debug_rows_launches), process-wide */
+long long sdrhip_debug_nfm_bank_launches(void);
+/* launches of the all-Cross fmDemod-form kernel of the bank's Pipe (sdrhip_pipe_nfm_bank: the boundary part of a ragged push),
+ * process-wide; sdrhip_nfm_bank_run never takes it */
+long long sdrhip_debug_nfm_bank_cross_launches(void);
+
 /* The FIR operators over rows: the filter, decimator and resampler stages behind a bank (second decimator per channel, resampler
  * and audio filter per station) in one launch set instead of one call per row.  in_base, k_begin, k_end, seam_block and out_block
  * mean what they mean to sdrhip_filter_run / sdrhip_decimator_run / sdrhip_resampler_run and are the same for every row; row r's
@@ -1221,6 +1293,27 @@ int sdrhip_pipe_tuner_bank_i16(sdrhip_pipe **p, const sdrhip_tuner_bank *b, int 
  * every other kind keep their bytes.  SDRHIP_ERR_ARG (and *p = NULL) before any device work for a null bank, block_size_out <= 0 and
  * an input_type outside 0 .. 2.  The AM bank (and its tuner bank) is borrowed and must outlive the pipe. */
 int sdrhip_pipe_am_bank(sdrhip_pipe **p, const sdrhip_am_bank *b, int block_size_out, int input_type);
+/* The narrow-band FM bank (sdrhip_nfm_bank_*) on host blocks: cfloat (input_type 0), u8 IQ (1) or int16 IQ (2) blocks in through the
+ * push and input_buffer calls of that type, every channel's demodulated blocks of exactly block_size_out FLOATS out through
+ * sdrhip_pipe_pop_rows / sdrhip_pipe_rows (sdrhip_pipe_pop with one channel).
+ * Definition: channel j's blocks are sdrhip_pipe_tuner_bank's blocks of the same pushes put through the reference's fmDemod Pipe
+ * (Demod.hs:40-46), started from (0, 0); fmDemod carries only the last sample, so block boundaries do not matter to it.  Bit for bit,
+ * for every sequence of block sizes, coalesced or adaptive.
+ * Machinery: sdrhip_pipe_am_bank's -- the [carried tail | staged] copy, the 16-byte alignment of the first window in device memory,
+ * equal blocks as ONE fmDemod-form tile launch with the block size as seam_block (sdrhip_debug_nfm_bank_launches), a block of another
+ * size as one all-Cross fmDemod-form launch over the outputs that straddle the boundary (sdrhip_debug_nfm_bank_cross_launches) plus
+ * one tile launch with seam_block 0.  The launches are the bank's fused route wherever it fits, whatever the bank's route setting and
+ * auto rule; a bank of another order or factor goes through the tuner bank and fmDemod's rows form.  The input is never read in place.
+ * STATE: two arrays of K (re, im) pairs live in device memory, zero at create; every launch reads one and writes the other, and they
+ * are swapped after every launch.  There is no host synchronisation between pushes.  ORDERING: consecutive submissions depend on
+ * each other through that state, so every launch of this pipe goes to ONE compute stream (the engine's first).
+ * sdrhip_pipe_set_coalesce / _set_adaptive, sdrhip_pipe_flush / _poll as for sdrhip_pipe_tuner_bank; the push call of another input
+ * type is SDRHIP_ERR_ARG.  Save / restore: the rows state of sdrhip_pipe_tuner_bank plus the 2 K state floats (save flushes, then
+ * reads them back); restore refuses another kind, row count, input type, block_size_out, factor, tap count and a truncated state,
+ * with the pipe unchanged.  The kind number is a new one at the end (11): states of every other kind keep their bytes.
+ * SDRHIP_ERR_ARG (and *p = NULL) before any device work for a null bank, block_size_out <= 0 and an input_type outside 0 .. 2.  The
+ * bank (and its tuner bank) is borrowed and must outlive the pipe. */
+int sdrhip_pipe_nfm_bank(sdrhip_pipe **p, const sdrhip_nfm_bank *b, int block_size_out, int input_type);
 int sdrhip_pipe_push_i16(sdrhip_pipe *p, const int16_t *iq, int n_samples);
 int16_t *sdrhip_pipe_input_buffer_i16(sdrhip_pipe *p, int n_samples);
 

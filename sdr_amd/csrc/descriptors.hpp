@@ -140,9 +140,30 @@ int am_bank_envelope(const TunerBankDesc* tb, hipStream_t s, const void* d_in, I
 int am_bank_envelope_cross(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_env,
                            int64_t env_stride, int64_t k_begin, int64_t k_end);
 
+
+// The narrow-band FM bank (include/sdr_hip.h, nfm_bank.cpp): a BORROWED tuner bank and fmDemod of each of its rows.
+struct NfmBankDesc {
+    const TunerBankDesc* tb = nullptr;
+    mutable int route = 0;                     // 0 = auto, 1 = fused, 2 = composed
+};
+// For the bank's Pipe (pipes.cpp), which owns its scratch and its two state arrays and has no route setting: the demodulated rows,
+// d_out + j * out_stride floats, from d_state (channels (re, im) pairs: every channel's output k_begin - 1) and into d_final (output
+// k_end - 1); the two do not overlap.  nfm_bank_phase: outputs [k_begin, k_end), k_end > k_begin, by the ONE fused launch where it
+// fits (0 <= seam_block < 2^30), else by the tuner bank into d_iq (channels rows of 2 * row_floats floats, 16-byte aligned; null = no
+// fall-back: SDRHIP_ERR_ARG) and fmDemod's rows form.  nfm_bank_phase_cross: every output Cross, one launch.
+int nfm_bank_phase(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out, int64_t out_stride,
+                   int64_t k_begin, int64_t k_end, int64_t seam_block, const float* d_state, float* d_final, float* d_iq,
+                   int64_t row_floats);
+// whether nfm_bank_phase takes the fused launch for this range (so that the Pipe keeps no complex scratch where it does)
+bool nfm_bank_fused_fits(const TunerBankDesc* tb, const void* d_in, InFmt fmt, int64_t in_base, int64_t k_begin, int64_t k_end,
+                         int64_t seam_block);
+int nfm_bank_phase_cross(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out,
+                         int64_t out_stride, int64_t k_begin, int64_t k_end, const float* d_state, float* d_final);
+
 }  // namespace sdrhip
 
 struct sdrhip_am_bank : sdrhip::AmBankDesc {};
+struct sdrhip_nfm_bank : sdrhip::NfmBankDesc {};
 struct sdrhip_filter : sdrhip::FirDesc {};
 struct sdrhip_decimator : sdrhip::FirDesc {};
 struct sdrhip_resampler : sdrhip::ResampDesc {};

@@ -385,7 +385,8 @@ bool launch_tuner_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, 
                        const int* periods, bool counts_as_bank);
 // What a kernel of the bank stores per finished output (`int OUT` template argument beside FMT): the complex value, or its
 // Data.Complex magnitude as one float (am.hpp: am_magnitude) -- the AM bank's envelope form.
-enum OutKind : int { OUT_IQ = 0, OUT_ENV = 1 };
+// OUT_FM: fm_phase (demod.hpp) of the finished output and its predecessor as one float -- the narrow-band FM bank's form.
+enum OutKind : int { OUT_IQ = 0, OUT_ENV = 1, OUT_FM = 2 };
 // launch_tuner_bank's launch set in the envelope form (am_bank.cpp): row j is g.count FLOATS at d_out + j * out_stride, any
 // out_stride >= g.count (odd ones included) when there is more than one channel, d_out at any float address.  Shapes and input
 // alignment as launch_tuner_bank; false = not this shape, nothing launched.  Counts in am_bank_launch_count (int16 input also in
@@ -398,6 +399,21 @@ bool launch_am_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, int
 bool launch_am_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_taps, const void* d_in, InFmt fmt, float* d_out,
                           int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods);
 long long am_bank_cross_launch_count();   // diagnostics: launches of the all-Cross envelope kernel
+// launch_tuner_bank's tile launch in the fmDemod form (nfm_bank.cpp): row j is g.count FLOATS at d_out + j * out_stride, output k =
+// fm_phase(y[k], y[k - 1]); d_state = `channels` (re, im) pairs, channel j's decimated output k_begin - 1 (null = zeros), d_final
+// (null = not wanted) receives output k_begin + count - 1.  The two must not overlap (the caller checks).  ONE launch: every Cross
+// output is computed in the tile, for any seam in [Lp, 2^30); a longer seam is refused.  Shapes and input alignment as
+// launch_tuner_bank; false = not this shape, nothing launched.  Counts in nfm_bank_launch_count (int16 input also in
+// tuner_i16_launch_count) and in no other counter.
+bool launch_nfm_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in,
+                     InFmt fmt, float* d_out, int64_t out_stride, const float* d_tables, int channels, const int* offsets,
+                     const int* periods, const float* d_state, float* d_final);
+// launch_tuner_bank_cross in the fmDemod form: every output Cross, thread t computes y[t] and y[t - 1] (the Pipe's ragged boundary)
+bool launch_nfm_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_taps, const void* d_in, InFmt fmt, float* d_out,
+                           int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods,
+                           const float* d_state, float* d_final);
+long long nfm_bank_launch_count();        // diagnostics: fmDemod-form tile launches, every format
+long long nfm_bank_cross_launch_count();  // diagnostics: launches of the all-Cross fmDemod-form kernel
 long long am_bank_launch_count();         // diagnostics: envelope tile launches, every format
 long long am_bank_fixup_launch_count();   // diagnostics: envelope fix-up launches
 long long tuner_bank_launch_count();    // diagnostics: banked launches, every format

@@ -37,7 +37,23 @@
 // value under the magnitude is the OUT_IQ launch's bit for bit.  Any out_stride >= count, any float-aligned row: a thread's pair is one
 // 8-byte store where row pointer + output index is 8-byte aligned and both outputs exist, 4-byte stores otherwise (the two
 // sequential-order kernels hold one output a thread: 4-byte stores).
+//
+// OUT_FM (the narrow-band FM bank, nfm_bank.cpp) stores fm_phase(y[k], y[k - 1]) (demod.hpp: fmDemod, Demod.hs:25-28) of the SAME finished
+// outputs, one float per output, with OUT_ENV's store rule.  fmDemod is not point-wise, so:
+//   - inside a tile a thread's first output takes its predecessor from the previous thread's second one, through NT pairs of LDS behind
+//     the tile (one barrier after the MAC walk and the Cross outputs);
+//   - across tiles NO workgroup waits on another: the tiles OVERLAP.  A tile still computes T::OUTS outputs but advances by T::OUTS - 2;
+//     thread 0's pair of every tile but the first is computed as a predecessor only and not stored, the first tile stores all of its
+//     outputs and its output 0 takes the predecessor from bank.fm_state (channel j's decimated output k_begin - 1; null = (0, 0),
+//     Demod.hs:41).  2 of 512 outputs are computed twice (0.4 %), tile starts stay multiples of 16 bytes (510 D samples of 2, 4 or 8
+//     bytes, D = 4 / 8 / 16), and the oscillator phase and the seam arithmetic of a tile follow the advance;
+//   - Cross outputs are ALWAYS computed in the tile (a later fix-up launch could not repair the two phase differences a Cross output
+//     takes part in), for any seam_block in [Lp, 2^30): the in-tile test reduces by a modulo where the other kinds subtract once, so a
+//     tile may hold any number of seams.  k_tuner_bank_crossfix has no OUT_FM form;
+//   - the thread that stores output count - 1 also writes its (re, im) to bank.fm_final[j] (null = not wanted): the next launch's state.
+// k_tuner_bank_cross<FMT, OUT_FM>: thread t computes y[t] and recomputes y[t - 1], both in sequential order; thread 0 takes fm_state.
 #include "am.hpp"
+#include "demod.hpp"
 #include "decimate_tile.hpp"
 #include "tuner_mix.hpp"
 
@@ -55,6 +71,10 @@ static std::atomic<long long> g_am_bank_fixup_launches{0};
 long long am_bank_fixup_launch_count() { return g_am_bank_fixup_launches.load(); }
 static std::atomic<long long> g_am_bank_cross_launches{0};
 long long am_bank_cross_launch_count() { return g_am_bank_cross_launches.load(); }
+static std::atomic<long long> g_nfm_bank_launches{0};
+long long nfm_bank_launch_count() { return g_nfm_bank_launches.load(); }
+static std::atomic<long long> g_nfm_bank_cross_launches{0};
+long long nfm_bank_cross_launch_count() { return g_nfm_bank_cross_launches.load(); }
 
 namespace {
 
@@ -65,6 +85,24 @@ struct BankChannels {
     int period[kTunerBankMaxChannels];
     int ph[kTunerBankMaxChannels];             // (k_begin D) mod period: the host's one 64-bit modulo per channel and launch
 };
+// OUT_FM's argument: the channels and the two state arrays, K (re, im) pairs each.  A type of its own, so that the argument segment of
+// the other kinds (and with it the offsets of their hidden arguments) stays what it was.
+struct BankChannelsFm : BankChannels {
+    const float* fm_state;                     // channel j's decimated output k_begin - 1; null = (0, 0)
+    float* fm_final;                           // receives output k_end - 1; null = not wanted
+};
+template <int OUT> struct BankArg { using type = BankChannels; };
+template <> struct BankArg<OUT_FM> { using type = BankChannelsFm; };
+
+// outputs a tile advances by, and the tiles of a launch: OUT_FM's tiles overlap by one thread's pair (see the head of this file)
+template <class T, int OUT>
+constexpr int tile_advance() { return OUT == OUT_FM ? T::OUTS - 2 : T::OUTS; }
+template <class T, int OUT>
+__host__ __device__ __forceinline__ int tile_count(int count)
+{
+    if constexpr (OUT == OUT_FM) return count <= T::OUTS ? 1 : (count - 2 + tile_advance<T, OUT>() - 1) / tile_advance<T, OUT>();
+    else return (count + T::OUTS - 1) / T::OUTS;
+}
 
 template <int D, int P, int R, int NT, int FMT, int OUT, int TC, bool GUARD>
 __global__ void __launch_bounds__(NT) k_tuner_bank_c4(const void* __restrict__ in, int64_t x0 /* sample index of output 0's window in `in` */,
@@ -72,7 +110,7 @@ __global__ void __launch_bounds__(NT) k_tuner_bank_c4(const void* __restrict__ i
                                                       int p_eff /* GUARD: taps of the filter (multiple of TC, <= P) */,
                                                       int inl_seam /* > 0: compute the Cross outputs of buffers this long HERE */,
                                                       int inl_r0 /* window start of output 0 inside its buffer */,
-                                                      const float2* __restrict__ osc /* every table */, BankChannels bank)
+                                                      const float2* __restrict__ osc /* every table */, typename BankArg<OUT>::type bank)
 {
     using T = Tile<D, P, R, NT>;
     using St = Stage<T, FMT, NT>;
@@ -80,7 +118,7 @@ __global__ void __launch_bounds__(NT) k_tuner_bank_c4(const void* __restrict__ i
     extern __shared__ __attribute__((aligned(16))) unsigned char tuner_bank_smem[];
     float2* lds = reinterpret_cast<float2*>(tuner_bank_smem);
 
-    const int ntiles = (count + T::OUTS - 1) / T::OUTS;
+    const int ntiles = tile_count<T, OUT>(count);
     const unsigned nch = (unsigned)bank.channels;
     const unsigned j = blockIdx.x % nch;
     const int tile = (int)(blockIdx.x / nch);
@@ -88,7 +126,7 @@ __global__ void __launch_bounds__(NT) k_tuner_bank_c4(const void* __restrict__ i
     osc += bank.off[j];
     out += (int64_t)j * bank.out_stride;
 
-    const int out0 = tile * T::OUTS;
+    const int out0 = tile * tile_advance<T, OUT>();
     const int64_t s0 = (int64_t)out0 * D;                     // first sample of the tile, relative to x0
     {
         St st;
@@ -96,7 +134,7 @@ __global__ void __launch_bounds__(NT) k_tuner_bank_c4(const void* __restrict__ i
         const int64_t av = total_avail - s0;
         st.load(in, x0 + s0, av > T::SPAN ? T::SPAN : (int)av);
         const uint32_t n = (uint32_t)bank.period[j];
-        constexpr uint32_t TS = (uint32_t)T::OUTS * D;
+        constexpr uint32_t TS = (uint32_t)tile_advance<T, OUT>() * D;
         const uint32_t ph = ((uint32_t)bank.ph[j] + (((uint32_t)tile % n) * (TS % n)) % n + (uint32_t)(threadIdx.x * St::SPV)) % n;
         tuner_store<T, FMT, NT>(st.r, lds, osc, n, ph);
     }
@@ -123,11 +161,50 @@ __global__ void __launch_bounds__(NT) k_tuner_bank_c4(const void* __restrict__ i
 #pragma unroll
         for (int r = 0; r < R; r++) {
             int rr = rt + (threadIdx.x * R + r) * D;
-            if (rr >= inl_seam) rr -= inl_seam;
+            if constexpr (OUT == OUT_FM) rr %= inl_seam;      // any seam >= plen: a tile may hold several (rr < 2^30 + OUTS D)
+            else if (rr >= inl_seam) rr -= inl_seam;
             cross[r] = rr + plen > inl_seam;
             any |= cross[r];
         }
         if (any) inline_cross_outputs<D, R, T, TC, GUARD>(win, taps, plen, cross, res);
+    }
+    if constexpr (OUT == OUT_FM) {
+        // the predecessor of a thread's first output is the previous thread's last one: NT pairs behind the tile (the tile itself
+        // may still be being read by slower waves)
+        float2* edge = lds + T::LDS_F2;
+        edge[threadIdx.x] = res[R - 1];
+        __syncthreads();
+        // thread 0 of a later tile holds predecessors only: nothing of it is stored, and it takes its own last output for a
+        // predecessor so that it does not send its wave into the full form
+        const bool lead = tile > 0 && threadIdx.x == 0;
+        float2 v[R + 1];
+        if (threadIdx.x > 0) v[0] = edge[threadIdx.x - 1];
+        else if (tile > 0) v[0] = res[R - 1];
+        else if (bank.fm_state != nullptr) v[0] = make_float2(bank.fm_state[2 * j], bank.fm_state[2 * j + 1]);
+        else v[0] = make_float2(0.0f, 0.0f);
+#pragma unroll
+        for (int r = 0; r < R; r++) v[r + 1] = res[r];
+        float y[R];
+        fm_phase_voted<R>(v, y);
+        if (lead) return;
+        float* dst = out + o;
+        if (R == 2 && o + R <= count && (reinterpret_cast<uintptr_t>(dst) & 7) == 0) {
+            *reinterpret_cast<float2*>(dst) = make_float2(y[0], y[R - 1]);
+        } else {
+#pragma unroll
+            for (int r = 0; r < R; r++)
+                if (o + r < count) dst[r] = y[r];
+        }
+        // the state of the next launch, by the thread that has stored the launch's last output
+        if (bank.fm_final != nullptr) {
+#pragma unroll
+            for (int r = 0; r < R; r++)
+                if (o + r == count - 1) {
+                    bank.fm_final[2 * j] = res[r].x;
+                    bank.fm_final[2 * j + 1] = res[r].y;
+                }
+        }
+        return;
     }
     if constexpr (OUT == OUT_ENV) {
         // one float per output: the pair as ONE 8-byte store where the row's pointer plus the output index is 8-byte aligned (the
@@ -193,7 +270,8 @@ __global__ void __launch_bounds__(256) k_tuner_bank_crossfix(Geom g, const float
 // slots.  Block b: channel b % K, outputs of block b / K.
 template <int FMT, int OUT>
 __global__ void __launch_bounds__(256) k_tuner_bank_cross(Geom g, const float* __restrict__ xtaps, const void* __restrict__ in,
-                                                           float* __restrict__ out, const float2* __restrict__ osc, BankChannels bank)
+                                                           float* __restrict__ out, const float2* __restrict__ osc,
+                                                           typename BankArg<OUT>::type bank)
 {
     const unsigned nch = (unsigned)bank.channels;
     const unsigned c = blockIdx.x % nch;
@@ -211,42 +289,70 @@ __global__ void __launch_bounds__(256) k_tuner_bank_cross(Geom g, const float* _
         re = re + mx.x * xtaps[j];
         im = im + mx.y * xtaps[j];
     }
+    if constexpr (OUT == OUT_FM) {
+        // the predecessor: output t - 1 once more, the same loop one window earlier (at most 16 outputs a channel in the Pipe's
+        // launches); thread 0 takes the state
+        float2 prev = make_float2(0.0f, 0.0f);
+        if (t > 0) {
+            const int64_t u = v - g.D;
+            uint32_t pq = (uint32_t)((uint64_t)u % n);
+            float pr = 0.0f, pi = 0.0f;
+            for (int j = 0; j < g.Lp; j++) {
+                const float2 mx = tuner_mul(tuner_sample<FMT>(in, u - g.in_base + j), osc[pq]);
+                pq = wrap_inc(pq, n);
+                pr = pr + mx.x * xtaps[j];
+                pi = pi + mx.y * xtaps[j];
+            }
+            prev = make_float2(pr, pi);
+        } else if (bank.fm_state != nullptr) {
+            prev = make_float2(bank.fm_state[2 * c], bank.fm_state[2 * c + 1]);
+        }
+        out[t] = fm_phase_sel(make_float2(re, im), prev);
+        if (t == g.count - 1 && bank.fm_final != nullptr) {
+            bank.fm_final[2 * c] = re;
+            bank.fm_final[2 * c + 1] = im;
+        }
+        return;
+    }
     if constexpr (OUT == OUT_ENV) out[t] = am_magnitude(re, im);
     else *reinterpret_cast<float2*>(out + 2 * (int64_t)t) = make_float2(re, im);
 }
 
 template <int D, int P, int FMT, int OUT, int TC, bool GUARD>
 void launch_tuner_bank_c4(hipStream_t s, const Geom& g, const float* taps, const void* in, float* out, bool inline_cross, bool* inlined,
-                          const float* d_tables, const BankChannels& bank)
+                          const float* d_tables, const typename BankArg<OUT>::type& bank)
 {
     constexpr int R = 2, NT = 256;
     using T = Tile<D, P, R, NT>;
+    // OUT_FM: NT pairs behind the tile, the threads' last outputs (the predecessors of their right neighbours' first ones)
+    constexpr size_t lds_bytes = T::LDS_BYTES + (OUT == OUT_FM ? NT * sizeof(float2) : 0);
     // the dynamic-LDS attribute is per device: one flag per (instantiation, device); idempotent, a race only repeats the call
     static std::atomic<bool> attr_set[64];
     auto kern = k_tuner_bank_c4<D, P, R, NT, FMT, OUT, TC, GUARD>;
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::LDS_BYTES);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
-    const int tiles = (g.count + T::OUTS - 1) / T::OUTS;       // at most 2^22: tiles * channels fits a 1-D grid
+    const int tiles = tile_count<T, OUT>(g.count);             // at most 2^22 + 2^14: tiles * channels fits a 1-D grid
     const unsigned grid = (unsigned)tiles * (unsigned)bank.channels;
     const int64_t x0 = g.k_begin * D - g.in_base;
     int inl_seam = 0, inl_r0 = 0;
-    if (inline_cross && g.seamBI >= (int64_t)T::OUTS * D + g.Lp && g.seamBI < (1 << 30)) {   // a tile spans less than one buffer
+    // a tile spans less than one buffer; OUT_FM's modulo takes any seam the launcher has admitted (Lp <= seam < 2^30)
+    if (inline_cross && (OUT == OUT_FM || g.seamBI >= (int64_t)T::OUTS * D + g.Lp) && g.seamBI < (1 << 30)) {
         inl_seam = (int)g.seamBI;
         inl_r0 = (int)((g.k_begin * D) % g.seamBI);
     }
     *inlined = inl_seam > 0;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), T::LDS_BYTES, s, in, x0, g.count, taps, out, g.Lp, inl_seam, inl_r0,
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds_bytes, s, in, x0, g.count, taps, out, g.Lp, inl_seam, inl_r0,
                        reinterpret_cast<const float2*>(d_tables), bank);
 }
 
 // the instantiation that serves the launch's shape (tuner_fused_fits has admitted it)
 template <int FMT, int OUT>
 void launch_tuner_bank_c4_shape(hipStream_t s, const Geom& g, int P, const float* taps, const void* in, float* out, bool inl, bool* inlined,
-                                const float* d_tables, const BankChannels& bank)
+                                const float* d_tables, const typename BankArg<OUT>::type& bank)
 {
 #define TUNER_BANK(DV, TCV, GV) launch_tuner_bank_c4<DV, 128, FMT, OUT, TCV, GV>(s, g, taps, in, out, inl, inlined, d_tables, bank)
     if (g.D == 4) TUNER_BANK(4, 4, true);
@@ -257,31 +363,38 @@ void launch_tuner_bank_c4_shape(hipStream_t s, const Geom& g, int P, const float
 #undef TUNER_BANK
 }
 
-// launch_tuner_bank (OUT_IQ: out_stride in floats of complex rows) and launch_am_bank (OUT_ENV: one float per output)
+// launch_tuner_bank (OUT_IQ: out_stride in floats of complex rows), launch_am_bank (OUT_ENV: one float per output) and
+// launch_nfm_bank (OUT_FM: one float per output, the state pairs fm_state / fm_final, every Cross output in the tile launch)
 template <int OUT>
 bool launch_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in, InFmt fmt,
                  float* d_out, int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods,
-                 bool counts_as_bank)
+                 bool counts_as_bank, const float* fm_state = nullptr, float* fm_final = nullptr)
 {
-    constexpr int64_t FPO = OUT == OUT_ENV ? 1 : 2;         // floats per output
+    constexpr int64_t FPO = OUT == OUT_IQ ? 2 : 1;          // floats per output
     if (channels < 1 || channels > kTunerBankMaxChannels) return false;
     if (OUT == OUT_IQ && (out_stride & 1) != 0) return false;
     if (channels > 1 && out_stride < FPO * (int64_t)g.count) return false;
-    // tuner_fused_fits reads d_out for the 8-byte alignment of complex rows alone; envelope rows are floats at any float address
-    if (OUT == OUT_ENV && (reinterpret_cast<uintptr_t>(d_out) & 3) != 0) return false;
-    const void* fit_out = OUT == OUT_ENV ? nullptr : d_out;
+    // tuner_fused_fits reads d_out for the 8-byte alignment of complex rows alone; envelope and phase rows are floats at any float address
+    if (OUT != OUT_IQ && (reinterpret_cast<uintptr_t>(d_out) & 3) != 0) return false;
+    if (OUT == OUT_FM && g.seamBI >= ((int64_t)1 << 30)) return false;      // the in-tile seam test works in 32 bits
+    const void* fit_out = OUT != OUT_IQ ? nullptr : d_out;
     for (int j = 0; j < channels; j++)
         if (!tuner_fused_fits(g, P, d_cross_taps != nullptr, d_in, fmt, fit_out, periods[j])) return false;
-    BankChannels bank = {};
+    typename BankArg<OUT>::type bank = {};
     bank.out_stride = out_stride;
     bank.channels = channels;
+    if constexpr (OUT == OUT_FM) {
+        bank.fm_state = fm_state;
+        bank.fm_final = fm_final;
+    }
     for (int j = 0; j < channels; j++) {
         bank.off[j] = offsets[j];
         bank.period[j] = periods[j];
         bank.ph[j] = (int)((g.k_begin * g.D) % periods[j]);
     }
     // launch-bound sizes compute their Cross outputs inside the tile kernel: launch_tuner_fused's decision
-    const bool inl = g.seamBI > 0 && g.count <= 5 * (int64_t)small_launch_outputs();
+    // (OUT_FM: always, whatever the size)
+    const bool inl = g.seamBI > 0 && (OUT == OUT_FM || g.count <= 5 * (int64_t)small_launch_outputs());
     bool inlined = false;
     switch (fmt) {
     case IN_U8: launch_tuner_bank_c4_shape<IN_U8, OUT>(s, g, P, d_plain_taps, d_in, d_out, inl, &inlined, d_tables, bank); break;
@@ -290,8 +403,10 @@ bool launch_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, int P,
     }
     if (fmt == IN_I16) g_tuner_i16_launches.fetch_add(1, std::memory_order_relaxed);
     if (OUT == OUT_ENV) g_am_bank_launches.fetch_add(1, std::memory_order_relaxed);
+    else if (OUT == OUT_FM) g_nfm_bank_launches.fetch_add(1, std::memory_order_relaxed);
     else if (counts_as_bank) g_tuner_bank_launches.fetch_add(1, std::memory_order_relaxed);
 
+    if constexpr (OUT != OUT_FM) {
     const SeamSpan sp = seam_span(g);
     if (sp.nseams > 0 && !inlined) {
         const unsigned per_channel = (unsigned)(((int64_t)sp.nseams * sp.per + 255) / 256);
@@ -301,6 +416,7 @@ bool launch_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, int P,
         hipLaunchKernelGGL(fix, grid, block, 0, s, g, d_cross_taps, d_in, d_out, sp.first, sp.nseams, sp.per,
                            reinterpret_cast<const float2*>(d_tables), bank);
         if (OUT == OUT_ENV) g_am_bank_fixup_launches.fetch_add(1, std::memory_order_relaxed);
+    }
     }
     return true;
 }
@@ -323,24 +439,38 @@ bool launch_am_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, int
                                 false);
 }
 
+bool launch_nfm_bank(hipStream_t s, const Geom& g, const float* d_plain_taps, int P, const float* d_cross_taps, const void* d_in,
+                     InFmt fmt, float* d_out, int64_t out_stride, const float* d_tables, int channels, const int* offsets,
+                     const int* periods, const float* d_state, float* d_final)
+{
+    return launch_bank<OUT_FM>(s, g, d_plain_taps, P, d_cross_taps, d_in, fmt, d_out, out_stride, d_tables, channels, offsets, periods,
+                               false, d_state, d_final);
+}
+
 namespace {
-// launch_tuner_bank_cross (OUT_IQ) and launch_am_bank_cross (OUT_ENV: float rows, any out_stride >= g.count, 4-byte stores)
+// launch_tuner_bank_cross (OUT_IQ), launch_am_bank_cross (OUT_ENV: float rows, any out_stride >= g.count, 4-byte stores) and
+// launch_nfm_bank_cross (OUT_FM: as OUT_ENV, with the state pairs)
 template <int OUT>
 bool launch_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_taps, const void* d_in, InFmt fmt, float* d_out,
-                       int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods)
+                       int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods,
+                       const float* fm_state = nullptr, float* fm_final = nullptr)
 {
     // launch_tuner_bank's refusals for channels and stride; one thread reads its window sample by sample: no alignment beyond the
     // element's own (a float, a u8 pair, an int16 pair)
     static const uintptr_t kInMask[3] = {/* IN_CF32 */ 7, /* IN_U8 */ 1, /* IN_I16 */ 3};
-    constexpr int64_t FPO = OUT == OUT_ENV ? 1 : 2;         // floats per output
+    constexpr int64_t FPO = OUT == OUT_IQ ? 2 : 1;          // floats per output
     if (channels < 1 || channels > kTunerBankMaxChannels) return false;
     if (OUT == OUT_IQ && (out_stride & 1) != 0) return false;
     if (channels > 1 && out_stride < FPO * (int64_t)g.count) return false;
     if (g.I != 1 || g.count <= 0 || g.k_begin < 0 || g.k_begin * g.D < g.in_base || d_cross_taps == nullptr) return false;
-    if ((reinterpret_cast<uintptr_t>(d_out) & (OUT == OUT_ENV ? 3 : 7)) != 0 || (reinterpret_cast<uintptr_t>(d_in) & kInMask[fmt]) != 0) return false;
-    BankChannels bank = {};
+    if ((reinterpret_cast<uintptr_t>(d_out) & (OUT != OUT_IQ ? 3 : 7)) != 0 || (reinterpret_cast<uintptr_t>(d_in) & kInMask[fmt]) != 0) return false;
+    typename BankArg<OUT>::type bank = {};
     bank.out_stride = out_stride;
     bank.channels = channels;
+    if constexpr (OUT == OUT_FM) {
+        bank.fm_state = fm_state;
+        bank.fm_final = fm_final;
+    }
     for (int j = 0; j < channels; j++) {
         if (periods[j] < 1) return false;
         bank.off[j] = offsets[j];
@@ -350,7 +480,8 @@ bool launch_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_taps, 
     const dim3 grid(per_channel * (unsigned)channels), block(256);
     auto cross = fmt == IN_U8 ? k_tuner_bank_cross<IN_U8, OUT> : fmt == IN_I16 ? k_tuner_bank_cross<IN_I16, OUT> : k_tuner_bank_cross<IN_CF32, OUT>;
     hipLaunchKernelGGL(cross, grid, block, 0, s, g, d_cross_taps, d_in, d_out, reinterpret_cast<const float2*>(d_tables), bank);
-    (OUT == OUT_ENV ? g_am_bank_cross_launches : g_tuner_bank_cross_launches).fetch_add(1, std::memory_order_relaxed);
+    (OUT == OUT_ENV ? g_am_bank_cross_launches : OUT == OUT_FM ? g_nfm_bank_cross_launches : g_tuner_bank_cross_launches)
+        .fetch_add(1, std::memory_order_relaxed);
     return true;
 }
 }  // namespace
@@ -365,6 +496,14 @@ bool launch_am_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_tap
                           int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods)
 {
     return launch_bank_cross<OUT_ENV>(s, g, d_cross_taps, d_in, fmt, d_out, out_stride, d_tables, channels, offsets, periods);
+}
+
+bool launch_nfm_bank_cross(hipStream_t s, const Geom& g, const float* d_cross_taps, const void* d_in, InFmt fmt, float* d_out,
+                           int64_t out_stride, const float* d_tables, int channels, const int* offsets, const int* periods,
+                           const float* d_state, float* d_final)
+{
+    return launch_bank_cross<OUT_FM>(s, g, d_cross_taps, d_in, fmt, d_out, out_stride, d_tables, channels, offsets, periods, d_state,
+                                     d_final);
 }
 
 }  // namespace sdrhip

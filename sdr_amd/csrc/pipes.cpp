@@ -44,6 +44,8 @@ enum PipeKind : int { PK_FILTER, PK_DECIMATOR, PK_RESAMPLER, PK_DEMOD, PK_DCBLOC
 // The waterfall Pipe's kind, the next number (10).  It stands behind the list, not in it: tests/test_pipe_am_bank_abi.py pins the line
 // above as the ten kinds whose saved states exist in the field.
 constexpr PipeKind PK_SPECTRUM = static_cast<PipeKind>(PK_AM_BANK + 1);
+// The narrow-band FM bank's Pipe, the next number again (11), behind the list for the same reason.
+constexpr PipeKind PK_NFM_BANK = static_cast<PipeKind>(PK_SPECTRUM + 1);
 
 struct sdrhip_pipe {
     PipeKind kind;
@@ -62,6 +64,13 @@ struct sdrhip_pipe {
     // without am_dc the slots' submissions run on streams of their own.
     bool am_dc = false;
     DevBuf am_iq[HostStream::kMaxSlots];
+    // PK_NFM_BANK: the narrow-band FM bank's Pipe -- the tuner bank's Pipe with ONE float per output, fmDemod of each channel over the
+    // whole stream.  Every channel's last decimated output lives in device memory: a launch reads nfm_state[nfm_cur] and writes the
+    // other array (the two must not overlap: kernels_tuner_bank.hip), and the host swaps them after every launch.  Consecutive
+    // submissions depend on each other through that state, so EVERY launch goes to compute stream 0 (as with am_dc).  Submissions the
+    // fused launch does not serve go through am_iq.
+    DevBuf nfm_state[2];
+    int nfm_cur = 0;
     // PK_SPECTRUM: the waterfall Pipe over a borrowed spectrum object.  Elements are samples in the object's own type (fmt); output
     // blocks are rows of block_out = n floats.  The engine's history holds exactly the carried tail (the samples from the first row
     // not yet produced onward) while nothing is staged; sp_skip samples of the stream are still to be dropped on arrival (hop > n).
@@ -208,8 +217,9 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
     // The AM bank's Pipe never reads in place, whatever the row count (a stated choice: the FM bank stream's sweep found no in-place
     // region), and with dcBlocker all its launches share compute stream 0: a submission's dcBlocker starts from the state its
     // predecessor's left on the device
-    const bool am = p->kind == PK_AM_BANK;
-    if (am && p->am_dc) cs = e.compute[0];
+    const bool nfm = p->kind == PK_NFM_BANK;
+    const bool am = p->kind == PK_AM_BANK || nfm;      // (the narrow-band FM bank's Pipe makes the same choice)
+    if (p->am_dc || nfm) cs = e.compute[0];
     const HostStream::Route route = !direct ? HostStream::kCopyEngines : (rows > 1 || am) ? HostStream::kSlotStream : HostStream::kInPlace;
     if ((p->kind == PK_TUNER_BANK || am) && route != HostStream::kInPlace) {
         // the copy may land anywhere in the slot's device buffer: put the banked launch's first window on a 16-byte boundary there,
@@ -222,6 +232,48 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
     int rc = e.submit(route, cs, first, (size_t)(tail + n) * ein, rows * row_floats, [&](hipStream_t s, const void* d_in, void* d_out) {
         const float* din = (const float*)d_in;
         float* dout = (float*)d_out;
+        if (p->kind == PK_NFM_BANK) {
+            // every row [cross | one] as PHASES, one float per output: the fused launch where it fits (dev_skew has aligned the first
+            // window), else tuner bank + fmDemod rows through the slot's complex scratch.  Each launch takes the state its predecessor
+            // left and leaves the next one's in the other array.
+            const int K = rows;
+            const int64_t count = m_end - m_done, np = (count + 3) & ~(int64_t)3;
+            int r;
+            // the complex scratch only where the tile part of this submission is NOT the fused launch (another order or factor): the
+            // fused launch never touches it, and 32 channels of it are K * 2 * np floats
+            // COUPLING: nfm_bank_fused_fits (nfm_fits, nfm_bank.cpp) must admit nothing that launch_bank<OUT_FM>
+            // (kernels_tuner_bank.hip) refuses -- today both apply tuner_fused_fits, the seam bound and the create-time limits on channels
+            // and periods, and the row stride here is the row's length.  Where they diverged, nfm_bank_phase would find no scratch for
+            // its fall-back and the submission would end in SDRHIP_ERR_ARG ("no scratch for the composed route"), not in wrong bits.
+            const int64_t t0 = uniform_seam > 0 ? m_done : m_split;
+            float* iq = nullptr;
+            if (m_end > t0 && !nfm_bank_fused_fits(p->bank, d_in, p->fmt, in_base, t0, m_end, uniform_seam > 0 ? uniform_seam : 0)) {
+                DevBuf& b = p->am_iq[si];
+                const size_t iq_bytes = (size_t)K * 2 * (size_t)np * sizeof(float);
+                if (iq_bytes > b.cap) SDRHIP_CHECK_HIP(hipStreamSynchronize(s));               // growing frees the old buffer
+                if ((r = b.ensure(iq_bytes)) != SDRHIP_OK) return r;
+                iq = (float*)b.p;
+            }
+            auto st_in = [&] { return (const float*)p->nfm_state[p->nfm_cur].p; };
+            auto st_out = [&] { return (float*)p->nfm_state[p->nfm_cur ^ 1].p; };
+            if (uniform_seam > 0) {
+                r = nfm_bank_phase(p->bank, s, d_in, p->fmt, in_base, dout, row_floats, m_done, m_end, uniform_seam, st_in(), st_out(), iq, np);
+                if (r == SDRHIP_OK) p->nfm_cur ^= 1;
+                return r;
+            }
+            const int64_t ncross = m_split - m_done;
+            if (ncross > 0) {
+                if ((r = nfm_bank_phase_cross(p->bank, s, d_in, p->fmt, in_base, dout, row_floats, m_done, m_split, st_in(), st_out())) != SDRHIP_OK)
+                    return r;
+                p->nfm_cur ^= 1;
+            }
+            if (m_end > m_split) {
+                r = nfm_bank_phase(p->bank, s, d_in, p->fmt, in_base, dout + ncross, row_floats, m_split, m_end, 0, st_in(), st_out(), iq, np);
+                if (r != SDRHIP_OK) return r;
+                p->nfm_cur ^= 1;
+            }
+            return SDRHIP_OK;
+        }
         if (p->kind == PK_AM_BANK) {
             // every row [cross | one] as ENVELOPES, one float per output: the fused launch set where it fits (dev_skew has aligned the
             // first window), else tuner bank + amDemod rows through the slot's complex scratch
@@ -594,6 +646,31 @@ int sdrhip_pipe_am_bank(sdrhip_pipe** pp, const sdrhip_am_bank* a, int block_siz
     return SDRHIP_OK;
 }
 
+int sdrhip_pipe_nfm_bank(sdrhip_pipe** pp, const sdrhip_nfm_bank* a, int block_size_out, int input_type)
+{
+    // (all of it before pipe_new, whose engine creates streams: a refused create has done no device work)
+    SDRHIP_REQUIRE(pp != nullptr, "sdrhip_pipe_nfm_bank");
+    *pp = nullptr;
+    SDRHIP_REQUIRE(a != nullptr, "sdrhip_pipe_nfm_bank: null bank");
+    SDRHIP_REQUIRE(block_size_out > 0, "sdrhip_pipe_nfm_bank: block_size_out > 0");
+    SDRHIP_REQUIRE(input_type >= 0 && input_type <= 2, "sdrhip_pipe_nfm_bank: input_type is 0 (cfloat blocks), 1 (u8 IQ) or 2 (int16 IQ)");
+    const TunerBankDesc* b = a->tb;
+    const FirDesc* f = &b->ch[0]->fir;
+    const int K = (int)b->ch.size();
+    int rc = pipe_new(pp, PK_NFM_BANK, f, nullptr, block_size_out, true, false, 1, f->factor, f->Lp, (InFmt)input_type);
+    if (rc != SDRHIP_OK) return rc;
+    sdrhip_pipe* p = *pp;
+    p->bank = b;
+    if (K > 1) p->eng.set_rows(K);
+    const size_t bytes = (size_t)K * 2 * sizeof(float);
+    for (int i = 0; i < 2; i++) {
+        if ((rc = p->nfm_state[i].ensure(bytes < 16 ? 16 : bytes)) != SDRHIP_OK) { delete p; *pp = nullptr; return rc; }
+        hipError_t e = hipMemsetAsync(p->nfm_state[i].p, 0, bytes, p->eng.compute[0]);   // every channel starts from (0, 0), Demod.hs:41
+        if (e != hipSuccess) { set_error("sdrhip_pipe_nfm_bank: %s", hipGetErrorString(e)); delete p; *pp = nullptr; return SDRHIP_ERR_HIP; }
+    }
+    return SDRHIP_OK;
+}
+
 int sdrhip_pipe_rows(const sdrhip_pipe* p)
 {
     SDRHIP_REQUIRE(p != nullptr, "sdrhip_pipe_rows");
@@ -870,8 +947,10 @@ static uint32_t pipe_state_version(const sdrhip_pipe* p) { return p->rows() > 1 
 struct PipeStateAm {
     int32_t dc_block, n_floats;
 };
+// The narrow-band FM bank's Pipe appends the same record: dc_block = 0, n_floats = 2 K, and every channel's last decimated (re, im).
 static size_t pipe_state_am_bytes(const sdrhip_pipe* p)
 {
+    if (p->kind == PK_NFM_BANK) return sizeof(PipeStateAm) + (size_t)p->rows() * 2 * sizeof(float);
     return p->kind != PK_AM_BANK ? 0 : sizeof(PipeStateAm) + (p->am_dc ? (size_t)p->rows() * 2 * sizeof(float) : 0);
 }
 static size_t pipe_state_header_bytes(const sdrhip_pipe* p) { return sizeof(PipeStateHeader) + (pipe_state_version(p) == 2 ? sizeof(PipeStateRows) : 0); }
@@ -964,6 +1043,14 @@ int sdrhip_pipe_save(sdrhip_pipe* p, void* buf, size_t capacity, size_t* used)
             SDRHIP_CHECK_HIP(hipMemcpy(o, p->dc_state.p, (size_t)x.n_floats * sizeof(float), hipMemcpyDeviceToHost));
         }
     }
+    if (p->kind == PK_NFM_BANK) {
+        // (the flush above has harvested every submission: the array the last launch wrote is the stream's state)
+        const PipeStateAm x = {0, 2 * p->rows()};
+        memcpy(o, &x, sizeof x);
+        o += sizeof x;
+        SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));
+        SDRHIP_CHECK_HIP(hipMemcpy(o, p->nfm_state[p->nfm_cur].p, (size_t)x.n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    }
     *used = need;
     return SDRHIP_OK;
 }
@@ -1015,7 +1102,7 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
     SDRHIP_REQUIRE(h.hist_n >= 0 && h.hist_n <= h.head_cap && h.pending >= 0 && h.n_blocks >= 0 && h.E_prev >= h.hist_n && h.m_done >= 0,
                    "sdrhip_pipe_restore: inconsistent state");
     if (p->kind == PK_FILTER || p->kind == PK_DECIMATOR || p->kind == PK_RESAMPLER || p->kind == PK_TUNER || p->kind == PK_TUNER_BANK ||
-        p->kind == PK_AM_BANK) {
+        p->kind == PK_AM_BANK || p->kind == PK_NFM_BANK) {
         // the next pending output must start inside what the pipe has seen, every output computable from those elements must be
         // done at most once, and the history must reach back to its first input (3 elements of alignment slack, 7 of u8, fir_submit):
         // otherwise the kernels would be sent in front of the staging buffer
@@ -1034,6 +1121,11 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
         SDRHIP_REQUIRE(x.dc_block == (p->am_dc ? 1 : 0) && x.n_floats == (p->am_dc ? 2 * p->rows() : 0),
                        "sdrhip_pipe_restore: the state belongs to an AM bank pipe of another dc_block");
     }
+    if (p->kind == PK_NFM_BANK) {
+        PipeStateAm x;
+        memcpy(&x, (const unsigned char*)buf + am_at, sizeof x);
+        SDRHIP_REQUIRE(x.dc_block == 0 && x.n_floats == 2 * p->rows(), "sdrhip_pipe_restore: the state belongs to a pipe of another row count");
+    }
     const unsigned char* in = p->eng.restore((const unsigned char*)buf + pipe_state_header_bytes(p), h.hist_n, h.pending);
     p->E_prev = h.E_prev;
     p->m_done = h.m_done;
@@ -1046,6 +1138,10 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
     if (p->kind == PK_AM_BANK && p->am_dc) {
         SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));       // the create call's memset
         SDRHIP_CHECK_HIP(hipMemcpy(p->dc_state.p, in + sizeof(PipeStateAm), (size_t)p->rows() * 2 * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (p->kind == PK_NFM_BANK) {
+        SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));       // the create call's memsets
+        SDRHIP_CHECK_HIP(hipMemcpy(p->nfm_state[p->nfm_cur].p, in + sizeof(PipeStateAm), (size_t)p->rows() * 2 * sizeof(float), hipMemcpyHostToDevice));
     }
     if (p->has_dev_state()) {
         SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));       // the create call's memset

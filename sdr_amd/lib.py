@@ -139,6 +139,19 @@ lib.sdrhip_debug_am_bank_fixup_launches.argtypes = []
 lib.sdrhip_debug_am_bank_fixup_launches.restype = C.c_longlong
 lib.sdrhip_debug_am_bank_cross_launches.argtypes = []
 lib.sdrhip_debug_am_bank_cross_launches.restype = C.c_longlong
+lib.sdrhip_nfm_bank_create.argtypes = [C.POINTER(_vp), _vp]
+lib.sdrhip_nfm_bank_destroy.argtypes = [_vp]
+lib.sdrhip_nfm_bank_destroy.restype = None
+lib.sdrhip_nfm_bank_channels.argtypes = [_vp]
+lib.sdrhip_nfm_bank_set_route.argtypes = [_vp, C.c_int]
+lib.sdrhip_nfm_bank_workspace_bytes.argtypes = [_vp, _i64]
+lib.sdrhip_nfm_bank_workspace_bytes.restype = C.c_size_t
+for _n in ("sdrhip_nfm_bank_run", "sdrhip_nfm_bank_run_u8", "sdrhip_nfm_bank_run_i16"):
+    getattr(lib, _n).argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, C.c_size_t]
+lib.sdrhip_debug_nfm_bank_launches.argtypes = []
+lib.sdrhip_debug_nfm_bank_launches.restype = C.c_longlong
+lib.sdrhip_debug_nfm_bank_cross_launches.argtypes = []
+lib.sdrhip_debug_nfm_bank_cross_launches.restype = C.c_longlong
 
 lib.sdrhip_resampler_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.c_int]
 lib.sdrhip_resampler_num_coeffs.argtypes = [_vp]
@@ -352,6 +365,7 @@ lib.sdrhip_pipe_input_buffer_u8.argtypes = [_vp, C.c_int]
 lib.sdrhip_pipe_input_buffer_u8.restype = _vp
 lib.sdrhip_pipe_tuner_bank_i16.argtypes = [C.POINTER(_vp), _vp, C.c_int]
 lib.sdrhip_pipe_am_bank.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int]
+lib.sdrhip_pipe_nfm_bank.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int]
 lib.sdrhip_pipe_push_i16.argtypes = [_vp, _i16p, C.c_int]
 lib.sdrhip_pipe_input_buffer_i16.argtypes = [_vp, C.c_int]
 lib.sdrhip_pipe_input_buffer_i16.restype = _vp
@@ -1042,6 +1056,63 @@ class AmBank(_Handle):
                   dc_state, workspace, workspace_bytes, stream)
 
 
+def nfm_bank_launches():
+    """fmDemod-form tile launches of the narrow-band FM bank's fused route so far (sdrhip_debug_nfm_bank_launches)."""
+    return int(lib.sdrhip_debug_nfm_bank_launches())
+
+
+def nfm_bank_cross_launches():
+    """Launches of the all-Cross fmDemod-form kernel of the narrow-band FM bank's Pipe so far (sdrhip_debug_nfm_bank_cross_launches)."""
+    return int(lib.sdrhip_debug_nfm_bank_cross_launches())
+
+
+class NfmBank(_Handle):
+    """fmDemod for every channel of a TunerBank: row j of a run is phase(y[k] * conj y[k - 1]) over the bank's complex row j, the
+    predecessor of output k_begin taken from `state` (K (re, im) pairs of device floats; None = zeros, the start of a stream) and
+    output k_end - 1 left in `final` (None = not wanted; the two must not overlap).  Consecutive runs over consecutive ranges that
+    swap the two arrays are one stream.  Bit for bit TunerBank.run -> fm_demod_run_rows on every route (sdr_hip.h,
+    sdrhip_nfm_bank_*).  The tuner bank is borrowed: the object keeps a reference to it."""
+    _destroy = lib.sdrhip_nfm_bank_destroy
+    ROUTE_AUTO, ROUTE_FUSED, ROUTE_COMPOSED = 0, 1, 2
+
+    def __init__(self, tuner_bank):
+        super().__init__()
+        self.tuner_bank = tuner_bank
+        check(lib.sdrhip_nfm_bank_create(C.byref(self.h), tuner_bank.h), "sdrhip_nfm_bank_create")
+
+    @property
+    def channels(self):
+        return check(lib.sdrhip_nfm_bank_channels(self.h), "sdrhip_nfm_bank_channels")
+
+    def set_route(self, route):
+        """0 = auto (sdr_hip.h), 1 = fused: ONE fmDemod-form launch of the banked tile kernel (a launch it does not serve is an
+        error), 2 = composed: the two calls of the definition."""
+        check(lib.sdrhip_nfm_bank_set_route(self.h, int(route)), "sdrhip_nfm_bank_set_route")
+
+    def workspace_bytes(self, count):
+        return int(lib.sdrhip_nfm_bank_workspace_bytes(self.h, int(count)))
+
+    def _run(self, fn, name, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block, state, final, workspace, workspace_bytes, stream):
+        check(fn(self.h, stream, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block, state, final, workspace, workspace_bytes), name)
+
+    def run(self, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block=0, state=None, final=None, workspace=None,
+            workspace_bytes=0, stream=None):
+        """cfloat input; channel j's floats [k_begin, k_end) -> d_out + 4 * j * out_stride bytes.  Pointers are device addresses."""
+        self._run(lib.sdrhip_nfm_bank_run, "sdrhip_nfm_bank_run", d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block, state,
+                  final, workspace, workspace_bytes, stream)
+
+    def run_u8(self, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block=0, state=None, final=None, workspace=None,
+               workspace_bytes=0, stream=None):
+        self._run(lib.sdrhip_nfm_bank_run_u8, "sdrhip_nfm_bank_run_u8", d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block,
+                  state, final, workspace, workspace_bytes, stream)
+
+    def run_i16(self, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block=0, state=None, final=None, workspace=None,
+                workspace_bytes=0, stream=None):
+        """interleaved int16 IQ input (4 bytes per sample); rows as run."""
+        self._run(lib.sdrhip_nfm_bank_run_i16, "sdrhip_nfm_bank_run_i16", d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block,
+                  state, final, workspace, workspace_bytes, stream)
+
+
 class FmChain(_Handle):
     """The FM receiver of examples/fm/fm.hs:34-41 as one device-resident object."""
     _destroy = lib.sdrhip_fm_chain_destroy
@@ -1537,6 +1608,12 @@ class Pipe(_Handle):
             check(lib.sdrhip_pipe_am_bank(C.byref(self.h), desc.h, block_size_out, 2 if input_i16 else int(bool(input_u8))), "sdrhip_pipe_am_bank")
             self.input_u8, self.input_i16 = bool(input_u8), bool(input_i16)
             self.complex_in = True
+        elif kind == "nfm_bank":
+            if input_u8 and input_i16:
+                raise ValueError("Pipe.nfm_bank: input_u8 and input_i16 exclude each other")
+            check(lib.sdrhip_pipe_nfm_bank(C.byref(self.h), desc.h, block_size_out, 2 if input_i16 else int(bool(input_u8))), "sdrhip_pipe_nfm_bank")
+            self.input_u8, self.input_i16 = bool(input_u8), bool(input_i16)
+            self.complex_in = True
         elif kind == "spectrum":
             hop, group, reduce, unit, floor_db = spectrum_args
             check(lib.sdrhip_pipe_spectrum(C.byref(self.h), desc.h, int(hop), int(group), int(reduce), int(unit), float(floor_db)),
@@ -1573,6 +1650,12 @@ class Pipe(_Handle):
         """The AM bank on host blocks: cfloat, u8 IQ or int16 IQ blocks in, every channel's audio (the envelope; with the bank's
         dc_block, dcBlocker of it, its state kept on the device) in blocks of block_size_out floats out."""
         return Pipe("am_bank", am_bank, block_size_out, input_u8=input_u8, input_i16=input_i16)
+
+    @staticmethod
+    def nfm_bank(nfm_bank, block_size_out, input_u8=False, input_i16=False):
+        """The narrow-band FM bank on host blocks: cfloat, u8 IQ or int16 IQ blocks in, every channel's fmDemod output (started from
+        (0, 0), its state kept on the device) in blocks of block_size_out floats out."""
+        return Pipe("nfm_bank", nfm_bank, block_size_out, input_u8=input_u8, input_i16=input_i16)
 
     @staticmethod
     def spectrum(spectrum, hop=None, group=1, reduce=REDUCE_MEAN_MAGNITUDE, unit=UNIT_LINEAR, floor_db=-200.0):
@@ -1671,7 +1754,7 @@ class Pipe(_Handle):
         return self._pop(check(lib.sdrhip_pipe_restore(self.h, state, len(state)), "sdrhip_pipe_restore"))
 
     def _pop(self, ready):
-        if self.kind in ("tuner_bank", "am_bank"):
+        if self.kind in ("tuner_bank", "am_bank", "nfm_bank"):
             if ready <= 0:
                 return []
             got = self.pop_rows(ready)
