@@ -8,7 +8,6 @@
 // tile launch writes d_out and there is no workspace; with it the envelope rows pass through the workspace, because dcBlocker's row
 // form refuses d_in == d_out.  Nothing is argued anew: the complex value under the magnitude is the banked launch's, the magnitude is
 // kernels_am.hip's device function (am.hpp), dcBlocker is called with the same rows, length, state and run-in on both routes.
-#include "am.hpp"
 #include "descriptors.hpp"
 
 namespace sdrhip {
@@ -42,8 +41,6 @@ bool am_bank_auto(int channels, int64_t samples, bool dc)
     return channels == 2 && samples >= kAmBankAutoDcTwoChannelsMinSamples;
 }
 
-int64_t row_floats(int64_t count) { return (count + 3) & ~(int64_t)3; }   // workspace rows start 16-byte aligned
-
 size_t route1_bytes(int K, int64_t count, bool dc)
 {
     return dc ? (size_t)K * (size_t)row_floats(count) * sizeof(float) + dc_blocker_rows_workspace_bytes(K, count) : 0;
@@ -74,17 +71,11 @@ int am_bank_run(const sdrhip_am_bank* b, hipStream_t s, const void* d_in, InFmt 
     SDRHIP_REQUIRE(d_in != nullptr && d_out != nullptr && (reinterpret_cast<uintptr_t>(d_out) & 3) == 0, "sdrhip_am_bank_run");
     SDRHIP_REQUIRE(fmt != IN_I16 || (reinterpret_cast<uintptr_t>(d_in) & 3) == 0,
                    "sdrhip_am_bank_run: int16 IQ at an address that is no multiple of 4");
-    Geom g;
-    g.in_base = in_base;
-    g.k_begin = k_begin;
-    g.count = (int)count;
-    g.I = 1;
-    g.D = d->factor;
-    g.Lp = d->Lp;
-    g.seamBI = seam_block;
+    const Geom g = bank_geom(d, in_base, k_begin, k_end, seam_block);
+    const BankForm form{BankForm::ENV};
     const int route = b->route;
     // where the tuner bank's banked launch fits (tuner_bank.cpp), the complex rows' alignment aside: there are none
-    const bool fits = d->corder == CO_L4 && tuner_fused_fits(g, d->Lp, true, d_in, fmt, nullptr, 1);
+    const bool fits = bank_fused_fits(tb, g, d_in, fmt, form, nullptr);
     if (route == 1 && !fits) {
         set_error("sdrhip_am_bank_run: the fused route serves what the tuner bank's banked launch serves -- the AVX order, factors 4 / 8 / 16, "
                   "up to 128 prepared taps, seam_block >= 0 and a 16-byte aligned first window; this launch is none of that (route 0 or 2 runs it)");
@@ -97,93 +88,31 @@ int am_bank_run(const sdrhip_am_bank* b, hipStream_t s, const void* d_in, InFmt 
                    "sdrhip_am_bank_run: a 16-byte aligned workspace of sdrhip_am_bank_workspace_bytes(b, count)");
 
     const int64_t np = row_floats(count);
+    // workspace: [complex rows (composed) | envelope rows (dc_block) | dcBlocker's own]; without dc_block the envelope rows are d_out's
+    auto run = [&](float* iq, float* ws_env) -> int {
+        float* env = dc ? ws_env : d_out;
+        const int64_t env_stride = dc ? np : out_stride;
+        int rc = iq == nullptr ? bank_fused(tb, s, g, d_in, fmt, form, env, env_stride)
+                               : bank_composed(tb, s, d_in, fmt, in_base, env, env_stride, k_begin, k_end, seam_block, form, iq);
+        if (rc != SDRHIP_OK || !dc) return rc;
+        float* dcw = env + (size_t)K * (size_t)np;
+        return sdrhip_dc_blocker_run_rows(s, env, np, d_out, out_stride, K, count, d_dc_state, d_dc_state, dcw,
+                                          ws_bytes - (size_t)(dcw - static_cast<float*>(d_ws)) * sizeof(float), 0);
+    };
     float* ws = static_cast<float*>(d_ws);
     if (fused) {
-        int rc = tb->ensure_device();
-        if (rc != SDRHIP_OK) return rc;
-        float* env = dc ? ws : d_out;
-        const int64_t env_stride = dc ? np : out_stride;
-        if (launch_am_bank(s, g, d->d_plain, d->Lp, d->d_cross, d_in, fmt, env, env_stride, tb->d_tables, K, tb->off, tb->period)) {
-            SDRHIP_CHECK_HIP(hipGetLastError());
-            if (!dc) return SDRHIP_OK;
-            void* dcw = ws + (size_t)K * (size_t)np;
-            return sdrhip_dc_blocker_run_rows(s, env, np, d_out, out_stride, K, count, d_dc_state, d_dc_state, dcw,
-                                              ws_bytes - (size_t)K * (size_t)np * sizeof(float), 0);
-        }
+        int rc = run(nullptr, ws);
+        if (rc != kBankNotThisShape) return rc;
         if (route == 1) {
             set_error("sdrhip_am_bank_run: the envelope launch refused a launch its predicate admitted");
             return SDRHIP_ERR_ARG;
         }
         // auto: nothing was launched and the composed route runs it (its workspace was asked for above), as the tuner bank falls through
     }
-    float* iq = ws;
-    float* env = ws + (size_t)K * 2 * (size_t)np;
-    // (tuner_bank_run is what sdrhip_tuner_bank_run / _run_u8 / _run_i16 call with their input type)
-    int rc = tuner_bank_run(tb, s, d_in, fmt, in_base, iq, 2 * np, k_begin, k_end, seam_block);
-    if (rc != SDRHIP_OK) return rc;
-    if (!dc) return sdrhip_am_demod_run_rows(s, iq, 2 * np, d_out, out_stride, K, count);
-    rc = sdrhip_am_demod_run_rows(s, iq, 2 * np, env, np, K, count);
-    if (rc != SDRHIP_OK) return rc;
-    void* dcw = env + (size_t)K * (size_t)np;
-    return sdrhip_dc_blocker_run_rows(s, env, np, d_out, out_stride, K, count, d_dc_state, d_dc_state, dcw,
-                                      ws_bytes - (size_t)K * 3 * (size_t)np * sizeof(float), 0);
+    return run(ws, ws + (size_t)K * 2 * (size_t)np);
 }
 
 }  // namespace
-
-int am_bank_envelope(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_env, int64_t env_stride,
-                     int64_t k_begin, int64_t k_end, int64_t seam_block, float* d_iq, int64_t row_floats_iq)
-{
-    const int K = (int)tb->ch.size();
-    const FirDesc* d = &tb->ch[0]->fir;
-    if (k_end <= k_begin) return SDRHIP_OK;
-    Geom g;
-    g.in_base = in_base;
-    g.k_begin = k_begin;
-    g.count = (int)(k_end - k_begin);
-    g.I = 1;
-    g.D = d->factor;
-    g.Lp = d->Lp;
-    g.seamBI = seam_block;
-    if (d->corder == CO_L4 && tuner_fused_fits(g, d->Lp, true, d_in, fmt, nullptr, 1)) {
-        int rc = tb->ensure_device();
-        if (rc != SDRHIP_OK) return rc;
-        if (launch_am_bank(s, g, d->d_plain, d->Lp, d->d_cross, d_in, fmt, d_env, env_stride, tb->d_tables, K, tb->off, tb->period)) {
-            SDRHIP_CHECK_HIP(hipGetLastError());
-            return SDRHIP_OK;
-        }
-    }
-    SDRHIP_REQUIRE(d_iq != nullptr, "am_bank_envelope: no scratch for the composed route");
-    int rc = tuner_bank_run(tb, s, d_in, fmt, in_base, d_iq, 2 * row_floats_iq, k_begin, k_end, seam_block);
-    if (rc != SDRHIP_OK) return rc;
-    launch_am_demod_rows(s, K, d_iq, 2 * row_floats_iq, d_env, env_stride, g.count);
-    SDRHIP_CHECK_HIP(hipGetLastError());
-    return SDRHIP_OK;
-}
-
-int am_bank_envelope_cross(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_env,
-                           int64_t env_stride, int64_t k_begin, int64_t k_end)
-{
-    const FirDesc* d = &tb->ch[0]->fir;
-    SDRHIP_REQUIRE(k_begin >= 0 && k_end > k_begin && k_begin * d->factor >= in_base, "am_bank_envelope_cross");
-    int rc = tb->ensure_device();
-    if (rc != SDRHIP_OK) return rc;
-    Geom g;
-    g.in_base = in_base;
-    g.k_begin = k_begin;
-    g.count = (int)(k_end - k_begin);
-    g.I = 1;
-    g.D = d->factor;
-    g.Lp = d->Lp;
-    g.seamBI = -1;
-    if (!launch_am_bank_cross(s, g, d->d_cross, d_in, fmt, d_env, env_stride, tb->d_tables, (int)tb->ch.size(), tb->off, tb->period)) {
-        set_error("am_bank_envelope_cross: the all-Cross envelope launch refused its channels, stride or pointers");
-        return SDRHIP_ERR_ARG;
-    }
-    SDRHIP_CHECK_HIP(hipGetLastError());
-    return SDRHIP_OK;
-}
-
 }  // namespace sdrhip
 
 using namespace sdrhip;

@@ -121,9 +121,39 @@ struct TunerBankDesc {
 };
 int tuner_bank_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out, int64_t out_stride,
                    int64_t k_begin, int64_t k_end, int64_t seam_block);
-// every output of [k_begin, k_end) Cross, all channels in one launch: the ragged pushes of the bank's Pipe (pipes.cpp)
-int tuner_bank_cross_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out,
-                         int64_t out_stride, int64_t k_begin, int64_t k_end);
+
+// ---- the output forms of the bank family (tuner_bank.cpp) ---------------------------------------------------------------------------
+// What the bank's kernel pair (kernels_tuner_bank.hip) stores for a finished output: the complex value (rows of 2 floats per output,
+// 8-byte aligned, an even stride), its envelope, or fmDemod's phase against the output before it (rows of 1 float per output at any
+// float address).  The phase form reads every channel's output k_begin - 1 from d_state (channels (re, im) pairs) and leaves output
+// k_end - 1 in d_final; the two do not overlap.
+struct BankForm {
+    enum Kind { IQ, ENV, PHASE } kind = IQ;
+    const float* d_state = nullptr;
+    float* d_final = nullptr;
+    bool state_overlaps(int channels) const;
+};
+inline int64_t row_floats(int64_t count) { return (count + 3) & ~(int64_t)3; }   // workspace rows start 16-byte aligned
+// channel 0's decimator over outputs [k_begin, k_end) (ranges and taps are the same for every channel)
+Geom bank_geom(const FirDesc* d, int64_t in_base, int64_t k_begin, int64_t k_end, int64_t seam_block);
+// whether the fused launch (set) takes this range in this form; d_out: the complex rows of the IQ form (the float forms ignore it)
+bool bank_fused_fits(const TunerBankDesc* tb, const Geom& g, const void* d_in, InFmt fmt, const BankForm& form, const float* d_out);
+// The steps the bank objects and the banks' Pipes are built from; row j of a form is at d_out + j * out_stride floats.
+// bank_fused: the fused launch (set); SDRHIP_OK = launched, kBankNotThisShape = nothing launched, negative = an error.
+// bank_composed (the float forms): the tuner bank into d_iq (channels rows of 2 * row_floats(count) floats, 16-byte aligned), then
+// amDemod's or fmDemod's rows form, through the C ABI as a caller without the bank objects makes the calls.
+// bank_cross: every output Cross, one launch for all channels (the ragged pushes of the banks' Pipes), no route and no auto rule.
+// bank_form_run: what the Pipes of the float forms run for the outputs inside a block -- bank_fused where bank_fused_fits says so,
+// else bank_composed (d_iq null = no fall-back: SDRHIP_ERR_ARG).
+constexpr int kBankNotThisShape = 1;
+int bank_fused(const TunerBankDesc* tb, hipStream_t s, const Geom& g, const void* d_in, InFmt fmt, const BankForm& form, float* d_out,
+               int64_t out_stride);
+int bank_composed(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out, int64_t out_stride,
+                  int64_t k_begin, int64_t k_end, int64_t seam_block, const BankForm& form, float* d_iq);
+int bank_cross(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out, int64_t out_stride,
+               int64_t k_begin, int64_t k_end, const BankForm& form);
+int bank_form_run(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out, int64_t out_stride,
+                  int64_t k_begin, int64_t k_end, int64_t seam_block, const BankForm& form, float* d_iq);
 
 // The AM bank (include/sdr_hip.h, am_bank.cpp): a BORROWED tuner bank, the envelope of each of its rows and, with dc_block, dcBlocker.
 struct AmBankDesc {
@@ -131,34 +161,12 @@ struct AmBankDesc {
     int dc_block = 0;
     mutable int route = 0;                     // 0 = auto, 1 = fused, 2 = composed
 };
-// For the bank's Pipe (pipes.cpp), which owns its scratch, runs dcBlocker itself and has no route setting: the envelope rows alone,
-// d_env + j * env_stride floats.  am_bank_envelope: outputs [k_begin, k_end) by the fused launch set where it fits (seam_block >= 0),
-// else by the tuner bank into d_iq (channels rows of 2 * row_floats floats, 16-byte aligned; null = no fall-back: SDRHIP_ERR_ARG) and
-// amDemod's rows form.  am_bank_envelope_cross: every output Cross, one launch (k_tuner_bank_cross in its envelope form).
-int am_bank_envelope(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_env, int64_t env_stride,
-                     int64_t k_begin, int64_t k_end, int64_t seam_block, float* d_iq, int64_t row_floats);
-int am_bank_envelope_cross(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_env,
-                           int64_t env_stride, int64_t k_begin, int64_t k_end);
-
 
 // The narrow-band FM bank (include/sdr_hip.h, nfm_bank.cpp): a BORROWED tuner bank and fmDemod of each of its rows.
 struct NfmBankDesc {
     const TunerBankDesc* tb = nullptr;
     mutable int route = 0;                     // 0 = auto, 1 = fused, 2 = composed
 };
-// For the bank's Pipe (pipes.cpp), which owns its scratch and its two state arrays and has no route setting: the demodulated rows,
-// d_out + j * out_stride floats, from d_state (channels (re, im) pairs: every channel's output k_begin - 1) and into d_final (output
-// k_end - 1); the two do not overlap.  nfm_bank_phase: outputs [k_begin, k_end), k_end > k_begin, by the ONE fused launch where it
-// fits (0 <= seam_block < 2^30), else by the tuner bank into d_iq (channels rows of 2 * row_floats floats, 16-byte aligned; null = no
-// fall-back: SDRHIP_ERR_ARG) and fmDemod's rows form.  nfm_bank_phase_cross: every output Cross, one launch.
-int nfm_bank_phase(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out, int64_t out_stride,
-                   int64_t k_begin, int64_t k_end, int64_t seam_block, const float* d_state, float* d_final, float* d_iq,
-                   int64_t row_floats);
-// whether nfm_bank_phase takes the fused launch for this range (so that the Pipe keeps no complex scratch where it does)
-bool nfm_bank_fused_fits(const TunerBankDesc* tb, const void* d_in, InFmt fmt, int64_t in_base, int64_t k_begin, int64_t k_end,
-                         int64_t seam_block);
-int nfm_bank_phase_cross(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out,
-                         int64_t out_stride, int64_t k_begin, int64_t k_end, const float* d_state, float* d_final);
 
 }  // namespace sdrhip
 

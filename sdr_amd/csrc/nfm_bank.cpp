@@ -59,36 +59,7 @@ bool nfm_bank_auto(int channels, int factor, int64_t seam_block, int64_t n)
     return false;
 }
 
-int64_t row_floats(int64_t count) { return (count + 3) & ~(int64_t)3; }   // workspace rows start 16-byte aligned
-
 size_t route2_bytes(int K, int64_t count) { return (size_t)K * 2 * (size_t)row_floats(count) * sizeof(float); }
-
-bool overlap(const float* a, const float* b, int K)
-{
-    if (a == nullptr || b == nullptr) return false;
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b), n = (uintptr_t)K * 2 * sizeof(float);
-    return x < y + n && y < x + n;
-}
-
-Geom geom_of(const FirDesc* d, int64_t in_base, int64_t k_begin, int64_t k_end, int64_t seam_block)
-{
-    Geom g;
-    g.in_base = in_base;
-    g.k_begin = k_begin;
-    g.count = (int)(k_end - k_begin);
-    g.I = 1;
-    g.D = d->factor;
-    g.Lp = d->Lp;
-    g.seamBI = seam_block;
-    return g;
-}
-
-// where the tuner bank's banked launch fits (tuner_bank.cpp), the complex rows' alignment aside (there are none), and the in-tile
-// seam test works in 32 bits
-bool nfm_fits(const FirDesc* d, const Geom& g, const void* d_in, InFmt fmt)
-{
-    return d->corder == CO_L4 && g.seamBI < ((int64_t)1 << 30) && tuner_fused_fits(g, d->Lp, true, d_in, fmt, nullptr, 1);
-}
 
 int nfm_bank_run(const sdrhip_nfm_bank* b, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out, int64_t out_stride,
                  int64_t k_begin, int64_t k_end, int64_t seam_block, const float* d_state, float* d_final, void* d_ws, size_t ws_bytes)
@@ -108,7 +79,8 @@ int nfm_bank_run(const sdrhip_nfm_bank* b, hipStream_t s, const void* d_in, InFm
                    "sdrhip_nfm_bank_run: int16 IQ at an address that is no multiple of 4");
     SDRHIP_REQUIRE((reinterpret_cast<uintptr_t>(d_state) & 3) == 0 && (reinterpret_cast<uintptr_t>(d_final) & 3) == 0,
                    "sdrhip_nfm_bank_run: state arrays are floats");
-    SDRHIP_REQUIRE(!overlap(d_state, d_final, K),
+    const BankForm form{BankForm::PHASE, d_state, d_final};
+    SDRHIP_REQUIRE(!form.state_overlaps(K),
                    "sdrhip_nfm_bank_run: d_state and d_final overlap (the launch's first tile reads one while its last writes the other)");
     if (count == 0) {
         // as sdrhip_fm_demod_run_rows over an empty range: d_final = d_state (or zeros), on every route
@@ -119,9 +91,11 @@ int nfm_bank_run(const sdrhip_nfm_bank* b, hipStream_t s, const void* d_in, InFm
         return SDRHIP_OK;
     }
     SDRHIP_REQUIRE(d_in != nullptr && d_out != nullptr, "sdrhip_nfm_bank_run");
-    const Geom g = geom_of(d, in_base, k_begin, k_end, seam_block);
+    const Geom g = bank_geom(d, in_base, k_begin, k_end, seam_block);
     const int route = b->route;
-    const bool fits = nfm_fits(d, g, d_in, fmt);
+    // where the tuner bank's banked launch fits (tuner_bank.cpp), the complex rows' alignment aside (there are none), and the in-tile
+    // seam test works in 32 bits
+    const bool fits = bank_fused_fits(tb, g, d_in, fmt, form, nullptr);
     if (route == 1 && !fits) {
         set_error("sdrhip_nfm_bank_run: the fused route serves what the tuner bank's banked launch serves -- the AVX order, factors 4 / 8 / 16, "
                   "up to 128 prepared taps, 0 <= seam_block < 2^30 and a 16-byte aligned first window; this launch is none of that (route 0 or 2 "
@@ -134,81 +108,18 @@ int nfm_bank_run(const sdrhip_nfm_bank* b, hipStream_t s, const void* d_in, InFm
     SDRHIP_REQUIRE(need == 0 || (d_ws != nullptr && ws_bytes >= need && (reinterpret_cast<uintptr_t>(d_ws) & 15) == 0),
                    "sdrhip_nfm_bank_run: a 16-byte aligned workspace of sdrhip_nfm_bank_workspace_bytes(b, count)");
     if (fused) {
-        int rc = tb->ensure_device();
-        if (rc != SDRHIP_OK) return rc;
-        if (launch_nfm_bank(s, g, d->d_plain, d->Lp, d->d_cross, d_in, fmt, d_out, out_stride, tb->d_tables, K, tb->off, tb->period, d_state,
-                            d_final)) {
-            SDRHIP_CHECK_HIP(hipGetLastError());
-            return SDRHIP_OK;
-        }
+        int rc = bank_fused(tb, s, g, d_in, fmt, form, d_out, out_stride);
+        if (rc != kBankNotThisShape) return rc;
         if (route == 1) {
             set_error("sdrhip_nfm_bank_run: the fmDemod-form launch refused a launch its predicate admitted");
             return SDRHIP_ERR_ARG;
         }
         // auto: nothing was launched and the composed route runs it (its workspace was asked for above)
     }
-    const int64_t np = row_floats(count);
-    float* iq = static_cast<float*>(d_ws);
-    // (tuner_bank_run is what sdrhip_tuner_bank_run / _run_u8 / _run_i16 call with their input type)
-    int rc = tuner_bank_run(tb, s, d_in, fmt, in_base, iq, 2 * np, k_begin, k_end, seam_block);
-    if (rc != SDRHIP_OK) return rc;
-    return sdrhip_fm_demod_run_rows(s, iq, 2 * np, k_begin, d_out, out_stride, K, k_begin, k_end, d_state, d_final);
+    return bank_composed(tb, s, d_in, fmt, in_base, d_out, out_stride, k_begin, k_end, seam_block, form, static_cast<float*>(d_ws));
 }
 
 }  // namespace
-
-// (the Pipe allocates nfm_bank_phase's fall-back scratch only where this is false: it must stay at least as strict as the launcher,
-// see the note in pipes.cpp)
-bool nfm_bank_fused_fits(const TunerBankDesc* tb, const void* d_in, InFmt fmt, int64_t in_base, int64_t k_begin, int64_t k_end,
-                         int64_t seam_block)
-{
-    const FirDesc* d = &tb->ch[0]->fir;
-    return k_begin >= 0 && k_end > k_begin && nfm_fits(d, geom_of(d, in_base, k_begin, k_end, seam_block), d_in, fmt);
-}
-
-int nfm_bank_phase(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out, int64_t out_stride,
-                   int64_t k_begin, int64_t k_end, int64_t seam_block, const float* d_state, float* d_final, float* d_iq,
-                   int64_t row_floats_iq)
-{
-    const int K = (int)tb->ch.size();
-    const FirDesc* d = &tb->ch[0]->fir;
-    SDRHIP_REQUIRE(k_begin >= 0 && k_end > k_begin && !overlap(d_state, d_final, K), "nfm_bank_phase");
-    const Geom g = geom_of(d, in_base, k_begin, k_end, seam_block);
-    if (nfm_fits(d, g, d_in, fmt)) {
-        int rc = tb->ensure_device();
-        if (rc != SDRHIP_OK) return rc;
-        if (launch_nfm_bank(s, g, d->d_plain, d->Lp, d->d_cross, d_in, fmt, d_out, out_stride, tb->d_tables, K, tb->off, tb->period, d_state,
-                            d_final)) {
-            SDRHIP_CHECK_HIP(hipGetLastError());
-            return SDRHIP_OK;
-        }
-    }
-    SDRHIP_REQUIRE(d_iq != nullptr, "nfm_bank_phase: no scratch for the composed route");
-    int rc = tuner_bank_run(tb, s, d_in, fmt, in_base, d_iq, 2 * row_floats_iq, k_begin, k_end, seam_block);
-    if (rc != SDRHIP_OK) return rc;
-    launch_fm_demod_rows(s, K, d_iq, 2 * row_floats_iq, d_out, out_stride, g.count, false, d_state, d_final);
-    SDRHIP_CHECK_HIP(hipGetLastError());
-    return SDRHIP_OK;
-}
-
-int nfm_bank_phase_cross(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out,
-                         int64_t out_stride, int64_t k_begin, int64_t k_end, const float* d_state, float* d_final)
-{
-    const FirDesc* d = &tb->ch[0]->fir;
-    SDRHIP_REQUIRE(k_begin >= 0 && k_end > k_begin && k_begin * d->factor >= in_base && !overlap(d_state, d_final, (int)tb->ch.size()),
-                   "nfm_bank_phase_cross");
-    int rc = tb->ensure_device();
-    if (rc != SDRHIP_OK) return rc;
-    const Geom g = geom_of(d, in_base, k_begin, k_end, -1);
-    if (!launch_nfm_bank_cross(s, g, d->d_cross, d_in, fmt, d_out, out_stride, tb->d_tables, (int)tb->ch.size(), tb->off, tb->period, d_state,
-                               d_final)) {
-        set_error("nfm_bank_phase_cross: the all-Cross fmDemod-form launch refused its channels, stride or pointers");
-        return SDRHIP_ERR_ARG;
-    }
-    SDRHIP_CHECK_HIP(hipGetLastError());
-    return SDRHIP_OK;
-}
-
 }  // namespace sdrhip
 
 using namespace sdrhip;

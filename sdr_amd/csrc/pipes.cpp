@@ -22,9 +22,9 @@
 //
 // The tuner bank's Pipe (sdrhip_pipe_tuner_bank) is the tuner's Pipe with the engine's rows: one submission computes every
 // channel's outputs into a row-major chunk which the harvest regroups into one fifo per channel.  Its blocks may be u8 IQ (2 bytes
-// per element from the staging buffer to the kernels' loaders) or int16 IQ (4 bytes per element, sdrhip_pipe_tuner_bank_i16).  With more than one row nothing is read in place: up to kDirectBytes
-// a submission is one copy on the slot's stream and the launch behind it, placed in device memory so that the banked launch's first
-// window is 16-byte aligned (HostStream::dev_skew).
+// per element from the staging buffer to the kernels' loaders) or int16 IQ (4 bytes per element, sdrhip_pipe_tuner_bank_i16).  With
+// more than one row nothing is read in place: up to kDirectBytes a submission is one copy on the slot's stream and the launch behind
+// it, placed in device memory so that the banked launch's first window is 16-byte aligned (HostStream::dev_skew).
 //
 // The waterfall Pipe (sdrhip_pipe_spectrum) is the spectrum operator's reducing form on the same engine: blocks of any size in, rows of
 // n floats out, the carried tail being the samples from the first row not yet produced onward (spectrum_push / spectrum_submit below).
@@ -57,6 +57,10 @@ struct sdrhip_pipe {
     // per element), and stay in that type up to the kernels' loaders
     const TunerBankDesc* bank = nullptr;
     InFmt fmt = IN_CF32;
+    // the bank Pipes' output form (descriptors.hpp) and its scratch policy: complex rows in am_iq for EVERY submission, or only for
+    // those whose tile part the fused launch does not take (the IQ form has no composed step and no scratch)
+    BankForm::Kind form = BankForm::IQ;
+    bool iq_always = false;
     // PK_AM_BANK: the AM bank's Pipe -- the tuner bank's Pipe with ONE float per output (the envelope; bank = the AM bank's tuner bank)
     // and, with am_dc, dcBlocker behind it on the device: its K state pairs live in dc_state, the envelope rows and dcBlocker's
     // workspace in dc_ws, and EVERY submission goes to compute stream 0, so each is ordered behind its predecessor by the stream.
@@ -175,6 +179,25 @@ static int ready_blocks(const sdrhip_pipe* p)
     return (int)(p->eng.pending() / ((size_t)p->block_out * p->esz_out()));
 }
 
+// room for `bytes` in a scratch buffer that launches already on stream s may still use: growing frees the old buffer, so they end first
+static int grow(DevBuf& b, size_t bytes, hipStream_t s)
+{
+    if (bytes > b.cap) SDRHIP_CHECK_HIP(hipStreamSynchronize(s));
+    return b.ensure(bytes);
+}
+
+// The launches of one submission (fir_submit below), run(k_begin, k_end, seam_block, outputs in front of k_begin in this submission):
+// a uniform run is ONE call over [m_done, m_end) with its seams; a ragged block is the Cross call over [m_done, m_split) (seam -1),
+// then the One call over [m_split, m_end) (seam 0).  An empty part is no call.
+template <class Run>
+static int submit_parts(int64_t m_done, int64_t m_split, int64_t m_end, int64_t uniform_seam, Run run)
+{
+    const int64_t t0 = uniform_seam > 0 ? m_done : m_split;
+    int r;
+    if (t0 > m_done && (r = run(m_done, t0, (int64_t)-1, (int64_t)0)) != SDRHIP_OK) return r;
+    return m_end > t0 ? run(t0, m_end, uniform_seam, t0 - m_done) : SDRHIP_OK;
+}
+
 // Submit the n elements staged in the current slot's pinned buffer.  uniform_seam > 0: they are whole blocks of that size
 // and so was everything before them, so the seams of the reference's input buffers are the multiples of uniform_seam and
 // ONE stream-API run covers the batch (interior seams included).  uniform_seam == 0: a single block of arbitrary size: the
@@ -228,114 +251,63 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
         const size_t off = (size_t)(k0 * p->D - keep_from) * ein;
         e.dev_skew = (16 - off % 16) % 16;
     }
-    const int64_t row_floats = (m_end - m_done) * p->esz_out();
-    int rc = e.submit(route, cs, first, (size_t)(tail + n) * ein, rows * row_floats, [&](hipStream_t s, const void* d_in, void* d_out) {
+    const int64_t row_len = (m_end - m_done) * p->esz_out();
+    int rc = e.submit(route, cs, first, (size_t)(tail + n) * ein, rows * row_len, [&](hipStream_t s, const void* d_in, void* d_out) {
         const float* din = (const float*)d_in;
         float* dout = (float*)d_out;
-        if (p->kind == PK_NFM_BANK) {
-            // every row [cross | one] as PHASES, one float per output: the fused launch where it fits (dev_skew has aligned the first
-            // window), else tuner bank + fmDemod rows through the slot's complex scratch.  Each launch takes the state its predecessor
-            // left and leaves the next one's in the other array.
-            const int K = rows;
-            const int64_t count = m_end - m_done, np = (count + 3) & ~(int64_t)3;
-            int r;
-            // the complex scratch only where the tile part of this submission is NOT the fused launch (another order or factor): the
-            // fused launch never touches it, and 32 channels of it are K * 2 * np floats
-            // COUPLING: nfm_bank_fused_fits (nfm_fits, nfm_bank.cpp) must admit nothing that launch_bank<OUT_FM>
-            // (kernels_tuner_bank.hip) refuses -- today both apply tuner_fused_fits, the seam bound and the create-time limits on channels
-            // and periods, and the row stride here is the row's length.  Where they diverged, nfm_bank_phase would find no scratch for
-            // its fall-back and the submission would end in SDRHIP_ERR_ARG ("no scratch for the composed route"), not in wrong bits.
-            const int64_t t0 = uniform_seam > 0 ? m_done : m_split;
-            float* iq = nullptr;
-            if (m_end > t0 && !nfm_bank_fused_fits(p->bank, d_in, p->fmt, in_base, t0, m_end, uniform_seam > 0 ? uniform_seam : 0)) {
-                DevBuf& b = p->am_iq[si];
-                const size_t iq_bytes = (size_t)K * 2 * (size_t)np * sizeof(float);
-                if (iq_bytes > b.cap) SDRHIP_CHECK_HIP(hipStreamSynchronize(s));               // growing frees the old buffer
-                if ((r = b.ensure(iq_bytes)) != SDRHIP_OK) return r;
-                iq = (float*)b.p;
-            }
-            auto st_in = [&] { return (const float*)p->nfm_state[p->nfm_cur].p; };
-            auto st_out = [&] { return (float*)p->nfm_state[p->nfm_cur ^ 1].p; };
-            if (uniform_seam > 0) {
-                r = nfm_bank_phase(p->bank, s, d_in, p->fmt, in_base, dout, row_floats, m_done, m_end, uniform_seam, st_in(), st_out(), iq, np);
-                if (r == SDRHIP_OK) p->nfm_cur ^= 1;
-                return r;
-            }
-            const int64_t ncross = m_split - m_done;
-            if (ncross > 0) {
-                if ((r = nfm_bank_phase_cross(p->bank, s, d_in, p->fmt, in_base, dout, row_floats, m_done, m_split, st_in(), st_out())) != SDRHIP_OK)
-                    return r;
-                p->nfm_cur ^= 1;
-            }
-            if (m_end > m_split) {
-                r = nfm_bank_phase(p->bank, s, d_in, p->fmt, in_base, dout + ncross, row_floats, m_split, m_end, 0, st_in(), st_out(), iq, np);
-                if (r != SDRHIP_OK) return r;
-                p->nfm_cur ^= 1;
-            }
-            return SDRHIP_OK;
+        if (p->bank == nullptr) {
+            // filter / decimator / resampler, or the tuner's mix + decimator: in_base is the absolute stream position of din[0], which
+            // is what selects the oscillator phase
+            return submit_parts(m_done, m_split, m_end, uniform_seam, [&](int64_t k0, int64_t k1, int64_t seam, int64_t off) {
+                float* o = dout + off * p->esz_out();
+                if (p->kind == PK_RESAMPLER) return resamp_run(p->rs, s, din, in_base, o, k0, k1, seam, seam > 0 ? p->block_out : 0);
+                if (p->kind == PK_TUNER) return tuner_run(p->tuner, s, din, IN_CF32, in_base, o, k0, k1, seam);
+                return fir_run(p->fir, s, din, false, in_base, o, k0, k1, seam);
+            });
         }
-        if (p->kind == PK_AM_BANK) {
-            // every row [cross | one] as ENVELOPES, one float per output: the fused launch set where it fits (dev_skew has aligned the
-            // first window), else tuner bank + amDemod rows through the slot's complex scratch
-            const int K = rows;
-            const int64_t count = m_end - m_done, np = (count + 3) & ~(int64_t)3;
-            int r;
-            float* env = dout;
-            int64_t env_stride = row_floats;
-            if (p->am_dc) {
-                const size_t need = (size_t)K * (size_t)np * sizeof(float) + dc_blocker_rows_workspace_bytes(K, count);
-                if (need > p->dc_ws.cap) SDRHIP_CHECK_HIP(hipStreamSynchronize(s));            // growing frees the old buffer
-                if ((r = p->dc_ws.ensure(need)) != SDRHIP_OK) return r;
-                env = (float*)p->dc_ws.p;
-                env_stride = np;
-            }
-            // (the complex scratch is kept ready for every submission: whether the fused launch takes one is the launcher's decision)
-            DevBuf& b = p->am_iq[si];
-            const size_t iq_bytes = (size_t)K * 2 * (size_t)np * sizeof(float);
-            if (iq_bytes > b.cap) SDRHIP_CHECK_HIP(hipStreamSynchronize(s));
-            if ((r = b.ensure(iq_bytes)) != SDRHIP_OK) return r;
-            float* iq = (float*)b.p;
-            if (uniform_seam > 0) {
-                r = am_bank_envelope(p->bank, s, d_in, p->fmt, in_base, env, env_stride, m_done, m_end, uniform_seam, iq, np);
-            } else {
-                const int64_t ncross = m_split - m_done;
-                r = SDRHIP_OK;
-                if (ncross > 0) r = am_bank_envelope_cross(p->bank, s, d_in, p->fmt, in_base, env, env_stride, m_done, m_split);
-                if (r == SDRHIP_OK) r = am_bank_envelope(p->bank, s, d_in, p->fmt, in_base, env + ncross, env_stride, m_split, m_end, 0, iq, np);
-            }
-            if (r != SDRHIP_OK || !p->am_dc) return r;
-            launch_dc_blocker_rows(s, K, count, env, np, dout, row_floats, (const float*)p->dc_state.p, (float*)p->dc_state.p,
-                                   env + (size_t)K * (size_t)np, 0);
-            SDRHIP_CHECK_HIP(hipGetLastError());
-            return SDRHIP_OK;
-        }
-        if (p->kind == PK_TUNER_BANK) {
-            // every row [cross | one], row_floats apart: the bank's own rule picks the banked launch or channel by channel
-            if (uniform_seam > 0) return tuner_bank_run(p->bank, s, d_in, p->fmt, in_base, dout, row_floats, m_done, m_end, uniform_seam);
-            const int64_t ncross = m_split - m_done;
-            int r;
-            if (ncross > 0 && (r = tuner_bank_cross_run(p->bank, s, d_in, p->fmt, in_base, dout, row_floats, m_done, m_split)) != SDRHIP_OK)
-                return r;
-            return tuner_bank_run(p->bank, s, d_in, p->fmt, in_base, dout + 2 * ncross, row_floats, m_split, m_end, 0);
-        }
-        // filter / decimator, or the tuner's mix + decimator: in_base is the absolute stream position of din[0], which is what
-        // selects the oscillator phase
-        auto fir_run = [&](const FirDesc* f, hipStream_t st, const float* in, bool, int64_t base, float* out, int64_t k0, int64_t k1, int64_t seam) {
-            if (p->kind == PK_TUNER) return tuner_run(p->tuner, st, in, IN_CF32, base, out, k0, k1, seam);
-            return sdrhip::fir_run(f, st, in, false, base, out, k0, k1, seam);
-        };
-        if (uniform_seam > 0) {
-            if (p->kind == PK_RESAMPLER) return resamp_run(p->rs, s, din, in_base, dout, m_done, m_end, uniform_seam, p->block_out);
-            return fir_run(p->fir, s, din, false, in_base, dout, m_done, m_end, uniform_seam);
-        }
-        const int64_t ncross = m_split - m_done;
+        // The banks: every row [cross | one] in the Pipe's form, row_len apart (dev_skew has aligned the tile part's first window).
+        // IQ: the bank's own rule picks the banked launch or channel by channel.  Envelopes and phases, one float per output: the
+        // fused launch (set) where it fits, else tuner bank + amDemod / fmDemod rows through the slot's complex scratch.
+        const int K = rows;
+        const int64_t count = m_end - m_done, np = row_floats(count);
         int r;
-        if (p->kind == PK_RESAMPLER) {
-            if (ncross > 0 && (r = resamp_run(p->rs, s, din, in_base, dout, m_done, m_split, -1)) != SDRHIP_OK) return r;
-            return resamp_run(p->rs, s, din, in_base, dout + ncross * p->esz_out(), m_split, m_end, 0);
+        float* out = dout;
+        int64_t stride = row_len;
+        if (p->am_dc) {
+            // dcBlocker's row form refuses d_in == d_out: the envelope rows pass through dc_ws, its own workspace behind them
+            if ((r = grow(p->dc_ws, (size_t)K * (size_t)np * sizeof(float) + dc_blocker_rows_workspace_bytes(K, count), s)) != SDRHIP_OK) return r;
+            out = (float*)p->dc_ws.p;
+            stride = np;
         }
-        if (ncross > 0 && (r = fir_run(p->fir, s, din, false, in_base, dout, m_done, m_split, -1)) != SDRHIP_OK) return r;
-        return fir_run(p->fir, s, din, false, in_base, dout + ncross * p->esz_out(), m_split, m_end, 0);
+        BankForm form{p->form};
+        // (the fused launch never touches the complex scratch, and 32 channels of it are K * 2 * np floats: a form that keeps it only
+        // where the tile part is not the fused launch asks the predicate that bank_form_run asks)
+        const int64_t t0 = uniform_seam > 0 ? m_done : m_split;
+        float* iq = nullptr;
+        if (p->iq_always || (form.kind != BankForm::IQ && m_end > t0 &&
+                             !bank_fused_fits(p->bank, bank_geom(p->fir, in_base, t0, m_end, uniform_seam), d_in, p->fmt, form, nullptr))) {
+            if ((r = grow(p->am_iq[si], (size_t)K * 2 * (size_t)np * sizeof(float), s)) != SDRHIP_OK) return r;
+            iq = (float*)p->am_iq[si].p;
+        }
+        r = submit_parts(m_done, m_split, m_end, uniform_seam, [&](int64_t k0, int64_t k1, int64_t seam, int64_t off) {
+            float* o = out + off * p->esz_out();
+            if (form.kind == BankForm::PHASE) {
+                // each launch takes the state its predecessor left and leaves the next one's in the other array
+                form.d_state = (const float*)p->nfm_state[p->nfm_cur].p;
+                form.d_final = (float*)p->nfm_state[p->nfm_cur ^ 1].p;
+            }
+            int rr;
+            if (seam < 0) rr = bank_cross(p->bank, s, d_in, p->fmt, in_base, o, stride, k0, k1, form);
+            else if (form.kind == BankForm::IQ) rr = tuner_bank_run(p->bank, s, d_in, p->fmt, in_base, o, stride, k0, k1, seam);
+            else rr = bank_form_run(p->bank, s, d_in, p->fmt, in_base, o, stride, k0, k1, seam, form, iq);
+            if (rr == SDRHIP_OK && form.kind == BankForm::PHASE) p->nfm_cur ^= 1;
+            return rr;
+        });
+        if (r != SDRHIP_OK || !p->am_dc) return r;
+        launch_dc_blocker_rows(s, K, count, out, np, dout, row_len, (const float*)p->dc_state.p, (float*)p->dc_state.p,
+                               out + (size_t)K * (size_t)np, 0);
+        SDRHIP_CHECK_HIP(hipGetLastError());
+        return SDRHIP_OK;
     });
     if (rc != SDRHIP_OK) return rc;
     p->m_done = m_end;
@@ -589,86 +561,76 @@ int sdrhip_pipe_tuner(sdrhip_pipe** pp, const sdrhip_tuner* t, int block_size_ou
     return rc;
 }
 
+// A pipe's state on the device: `bytes` of `buf` (at least 16), zeros -- set on the first compute stream -- or a copy of `init`.  On
+// failure the pipe is destroyed and *pp is null.
+static int pipe_dev_state(sdrhip_pipe** pp, DevBuf& buf, size_t bytes, const void* init, const char* who)
+{
+    sdrhip_pipe* p = *pp;
+    int rc = buf.ensure(bytes < 16 ? 16 : bytes);
+    if (rc == SDRHIP_OK) {
+        hipError_t e = init ? hipMemcpy(buf.p, init, bytes, hipMemcpyHostToDevice) : hipMemsetAsync(buf.p, 0, bytes, p->eng.compute[0]);
+        if (e == hipSuccess) return SDRHIP_OK;
+        set_error("%s: %s", who, hipGetErrorString(e));
+        rc = SDRHIP_ERR_HIP;
+    }
+    delete p;
+    *pp = nullptr;
+    return rc;
+}
+
+// The four bank Pipes: the checks (all of them before pipe_new, whose engine creates streams: a refused create has done no device
+// work), the pipe with one engine row per channel, and the form's state on the device: `nstate` arrays (dc_state; nfm_state[0 .. 1])
+// of one pair of floats per channel, zeroed (dcBlocker: func 0 0, Filter.hs:731; fmDemod: every channel starts from (0, 0),
+// Demod.hs:41).  max_type: the last input type the call takes (1: sdrhip_pipe_tuner_bank's input_u8).
+static int bank_pipe_new(sdrhip_pipe** pp, const char* who, const TunerBankDesc* b, int block_size_out, int input_type, int max_type,
+                         PipeKind kind, BankForm::Kind form, int nstate)
+{
+#define BANK_PIPE_REQUIRE(cond, what)                                                     \
+    if (!(cond)) {                                                                        \
+        set_error("%s" what ": requirement `%s` violated", who, #cond);                   \
+        return SDRHIP_ERR_ARG;                                                            \
+    }
+    BANK_PIPE_REQUIRE(pp != nullptr, "");
+    *pp = nullptr;
+    BANK_PIPE_REQUIRE(b != nullptr, ": null bank");
+    BANK_PIPE_REQUIRE(block_size_out > 0, ": block_size_out > 0");
+    if (max_type == 1) BANK_PIPE_REQUIRE(input_type == 0 || input_type == 1, ": input_u8 is 0 (cfloat blocks) or 1 (u8 IQ blocks)");
+    BANK_PIPE_REQUIRE(input_type >= 0 && input_type <= 2, ": input_type is 0 (cfloat blocks), 1 (u8 IQ) or 2 (int16 IQ)");
+#undef BANK_PIPE_REQUIRE
+    const FirDesc* f = &b->ch[0]->fir;
+    const int K = (int)b->ch.size();
+    int rc = pipe_new(pp, kind, f, nullptr, block_size_out, true, form == BankForm::IQ, 1, f->factor, f->Lp, (InFmt)input_type);
+    if (rc != SDRHIP_OK) return rc;
+    sdrhip_pipe* p = *pp;
+    p->bank = b;
+    p->form = form;
+    p->iq_always = form == BankForm::ENV;      // (whether the fused launch takes a submission is left to the launcher)
+    p->am_dc = kind == PK_AM_BANK && nstate == 1;
+    if (K > 1) p->eng.set_rows(K);
+    DevBuf* state = kind == PK_NFM_BANK ? p->nfm_state : &p->dc_state;
+    for (int i = 0; i < nstate && rc == SDRHIP_OK; i++) rc = pipe_dev_state(pp, state[i], (size_t)K * 2 * sizeof(float), nullptr, who);
+    return rc;
+}
+
 int sdrhip_pipe_tuner_bank(sdrhip_pipe** pp, const sdrhip_tuner_bank* b, int block_size_out, int input_u8)
 {
-    // (all of it before pipe_new, whose engine creates streams: a refused create has done no device work)
-    SDRHIP_REQUIRE(pp != nullptr, "sdrhip_pipe_tuner_bank");
-    *pp = nullptr;
-    SDRHIP_REQUIRE(b != nullptr, "sdrhip_pipe_tuner_bank: null bank");
-    SDRHIP_REQUIRE(block_size_out > 0, "sdrhip_pipe_tuner_bank: block_size_out > 0");
-    SDRHIP_REQUIRE(input_u8 == 0 || input_u8 == 1, "sdrhip_pipe_tuner_bank: input_u8 is 0 (cfloat blocks) or 1 (u8 IQ blocks)");
-    const FirDesc* f = &b->ch[0]->fir;
-    int rc = pipe_new(pp, PK_TUNER_BANK, f, nullptr, block_size_out, true, true, 1, f->factor, f->Lp, input_u8 == 1 ? IN_U8 : IN_CF32);
-    if (rc != SDRHIP_OK) return rc;
-    (*pp)->bank = b;
-    if (b->ch.size() > 1) (*pp)->eng.set_rows((int)b->ch.size());
-    return SDRHIP_OK;
+    return bank_pipe_new(pp, "sdrhip_pipe_tuner_bank", b, block_size_out, input_u8, 1, PK_TUNER_BANK, BankForm::IQ, 0);
 }
 
 int sdrhip_pipe_tuner_bank_i16(sdrhip_pipe** pp, const sdrhip_tuner_bank* b, int block_size_out)
 {
-    // (all of it before pipe_new, as above)
-    SDRHIP_REQUIRE(pp != nullptr, "sdrhip_pipe_tuner_bank_i16");
-    *pp = nullptr;
-    SDRHIP_REQUIRE(b != nullptr, "sdrhip_pipe_tuner_bank_i16: null bank");
-    SDRHIP_REQUIRE(block_size_out > 0, "sdrhip_pipe_tuner_bank_i16: block_size_out > 0");
-    const FirDesc* f = &b->ch[0]->fir;
-    int rc = pipe_new(pp, PK_TUNER_BANK, f, nullptr, block_size_out, true, true, 1, f->factor, f->Lp, IN_I16);
-    if (rc != SDRHIP_OK) return rc;
-    (*pp)->bank = b;
-    if (b->ch.size() > 1) (*pp)->eng.set_rows((int)b->ch.size());
-    return SDRHIP_OK;
+    return bank_pipe_new(pp, "sdrhip_pipe_tuner_bank_i16", b, block_size_out, IN_I16, 2, PK_TUNER_BANK, BankForm::IQ, 0);
 }
 
 int sdrhip_pipe_am_bank(sdrhip_pipe** pp, const sdrhip_am_bank* a, int block_size_out, int input_type)
 {
-    // (all of it before pipe_new, whose engine creates streams: a refused create has done no device work)
-    SDRHIP_REQUIRE(pp != nullptr, "sdrhip_pipe_am_bank");
-    *pp = nullptr;
-    SDRHIP_REQUIRE(a != nullptr, "sdrhip_pipe_am_bank: null bank");
-    SDRHIP_REQUIRE(block_size_out > 0, "sdrhip_pipe_am_bank: block_size_out > 0");
-    SDRHIP_REQUIRE(input_type >= 0 && input_type <= 2, "sdrhip_pipe_am_bank: input_type is 0 (cfloat blocks), 1 (u8 IQ) or 2 (int16 IQ)");
-    const TunerBankDesc* b = a->tb;
-    const FirDesc* f = &b->ch[0]->fir;
-    const int K = (int)b->ch.size();
-    int rc = pipe_new(pp, PK_AM_BANK, f, nullptr, block_size_out, true, false, 1, f->factor, f->Lp, (InFmt)input_type);
-    if (rc != SDRHIP_OK) return rc;
-    sdrhip_pipe* p = *pp;
-    p->bank = b;
-    p->am_dc = a->dc_block != 0;
-    if (K > 1) p->eng.set_rows(K);
-    if (p->am_dc) {
-        const size_t bytes = (size_t)K * 2 * sizeof(float);
-        if ((rc = p->dc_state.ensure(bytes < 16 ? 16 : bytes)) != SDRHIP_OK) { delete p; *pp = nullptr; return rc; }
-        hipError_t e = hipMemsetAsync(p->dc_state.p, 0, bytes, p->eng.compute[0]);   // every channel: func 0 0, Filter.hs:731
-        if (e != hipSuccess) { set_error("sdrhip_pipe_am_bank: %s", hipGetErrorString(e)); delete p; *pp = nullptr; return SDRHIP_ERR_HIP; }
-    }
-    return SDRHIP_OK;
+    return bank_pipe_new(pp, "sdrhip_pipe_am_bank", a ? a->tb : nullptr, block_size_out, input_type, 2, PK_AM_BANK, BankForm::ENV,
+                         a && a->dc_block != 0 ? 1 : 0);
 }
 
 int sdrhip_pipe_nfm_bank(sdrhip_pipe** pp, const sdrhip_nfm_bank* a, int block_size_out, int input_type)
 {
-    // (all of it before pipe_new, whose engine creates streams: a refused create has done no device work)
-    SDRHIP_REQUIRE(pp != nullptr, "sdrhip_pipe_nfm_bank");
-    *pp = nullptr;
-    SDRHIP_REQUIRE(a != nullptr, "sdrhip_pipe_nfm_bank: null bank");
-    SDRHIP_REQUIRE(block_size_out > 0, "sdrhip_pipe_nfm_bank: block_size_out > 0");
-    SDRHIP_REQUIRE(input_type >= 0 && input_type <= 2, "sdrhip_pipe_nfm_bank: input_type is 0 (cfloat blocks), 1 (u8 IQ) or 2 (int16 IQ)");
-    const TunerBankDesc* b = a->tb;
-    const FirDesc* f = &b->ch[0]->fir;
-    const int K = (int)b->ch.size();
-    int rc = pipe_new(pp, PK_NFM_BANK, f, nullptr, block_size_out, true, false, 1, f->factor, f->Lp, (InFmt)input_type);
-    if (rc != SDRHIP_OK) return rc;
-    sdrhip_pipe* p = *pp;
-    p->bank = b;
-    if (K > 1) p->eng.set_rows(K);
-    const size_t bytes = (size_t)K * 2 * sizeof(float);
-    for (int i = 0; i < 2; i++) {
-        if ((rc = p->nfm_state[i].ensure(bytes < 16 ? 16 : bytes)) != SDRHIP_OK) { delete p; *pp = nullptr; return rc; }
-        hipError_t e = hipMemsetAsync(p->nfm_state[i].p, 0, bytes, p->eng.compute[0]);   // every channel starts from (0, 0), Demod.hs:41
-        if (e != hipSuccess) { set_error("sdrhip_pipe_nfm_bank: %s", hipGetErrorString(e)); delete p; *pp = nullptr; return SDRHIP_ERR_HIP; }
-    }
-    return SDRHIP_OK;
+    return bank_pipe_new(pp, "sdrhip_pipe_nfm_bank", a ? a->tb : nullptr, block_size_out, input_type, 2, PK_NFM_BANK, BankForm::PHASE, 2);
 }
 
 int sdrhip_pipe_rows(const sdrhip_pipe* p)
@@ -702,11 +664,7 @@ int sdrhip_pipe_dc_blocker(sdrhip_pipe** pp)
     SDRHIP_REQUIRE(pp != nullptr, "sdrhip_pipe_dc_blocker");
     int rc = pipe_new(pp, PK_DCBLOCK, nullptr, nullptr, 0, false, false, 1, 1, 1);
     if (rc != SDRHIP_OK) return rc;
-    sdrhip_pipe* p = *pp;
-    if ((rc = p->dc_state.ensure(16)) != SDRHIP_OK) { delete p; *pp = nullptr; return rc; }
-    hipError_t e = hipMemsetAsync(p->dc_state.p, 0, 16, p->eng.compute[0]);   // func 0 0, Filter.hs:732
-    if (e != hipSuccess) { set_error("sdrhip_pipe_dc_blocker: %s", hipGetErrorString(e)); delete p; *pp = nullptr; return SDRHIP_ERR_HIP; }
-    return SDRHIP_OK;
+    return pipe_dev_state(pp, (*pp)->dc_state, 16, nullptr, "sdrhip_pipe_dc_blocker");       // func 0 0, Filter.hs:732
 }
 
 int sdrhip_pipe_agc(sdrhip_pipe** pp, float mu, float reference)
@@ -714,14 +672,10 @@ int sdrhip_pipe_agc(sdrhip_pipe** pp, float mu, float reference)
     SDRHIP_REQUIRE(pp != nullptr, "sdrhip_pipe_agc");
     int rc = pipe_new(pp, PK_AGC, nullptr, nullptr, 0, true, true, 1, 1, 1);
     if (rc != SDRHIP_OK) return rc;
-    sdrhip_pipe* p = *pp;
-    p->agc_mu = mu;
-    p->agc_ref = reference;
-    if ((rc = p->dc_state.ensure(16)) != SDRHIP_OK) { delete p; *pp = nullptr; return rc; }
+    (*pp)->agc_mu = mu;
+    (*pp)->agc_ref = reference;
     const float init[4] = {1.0f, 0.0f, 0.0f, 0.0f};                           // pMapAccum (agc mu reference) 1, Util.hs:348
-    hipError_t e = hipMemcpy(p->dc_state.p, init, 16, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { set_error("sdrhip_pipe_agc: %s", hipGetErrorString(e)); delete p; *pp = nullptr; return SDRHIP_ERR_HIP; }
-    return SDRHIP_OK;
+    return pipe_dev_state(pp, (*pp)->dc_state, sizeof init, init, "sdrhip_pipe_agc");
 }
 
 // ---- map stages (fmDemod, amDemod, dcBlockingFilter, agcPipe): one output vector per input vector ------------------------------
@@ -749,14 +703,12 @@ static int map_submit(sdrhip_pipe* p)
         } else if (p->kind == PK_AM) {
             launch_am_demod_rows(s, 1, (const float*)d_in, 0, (float*)d_out, 0, n);
         } else if (p->kind == PK_AGC) {
-            if (agc_workspace_bytes(n) > p->dc_ws.cap) SDRHIP_CHECK_HIP(hipStreamSynchronize(s));            // growing frees the old buffer
-            int rc = p->dc_ws.ensure(agc_workspace_bytes(n));
+            int rc = grow(p->dc_ws, agc_workspace_bytes(n), s);
             if (rc != SDRHIP_OK) return rc;
             launch_agc(s, n, p->agc_mu, p->agc_ref, 1.0f, (const float*)d_in, (float*)d_out, (float*)p->dc_state.p, p->dc_ws.p, 0,
                        (const float*)p->dc_state.p);
         } else {
-            if (dc_blocker_workspace_bytes(n) > p->dc_ws.cap) SDRHIP_CHECK_HIP(hipStreamSynchronize(s));     // growing frees the old buffer
-            int rc = p->dc_ws.ensure(dc_blocker_workspace_bytes(n));
+            int rc = grow(p->dc_ws, dc_blocker_workspace_bytes(n), s);
             if (rc != SDRHIP_OK) return rc;
             launch_dc_blocker(s, n, 0.0f, 0.0f, (const float*)d_in, (float*)d_out, (float*)p->dc_state.p, p->dc_ws.p, 0,
                               (const float*)p->dc_state.p);
@@ -948,11 +900,19 @@ struct PipeStateAm {
     int32_t dc_block, n_floats;
 };
 // The narrow-band FM bank's Pipe appends the same record: dc_block = 0, n_floats = 2 K, and every channel's last decimated (re, im).
-static size_t pipe_state_am_bytes(const sdrhip_pipe* p)
+struct PipeAmRecord {
+    bool present;
+    PipeStateAm x;
+    void* d_floats;       // where the floats live on the device
+    size_t bytes() const { return present ? sizeof x + (size_t)x.n_floats * sizeof(float) : 0; }
+};
+static PipeAmRecord pipe_state_am(const sdrhip_pipe* p)
 {
-    if (p->kind == PK_NFM_BANK) return sizeof(PipeStateAm) + (size_t)p->rows() * 2 * sizeof(float);
-    return p->kind != PK_AM_BANK ? 0 : sizeof(PipeStateAm) + (p->am_dc ? (size_t)p->rows() * 2 * sizeof(float) : 0);
+    if (p->kind == PK_NFM_BANK) return {true, {0, 2 * p->rows()}, p->nfm_state[p->nfm_cur].p};
+    if (p->kind == PK_AM_BANK) return {true, {p->am_dc ? 1 : 0, p->am_dc ? 2 * p->rows() : 0}, p->dc_state.p};
+    return {false, {0, 0}, nullptr};
 }
+static size_t pipe_state_am_bytes(const sdrhip_pipe* p) { return pipe_state_am(p).bytes(); }
 static size_t pipe_state_header_bytes(const sdrhip_pipe* p) { return sizeof(PipeStateHeader) + (pipe_state_version(p) == 2 ? sizeof(PipeStateRows) : 0); }
 // Version 3: the waterfall Pipe.  This header, the carried tail (tail_n samples in the input's own type), the rows not yet popped
 // (pending floats).  pos = samples pushed so far; the tail starts at stream sample rows_done * group * hop = pos - tail_n (skip == 0)
@@ -1033,23 +993,16 @@ int sdrhip_pipe_save(sdrhip_pipe* p, void* buf, size_t capacity, size_t* used)
     }
     unsigned char* o = p->eng.save((unsigned char*)buf + pipe_state_header_bytes(p));
     for (int len : p->demod_blocks) { const int32_t v = len; memcpy(o, &v, sizeof v); o += sizeof v; }
-    if (p->kind == PK_AM_BANK) {
-        // the flush above has harvested every submission, so the dcBlocker floats on the device are the stream's (as the dcBlocker Pipe's save)
-        const PipeStateAm x = {p->am_dc ? 1 : 0, p->am_dc ? 2 * p->rows() : 0};
-        memcpy(o, &x, sizeof x);
-        o += sizeof x;
-        if (p->am_dc) {
+    const PipeAmRecord am = pipe_state_am(p);
+    if (am.present) {
+        // the flush above has harvested every submission, so the floats on the device -- dcBlocker's pairs (as the dcBlocker Pipe's
+        // save), or the array the last fmDemod-form launch wrote -- are the stream's
+        memcpy(o, &am.x, sizeof am.x);
+        o += sizeof am.x;
+        if (am.x.n_floats > 0) {
             SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));
-            SDRHIP_CHECK_HIP(hipMemcpy(o, p->dc_state.p, (size_t)x.n_floats * sizeof(float), hipMemcpyDeviceToHost));
+            SDRHIP_CHECK_HIP(hipMemcpy(o, am.d_floats, (size_t)am.x.n_floats * sizeof(float), hipMemcpyDeviceToHost));
         }
-    }
-    if (p->kind == PK_NFM_BANK) {
-        // (the flush above has harvested every submission: the array the last launch wrote is the stream's state)
-        const PipeStateAm x = {0, 2 * p->rows()};
-        memcpy(o, &x, sizeof x);
-        o += sizeof x;
-        SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));
-        SDRHIP_CHECK_HIP(hipMemcpy(o, p->nfm_state[p->nfm_cur].p, (size_t)x.n_floats * sizeof(float), hipMemcpyDeviceToHost));
     }
     *used = need;
     return SDRHIP_OK;
@@ -1114,17 +1067,14 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
                        "sdrhip_pipe_restore: the position and the history of the state do not belong together");
     }
     const size_t am_at = pipe_state_header_bytes(p) + p->eng.state_bytes(h.hist_n, h.pending) + (size_t)h.n_blocks * sizeof(int32_t);
-    SDRHIP_REQUIRE(bytes >= am_at + pipe_state_am_bytes(p), "sdrhip_pipe_restore: truncated state");
-    if (p->kind == PK_AM_BANK) {
+    const PipeAmRecord am = pipe_state_am(p);
+    SDRHIP_REQUIRE(bytes >= am_at + am.bytes(), "sdrhip_pipe_restore: truncated state");
+    if (am.present) {
         PipeStateAm x;
         memcpy(&x, (const unsigned char*)buf + am_at, sizeof x);
-        SDRHIP_REQUIRE(x.dc_block == (p->am_dc ? 1 : 0) && x.n_floats == (p->am_dc ? 2 * p->rows() : 0),
-                       "sdrhip_pipe_restore: the state belongs to an AM bank pipe of another dc_block");
-    }
-    if (p->kind == PK_NFM_BANK) {
-        PipeStateAm x;
-        memcpy(&x, (const unsigned char*)buf + am_at, sizeof x);
-        SDRHIP_REQUIRE(x.dc_block == 0 && x.n_floats == 2 * p->rows(), "sdrhip_pipe_restore: the state belongs to a pipe of another row count");
+        SDRHIP_REQUIRE(x.dc_block == am.x.dc_block && x.n_floats == am.x.n_floats,
+                       p->kind == PK_AM_BANK ? "sdrhip_pipe_restore: the state belongs to an AM bank pipe of another dc_block"
+                                             : "sdrhip_pipe_restore: the state belongs to a pipe of another row count");
     }
     const unsigned char* in = p->eng.restore((const unsigned char*)buf + pipe_state_header_bytes(p), h.hist_n, h.pending);
     p->E_prev = h.E_prev;
@@ -1135,13 +1085,9 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
     p->last_im = h.last_im;
     p->demod_blocks.clear();
     for (int i = 0; i < h.n_blocks; i++) { int32_t v; memcpy(&v, in, sizeof v); in += sizeof v; p->demod_blocks.push_back(v); }
-    if (p->kind == PK_AM_BANK && p->am_dc) {
-        SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));       // the create call's memset
-        SDRHIP_CHECK_HIP(hipMemcpy(p->dc_state.p, in + sizeof(PipeStateAm), (size_t)p->rows() * 2 * sizeof(float), hipMemcpyHostToDevice));
-    }
-    if (p->kind == PK_NFM_BANK) {
+    if (am.x.n_floats > 0) {
         SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));       // the create call's memsets
-        SDRHIP_CHECK_HIP(hipMemcpy(p->nfm_state[p->nfm_cur].p, in + sizeof(PipeStateAm), (size_t)p->rows() * 2 * sizeof(float), hipMemcpyHostToDevice));
+        SDRHIP_CHECK_HIP(hipMemcpy(am.d_floats, in + sizeof(PipeStateAm), (size_t)am.x.n_floats * sizeof(float), hipMemcpyHostToDevice));
     }
     if (p->has_dev_state()) {
         SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));       // the create call's memset

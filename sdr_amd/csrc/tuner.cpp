@@ -121,14 +121,7 @@ int tuner_run(const TunerDesc* t, hipStream_t s, const void* d_in, InFmt fmt, in
     SDRHIP_REQUIRE(fmt != IN_I16 || (reinterpret_cast<uintptr_t>(d_in) & 3) == 0, "tuner_run: int16 IQ at an address that is no multiple of 4");
     int rc = t->ensure_device();
     if (rc != SDRHIP_OK) return rc;
-    Geom g;
-    g.in_base = in_base;
-    g.k_begin = k_begin;
-    g.count = (int)(k_end - k_begin);
-    g.I = 1;
-    g.D = d->factor;
-    g.Lp = d->Lp;
-    g.seamBI = seam_block;
+    const Geom g = bank_geom(d, in_base, k_begin, k_end, seam_block);      // (a tuner is one channel of a bank)
     const int route = t->route;
     if (route != 2) {
         const bool fused = d->corder == CO_L4 && launch_tuner_fused(s, g, d->d_plain, d->Lp, d->d_cross, d_in, fmt, d_out, t->d_osc, t->period);

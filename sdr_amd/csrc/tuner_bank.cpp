@@ -71,29 +71,17 @@ int tuner_bank_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, InFm
     SDRHIP_REQUIRE(d_in != nullptr && d_out != nullptr, "sdrhip_tuner_bank_run");
     SDRHIP_REQUIRE(fmt != IN_I16 || (reinterpret_cast<uintptr_t>(d_in) & 3) == 0,
                    "sdrhip_tuner_bank_run: int16 IQ at an address that is no multiple of 4");
-    Geom g;
-    g.in_base = in_base;
-    g.k_begin = k_begin;
-    g.count = (int)(k_end - k_begin);
-    g.I = 1;
-    g.D = d->factor;
-    g.Lp = d->Lp;
-    g.seamBI = seam_block;
+    const Geom g = bank_geom(d, in_base, k_begin, k_end, seam_block);
     const int route = b->route;
-    // the Cross taps are the prepared plain taps, on the device once the descriptor is (FirDesc::ensure_device)
-    const bool fits = d->corder == CO_L4 && tuner_fused_fits(g, d->Lp, true, d_in, fmt, d_out, 1);
+    const bool fits = bank_fused_fits(b, g, d_in, fmt, BankForm{}, d_out);
     if (route == 1 && !fits) {
         set_error("sdrhip_tuner_bank_run: the banked launch serves the AVX order, factors 4 / 8 / 16, up to 128 prepared taps, seam_block >= 0 "
                   "and a 16-byte aligned first window; this launch is none of that (route 0 or 2 runs it)");
         return SDRHIP_ERR_ARG;
     }
     if (fits && (route == 1 || (route == 0 && bank_auto(K, (int64_t)g.count * g.D)))) {
-        int rc = b->ensure_device();
-        if (rc != SDRHIP_OK) return rc;
-        if (launch_tuner_bank(s, g, d->d_plain, d->Lp, d->d_cross, d_in, fmt, d_out, out_stride, b->d_tables, K, b->off, b->period, true)) {
-            SDRHIP_CHECK_HIP(hipGetLastError());
-            return SDRHIP_OK;
-        }
+        int rc = bank_fused(b, s, g, d_in, fmt, BankForm{}, d_out, out_stride);
+        if (rc != kBankNotThisShape) return rc;
         if (route == 1) {
             set_error("sdrhip_tuner_bank_run: the banked launch refused a launch its predicate admitted");
             return SDRHIP_ERR_ARG;
@@ -106,18 +94,16 @@ int tuner_bank_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, InFm
     return SDRHIP_OK;
 }
 
-// Outputs [k_begin, k_end) of every channel, all Cross, in ONE launch (kernels_tuner_bank.hip: k_tuner_bank_cross): what
-// tuner_bank_run(..., seam_block = -1) computes channel by channel, for the bank's Pipe (pipes.cpp) and nobody else -- the routes and
-// the auto rule of sdrhip_tuner_bank_run are not involved.
-int tuner_bank_cross_run(const TunerBankDesc* b, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out,
-                         int64_t out_stride, int64_t k_begin, int64_t k_end)
+// ---- the output forms (descriptors.hpp: BankForm) -----------------------------------------------------------------------------------
+bool BankForm::state_overlaps(int channels) const
 {
-    SDRHIP_REQUIRE(b != nullptr && d_in != nullptr && d_out != nullptr, "tuner_bank_cross_run");
-    const FirDesc* d = &b->ch[0]->fir;
-    SDRHIP_REQUIRE(k_begin >= 0 && k_end > k_begin && k_end - k_begin < (int64_t)0x7fffffff, "tuner_bank_cross_run");
-    SDRHIP_REQUIRE(k_begin * d->factor >= in_base, "tuner_bank_cross_run: first window starts before d_in");
-    int rc = b->ensure_device();
-    if (rc != SDRHIP_OK) return rc;
+    if (kind != PHASE || d_state == nullptr || d_final == nullptr) return false;
+    const uintptr_t x = reinterpret_cast<uintptr_t>(d_state), y = reinterpret_cast<uintptr_t>(d_final), n = (uintptr_t)channels * 2 * sizeof(float);
+    return x < y + n && y < x + n;
+}
+
+Geom bank_geom(const FirDesc* d, int64_t in_base, int64_t k_begin, int64_t k_end, int64_t seam_block)
+{
     Geom g;
     g.in_base = in_base;
     g.k_begin = k_begin;
@@ -125,13 +111,99 @@ int tuner_bank_cross_run(const TunerBankDesc* b, hipStream_t s, const void* d_in
     g.I = 1;
     g.D = d->factor;
     g.Lp = d->Lp;
-    g.seamBI = -1;
-    if (!launch_tuner_bank_cross(s, g, d->d_cross, d_in, fmt, d_out, out_stride, b->d_tables, (int)b->ch.size(), b->off, b->period)) {
-        set_error("tuner_bank_cross_run: the all-Cross launch refused its channels, stride or pointers");
+    g.seamBI = seam_block;
+    return g;
+}
+
+// Where the banked launch fits: the tuner's fused route (the Cross taps are the prepared plain taps, on the device once the descriptor
+// is), the alignment of complex rows for the form that has them, and for the phase form an in-tile seam test that works in 32 bits.
+// The bank objects, the Pipes and bank_fused all ask here.  launch_bank<OUT> (kernels_tuner_bank.hip) additionally refuses channel
+// counts and periods that the create calls exclude, and strides and float-row addresses that every caller has checked or made itself.
+bool bank_fused_fits(const TunerBankDesc* tb, const Geom& g, const void* d_in, InFmt fmt, const BankForm& form, const float* d_out)
+{
+    const FirDesc* d = &tb->ch[0]->fir;
+    if (form.kind == BankForm::PHASE && g.seamBI >= ((int64_t)1 << 30)) return false;
+    return d->corder == CO_L4 && tuner_fused_fits(g, d->Lp, true, d_in, fmt, form.kind == BankForm::IQ ? d_out : nullptr, 1);
+}
+
+int bank_fused(const TunerBankDesc* tb, hipStream_t s, const Geom& g, const void* d_in, InFmt fmt, const BankForm& form, float* d_out,
+               int64_t out_stride)
+{
+    int rc = tb->ensure_device();
+    if (rc != SDRHIP_OK) return rc;
+    const FirDesc* d = &tb->ch[0]->fir;
+    const int K = (int)tb->ch.size();
+    bool launched;
+    switch (form.kind) {
+    case BankForm::IQ:
+        launched = launch_tuner_bank(s, g, d->d_plain, d->Lp, d->d_cross, d_in, fmt, d_out, out_stride, tb->d_tables, K, tb->off, tb->period, true);
+        break;
+    case BankForm::ENV:
+        launched = launch_am_bank(s, g, d->d_plain, d->Lp, d->d_cross, d_in, fmt, d_out, out_stride, tb->d_tables, K, tb->off, tb->period);
+        break;
+    default:
+        launched = launch_nfm_bank(s, g, d->d_plain, d->Lp, d->d_cross, d_in, fmt, d_out, out_stride, tb->d_tables, K, tb->off, tb->period,
+                                   form.d_state, form.d_final);
+    }
+    if (!launched) return kBankNotThisShape;
+    SDRHIP_CHECK_HIP(hipGetLastError());
+    return SDRHIP_OK;
+}
+
+int bank_composed(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out, int64_t out_stride,
+                  int64_t k_begin, int64_t k_end, int64_t seam_block, const BankForm& form, float* d_iq)
+{
+    const int K = (int)tb->ch.size();
+    const int64_t np = row_floats(k_end - k_begin);
+    // (tuner_bank_run is what sdrhip_tuner_bank_run / _run_u8 / _run_i16 call with their input type)
+    int rc = tuner_bank_run(tb, s, d_in, fmt, in_base, d_iq, 2 * np, k_begin, k_end, seam_block);
+    if (rc != SDRHIP_OK) return rc;
+    if (form.kind == BankForm::ENV) return sdrhip_am_demod_run_rows(s, d_iq, 2 * np, d_out, out_stride, K, k_end - k_begin);
+    return sdrhip_fm_demod_run_rows(s, d_iq, 2 * np, k_begin, d_out, out_stride, K, k_begin, k_end, form.d_state, form.d_final);
+}
+
+// Outputs [k_begin, k_end) of every channel, all Cross, in ONE launch (kernels_tuner_bank.hip: k_tuner_bank_cross): what
+// tuner_bank_run(..., seam_block = -1) computes channel by channel, for the banks' Pipes (pipes.cpp) and nobody else -- the routes and
+// the auto rules of the bank objects are not involved.
+int bank_cross(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out, int64_t out_stride,
+               int64_t k_begin, int64_t k_end, const BankForm& form)
+{
+    SDRHIP_REQUIRE(tb != nullptr && d_in != nullptr && d_out != nullptr, "bank_cross");
+    const FirDesc* d = &tb->ch[0]->fir;
+    const int K = (int)tb->ch.size();
+    SDRHIP_REQUIRE(k_begin >= 0 && k_end > k_begin && k_end - k_begin < (int64_t)0x7fffffff, "bank_cross");
+    SDRHIP_REQUIRE(k_begin * d->factor >= in_base, "bank_cross: first window starts before d_in");
+    SDRHIP_REQUIRE(!form.state_overlaps(K), "bank_cross: d_state and d_final overlap");
+    int rc = tb->ensure_device();
+    if (rc != SDRHIP_OK) return rc;
+    const Geom g = bank_geom(d, in_base, k_begin, k_end, -1);
+    bool launched;
+    switch (form.kind) {
+    case BankForm::IQ: launched = launch_tuner_bank_cross(s, g, d->d_cross, d_in, fmt, d_out, out_stride, tb->d_tables, K, tb->off, tb->period); break;
+    case BankForm::ENV: launched = launch_am_bank_cross(s, g, d->d_cross, d_in, fmt, d_out, out_stride, tb->d_tables, K, tb->off, tb->period); break;
+    default:
+        launched = launch_nfm_bank_cross(s, g, d->d_cross, d_in, fmt, d_out, out_stride, tb->d_tables, K, tb->off, tb->period, form.d_state,
+                                         form.d_final);
+    }
+    if (!launched) {
+        set_error("bank_cross: the all-Cross launch refused its channels, stride or pointers");
         return SDRHIP_ERR_ARG;
     }
     SDRHIP_CHECK_HIP(hipGetLastError());
     return SDRHIP_OK;
+}
+
+int bank_form_run(const TunerBankDesc* tb, hipStream_t s, const void* d_in, InFmt fmt, int64_t in_base, float* d_out, int64_t out_stride,
+                  int64_t k_begin, int64_t k_end, int64_t seam_block, const BankForm& form, float* d_iq)
+{
+    SDRHIP_REQUIRE(form.kind != BankForm::IQ && k_begin >= 0 && k_end > k_begin && !form.state_overlaps((int)tb->ch.size()), "bank_form_run");
+    const Geom g = bank_geom(&tb->ch[0]->fir, in_base, k_begin, k_end, seam_block);
+    if (bank_fused_fits(tb, g, d_in, fmt, form, d_out)) {
+        int rc = bank_fused(tb, s, g, d_in, fmt, form, d_out, out_stride);
+        if (rc != kBankNotThisShape) return rc;
+    }
+    SDRHIP_REQUIRE(d_iq != nullptr, "bank_form_run: no scratch for the composed route");
+    return bank_composed(tb, s, d_in, fmt, in_base, d_out, out_stride, k_begin, k_end, seam_block, form, d_iq);
 }
 
 }  // namespace sdrhip
