@@ -1,6 +1,7 @@
 /* airband_replay.c -- the AM receiver for every channel of one u8 or int16 IQ capture, through nothing but the C ABI.
  *
  *     airband_replay CAPTURE TAPS.f32 OUT_PREFIX --channels NUM/DEN[,NUM/DEN...] [--no-dc] [--factor D] [--block-out N] [--push SAMPLES] [--s16]
+ *                    [--audio RESAMP_TAPS.f32 AUDIO_HALF_TAPS.f32 [--ratio I/D] [--gain G]]
  *
  * CAPTURE: interleaved unsigned 8-bit (I, Q) pairs (an RTL-SDR dump); with --s16 interleaved signed 16-bit pairs in host byte order (a
  * BladeRF dump).  TAPS.f32: the decimator's coefficients, raw float32.  Channel j is the capture shifted by NUM/DEN cycles per sample
@@ -8,6 +9,9 @@
  * --no-dc is given, put through dcBlocker; its audio goes to OUT_PREFIX.chJ.f32 as float32, whole blocks of N (default 1024) only, as
  * the Pipe yields them.  The capture is pushed SAMPLES (default 8192) at a time, the rest in one shorter push.  ONE Pipe for all
  * channels (sdrhip_pipe_am_bank over sdrhip_am_bank over sdrhip_tuner_bank): one copy over the link per push, K float rows back.
+ * With --audio the files hold the receiver's AUDIO instead: that signal resampled by I/D (default 3/10) with the taps of
+ * RESAMP_TAPS.f32, filtered with the symmetric filter whose first half is AUDIO_HALF_TAPS.f32 and multiplied by G (default 1), every
+ * Pipe of those stages with blocks of N -- sdrhip_pipe_am_bank_audio over an sdrhip_audio_tail, still ONE Pipe.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -59,7 +63,9 @@ static void drain(sdrhip_pipe *p, int ready, int channels, int block_out, float 
 int main(int argc, char **argv)
 {
     const char *spec = NULL;
-    int factor = 8, block_out = 1024, push = 8192, s16 = 0, dc = 1;
+    const char *resamp_path = NULL, *audio_path = NULL;
+    int factor = 8, block_out = 1024, push = 8192, s16 = 0, dc = 1, interp = 3, decim = 10;
+    float gain = 1.0f;
     if (argc < 4) {
         fprintf(stderr, "usage: %s CAPTURE.u8 TAPS.f32 OUT_PREFIX --channels NUM/DEN[,...] [--no-dc] [--factor D] [--block-out N] [--push SAMPLES] [--s16]\n", argv[0]);
         return 2;
@@ -67,11 +73,22 @@ int main(int argc, char **argv)
     for (int i = 4; i < argc; i += 2) {
         if (!strcmp(argv[i], "--s16")) { s16 = 1; i--; continue; }
         if (!strcmp(argv[i], "--no-dc")) { dc = 0; i--; continue; }
+        if (!strcmp(argv[i], "--audio")) {
+            if (i + 2 >= argc) { fprintf(stderr, "airband_replay: --audio needs RESAMP_TAPS.f32 AUDIO_HALF_TAPS.f32\n"); return 2; }
+            resamp_path = argv[i + 1];
+            audio_path = argv[i + 2];
+            i++;
+            continue;
+        }
         if (i + 1 >= argc) { fprintf(stderr, "airband_replay: %s needs a value\n", argv[i]); return 2; }
         if (!strcmp(argv[i], "--channels")) spec = argv[i + 1];
         else if (!strcmp(argv[i], "--factor")) factor = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--block-out")) block_out = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--push")) push = atoi(argv[i + 1]);
+        else if (!strcmp(argv[i], "--gain")) gain = (float)atof(argv[i + 1]);
+        else if (!strcmp(argv[i], "--ratio")) {
+            if (sscanf(argv[i + 1], "%d/%d", &interp, &decim) != 2) { fprintf(stderr, "airband_replay: --ratio I/D\n"); return 2; }
+        }
         else { fprintf(stderr, "airband_replay: unknown option %s\n", argv[i]); return 2; }
     }
     if (!spec || factor < 1 || block_out < 1 || push < 1) { fprintf(stderr, "airband_replay: --channels NUM/DEN[,...] is required\n"); return 2; }
@@ -102,7 +119,16 @@ int main(int argc, char **argv)
     sdrhip_am_bank *am = NULL;
     if (sdrhip_am_bank_create(&am, bank, dc) != SDRHIP_OK) die("sdrhip_am_bank_create");
     sdrhip_pipe *pipe = NULL;
-    if (sdrhip_pipe_am_bank(&pipe, am, block_out, s16 ? 2 : 1) != SDRHIP_OK) die("sdrhip_pipe_am_bank");
+    sdrhip_audio_tail *tail = NULL;
+    if (resamp_path) {
+        int nr = 0, na = 0;
+        float *rt = read_floats(resamp_path, &nr), *ah = read_floats(audio_path, &na);
+        if (sdrhip_audio_tail_create(&tail, 2 /* the AVX order */, interp, decim, rt, nr, ah, na, gain, block_out) != SDRHIP_OK)
+            die("sdrhip_audio_tail_create");
+        free(rt);
+        free(ah);
+        if (sdrhip_pipe_am_bank_audio(&pipe, am, tail, s16 ? 2 : 1) != SDRHIP_OK) die("sdrhip_pipe_am_bank_audio");
+    } else if (sdrhip_pipe_am_bank(&pipe, am, block_out, s16 ? 2 : 1) != SDRHIP_OK) die("sdrhip_pipe_am_bank");
 
     FILE *cap = fopen(argv[1], "rb");
     if (!cap) { perror(argv[1]); return 1; }
@@ -140,6 +166,7 @@ int main(int argc, char **argv)
     free(rows);
     free(taps);
     sdrhip_pipe_destroy(pipe);
+    sdrhip_audio_tail_destroy(tail);
     sdrhip_am_bank_destroy(am);
     sdrhip_tuner_bank_destroy(bank);
     return 0;

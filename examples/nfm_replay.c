@@ -1,6 +1,7 @@
 /* nfm_replay.c -- the narrow-band FM demodulator for every channel of one u8 or int16 IQ capture, through nothing but the C ABI.
  *
  *     nfm_replay CAPTURE TAPS.f32 OUT_PREFIX --channels NUM/DEN[,NUM/DEN...] [--factor D] [--block-out N] [--push SAMPLES] [--s16]
+ *                [--audio RESAMP_TAPS.f32 AUDIO_HALF_TAPS.f32 [--ratio I/D] [--gain G]]
  *
  * CAPTURE: interleaved unsigned 8-bit (I, Q) pairs (an RTL-SDR dump); with --s16 interleaved signed 16-bit pairs in host byte order (a
  * BladeRF dump).  TAPS.f32: the decimator's coefficients, raw float32.  Channel j is the capture shifted by NUM/DEN cycles per sample
@@ -9,6 +10,10 @@
  * capture is pushed SAMPLES (default 8192) at a time, the rest in one shorter push.  ONE Pipe for all channels (sdrhip_pipe_nfm_bank
  * over sdrhip_nfm_bank over sdrhip_tuner_bank): one copy over the link per push, K float rows back.  What follows the demodulator
  * in a receiver (a second decimator, de-emphasis, squelch) is the caller's.
+ * With --audio the files hold AUDIO instead: the demodulated samples resampled by I/D (default 3/10: 160 ksample/s to 48 k) with the
+ * taps of RESAMP_TAPS.f32, filtered with the symmetric filter whose first half is AUDIO_HALF_TAPS.f32 and multiplied by G (default
+ * 1), every Pipe of those stages with blocks of N -- sdrhip_pipe_nfm_bank_audio over an sdrhip_audio_tail, still ONE Pipe, one copy
+ * over the link per push and K audio rows back.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -60,18 +65,31 @@ static void drain(sdrhip_pipe *p, int ready, int channels, int block_out, float 
 int main(int argc, char **argv)
 {
     const char *spec = NULL;
-    int factor = 8, block_out = 1024, push = 8192, s16 = 0;
+    const char *resamp_path = NULL, *audio_path = NULL;
+    int factor = 8, block_out = 1024, push = 8192, s16 = 0, interp = 3, decim = 10;
+    float gain = 1.0f;
     if (argc < 4) {
         fprintf(stderr, "usage: %s CAPTURE.u8 TAPS.f32 OUT_PREFIX --channels NUM/DEN[,...] [--factor D] [--block-out N] [--push SAMPLES] [--s16]\n", argv[0]);
         return 2;
     }
     for (int i = 4; i < argc; i += 2) {
         if (!strcmp(argv[i], "--s16")) { s16 = 1; i--; continue; }
+        if (!strcmp(argv[i], "--audio")) {
+            if (i + 2 >= argc) { fprintf(stderr, "nfm_replay: --audio needs RESAMP_TAPS.f32 AUDIO_HALF_TAPS.f32\n"); return 2; }
+            resamp_path = argv[i + 1];
+            audio_path = argv[i + 2];
+            i++;
+            continue;
+        }
         if (i + 1 >= argc) { fprintf(stderr, "nfm_replay: %s needs a value\n", argv[i]); return 2; }
         if (!strcmp(argv[i], "--channels")) spec = argv[i + 1];
         else if (!strcmp(argv[i], "--factor")) factor = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--block-out")) block_out = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--push")) push = atoi(argv[i + 1]);
+        else if (!strcmp(argv[i], "--gain")) gain = (float)atof(argv[i + 1]);
+        else if (!strcmp(argv[i], "--ratio")) {
+            if (sscanf(argv[i + 1], "%d/%d", &interp, &decim) != 2) { fprintf(stderr, "nfm_replay: --ratio I/D\n"); return 2; }
+        }
         else { fprintf(stderr, "nfm_replay: unknown option %s\n", argv[i]); return 2; }
     }
     if (!spec || factor < 1 || block_out < 1 || push < 1) { fprintf(stderr, "nfm_replay: --channels NUM/DEN[,...] is required\n"); return 2; }
@@ -102,7 +120,16 @@ int main(int argc, char **argv)
     sdrhip_nfm_bank *nfm = NULL;
     if (sdrhip_nfm_bank_create(&nfm, bank) != SDRHIP_OK) die("sdrhip_nfm_bank_create");
     sdrhip_pipe *pipe = NULL;
-    if (sdrhip_pipe_nfm_bank(&pipe, nfm, block_out, s16 ? 2 : 1) != SDRHIP_OK) die("sdrhip_pipe_nfm_bank");
+    sdrhip_audio_tail *tail = NULL;
+    if (resamp_path) {
+        int nr = 0, na = 0;
+        float *rt = read_floats(resamp_path, &nr), *ah = read_floats(audio_path, &na);
+        if (sdrhip_audio_tail_create(&tail, 2 /* the AVX order */, interp, decim, rt, nr, ah, na, gain, block_out) != SDRHIP_OK)
+            die("sdrhip_audio_tail_create");
+        free(rt);
+        free(ah);
+        if (sdrhip_pipe_nfm_bank_audio(&pipe, nfm, tail, s16 ? 2 : 1) != SDRHIP_OK) die("sdrhip_pipe_nfm_bank_audio");
+    } else if (sdrhip_pipe_nfm_bank(&pipe, nfm, block_out, s16 ? 2 : 1) != SDRHIP_OK) die("sdrhip_pipe_nfm_bank");
 
     FILE *cap = fopen(argv[1], "rb");
     if (!cap) { perror(argv[1]); return 1; }
@@ -140,6 +167,7 @@ int main(int argc, char **argv)
     free(rows);
     free(taps);
     sdrhip_pipe_destroy(pipe);
+    sdrhip_audio_tail_destroy(tail);
     sdrhip_nfm_bank_destroy(nfm);
     sdrhip_tuner_bank_destroy(bank);
     return 0;

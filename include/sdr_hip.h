@@ -727,6 +727,66 @@ int sdrhip_debug_fir_rows_plan(const void *desc, int kind, int rows, int64_t k_b
 long long sdrhip_debug_fir_rows_launches(void);   /* banked tile launches, process-wide; fix-up launches not counted */
 long long sdrhip_debug_fir_rows_fixups(void);     /* banked fix-up launches, process-wide */
 
+/* ---- audio tail: the audio stages behind the AM and narrow-band FM banks, over rows ---- */
+/* Every row of real demodulated samples y (the AM bank's envelope, the narrow-band FM bank's phase, 150 .. 300 ksample/s) through
+ *     firResampler(block)  >->  firFilter(block)  >->  (* gain)
+ * to audio.  The create arguments mean what they mean to sdrhip_fm_chain_create; `block` is the one block size of every Pipe of
+ * the tail (0 = contiguous).  The tail owns a real sdrhip_resampler and a symmetric real sdrhip_filter of these arguments and
+ * refuses what those two creates refuse, and a block shorter than a stage's filter.
+ * Plan functions (host arithmetic, no device): _ready(n_y) = the audio outputs whose whole receptive field lies in y[0, n_y);
+ * _first_input(q) = the first y index audio output q reads; _max_halo = the longest receptive field of any output, in y samples;
+ * _workspace_bytes(rows, n_y) = what routes 0 and 2 ask for with n_y readable elements per row (0 on bad arguments);
+ * _block = the block it was created with; _fused_fits = 1 where route 1 serves this tail, else 0.  The arithmetic is the FM
+ * chain's (sdrhip_fm_chain_ready / _max_halo) without its decimator and fmDemod.
+ * sdrhip_audio_tail_run_rows: row r's d_y[0] is ITS stream element y_base and n_y elements are readable; audio outputs [q0, q1) of
+ * row r go to d_audio + r * audio_stride.  Asynchronous on `stream`; after the first run no allocation, no host synchronisation
+ * and no host-to-device copy.  Floats of d_audio outside the rows' outputs are not touched.
+ * Routes (same bits).  2 = composed, the DEFINITION: sdrhip_resampler_run_rows(seam_block = block, out_block = block) for
+ * z outputs [q0, q1 + numCoeffsF - 1), then sdrhip_filter_run_rows(seam_block = block), then sdrhip_scale_run(gain), the z and
+ * filter rows in d_workspace -- the row forms on their banked route wherever it serves the shape, else row by row (not on their
+ * auto route: the same launch sets whatever the rows and the length, and their auto rule was read from other shapes).  Nothing new
+ * is argued about bits.  1 = fused: ONE launch of k_audio_tail_rows and nothing else, no workspace (a null one is accepted); it
+ * serves the FM chain's tail -- ratio 3/10 with 64-float polyphase groups, 64 half-taps, the AVX order -- with block 0 or a block
+ * of at least a tile (7314 outputs for 192 prepared resampler taps) and at most 2^28.  0 = auto: the rule below.
+ * SDRHIP_ERR_ARG, before any device work and with nothing written: a null handle, rows outside 1 .. SDRHIP_ROWS_MAX, a route
+ * outside 0 .. 2, a negative index, and with a non-empty range a receptive field that does not lie in [y_base, y_base + n_y), a
+ * null d_y or d_audio, d_y == d_audio, with rows > 1 an audio_stride < q1 - q0 or a y_stride < n_y, on routes 0 and 2 a null
+ * workspace or one shorter than _workspace_bytes(rows, n_y), route 1 on a tail it does not serve.  An empty range is SDRHIP_OK
+ * and touches nothing.
+ * Auto rule.  Auto takes route 1 exactly where it fits AND the run lies at points of the measured sweep where route 1's slowest
+ * round was below route 2's fastest (tools/audio_tail_bench.py, profiles/audio_tail_bench.txt: 1 / 2 / 8 / 32 rows x 153 / 2458 /
+ * 39322 / 314574 audio outputs per row, block 0 and 8192, the two routes alternating in one process, 7 rounds), in each of three
+ * row layouts, which the rule tells apart by the strides: BACK TO BACK (one row, or y_stride == n_y and audio_stride == q1 - q0);
+ * Y STRIDED (y_stride != n_y, audio rows back to back -- the audio Pipes' runs: padded y rows behind a carried history; measured
+ * with an odd stride and the first row 4 bytes past a 16-byte boundary, so that rows meet the 4-, 8- and 16-byte loaders); AUDIO
+ * STRIDED (audio_stride != q1 - q0, where route 2 scales row by row; measured with both sides strided).
+ * Route 1 was ahead at all 96 points -- fused / composed, medians: back to back 0.46 .. 0.71 (one row of 153 outputs 6.3 against
+ * 13.9 us; 32 rows of 314574 outputs 83 against 180 us with block 0, 115 against 208 us with block 8192), y strided 0.47 .. 0.78
+ * (32 rows of 153 outputs 8.1 against 10.7 us, of 314574 outputs 122 against 209 us, block 8192), audio strided 0.07 .. 0.69 (32
+ * rows of 2458 outputs 13.9 against 124 us) -- so inside the sweep, 1 .. 32 rows of 153 .. 314574 outputs, auto is route 1 wherever
+ * it fits, in every layout, and route 2 everywhere else.  The tables are per layout and block all the same: a run between two
+ * measured row counts or sizes is fused only where all its measured neighbours are, a block other than 0 and 8192 must hold in
+ * both block tables.  Not measured, hence composed: fewer than 153 or more than 314574 outputs per row, more than 32 rows.  Not
+ * measured and not told apart by the rule: strides and offsets other than the three layouts' (a run is classed by which side is
+ * strided, not by how far), other blocks than 0 and 8192 that fit, a tile smaller than 2046 outputs. */
+typedef struct sdrhip_audio_tail sdrhip_audio_tail;
+int sdrhip_audio_tail_create(sdrhip_audio_tail **t, int order, int interpolation, int decimation, const float *resamp_taps,
+                             int n_resamp_taps, const float *audio_half_taps, int n_audio_half, float gain, int64_t block);
+void sdrhip_audio_tail_destroy(sdrhip_audio_tail *t);
+int64_t sdrhip_audio_tail_ready(const sdrhip_audio_tail *t, int64_t n_y);
+int64_t sdrhip_audio_tail_first_input(const sdrhip_audio_tail *t, int64_t q);
+int64_t sdrhip_audio_tail_max_halo(const sdrhip_audio_tail *t);
+int64_t sdrhip_audio_tail_block(const sdrhip_audio_tail *t);
+int sdrhip_audio_tail_fused_fits(const sdrhip_audio_tail *t);
+/* shape[0 .. 3] = interpolation, decimation, numCoeffsR (the resampler's prepared taps), numCoeffsF (the filter's) */
+int sdrhip_audio_tail_shape(const sdrhip_audio_tail *t, int32_t *shape);
+size_t sdrhip_audio_tail_workspace_bytes(const sdrhip_audio_tail *t, int rows, int64_t n_y);
+int sdrhip_audio_tail_set_route(sdrhip_audio_tail *t, int route);
+int sdrhip_audio_tail_run_rows(const sdrhip_audio_tail *t, void *stream, const float *d_y, int64_t y_stride, int64_t y_base,
+                               int64_t n_y, float *d_audio, int64_t audio_stride, int rows, int64_t q0, int64_t q1,
+                               void *d_workspace, size_t workspace_bytes);
+long long sdrhip_debug_audio_tail_launches(void);   /* launches of k_audio_tail_rows (route 1: exactly one per run), process-wide */
+
 /* ---- the record seam on HOST vectors (hs_sources/SDR/Filter.hs:116-144) ---- */
 /* The closures a Haskell constructor puts into the reference's own Filter / Decimator / Resampler records, so that
  * the reference's UNCHANGED Pipes (firFilter / firDecimator / firResampler, Filter.hs:532-727) drive the device:
@@ -1314,6 +1374,26 @@ int sdrhip_pipe_am_bank(sdrhip_pipe **p, const sdrhip_am_bank *b, int block_size
  * SDRHIP_ERR_ARG (and *p = NULL) before any device work for a null bank, block_size_out <= 0 and an input_type outside 0 .. 2.  The
  * bank (and its tuner bank) is borrowed and must outlive the pipe. */
 int sdrhip_pipe_nfm_bank(sdrhip_pipe **p, const sdrhip_nfm_bank *b, int block_size_out, int input_type);
+/* The two banks with their audio stages, on host blocks: IQ blocks in (input_type and the push / input_buffer calls as above), every
+ * channel's AUDIO out in blocks of exactly `block` floats -- the block the tail was created with, at least 1 -- through
+ * sdrhip_pipe_pop_rows / sdrhip_pipe_rows (sdrhip_pipe_pop with one channel), every row in lockstep.
+ * Definition: channel j's blocks are those of  sdrhip_pipe_am_bank / sdrhip_pipe_nfm_bank with block_size_out = block
+ * >-> firResampler(block) >-> firFilter(block) >-> (* gain)  over the same pushes, bit for bit, for every sequence of block sizes,
+ * coalesced or adaptive.
+ * Per submission: the bank part is the bank Pipe's -- the same launches, states and alignment, everything on ONE compute stream (the
+ * engine's first) -- but its demodulated rows stay on the device, behind the elements carried from earlier submissions; then ONE
+ * sdrhip_audio_tail_run_rows computes the audio outputs that became ready (sdrhip_audio_tail_ready of the demodulated count so
+ * far) into the result, on the tail's route (auto: sdrhip_audio_tail_set_route); then the elements from the next audio output's
+ * first input on (at most sdrhip_audio_tail_max_halo per row) are copied to the front of a second rows buffer by a 2-D device copy.
+ * A submission that completes no audio output runs the bank part and no tail launch.  No host synchronisation between pushes once
+ * the rows buffers and the tail's workspace have the size of the largest push.
+ * Save / restore: the bank Pipe's state for that kind, the audio position, the tail's shape and the carried rows read back from
+ * the device (save flushes).  Restore refuses another kind, row count, input type, block, factor, tap count, dc_block, resampler
+ * ratio, other tail tap counts and a truncated state, with the pipe unchanged.  The kind numbers are new ones at the end (12, 13):
+ * states of every other kind keep their bytes.  SDRHIP_ERR_ARG (and *p = NULL) before any device work for a null bank, a null tail,
+ * a tail of block 0 and an input_type outside 0 .. 2.  The bank and the tail are borrowed and must outlive the pipe. */
+int sdrhip_pipe_am_bank_audio(sdrhip_pipe **p, const sdrhip_am_bank *b, const sdrhip_audio_tail *tail, int input_type);
+int sdrhip_pipe_nfm_bank_audio(sdrhip_pipe **p, const sdrhip_nfm_bank *b, const sdrhip_audio_tail *tail, int input_type);
 int sdrhip_pipe_push_i16(sdrhip_pipe *p, const int16_t *iq, int n_samples);
 int16_t *sdrhip_pipe_input_buffer_i16(sdrhip_pipe *p, int n_samples);
 

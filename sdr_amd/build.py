@@ -34,7 +34,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 # v_pk_* (no faster than scalar on gfx950: 4 cycles vs 2) and pays for it in v_mov shuffles.
 FILE_FLAGS = {"kernels_chain.hip": ["-fno-slp-vectorize"], "kernels_split.hip": ["-fno-slp-vectorize"],
               "kernels_crossfix.hip": ["-fno-slp-vectorize"], "kernels_fir_rows.hip": ["-fno-slp-vectorize"],
-              "kernels_tail.hip": ["-fno-slp-vectorize"], "kernels_cplx.hip": ["-fno-slp-vectorize"],
+              "kernels_tail.hip": ["-fno-slp-vectorize"], "kernels_tail_rows.hip": ["-fno-slp-vectorize"], "kernels_cplx.hip": ["-fno-slp-vectorize"],
               "kernels_resample_cycle.hip": ["-fno-slp-vectorize"], "kernels_decimate_real.hip": ["-fno-slp-vectorize"],
               # packed operations written out as 2-vectors; the vectoriser would undo the DPP-fused additions
               "kernels_systolic.hip": ["-fno-slp-vectorize"],

@@ -187,6 +187,23 @@ void plan_out(const FirRowsPlan& p, const FirRowsPlan& one, int* plan)
 }
 
 }  // namespace
+
+bool fir_rows_banked(const FirDesc* d, int rows, int64_t k_begin, int64_t k_end, int64_t seam_block)
+{
+    if (k_end <= k_begin || k_end - k_begin >= (int64_t)0x7fffffff) return false;
+    return fir_rows_plan(fir_geom(d, k_begin * d->factor, k_begin, k_end, seam_block), rows, d->cplx, d->lanes, d->corder, d->sym, fir_split_ntaps(d),
+                         nullptr);
+}
+
+bool resamp_rows_banked(const ResampDesc* r, int rows, int64_t k_begin, int64_t k_end, int64_t seam_block)
+{
+    if (k_end <= k_begin || k_end - k_begin >= (int64_t)0x7fffffff) return false;
+    Geom g;
+    ResampTable t;
+    resamp_geom(r, r->in_offset(k_begin), k_begin, k_end, seam_block, 0, g, t);
+    return resample_rows_plan(g, rows, r->cplx, r->lanes, r->corder, t, nullptr);
+}
+
 }  // namespace sdrhip
 
 using namespace sdrhip;

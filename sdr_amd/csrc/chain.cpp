@@ -32,6 +32,7 @@
 #include <exception>
 #include "descriptors.hpp"
 #include "host_stream.hpp"
+#include "tail_plan.hpp"
 
 using namespace sdrhip;
 
@@ -176,15 +177,14 @@ struct sdrhip_fm_chain {
     // first input sample in the receptive field of audio output q
     int64_t start(int64_t q) const
     {
-        int64_t k = resamp.in_offset(q);
+        int64_t k = tail_first_y(resamp, q);
         if (k > 0) k -= 1;  // fmDemod looks one decimator output back (Demod.hs:28)
         return k * decim.factor;
     }
     // one past the last input sample in the receptive field of audio output q
     int64_t end(int64_t q) const
     {
-        int64_t m_last = q + audio.Lp - 1;
-        int64_t k_last = resamp.in_offset(m_last) + y_reach() - 1;
+        int64_t k_last = tail_end_y(resamp, audio, q) - 1;
         return k_last * decim.factor + decim.Lp;
     }
     // smallest q with start(q) >= s
@@ -269,25 +269,13 @@ int sdrhip_fm_chain_plan(const sdrhip_fm_chain* c, int64_t s0, int64_t s1, int64
 int64_t sdrhip_fm_chain_ready(const sdrhip_fm_chain* c, int64_t n_samples)
 {
     if (!c || n_samples < 0) return -1;
-    if (c->end(0) > n_samples) return 0;
-    int64_t lo = 0, hi = 1;                        // invariant: end(lo) <= n_samples < end(hi); end() is non-decreasing
-    while (c->end(hi) <= n_samples) { lo = hi; hi *= 2; }
-    while (lo + 1 < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (c->end(mid) <= n_samples) lo = mid; else hi = mid;
-    }
-    return hi;
+    return ready_by_end([c](int64_t q) { return c->end(q); }, n_samples);      // end() is non-decreasing
 }
 
 int64_t sdrhip_fm_chain_max_halo(const sdrhip_fm_chain* c)
 {
     if (!c) return -1;
-    int64_t worst = 0;
-    for (int64_t q = 0; q <= 2 * c->resamp.I + 2; q++) {
-        int64_t len = c->end(q) - c->start(q);
-        if (len > worst) worst = len;
-    }
-    return worst;
+    return longest_field([c](int64_t q) { return c->start(q); }, [c](int64_t q) { return c->end(q); }, c->resamp.I);
 }
 
 int64_t sdrhip_fm_chain_halo_samples(const sdrhip_fm_chain* c)

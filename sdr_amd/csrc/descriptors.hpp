@@ -82,6 +82,11 @@ int resamp_run_demod(const ResampDesc* r, hipStream_t s, const float* d_iq, bool
                      int64_t in_base, float* d_out, int64_t k_begin, int64_t k_end, int64_t seam_block, int64_t out_block,
                      bool* demod_fused);
 
+// abi_fir_rows.cpp: does the banked route of the row forms (sdrhip_*_run_rows, route 1) serve outputs [k_begin, k_end) of `rows` rows
+// of this descriptor?  Host arithmetic (the plan sdrhip_debug_fir_rows_plan reports), for callers that pick the route themselves.
+bool fir_rows_banked(const FirDesc* d, int rows, int64_t k_begin, int64_t k_end, int64_t seam_block);
+bool resamp_rows_banked(const ResampDesc* r, int rows, int64_t k_begin, int64_t k_end, int64_t seam_block);
+
 // The tuner (include/sdr_hip.h): a complex decimator's prepared taps plus the oscillator table.  Immutable after create except for
 // the route and the scratch lanes of the two-pass route, so host threads may share one.
 // (its input format: InFmt, kernels.hpp)

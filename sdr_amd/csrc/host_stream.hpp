@@ -160,7 +160,7 @@ struct HostStream {
             else if (head > (1u << 20) && head * 2 > f.size()) { f.erase(f.begin(), f.begin() + head); head = 0; }   // compact occasionally
             const size_t old = f.size();
             f.resize(old + per_row);
-            memcpy(f.data() + old, (const float*)sl.hout.p + (size_t)r * per_row, per_row * sizeof(float));
+            if (per_row > 0) memcpy(f.data() + old, (const float*)sl.hout.p + (size_t)r * per_row, per_row * sizeof(float));
         }
         sl.busy = false;
         return SDRHIP_OK;
@@ -245,16 +245,20 @@ struct HostStream {
     // Submit the current slot: `first` .. `first + in_bytes` is its [carried tail | staged] in the staging buffer, out_floats
     // results are expected (none: no launch; with rows > 1 the total of all rows, each out_floats / rows long).  launch(stream, d_in, d_out) enqueues the operator's kernels on `stream` and
     // returns an SDRHIP_* code.  The oldest submission is harvested afterwards: its slot is the next to be filled.
+    // always_launch: the operator keeps state on the device that every submission moves on (the audio Pipes' demodulated rows), so
+    // launch() runs even when no result is expected -- with d_out as it happens to be (possibly null) -- and the slot counts as busy
+    // with no floats to harvest, so that its buffers are not reused before those kernels are done.
     template <class Launch>
-    int submit(Route route, hipStream_t cs, const void* first, size_t in_bytes, int64_t out_floats, Launch&& launch)
+    int submit(Route route, hipStream_t cs, const void* first, size_t in_bytes, int64_t out_floats, Launch&& launch, bool always_launch = false)
     {
+        const bool run = out_floats > 0 || always_launch;
         Slot& sl = slot[cur()];
         const size_t out_bytes = (size_t)out_floats * sizeof(float);
         int rc;
         sl.n_out = 0;
         if (out_floats > 0 && (rc = sl.hout.ensure(out_bytes)) != SDRHIP_OK) return rc;
         if (route != kCopyEngines) {
-            if (out_floats > 0) {
+            if (run) {
                 const void* d_in = sl.hin.dev_ptr(first);
                 if (route == kSlotStream) {
                     if ((rc = sl.din.ensure(in_bytes + 64 + dev_skew)) != SDRHIP_OK) return rc;
@@ -274,6 +278,12 @@ struct HostStream {
             SDRHIP_CHECK_HIP(hipMemcpyAsync((char*)sl.din.p + dev_skew, first, in_bytes, hipMemcpyHostToDevice, up));
             SDRHIP_CHECK_HIP(hipEventRecord(sl.ev_up, up));
             sl.direct = false;
+            if (run && out_floats == 0) {
+                SDRHIP_CHECK_HIP(hipStreamWaitEvent(cs, sl.ev_up, 0));
+                if ((rc = launch(cs, (const void*)((const char*)sl.din.p + dev_skew), sl.dout.p)) != SDRHIP_OK) return rc;
+                SDRHIP_CHECK_HIP(hipEventRecord(sl.ev, cs));
+                sl.busy = true;
+            }
             if (out_floats > 0) {
                 SDRHIP_CHECK_HIP(hipStreamWaitEvent(cs, sl.ev_up, 0));
                 if ((rc = sl.dout.ensure(out_bytes)) != SDRHIP_OK) return rc;

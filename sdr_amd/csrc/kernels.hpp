@@ -307,6 +307,13 @@ constexpr int kTailTileOutputs = 2046;   // audio outputs one workgroup of the f
 bool fm_tail_fused_fits(int rLp, int64_t seam);
 void launch_fm_tail_fused(hipStream_t s, const float* d_d, int64_t kd0, int64_t kd1, int64_t ky0, int64_t ky1, float* d_audio,
                           int64_t q0, int64_t q1, const FmTailTables& t);
+// kernels_tail_rows.hip: the same tile over ROWS of real y (the audio tail behind the AM / narrow-band FM bank, audio_tail.cpp):
+// 3/10 resampler -> symmetric filter (* gain), one launch for all rows, the row on the grid's second axis.  Row r's y[0] is its
+// stream element y_base, n_y elements readable (others are read as zeros); its outputs [q0, q1) go to d_audio + r * audio_stride.
+// Shape and fit are k_fm_tail's: fm_tail_shape_ok and fm_tail_fused_fits.  Launches unconditionally and counts.
+void launch_audio_tail_rows(hipStream_t s, const float* d_y, int64_t y_stride, int64_t y_base, int64_t n_y, float* d_audio,
+                            int64_t audio_stride, int rows, int64_t q0, int64_t q1, const FmTailTables& t);
+long long audio_tail_launch_count();   // diagnostics: launches of k_audio_tail_rows
 // kernels_small.hip: the WHOLE chain (u8 IQ -> /8 decimator -> fmDemod -> 3/10 resampler -> symmetric filter * gain) as one
 // kernel for launch-bound runs; d_in holds samples [s0, s0 + n_in).  tile_outputs: audio outputs per workgroup (0 = chosen
 // from the size of the run, < 0 = the largest).  fits (given fm_tail_shape_ok): /8 decimator with 128 padded taps in the AVX

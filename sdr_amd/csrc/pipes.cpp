@@ -46,6 +46,9 @@ enum PipeKind : int { PK_FILTER, PK_DECIMATOR, PK_RESAMPLER, PK_DEMOD, PK_DCBLOC
 constexpr PipeKind PK_SPECTRUM = static_cast<PipeKind>(PK_AM_BANK + 1);
 // The narrow-band FM bank's Pipe, the next number again (11), behind the list for the same reason.
 constexpr PipeKind PK_NFM_BANK = static_cast<PipeKind>(PK_SPECTRUM + 1);
+// The audio Pipes of the two banks (sdrhip_pipe_am_bank_audio, sdrhip_pipe_nfm_bank_audio), the next two numbers (12, 13).
+constexpr PipeKind PK_AM_BANK_AUDIO = static_cast<PipeKind>(PK_NFM_BANK + 1);
+constexpr PipeKind PK_NFM_BANK_AUDIO = static_cast<PipeKind>(PK_NFM_BANK + 2);
 
 struct sdrhip_pipe {
     PipeKind kind;
@@ -75,6 +78,18 @@ struct sdrhip_pipe {
     // fused launch does not serve go through am_iq.
     DevBuf nfm_state[2];
     int nfm_cur = 0;
+    // PK_AM_BANK_AUDIO / PK_NFM_BANK_AUDIO: the bank's Pipe with the audio tail (a BORROWED sdrhip_audio_tail) behind it on the device.
+    // The bank part of a submission is the bank Pipe's, but writes its demodulated rows into y_rows[y_cur] (K rows of y_stride floats)
+    // behind the y_n elements carried from earlier submissions; row element 0 is demodulated output m_done - y_n of the stream.  One
+    // audio_tail run then computes the audio outputs [a_done, ready(m_end)) into the result chunk, and the elements from the next
+    // output's first input on are copied to the front of the other buffer (a 2-D device copy on the same stream).  Everything goes to
+    // compute stream 0.  block_out is the tail's block.
+    const sdrhip_audio_tail* tail = nullptr;
+    DevBuf y_rows[2], tail_ws;
+    int y_cur = 0;
+    int64_t y_stride = 0, y_n = 0, a_done = 0;
+    bool am_kind() const { return kind == PK_AM_BANK || kind == PK_AM_BANK_AUDIO; }
+    bool nfm_kind() const { return kind == PK_NFM_BANK || kind == PK_NFM_BANK_AUDIO; }
     // PK_SPECTRUM: the waterfall Pipe over a borrowed spectrum object.  Elements are samples in the object's own type (fmt); output
     // blocks are rows of block_out = n floats.  The engine's history holds exactly the carried tail (the samples from the first row
     // not yet produced onward) while nothing is staged; sp_skip samples of the stream are still to be dropped on arrival (hop > n).
@@ -186,6 +201,61 @@ static int grow(DevBuf& b, size_t bytes, hipStream_t s)
     return b.ensure(bytes);
 }
 
+// ---- the audio Pipes' device rows ---------------------------------------------------------------------------------------------------
+// Room for `need` floats per row in both rows buffers.  Growing (the first submission, or a larger push than any before) waits for the
+// launches on s that still use the old buffers and moves the y_n carried elements of every row over.
+static int audio_rows_room(sdrhip_pipe* p, int64_t need, hipStream_t s)
+{
+    if (need <= p->y_stride) return SDRHIP_OK;
+    const int K = p->rows();
+    const int64_t stride = row_floats(need + need / 4 + 512);
+    DevBuf bigger[2];
+    int rc;
+    for (DevBuf& b : bigger)
+        if ((rc = b.ensure((size_t)K * (size_t)stride * sizeof(float))) != SDRHIP_OK) return rc;
+    SDRHIP_CHECK_HIP(hipStreamSynchronize(s));
+    if (p->y_n > 0)
+        SDRHIP_CHECK_HIP(hipMemcpy2D(bigger[0].p, (size_t)stride * sizeof(float), p->y_rows[p->y_cur].p, (size_t)p->y_stride * sizeof(float),
+                                     (size_t)p->y_n * sizeof(float), (size_t)K, hipMemcpyDeviceToDevice));
+    for (int i = 0; i < 2; i++) {
+        std::swap(p->y_rows[i].p, bigger[i].p);
+        std::swap(p->y_rows[i].cap, bigger[i].cap);
+    }
+    p->y_cur = 0;
+    p->y_stride = stride;
+    return SDRHIP_OK;
+}
+
+// Behind the bank part of a submission that wrote demodulated outputs [m_done, m_done + count) of every row: the audio outputs
+// [a_done, a_end) into the chunk by ONE audio_tail run (none when a_end == a_done), then the carry -- the elements from
+// first_input(a_end) on go to the front of the other rows buffer.
+static int audio_rows_tail(sdrhip_pipe* p, hipStream_t s, float* d_chunk, int64_t m_done, int64_t count, int64_t a_end)
+{
+    const int K = p->rows();
+    const int64_t n_y = p->y_n + count, y_base = m_done - p->y_n;
+    if (a_end == p->a_done) {
+        p->y_n = n_y;
+        return SDRHIP_OK;
+    }
+    float* y = (float*)p->y_rows[p->y_cur].p;
+    const size_t ws = sdrhip_audio_tail_workspace_bytes(p->tail, K, n_y);
+    int rc = grow(p->tail_ws, ws, s);
+    if (rc != SDRHIP_OK) return rc;
+    if ((rc = sdrhip_audio_tail_run_rows(p->tail, s, y, p->y_stride, y_base, n_y, d_chunk, a_end - p->a_done, K, p->a_done, a_end, p->tail_ws.p,
+                                         ws)) != SDRHIP_OK)
+        return rc;
+    int64_t keep = m_done + count - sdrhip_audio_tail_first_input(p->tail, a_end);
+    if (keep < 0) keep = 0;
+    if (keep > n_y) keep = n_y;
+    if (keep > 0)
+        SDRHIP_CHECK_HIP(hipMemcpy2DAsync(p->y_rows[p->y_cur ^ 1].p, (size_t)p->y_stride * sizeof(float), y + (n_y - keep),
+                                          (size_t)p->y_stride * sizeof(float), (size_t)keep * sizeof(float), (size_t)K,
+                                          hipMemcpyDeviceToDevice, s));
+    p->y_cur ^= 1;
+    p->y_n = keep;
+    return SDRHIP_OK;
+}
+
 // The launches of one submission (fir_submit below), run(k_begin, k_end, seam_block, outputs in front of k_begin in this submission):
 // a uniform run is ONE call over [m_done, m_end) with its seams; a ragged block is the Cross call over [m_done, m_split) (seam -1),
 // then the One call over [m_split, m_end) (seam 0).  An empty part is no call.
@@ -240,9 +310,10 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
     // The AM bank's Pipe never reads in place, whatever the row count (a stated choice: the FM bank stream's sweep found no in-place
     // region), and with dcBlocker all its launches share compute stream 0: a submission's dcBlocker starts from the state its
     // predecessor's left on the device
-    const bool nfm = p->kind == PK_NFM_BANK;
-    const bool am = p->kind == PK_AM_BANK || nfm;      // (the narrow-band FM bank's Pipe makes the same choice)
-    if (p->am_dc || nfm) cs = e.compute[0];
+    const bool nfm = p->nfm_kind();
+    const bool am = p->am_kind() || nfm;      // (the narrow-band FM bank's Pipe makes the same choice)
+    const bool audio = p->tail != nullptr;    // (the demodulated rows live on the device from submission to submission)
+    if (p->am_dc || nfm || audio) cs = e.compute[0];
     const HostStream::Route route = !direct ? HostStream::kCopyEngines : (rows > 1 || am) ? HostStream::kSlotStream : HostStream::kInPlace;
     if ((p->kind == PK_TUNER_BANK || am) && route != HostStream::kInPlace) {
         // the copy may land anywhere in the slot's device buffer: put the banked launch's first window on a 16-byte boundary there,
@@ -251,7 +322,13 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
         const size_t off = (size_t)(k0 * p->D - keep_from) * ein;
         e.dev_skew = (16 - off % 16) % 16;
     }
-    const int64_t row_len = (m_end - m_done) * p->esz_out();
+    // the audio Pipes: the chunk holds the audio outputs that became ready, [a_done, a_end) of every row
+    int64_t a_end = p->a_done;
+    if (audio) {
+        a_end = sdrhip_audio_tail_ready(p->tail, m_end);
+        if (a_end < p->a_done) a_end = p->a_done;
+    }
+    const int64_t row_len = audio ? a_end - p->a_done : (m_end - m_done) * p->esz_out();
     int rc = e.submit(route, cs, first, (size_t)(tail + n) * ein, rows * row_len, [&](hipStream_t s, const void* d_in, void* d_out) {
         const float* din = (const float*)d_in;
         float* dout = (float*)d_out;
@@ -271,8 +348,16 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
         const int K = rows;
         const int64_t count = m_end - m_done, np = row_floats(count);
         int r;
-        float* out = dout;
-        int64_t stride = row_len;
+        // where the form's rows end up: the result chunk, or (the audio Pipes) the device rows buffer behind the carried history
+        float* fin = dout;
+        int64_t fin_stride = row_len;
+        if (audio) {
+            if ((r = audio_rows_room(p, p->y_n + count, s)) != SDRHIP_OK) return r;
+            fin = (float*)p->y_rows[p->y_cur].p + p->y_n;
+            fin_stride = p->y_stride;
+        }
+        float* out = fin;
+        int64_t stride = fin_stride;
         if (p->am_dc) {
             // dcBlocker's row form refuses d_in == d_out: the envelope rows pass through dc_ws, its own workspace behind them
             if ((r = grow(p->dc_ws, (size_t)K * (size_t)np * sizeof(float) + dc_blocker_rows_workspace_bytes(K, count), s)) != SDRHIP_OK) return r;
@@ -303,15 +388,18 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
             if (rr == SDRHIP_OK && form.kind == BankForm::PHASE) p->nfm_cur ^= 1;
             return rr;
         });
-        if (r != SDRHIP_OK || !p->am_dc) return r;
-        launch_dc_blocker_rows(s, K, count, out, np, dout, row_len, (const float*)p->dc_state.p, (float*)p->dc_state.p,
-                               out + (size_t)K * (size_t)np, 0);
-        SDRHIP_CHECK_HIP(hipGetLastError());
-        return SDRHIP_OK;
-    });
+        if (r != SDRHIP_OK) return r;
+        if (p->am_dc) {
+            launch_dc_blocker_rows(s, K, count, out, np, fin, fin_stride, (const float*)p->dc_state.p, (float*)p->dc_state.p,
+                                   out + (size_t)K * (size_t)np, 0);
+            SDRHIP_CHECK_HIP(hipGetLastError());
+        }
+        return audio ? audio_rows_tail(p, s, dout, m_done, count, a_end) : SDRHIP_OK;
+    }, audio && m_end > m_done);
     if (rc != SDRHIP_OK) return rc;
     p->m_done = m_end;
     p->E_prev = E;
+    p->a_done = a_end;
     return SDRHIP_OK;
 }
 
@@ -605,9 +693,9 @@ static int bank_pipe_new(sdrhip_pipe** pp, const char* who, const TunerBankDesc*
     p->bank = b;
     p->form = form;
     p->iq_always = form == BankForm::ENV;      // (whether the fused launch takes a submission is left to the launcher)
-    p->am_dc = kind == PK_AM_BANK && nstate == 1;
+    p->am_dc = p->am_kind() && nstate == 1;
     if (K > 1) p->eng.set_rows(K);
-    DevBuf* state = kind == PK_NFM_BANK ? p->nfm_state : &p->dc_state;
+    DevBuf* state = p->nfm_kind() ? p->nfm_state : &p->dc_state;
     for (int i = 0; i < nstate && rc == SDRHIP_OK; i++) rc = pipe_dev_state(pp, state[i], (size_t)K * 2 * sizeof(float), nullptr, who);
     return rc;
 }
@@ -631,6 +719,33 @@ int sdrhip_pipe_am_bank(sdrhip_pipe** pp, const sdrhip_am_bank* a, int block_siz
 int sdrhip_pipe_nfm_bank(sdrhip_pipe** pp, const sdrhip_nfm_bank* a, int block_size_out, int input_type)
 {
     return bank_pipe_new(pp, "sdrhip_pipe_nfm_bank", a ? a->tb : nullptr, block_size_out, input_type, 2, PK_NFM_BANK, BankForm::PHASE, 2);
+}
+
+// The audio Pipes: the bank's Pipe with block_size_out = the tail's block, >-> firResampler(block) >-> firFilter(block) >-> (* gain),
+// the tail on the device rows (audio_rows_tail above).  The tail is borrowed, as the bank is.
+static int bank_audio_pipe_new(sdrhip_pipe** pp, const char* who, const TunerBankDesc* b, const sdrhip_audio_tail* tail, int input_type,
+                               PipeKind kind, BankForm::Kind form, int nstate)
+{
+    if (pp != nullptr) *pp = nullptr;
+    const int64_t block = sdrhip_audio_tail_block(tail);
+    if (pp == nullptr || tail == nullptr || block < 1 || block > (int64_t)0x7fffffff) {
+        set_error("%s: requirement `a pipe pointer, an audio tail, and a tail created with a block of at least 1` violated", who);
+        return SDRHIP_ERR_ARG;
+    }
+    int rc = bank_pipe_new(pp, who, b, (int)block, input_type, 2, kind, form, nstate);
+    if (rc == SDRHIP_OK) (*pp)->tail = tail;
+    return rc;
+}
+
+int sdrhip_pipe_am_bank_audio(sdrhip_pipe** pp, const sdrhip_am_bank* a, const sdrhip_audio_tail* tail, int input_type)
+{
+    return bank_audio_pipe_new(pp, "sdrhip_pipe_am_bank_audio", a ? a->tb : nullptr, tail, input_type, PK_AM_BANK_AUDIO, BankForm::ENV,
+                               a && a->dc_block != 0 ? 1 : 0);
+}
+
+int sdrhip_pipe_nfm_bank_audio(sdrhip_pipe** pp, const sdrhip_nfm_bank* a, const sdrhip_audio_tail* tail, int input_type)
+{
+    return bank_audio_pipe_new(pp, "sdrhip_pipe_nfm_bank_audio", a ? a->tb : nullptr, tail, input_type, PK_NFM_BANK_AUDIO, BankForm::PHASE, 2);
 }
 
 int sdrhip_pipe_rows(const sdrhip_pipe* p)
@@ -908,11 +1023,21 @@ struct PipeAmRecord {
 };
 static PipeAmRecord pipe_state_am(const sdrhip_pipe* p)
 {
-    if (p->kind == PK_NFM_BANK) return {true, {0, 2 * p->rows()}, p->nfm_state[p->nfm_cur].p};
-    if (p->kind == PK_AM_BANK) return {true, {p->am_dc ? 1 : 0, p->am_dc ? 2 * p->rows() : 0}, p->dc_state.p};
+    if (p->nfm_kind()) return {true, {0, 2 * p->rows()}, p->nfm_state[p->nfm_cur].p};
+    if (p->am_kind()) return {true, {p->am_dc ? 1 : 0, p->am_dc ? 2 * p->rows() : 0}, p->dc_state.p};
     return {false, {0, 0}, nullptr};
 }
-static size_t pipe_state_am_bytes(const sdrhip_pipe* p) { return pipe_state_am(p).bytes(); }
+// The audio Pipes append, behind that record: the audio position, the tail's shape (so that a state is restored only into a pipe of
+// the same resampler ratio and tap counts) and the y_n carried demodulated elements of every row, row after row.
+struct PipeStateAudio {
+    int64_t a_done, y_n;
+    int32_t shape[4];        // sdrhip_audio_tail_shape: interpolation, decimation, numCoeffsR, numCoeffsF
+};
+static size_t pipe_state_audio_bytes(const sdrhip_pipe* p)
+{
+    return p->tail ? sizeof(PipeStateAudio) + (size_t)p->rows() * (size_t)p->y_n * sizeof(float) : 0;
+}
+static size_t pipe_state_am_bytes(const sdrhip_pipe* p) { return pipe_state_am(p).bytes() + pipe_state_audio_bytes(p); }
 static size_t pipe_state_header_bytes(const sdrhip_pipe* p) { return sizeof(PipeStateHeader) + (pipe_state_version(p) == 2 ? sizeof(PipeStateRows) : 0); }
 // Version 3: the waterfall Pipe.  This header, the carried tail (tail_n samples in the input's own type), the rows not yet popped
 // (pending floats).  pos = samples pushed so far; the tail starts at stream sample rows_done * group * hop = pos - tail_n (skip == 0)
@@ -1002,6 +1127,18 @@ int sdrhip_pipe_save(sdrhip_pipe* p, void* buf, size_t capacity, size_t* used)
         if (am.x.n_floats > 0) {
             SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));
             SDRHIP_CHECK_HIP(hipMemcpy(o, am.d_floats, (size_t)am.x.n_floats * sizeof(float), hipMemcpyDeviceToHost));
+            o += (size_t)am.x.n_floats * sizeof(float);
+        }
+    }
+    if (p->tail) {
+        PipeStateAudio x = {p->a_done, p->y_n, {0, 0, 0, 0}};
+        (void)sdrhip_audio_tail_shape(p->tail, x.shape);
+        memcpy(o, &x, sizeof x);
+        o += sizeof x;
+        if (p->y_n > 0) {
+            SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));
+            SDRHIP_CHECK_HIP(hipMemcpy2D(o, (size_t)p->y_n * sizeof(float), p->y_rows[p->y_cur].p, (size_t)p->y_stride * sizeof(float),
+                                         (size_t)p->y_n * sizeof(float), (size_t)p->rows(), hipMemcpyDeviceToHost));
         }
     }
     *used = need;
@@ -1055,7 +1192,7 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
     SDRHIP_REQUIRE(h.hist_n >= 0 && h.hist_n <= h.head_cap && h.pending >= 0 && h.n_blocks >= 0 && h.E_prev >= h.hist_n && h.m_done >= 0,
                    "sdrhip_pipe_restore: inconsistent state");
     if (p->kind == PK_FILTER || p->kind == PK_DECIMATOR || p->kind == PK_RESAMPLER || p->kind == PK_TUNER || p->kind == PK_TUNER_BANK ||
-        p->kind == PK_AM_BANK || p->kind == PK_NFM_BANK) {
+        p->am_kind() || p->nfm_kind()) {
         // the next pending output must start inside what the pipe has seen, every output computable from those elements must be
         // done at most once, and the history must reach back to its first input (3 elements of alignment slack, 7 of u8, fir_submit):
         // otherwise the kernels would be sent in front of the staging buffer
@@ -1068,13 +1205,35 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
     }
     const size_t am_at = pipe_state_header_bytes(p) + p->eng.state_bytes(h.hist_n, h.pending) + (size_t)h.n_blocks * sizeof(int32_t);
     const PipeAmRecord am = pipe_state_am(p);
-    SDRHIP_REQUIRE(bytes >= am_at + am.bytes(), "sdrhip_pipe_restore: truncated state");
+    SDRHIP_REQUIRE(bytes >= am_at + am.bytes() + (p->tail ? sizeof(PipeStateAudio) : 0), "sdrhip_pipe_restore: truncated state");
     if (am.present) {
         PipeStateAm x;
         memcpy(&x, (const unsigned char*)buf + am_at, sizeof x);
         SDRHIP_REQUIRE(x.dc_block == am.x.dc_block && x.n_floats == am.x.n_floats,
-                       p->kind == PK_AM_BANK ? "sdrhip_pipe_restore: the state belongs to an AM bank pipe of another dc_block"
-                                             : "sdrhip_pipe_restore: the state belongs to a pipe of another row count");
+                       p->am_kind() ? "sdrhip_pipe_restore: the state belongs to an AM bank pipe of another dc_block"
+                                    : "sdrhip_pipe_restore: the state belongs to a pipe of another row count");
+    }
+    PipeStateAudio au = {0, 0, {0, 0, 0, 0}};
+    const unsigned char* au_floats = nullptr;
+    if (p->tail) {
+        int32_t shape[4];
+        memcpy(&au, (const unsigned char*)buf + am_at + am.bytes(), sizeof au);
+        (void)sdrhip_audio_tail_shape(p->tail, shape);
+        SDRHIP_REQUIRE(memcmp(au.shape, shape, sizeof shape) == 0,
+                       "sdrhip_pipe_restore: the state belongs to an audio pipe of another resampler ratio or other tail tap counts");
+        // every audio output the demodulated outputs so far complete is done, and the carried rows reach back to the next one's first input
+        SDRHIP_REQUIRE(au.a_done == sdrhip_audio_tail_ready(p->tail, h.m_done) && au.y_n >= 0 && au.y_n <= h.m_done &&
+                           sdrhip_audio_tail_first_input(p->tail, au.a_done) >= h.m_done - au.y_n &&
+                           au.y_n <= h.m_done - sdrhip_audio_tail_first_input(p->tail, au.a_done) + sdrhip_audio_tail_max_halo(p->tail),
+                       "sdrhip_pipe_restore: inconsistent state");
+        SDRHIP_REQUIRE((bytes - (am_at + am.bytes() + sizeof au)) / sizeof(float) >= (size_t)p->rows() * (size_t)au.y_n,
+                       "sdrhip_pipe_restore: truncated state");
+        au_floats = (const unsigned char*)buf + am_at + am.bytes() + sizeof au;
+    }
+    // (the one step that can fail for want of memory comes before anything is put back: a failed restore leaves the pipe fresh)
+    if (p->tail) {
+        int rc = audio_rows_room(p, au.y_n + 1, p->eng.compute[0]);
+        if (rc != SDRHIP_OK) return rc;
     }
     const unsigned char* in = p->eng.restore((const unsigned char*)buf + pipe_state_header_bytes(p), h.hist_n, h.pending);
     p->E_prev = h.E_prev;
@@ -1092,6 +1251,13 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
     if (p->has_dev_state()) {
         SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));       // the create call's memset
         SDRHIP_CHECK_HIP(hipMemcpy(p->dc_state.p, h.dc, 16, hipMemcpyHostToDevice));
+    }
+    if (p->tail) {
+        p->a_done = au.a_done;
+        if (au.y_n > 0)
+            SDRHIP_CHECK_HIP(hipMemcpy2D(p->y_rows[p->y_cur].p, (size_t)p->y_stride * sizeof(float), au_floats, (size_t)au.y_n * sizeof(float),
+                                         (size_t)au.y_n * sizeof(float), (size_t)p->rows(), hipMemcpyHostToDevice));
+        p->y_n = au.y_n;
     }
     return ready_blocks(p);
 }

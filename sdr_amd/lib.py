@@ -330,6 +330,23 @@ lib.sdrhip_debug_fir_rows_launches.argtypes = []
 lib.sdrhip_debug_fir_rows_launches.restype = C.c_longlong
 lib.sdrhip_debug_fir_rows_fixups.argtypes = []
 lib.sdrhip_debug_fir_rows_fixups.restype = C.c_longlong
+lib.sdrhip_audio_tail_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, _f32p, C.c_int, _f32p, C.c_int, C.c_float, _i64]
+lib.sdrhip_audio_tail_destroy.argtypes = [_vp]
+lib.sdrhip_audio_tail_destroy.restype = None
+for _n in ("ready", "first_input"):
+    getattr(lib, "sdrhip_audio_tail_" + _n).argtypes = [_vp, _i64]
+    getattr(lib, "sdrhip_audio_tail_" + _n).restype = _i64
+for _n in ("max_halo", "block"):
+    getattr(lib, "sdrhip_audio_tail_" + _n).argtypes = [_vp]
+    getattr(lib, "sdrhip_audio_tail_" + _n).restype = _i64
+lib.sdrhip_audio_tail_fused_fits.argtypes = [_vp]
+lib.sdrhip_audio_tail_shape.argtypes = [_vp, C.POINTER(C.c_int32)]
+lib.sdrhip_audio_tail_workspace_bytes.argtypes = [_vp, C.c_int, _i64]
+lib.sdrhip_audio_tail_workspace_bytes.restype = C.c_size_t
+lib.sdrhip_audio_tail_set_route.argtypes = [_vp, C.c_int]
+lib.sdrhip_audio_tail_run_rows.argtypes = [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, C.c_int, _i64, _i64, _vp, C.c_size_t]
+lib.sdrhip_debug_audio_tail_launches.argtypes = []
+lib.sdrhip_debug_audio_tail_launches.restype = C.c_longlong
 
 lib.sdrhip_fm_stream_create.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int]
 lib.sdrhip_fm_stream_destroy.argtypes = [_vp]
@@ -366,6 +383,8 @@ lib.sdrhip_pipe_input_buffer_u8.restype = _vp
 lib.sdrhip_pipe_tuner_bank_i16.argtypes = [C.POINTER(_vp), _vp, C.c_int]
 lib.sdrhip_pipe_am_bank.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int]
 lib.sdrhip_pipe_nfm_bank.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int]
+lib.sdrhip_pipe_am_bank_audio.argtypes = [C.POINTER(_vp), _vp, _vp, C.c_int]
+lib.sdrhip_pipe_nfm_bank_audio.argtypes = [C.POINTER(_vp), _vp, _vp, C.c_int]
 lib.sdrhip_pipe_push_i16.argtypes = [_vp, _i16p, C.c_int]
 lib.sdrhip_pipe_input_buffer_i16.argtypes = [_vp, C.c_int]
 lib.sdrhip_pipe_input_buffer_i16.restype = _vp
@@ -874,6 +893,72 @@ class Resampler(_Handle):
         """sdrhip_resampler_run_rows: as Filter.run_rows, with the Pipe's output block size as in run()."""
         return _fir_rows_call(lib.sdrhip_resampler_run_rows, "sdrhip_resampler_run_rows", self, x, out, k_begin, k_end, in_base,
                               (seam_block, out_block), route, stream, in_stride, out_stride, rows)
+
+
+AUDIO_TAIL_AUTO, AUDIO_TAIL_FUSED, AUDIO_TAIL_COMPOSED = 0, 1, 2
+
+
+def audio_tail_launches():
+    """sdrhip_debug_audio_tail_launches: launches of the fused audio-tail kernel in this process."""
+    return int(lib.sdrhip_debug_audio_tail_launches())
+
+
+class AudioTail(_Handle):
+    """sdrhip_audio_tail: firResampler(block) >-> firFilter(block) >-> (* gain) over rows of real demodulated samples -- the audio
+    stages behind AmBank / NfmBank.  Arguments as FmChain's tail; block = the one block size of every Pipe (0 = contiguous).
+    ready / first_input / max_halo / workspace_bytes are host arithmetic and need no GPU."""
+    _destroy = lib.sdrhip_audio_tail_destroy
+
+    def __init__(self, interpolation, decimation, resamp_taps, audio_half_taps, gain=1.0, block=0, order=ORDER_AVX):
+        super().__init__()
+        r, a = _f32(resamp_taps), _f32(audio_half_taps)
+        check(lib.sdrhip_audio_tail_create(C.byref(self.h), order, interpolation, decimation, _fp(r), r.size, _fp(a), a.size, gain, block),
+              "sdrhip_audio_tail_create")
+        self.block = block
+
+    def ready(self, n_y):
+        return lib.sdrhip_audio_tail_ready(self.h, n_y)
+
+    def first_input(self, q):
+        return lib.sdrhip_audio_tail_first_input(self.h, q)
+
+    def max_halo(self):
+        return lib.sdrhip_audio_tail_max_halo(self.h)
+
+    def fused_fits(self):
+        return bool(check(lib.sdrhip_audio_tail_fused_fits(self.h), "sdrhip_audio_tail_fused_fits"))
+
+    def workspace_bytes(self, rows, n_y):
+        return lib.sdrhip_audio_tail_workspace_bytes(self.h, rows, n_y)
+
+    def set_route(self, route):
+        """0 = auto, 1 = the fused kernel (one launch, no workspace), 2 = the composition of the row forms (the definition)"""
+        check(lib.sdrhip_audio_tail_set_route(self.h, route), "sdrhip_audio_tail_set_route")
+
+    def run_rows(self, y, audio, q0, q1, y_base=0, n_y=None, workspace=None, workspace_bytes=None, stream=None, y_stride=None,
+                 audio_stride=None, rows=None):
+        """sdrhip_audio_tail_run_rows: audio outputs [q0, q1) of every row; row r of y holds its stream elements [y_base, y_base + n_y).
+        y / audio: 2-D float32 device tensors with contiguous rows and any row stride (n_y defaults to y's width), on the current
+        stream -- or device pointers with y_stride / audio_stride (floats), rows and n_y.  workspace: a device tensor or a pointer
+        with workspace_bytes (routes 0 and 2).  No synchronisation.  -> audio"""
+        name = "sdrhip_audio_tail_run_rows"
+        py, yst, r_in = _fir_rows_side(y, y_stride, rows, False, name)
+        pa, ast, r_out = _fir_rows_side(audio, audio_stride, rows, False, name)
+        rows = rows if rows is not None else r_in if r_in is not None else r_out
+        if rows is None or any(r is not None and r != rows for r in (r_in, r_out)):
+            raise ValueError(f"{name}: the two sides must have the same number of rows (pointers: pass rows=)")
+        if n_y is None:
+            if isinstance(y, int) or y is None:
+                raise ValueError(f"{name}: a pointer needs n_y")
+            n_y = y.shape[1]
+        if workspace is not None and not isinstance(workspace, int):
+            workspace_bytes = workspace.numel() * workspace.element_size() if workspace_bytes is None else workspace_bytes
+            workspace = _dptr(workspace)
+        if stream is None and not (isinstance(y, int) and isinstance(audio, int)):
+            import torch
+            stream = torch.cuda.current_stream().cuda_stream
+        check(lib.sdrhip_audio_tail_run_rows(self.h, stream, py, yst, y_base, n_y, pa, ast, rows, q0, q1, workspace, workspace_bytes or 0), name)
+        return audio
 
 
 TUNER_ROUTE_AUTO, TUNER_ROUTE_FUSED, TUNER_ROUTE_TWO_PASS = 0, 1, 2
@@ -1614,6 +1699,14 @@ class Pipe(_Handle):
             check(lib.sdrhip_pipe_nfm_bank(C.byref(self.h), desc.h, block_size_out, 2 if input_i16 else int(bool(input_u8))), "sdrhip_pipe_nfm_bank")
             self.input_u8, self.input_i16 = bool(input_u8), bool(input_i16)
             self.complex_in = True
+        elif kind in ("am_bank_audio", "nfm_bank_audio"):
+            if input_u8 and input_i16:
+                raise ValueError(f"Pipe.{kind}: input_u8 and input_i16 exclude each other")
+            bank, tail = desc
+            fn = lib.sdrhip_pipe_am_bank_audio if kind == "am_bank_audio" else lib.sdrhip_pipe_nfm_bank_audio
+            check(fn(C.byref(self.h), bank.h, tail.h, 2 if input_i16 else int(bool(input_u8))), "sdrhip_pipe_" + kind)
+            self.input_u8, self.input_i16 = bool(input_u8), bool(input_i16)
+            self.complex_in = True
         elif kind == "spectrum":
             hop, group, reduce, unit, floor_db = spectrum_args
             check(lib.sdrhip_pipe_spectrum(C.byref(self.h), desc.h, int(hop), int(group), int(reduce), int(unit), float(floor_db)),
@@ -1656,6 +1749,17 @@ class Pipe(_Handle):
         """The narrow-band FM bank on host blocks: cfloat, u8 IQ or int16 IQ blocks in, every channel's fmDemod output (started from
         (0, 0), its state kept on the device) in blocks of block_size_out floats out."""
         return Pipe("nfm_bank", nfm_bank, block_size_out, input_u8=input_u8, input_i16=input_i16)
+
+    @staticmethod
+    def am_bank_audio(am_bank, tail, input_u8=False, input_i16=False):
+        """The AM bank and its audio stages on host blocks: IQ blocks in, every channel's audio -- Pipe.am_bank's blocks >->
+        firResampler >-> firFilter >-> (* gain), all with the AudioTail's block -- in blocks of tail.block floats out."""
+        return Pipe("am_bank_audio", (am_bank, tail), tail.block, input_u8=input_u8, input_i16=input_i16)
+
+    @staticmethod
+    def nfm_bank_audio(nfm_bank, tail, input_u8=False, input_i16=False):
+        """The narrow-band FM bank and its audio stages on host blocks: as Pipe.am_bank_audio behind Pipe.nfm_bank."""
+        return Pipe("nfm_bank_audio", (nfm_bank, tail), tail.block, input_u8=input_u8, input_i16=input_i16)
 
     @staticmethod
     def spectrum(spectrum, hop=None, group=1, reduce=REDUCE_MEAN_MAGNITUDE, unit=UNIT_LINEAR, floor_db=-200.0):
@@ -1754,7 +1858,7 @@ class Pipe(_Handle):
         return self._pop(check(lib.sdrhip_pipe_restore(self.h, state, len(state)), "sdrhip_pipe_restore"))
 
     def _pop(self, ready):
-        if self.kind in ("tuner_bank", "am_bank", "nfm_bank"):
+        if self.kind in ("tuner_bank", "am_bank", "nfm_bank", "am_bank_audio", "nfm_bank_audio"):
             if ready <= 0:
                 return []
             got = self.pop_rows(ready)
