@@ -2,6 +2,7 @@
  *
  *     airband_replay CAPTURE TAPS.f32 OUT_PREFIX --channels NUM/DEN[,NUM/DEN...] [--no-dc] [--factor D] [--block-out N] [--push SAMPLES] [--s16]
  *                    [--audio RESAMP_TAPS.f32 AUDIO_HALF_TAPS.f32 [--ratio I/D] [--gain G]]
+ *                    [--narrow TAPS2.f32 D2 [--block-mid N]]
  *
  * CAPTURE: interleaved unsigned 8-bit (I, Q) pairs (an RTL-SDR dump); with --s16 interleaved signed 16-bit pairs in host byte order (a
  * BladeRF dump).  TAPS.f32: the decimator's coefficients, raw float32.  Channel j is the capture shifted by NUM/DEN cycles per sample
@@ -12,6 +13,9 @@
  * With --audio the files hold the receiver's AUDIO instead: that signal resampled by I/D (default 3/10) with the taps of
  * RESAMP_TAPS.f32, filtered with the symmetric filter whose first half is AUDIO_HALF_TAPS.f32 and multiplied by G (default 1), every
  * Pipe of those stages with blocks of N -- sdrhip_pipe_am_bank_audio over an sdrhip_audio_tail, still ONE Pipe.
+ * With --narrow the files hold the NARROW channel instead: a second complex decimator by D2 with the coefficients of TAPS2.f32 between
+ * the first decimator and the demodulator -- firDecimator deci1 N_mid >-> firDecimator deci2 N >-> demodulator, N_mid from --block-mid
+ * (default 1024 stage-1 outputs) -- as ONE Pipe still: sdrhip_pipe_narrow_bank over sdrhip_narrow_bank.  --narrow excludes --audio.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -63,7 +67,8 @@ static void drain(sdrhip_pipe *p, int ready, int channels, int block_out, float 
 int main(int argc, char **argv)
 {
     const char *spec = NULL;
-    const char *resamp_path = NULL, *audio_path = NULL;
+    const char *resamp_path = NULL, *audio_path = NULL, *narrow_path = NULL;
+    int factor2 = 0, block_mid = 1024;
     int factor = 8, block_out = 1024, push = 8192, s16 = 0, dc = 1, interp = 3, decim = 10;
     float gain = 1.0f;
     if (argc < 4) {
@@ -80,11 +85,19 @@ int main(int argc, char **argv)
             i++;
             continue;
         }
+        if (!strcmp(argv[i], "--narrow")) {
+            if (i + 2 >= argc) { fprintf(stderr, "airband_replay: --narrow needs TAPS2.f32 D2\n"); return 2; }
+            narrow_path = argv[i + 1];
+            factor2 = atoi(argv[i + 2]);
+            i++;
+            continue;
+        }
         if (i + 1 >= argc) { fprintf(stderr, "airband_replay: %s needs a value\n", argv[i]); return 2; }
         if (!strcmp(argv[i], "--channels")) spec = argv[i + 1];
         else if (!strcmp(argv[i], "--factor")) factor = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--block-out")) block_out = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--push")) push = atoi(argv[i + 1]);
+        else if (!strcmp(argv[i], "--block-mid")) block_mid = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--gain")) gain = (float)atof(argv[i + 1]);
         else if (!strcmp(argv[i], "--ratio")) {
             if (sscanf(argv[i + 1], "%d/%d", &interp, &decim) != 2) { fprintf(stderr, "airband_replay: --ratio I/D\n"); return 2; }
@@ -92,6 +105,11 @@ int main(int argc, char **argv)
         else { fprintf(stderr, "airband_replay: unknown option %s\n", argv[i]); return 2; }
     }
     if (!spec || factor < 1 || block_out < 1 || push < 1) { fprintf(stderr, "airband_replay: --channels NUM/DEN[,...] is required\n"); return 2; }
+
+    if (narrow_path && (resamp_path || factor2 < 1 || block_mid < 1)) {
+        fprintf(stderr, "airband_replay: --narrow TAPS2.f32 D2 [--block-mid N], without --audio\n");
+        return 2;
+    }
 
     /* the channels' shift tables */
     float *tables[MAX_CH];
@@ -120,7 +138,16 @@ int main(int argc, char **argv)
     if (sdrhip_am_bank_create(&am, bank, dc) != SDRHIP_OK) die("sdrhip_am_bank_create");
     sdrhip_pipe *pipe = NULL;
     sdrhip_audio_tail *tail = NULL;
-    if (resamp_path) {
+    sdrhip_decimator *deci2 = NULL;
+    sdrhip_narrow_bank *narrow = NULL;
+    if (narrow_path) {
+        int nt2 = 0;
+        float *t2 = read_floats(narrow_path, &nt2);
+        if (sdrhip_decimator_create(&deci2, 2 /* the AVX order */, 1 /* complex data */, factor2, t2, nt2) != SDRHIP_OK) die("sdrhip_decimator_create");
+        free(t2);
+        if (sdrhip_narrow_bank_create(&narrow, bank, deci2, SDRHIP_NARROW_ENV, dc) != SDRHIP_OK) die("sdrhip_narrow_bank_create");
+        if (sdrhip_pipe_narrow_bank(&pipe, narrow, block_mid, block_out, s16 ? 2 : 1) != SDRHIP_OK) die("sdrhip_pipe_narrow_bank");
+    } else if (resamp_path) {
         int nr = 0, na = 0;
         float *rt = read_floats(resamp_path, &nr), *ah = read_floats(audio_path, &na);
         if (sdrhip_audio_tail_create(&tail, 2 /* the AVX order */, interp, decim, rt, nr, ah, na, gain, block_out) != SDRHIP_OK)
@@ -167,6 +194,8 @@ int main(int argc, char **argv)
     free(taps);
     sdrhip_pipe_destroy(pipe);
     sdrhip_audio_tail_destroy(tail);
+    sdrhip_narrow_bank_destroy(narrow);
+    sdrhip_decimator_destroy(deci2);
     sdrhip_am_bank_destroy(am);
     sdrhip_tuner_bank_destroy(bank);
     return 0;

@@ -669,6 +669,93 @@ long long sdrhip_debug_nfm_bank_launches(void);
  * process-wide; sdrhip_nfm_bank_run never takes it */
 long long sdrhip_debug_nfm_bank_cross_launches(void);
 
+/* ---- narrow-channel bank: a second decimator and the demodulator behind the tuner bank ---- */
+/* The AM and narrow-band FM banks demodulate at the tuner bank's output rate, 150 .. 300 ksample/s; the channels they are named for are
+ * 8.33 / 12.5 / 25 kHz wide, and a demodulator is non-linear: the noise of the whole band it is fed lands in the audio.  The narrow
+ * bank puts a second complex decimator in front of it:   tuner -> firDecimator D1 -> firDecimator D2 -> (magnitude | fmDemod) [-> dcBlocker]
+ * Create: tuner_bank and decimator2 are BORROWED and must outlive the bank.  decimator2 is an sdrhip_decimator on complex data
+ * (decimateAVXRC and its kin), factor D2, prepared length Lp2 = sdrhip_decimator_num_coeffs.  form: SDRHIP_NARROW_ENV (`magnitude`) or
+ * SDRHIP_NARROW_FM (fmDemod); dc_block (dcBlocker behind the envelope) is legal with SDRHIP_NARROW_ENV only.  SDRHIP_ERR_ARG (and
+ * *b = NULL) for a null tuner bank, a null decimator, a decimator on real data, a form out of range, dc_block outside 0 / 1 and
+ * dc_block with SDRHIP_NARROW_FM.
+ * Definition (and route 2): channel j's row is d_out + j * out_stride floats and holds the stage-2 outputs [k_begin, k_end) of
+ *   - sdrhip_tuner_bank_run / _run_u8 / _run_i16 over the stage-1 outputs [j_begin, j_end) = [k_begin D2, (k_end - 1) D2 + Lp2)
+ *     (sdrhip_narrow_bank_stage1_range; an empty range gives j_begin == j_end) with seam_block, into complex rows of the workspace,
+ *   - sdrhip_decimator_run_rows(decimator2, ..., in_base = j_begin, seam_block2, route 0),
+ *   - sdrhip_am_demod_run_rows (ENV), or sdrhip_fm_demod_run_rows with d_last_iq = d_state and d_last_out = d_final (FM),
+ *   - with dc_block, sdrhip_dc_blocker_run_rows from and to d_dc_state, with a workspace and the default run-in
+ * -- bit for bit on every route, for every pair of seam blocks, in_base, cut into consecutive launches and out_stride.  Floats of
+ * d_out outside the K rows' [0, k_end - k_begin) are not touched.
+ * seam_block is the first decimator Pipe's input block in samples, as sdrhip_tuner_bank_run takes it.  seam_block2 counts STAGE-1
+ * OUTPUTS: the first decimator Pipe's output block size, which is the second one's input block; 0 = no seams, otherwise at least Lp2.
+ * d_state / d_final: K (re, im) pairs, every channel's STAGE-2 output k_begin - 1 and k_end - 1; SDRHIP_NARROW_FM only (NULL with ENV),
+ * NULL is legal, the two must not overlap, and consecutive runs over consecutive ranges that swap them are one stream: the rules of
+ * sdrhip_nfm_bank_run.  d_dc_state: 2 K device floats, read and written, with dc_block and NULL without; THE STATE BELONGS TO OUTPUT
+ * k_begin, as sdrhip_am_bank_run's does, and consecutive runs that reuse it are one stream.
+ * Workspace: sdrhip_narrow_bank_workspace_bytes(b, count) bytes for count = k_end - k_begin outputs, 16-byte aligned, used during the
+ * run only: the stage-1 complex rows (16-byte aligned rows, laid out by the object), on routes 0 and 2 the stage-2 complex rows, and
+ * with dc_block the envelope rows and dcBlocker's own.  The function answers for the bank's CURRENT route setting: route 1's figure is
+ * at most route 2's, a workspace of route 2's size serves every route, and route 0 asks for route 2's because it may fall back.  0 for
+ * a null bank, a count outside 1 .. 2^31 - 2 and a count whose stage-1 range has 2^31 - 1 outputs or more.
+ * Run: SDRHIP_ERR_ARG before any device work, with nothing written, for whatever the composed calls refuse (a range outside
+ * 0 <= k_begin <= k_end, seam_block in (0, numCoeffs), out_stride < k_end - k_begin with more than one channel, an int16 input off a
+ * multiple of 4, the tuner bank's route 1 forced on a stage-1 launch it does not serve, ...), a first window before d_in
+ * (j_begin D1 < in_base), 0 < seam_block2 < Lp2 (or a negative one), a workspace that is null, short or not 16-byte aligned, state
+ * pointers that do not match the form, overlapping state arrays, a d_out or a state array off a float's alignment, and route 1 forced
+ * on a shape it does not serve.  An empty range is SDRHIP_OK: with SDRHIP_NARROW_FM it copies d_state (or zeros) to d_final, the dc state
+ * is left as it is, no workspace is asked for.  Asynchronous on `stream`; after the first run a run on route 1 makes no allocation, no
+ * host synchronisation and no host-to-device copy.  A bank is immutable after create (but for set_route) and may be shared by host
+ * threads; two streams take two sets of state arrays and two workspaces.
+ * Routes (same bits).  1 = fused: the tuner bank on ITS route setting into the workspace rows, then exactly ONE launch of
+ * k_narrow_rows for all channels -- the second decimator with the demodulator as its store: one workgroup per (tile of 256 outputs,
+ * channel), the tile's input span staged into LDS with 16-byte loads, one thread per output, a One output summed in decimateAVXRC's
+ * order, a Cross output sequentially by the same thread (any number of seams a tile), then `magnitude`, or fmDemod's phase with the
+ * predecessor from the neighbouring thread, from an overlap of one output between tiles, or from d_state; the last tile writes
+ * d_final.  No stage-2 complex row is written or read back.  With dc_block the sdrhip_dc_blocker_run_rows launch set follows, from
+ * envelope rows in the workspace.  It serves the AVX order, D2 <= 16, Lp2 <= 128 and seam_block2 equal to 0 or in [Lp2, 2^30), and is
+ * SDRHIP_ERR_ARG elsewhere.  2 = composed: the calls of the definition.  0 = auto (default): route 1 where it fits AND the run lies at
+ * points of the measured sweep where route 1's slowest round was below route 2's fastest for all three input types
+ * (tools/narrow_bank_bench.py, profiles/narrow_bank_bench.txt: 1 / 2 / 8 / 32 channels x launches of 8192, 2^17, 2^20 and 2^24 input
+ * samples through the 128-tap / 8 tuner bank -- 1009 / 16369 / 131057 / 2097137 stage-1 outputs a channel -- u8 / cfloat / int16, the
+ * envelope form without and with dcBlocker and the fmDemod form, second decimators 24 taps / 4 and 61 taps / 5, (seam_block,
+ * seam_block2) = (0, 0) and (8192, 1024), the two routes alternating in one process, 7 rounds, windows of 0.05 s; 576 points).  The rule
+ * is the transcript's closing tables, held as masks in narrow_bank.cpp, over count = k_end - k_begin against the measured launches'
+ * 247 / 4087 / 32759 / 524279 outputs a channel (factor 4) and 190 / 3262 / 26199 / 419415 (factor 5): a count at a measured size takes
+ * that point, between two measured sizes both neighbours must be ahead, and a channel count between two measured ones takes both
+ * neighbours.  Without dcBlocker route 1 is ahead at 120 of the 128 table cells: at every cell up to 2^20 samples
+ * (medians 0.35 .. 0.94 of route 2's time: 10.8 against 13.7 us for one channel at 8192 samples of u8, envelope, 24 / 4; 19.8 against
+ * 40.9 us for 8 channels at 2^17 samples, fmDemod, 61 / 5, seamed) and NOT at 2^24 samples with 8 and 32 channels at factor 4 (0.97
+ * .. 1.04: one thread per output is no faster than the banked tile kernel there).  With dcBlocker its walk is most of either route
+ * (0.81 .. 1.08, level from 2^20 samples on) and 49 of 64 cells are ahead.  NOT MEASURED, hence route 2: counts below the smallest or
+ * above the largest measured one, more than 32 channels, second factors other than 4 and 5,
+ * more prepared taps than the measured decimator of that factor (24, 64; fewer are held to the rule unmeasured), seam_block2 other
+ * than 0 and 1024.  seam_block and the tuner bank's own shape are not told apart: stage 1 is the same call on both routes. */
+#define SDRHIP_NARROW_ENV 0
+#define SDRHIP_NARROW_FM  1
+typedef struct sdrhip_narrow_bank sdrhip_narrow_bank;
+int sdrhip_narrow_bank_create(sdrhip_narrow_bank **b, const sdrhip_tuner_bank *tuner_bank, const sdrhip_decimator *decimator2, int form,
+                              int dc_block);
+void sdrhip_narrow_bank_destroy(sdrhip_narrow_bank *b);
+int sdrhip_narrow_bank_channels(const sdrhip_narrow_bank *b);
+int sdrhip_narrow_bank_set_route(sdrhip_narrow_bank *b, int route);          /* 0 auto, 1 fused, 2 composed */
+size_t sdrhip_narrow_bank_workspace_bytes(const sdrhip_narrow_bank *b, int64_t count);
+/* host arithmetic: the stage-1 outputs [*j_begin, *j_end) that stage-2 outputs [k_begin, k_end) read */
+int sdrhip_narrow_bank_stage1_range(const sdrhip_narrow_bank *b, int64_t k_begin, int64_t k_end, int64_t *j_begin, int64_t *j_end);
+int sdrhip_narrow_bank_run(const sdrhip_narrow_bank *b, void *stream, const float *d_in, int64_t in_base, float *d_out, int64_t out_stride,
+                           int64_t k_begin, int64_t k_end, int64_t seam_block, int64_t seam_block2, const float *d_state, float *d_final,
+                           float *d_dc_state, void *d_workspace, size_t workspace_bytes);
+int sdrhip_narrow_bank_run_u8(const sdrhip_narrow_bank *b, void *stream, const uint8_t *d_in_iq, int64_t in_base, float *d_out,
+                              int64_t out_stride, int64_t k_begin, int64_t k_end, int64_t seam_block, int64_t seam_block2,
+                              const float *d_state, float *d_final, float *d_dc_state, void *d_workspace, size_t workspace_bytes);
+int sdrhip_narrow_bank_run_i16(const sdrhip_narrow_bank *b, void *stream, const int16_t *d_in_iq, int64_t in_base, float *d_out,
+                               int64_t out_stride, int64_t k_begin, int64_t k_end, int64_t seam_block, int64_t seam_block2,
+                               const float *d_state, float *d_final, float *d_dc_state, void *d_workspace, size_t workspace_bytes);
+/* launches of k_narrow_rows (route 1: exactly one per run; none counts in sdrhip_debug_fir_rows_launches,
+ * sdrhip_debug_am_demod_launches or sdrhip_debug_rows_launches), process-wide */
+long long sdrhip_debug_narrow_bank_launches(void);
+/* outputs a tile of k_narrow_rows advances by: 256 (ENV), 255 (FM: tiles overlap by one output); 0 for a form out of range */
+int sdrhip_debug_narrow_bank_tile(int form);
+
 /* The FIR operators over rows: the filter, decimator and resampler stages behind a bank (second decimator per channel, resampler
  * and audio filter per station) in one launch set instead of one call per row.  in_base, k_begin, k_end, seam_block and out_block
  * mean what they mean to sdrhip_filter_run / sdrhip_decimator_run / sdrhip_resampler_run and are the same for every row; row r's
@@ -1394,6 +1481,23 @@ int sdrhip_pipe_nfm_bank(sdrhip_pipe **p, const sdrhip_nfm_bank *b, int block_si
  * a tail of block 0 and an input_type outside 0 .. 2.  The bank and the tail are borrowed and must outlive the pipe. */
 int sdrhip_pipe_am_bank_audio(sdrhip_pipe **p, const sdrhip_am_bank *b, const sdrhip_audio_tail *tail, int input_type);
 int sdrhip_pipe_nfm_bank_audio(sdrhip_pipe **p, const sdrhip_nfm_bank *b, const sdrhip_audio_tail *tail, int input_type);
+/* The narrow-channel bank (sdrhip_narrow_bank_*) on host blocks:
+ *     firDecimator deci1 block_mid >-> firDecimator deci2 block_size_out >-> P.map (magnitude | fmDemod) [>-> dcBlockingFilter]
+ * for the K channels, cfloat (input_type 0), u8 IQ (1) or int16 IQ (2) blocks in, blocks of block_size_out floats per channel out
+ * through sdrhip_pipe_pop_rows / _pop.  The narrow bank -- and through it the tuner bank and the second decimator -- is BORROWED.
+ * The bank part of a submission is the tuner bank Pipe's, unchanged (the uniform route and the ragged route: one all-Cross launch plus
+ * one banked launch), but writes its complex rows behind the carried history of a device rows buffer: the mechanism of the audio
+ * Pipes with complex elements.  ONE narrow run then computes the stage-2 outputs that became ready -- those of the WHOLE blocks of
+ * block_mid stage-1 outputs so far: stage 2 only ever sees blocks of exactly block_mid, whatever the push sizes were -- with
+ * seam_block2 = block_mid into the result chunk: the fused launch (route 1 of sdrhip_narrow_bank_run) wherever it fits, else the
+ * composed calls, whatever the bank's route setting and auto rule; a 2-D device copy carries the rows' unread tail to the front of a
+ * second buffer.  A submission that completes no stage-2 output runs the bank part only.  Every launch goes to ONE compute stream.
+ * Save / restore: the bank Pipe's state plus the stage-2 position, block_mid, the second decimator's factor and prepared length, the
+ * form, dc_block, fmDemod's pairs or dcBlocker's state, and the carried complex rows; restore refuses every mismatch of these.  Kind
+ * number 14; the states of all other kinds keep their bytes.  SDRHIP_ERR_ARG (and *p = NULL), before any device work: a null pointer
+ * or bank, block_size_out < 1, an input_type outside 0 .. 2, block_mid < numCoeffs + factor of the second decimator (the reference's
+ * `assert "decimate 1"`: after a crossover a block still holds one whole filter). */
+int sdrhip_pipe_narrow_bank(sdrhip_pipe **p, const sdrhip_narrow_bank *b, int block_mid, int block_size_out, int input_type);
 int sdrhip_pipe_push_i16(sdrhip_pipe *p, const int16_t *iq, int n_samples);
 int16_t *sdrhip_pipe_input_buffer_i16(sdrhip_pipe *p, int n_samples);
 

@@ -173,10 +173,30 @@ struct NfmBankDesc {
     mutable int route = 0;                     // 0 = auto, 1 = fused, 2 = composed
 };
 
+// The narrow-channel bank (include/sdr_hip.h, narrow_bank.cpp): a BORROWED tuner bank, a BORROWED complex second decimator, the
+// demodulator (NarrowForm, kernels.hpp) and, with the envelope form, dcBlocker.
+struct NarrowBankDesc {
+    const TunerBankDesc* tb = nullptr;
+    const FirDesc* d2 = nullptr;
+    int form = NARROW_ENV;
+    int dc_block = 0;
+    mutable int route = 0;                     // 0 = auto, 1 = fused, 2 = composed
+};
+// narrow_bank.cpp: everything behind the tuner bank over complex rows that exist (row j at d_rows + j * stride floats, element 0 =
+// stage-1 output in_base, n_in readable): ONE k_narrow_rows launch where `fused` (narrow_stage2_fits says whether it may be), else
+// the decimator's and the demodulator's rows forms; then dcBlocker's.  A caller that passes fused has made d2->ensure_device().  ws: narrow_stage2_bytes, 16-byte aligned.
+size_t narrow_stage2_bytes(const NarrowBankDesc* b, int K, int64_t count, bool fused);
+bool narrow_stage2_fits(const NarrowBankDesc* b, int K, const float* d_rows, int64_t stride, int64_t in_base, int64_t k_begin, int64_t k_end,
+                        int64_t seam_block2);
+int narrow_stage2(const NarrowBankDesc* b, hipStream_t s, bool fused, const float* d_rows, int64_t stride, int64_t in_base, int64_t n_in,
+                  float* d_out, int64_t out_stride, int64_t k_begin, int64_t k_end, int64_t seam_block2, const float* d_state, float* d_final,
+                  float* d_dc_state, float* ws, size_t ws_bytes);
+
 }  // namespace sdrhip
 
 struct sdrhip_am_bank : sdrhip::AmBankDesc {};
 struct sdrhip_nfm_bank : sdrhip::NfmBankDesc {};
+struct sdrhip_narrow_bank : sdrhip::NarrowBankDesc {};
 struct sdrhip_filter : sdrhip::FirDesc {};
 struct sdrhip_decimator : sdrhip::FirDesc {};
 struct sdrhip_resampler : sdrhip::ResampDesc {};

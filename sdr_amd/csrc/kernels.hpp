@@ -425,6 +425,22 @@ long long am_bank_launch_count();         // diagnostics: envelope tile launches
 long long am_bank_fixup_launch_count();   // diagnostics: envelope fix-up launches
 long long tuner_bank_launch_count();    // diagnostics: banked launches, every format
 long long tuner_i16_launch_count();     // diagnostics: int16 launches of the tile kernel, bank or one-row
+// kernels_narrow.hip: the narrow-channel bank's kernel (narrow_bank.cpp) -- the complex SECOND decimator over the `channels` rows the
+// tuner bank has written, with the demodulator as its store.  g is the second decimator's launch (g.in_base = the stage-1 index of
+// every row's d_in[0]); row j is d_in + j * in_stride floats, 16-byte aligned (in_stride a multiple of 4), n_in complex samples
+// readable; its outputs go to d_out + j * out_stride as one float each: am_magnitude (NARROW_ENV) or fm_phase against the output
+// before (NARROW_FM: d_state / d_final as launch_nfm_bank's, not overlapping).  Every Cross output is computed in the tile.  Serves
+// the AVX "RC" order, factor <= 16, up to 128 prepared taps (a multiple of 4), seam 0 or in [Lp, 2^30); ONE launch, counted;
+// false = not this shape or a window outside the rows, nothing launched.
+enum NarrowForm : int { NARROW_ENV = 0, NARROW_FM = 1 };
+constexpr int kNarrowTileThreads = 256, kNarrowMaxFactor = 16, kNarrowMaxTaps = 128;
+// outputs a tile advances by: NARROW_FM's tiles overlap by one output (the predecessor of a tile's first phase)
+__host__ __device__ constexpr int narrow_tile_advance(int form) { return form == NARROW_FM ? kNarrowTileThreads - 1 : kNarrowTileThreads; }
+int narrow_tile_count(int form, int count);
+bool narrow_rows_fits(const Geom& g, ComplexOrder corder, int channels, const float* d_in, int64_t in_stride);
+bool launch_narrow_rows(hipStream_t s, const Geom& g, int form, ComplexOrder corder, const float* d_plain_taps, const float* d_in,
+                        int64_t in_stride, int64_t n_in, float* d_out, int64_t out_stride, int channels, const float* d_state, float* d_final);
+long long narrow_bank_launch_count();     // diagnostics: launches of k_narrow_rows
 // Outputs [g.k_begin, g.k_begin + g.count) of every channel in the reference's sequential order, all of them (g.seamBI is not read):
 // the Cross part of a ragged push of the tuner bank's Pipe (pipes.cpp), one thread per (channel, output).  The refusals of
 // launch_tuner_bank for channels and stride, no alignment beyond the element's own; false = refused, nothing launched.

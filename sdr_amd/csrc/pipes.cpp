@@ -49,6 +49,8 @@ constexpr PipeKind PK_NFM_BANK = static_cast<PipeKind>(PK_SPECTRUM + 1);
 // The audio Pipes of the two banks (sdrhip_pipe_am_bank_audio, sdrhip_pipe_nfm_bank_audio), the next two numbers (12, 13).
 constexpr PipeKind PK_AM_BANK_AUDIO = static_cast<PipeKind>(PK_NFM_BANK + 1);
 constexpr PipeKind PK_NFM_BANK_AUDIO = static_cast<PipeKind>(PK_NFM_BANK + 2);
+// The narrow-channel bank's Pipe (sdrhip_pipe_narrow_bank), the next number (14).
+constexpr PipeKind PK_NARROW_BANK = static_cast<PipeKind>(PK_NFM_BANK + 3);
 
 struct sdrhip_pipe {
     PipeKind kind;
@@ -88,6 +90,21 @@ struct sdrhip_pipe {
     DevBuf y_rows[2], tail_ws;
     int y_cur = 0;
     int64_t y_stride = 0, y_n = 0, a_done = 0;
+    // PK_NARROW_BANK: the tuner bank's Pipe with the narrow bank's stage 2 (a BORROWED sdrhip_narrow_bank: second decimator, demodulator,
+    // dcBlocker) behind it on the device, by the audio Pipes' mechanism with COMPLEX elements: the bank part writes complex rows into
+    // y_rows[y_cur] behind the y_n carried stage-1 outputs, one narrow_stage2 run with seam_block2 = block_mid computes the stage-2
+    // outputs [a_done, narrow_ready(m_end)) into the chunk -- stage 2 sees whole blocks of block_mid only, as the second firDecimator
+    // behind `firDecimator deci1 block_mid` does -- and the elements from stage-1 output a_end * D2 on are carried.  fmDemod's pairs
+    // live in nfm_state (swapped after every narrow run), dcBlocker's in dc_state.  block_out is the Pipe's own output block.
+    const NarrowBankDesc* narrow = nullptr;
+    int64_t block_mid = 0;
+    bool rows_tail() const { return tail != nullptr || narrow != nullptr; }
+    int yw() const { return narrow ? 2 : 1; }             // floats per carried element
+    int64_t narrow_ready(int64_t m) const
+    {
+        const int64_t n1 = m / block_mid * block_mid;
+        return n1 >= narrow->d2->Lp ? (n1 - narrow->d2->Lp) / narrow->d2->factor + 1 : 0;
+    }
     bool am_kind() const { return kind == PK_AM_BANK || kind == PK_AM_BANK_AUDIO; }
     bool nfm_kind() const { return kind == PK_NFM_BANK || kind == PK_NFM_BANK_AUDIO; }
     // PK_SPECTRUM: the waterfall Pipe over a borrowed spectrum object.  Elements are samples in the object's own type (fmt); output
@@ -206,6 +223,8 @@ static int grow(DevBuf& b, size_t bytes, hipStream_t s)
 // launches on s that still use the old buffers and moves the y_n carried elements of every row over.
 static int audio_rows_room(sdrhip_pipe* p, int64_t need, hipStream_t s)
 {
+    const int64_t w = p->yw();
+    need *= w;
     if (need <= p->y_stride) return SDRHIP_OK;
     const int K = p->rows();
     const int64_t stride = row_floats(need + need / 4 + 512);
@@ -216,7 +235,7 @@ static int audio_rows_room(sdrhip_pipe* p, int64_t need, hipStream_t s)
     SDRHIP_CHECK_HIP(hipStreamSynchronize(s));
     if (p->y_n > 0)
         SDRHIP_CHECK_HIP(hipMemcpy2D(bigger[0].p, (size_t)stride * sizeof(float), p->y_rows[p->y_cur].p, (size_t)p->y_stride * sizeof(float),
-                                     (size_t)p->y_n * sizeof(float), (size_t)K, hipMemcpyDeviceToDevice));
+                                     (size_t)(p->y_n * w) * sizeof(float), (size_t)K, hipMemcpyDeviceToDevice));
     for (int i = 0; i < 2; i++) {
         std::swap(p->y_rows[i].p, bigger[i].p);
         std::swap(p->y_rows[i].cap, bigger[i].cap);
@@ -250,6 +269,44 @@ static int audio_rows_tail(sdrhip_pipe* p, hipStream_t s, float* d_chunk, int64_
     if (keep > 0)
         SDRHIP_CHECK_HIP(hipMemcpy2DAsync(p->y_rows[p->y_cur ^ 1].p, (size_t)p->y_stride * sizeof(float), y + (n_y - keep),
                                           (size_t)p->y_stride * sizeof(float), (size_t)keep * sizeof(float), (size_t)K,
+                                          hipMemcpyDeviceToDevice, s));
+    p->y_cur ^= 1;
+    p->y_n = keep;
+    return SDRHIP_OK;
+}
+
+// The narrow Pipe's part behind the bank part of a submission that wrote the complex stage-1 outputs [m_done, m_done + count) of every
+// row: the stage-2 outputs [a_done, a_end) into the chunk by ONE narrow_stage2 run (none when a_end == a_done) -- the fused launch
+// wherever it fits, whatever the bank's route setting and auto rule (those belong to sdrhip_narrow_bank_run) -- then the carry: the
+// elements from stage-1 output a_end * D2 on go to the front of the other rows buffer.
+static int narrow_rows_tail(sdrhip_pipe* p, hipStream_t s, float* d_chunk, int64_t m_done, int64_t count, int64_t a_end)
+{
+    const int K = p->rows();
+    const NarrowBankDesc* nb = p->narrow;
+    const int64_t n_y = p->y_n + count, y_base = m_done - p->y_n;
+    if (a_end == p->a_done) {
+        p->y_n = n_y;
+        return SDRHIP_OK;
+    }
+    float* y = (float*)p->y_rows[p->y_cur].p;
+    const int64_t n = a_end - p->a_done;
+    const bool fused = narrow_stage2_fits(nb, K, y, p->y_stride, y_base, p->a_done, a_end, p->block_mid);
+    const size_t ws = narrow_stage2_bytes(nb, K, n, fused);
+    int rc = grow(p->tail_ws, ws > 16 ? ws : 16, s);
+    if (rc != SDRHIP_OK) return rc;
+    const bool fm = nb->form == NARROW_FM;
+    if (fused && (rc = nb->d2->ensure_device()) != SDRHIP_OK) return rc;
+    rc = narrow_stage2(nb, s, fused, y, p->y_stride, y_base, n_y, d_chunk, n, p->a_done, a_end, p->block_mid,
+                       fm ? (const float*)p->nfm_state[p->nfm_cur].p : nullptr, fm ? (float*)p->nfm_state[p->nfm_cur ^ 1].p : nullptr,
+                       nb->dc_block ? (float*)p->dc_state.p : nullptr, (float*)p->tail_ws.p, ws);
+    if (rc != SDRHIP_OK) return rc;
+    if (fm) p->nfm_cur ^= 1;
+    int64_t keep = m_done + count - a_end * nb->d2->factor;
+    if (keep < 0) keep = 0;
+    if (keep > n_y) keep = n_y;
+    if (keep > 0)
+        SDRHIP_CHECK_HIP(hipMemcpy2DAsync(p->y_rows[p->y_cur ^ 1].p, (size_t)p->y_stride * sizeof(float), y + 2 * (n_y - keep),
+                                          (size_t)p->y_stride * sizeof(float), (size_t)(2 * keep) * sizeof(float), (size_t)K,
                                           hipMemcpyDeviceToDevice, s));
     p->y_cur ^= 1;
     p->y_n = keep;
@@ -312,10 +369,11 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
     // predecessor's left on the device
     const bool nfm = p->nfm_kind();
     const bool am = p->am_kind() || nfm;      // (the narrow-band FM bank's Pipe makes the same choice)
-    const bool audio = p->tail != nullptr;    // (the demodulated rows live on the device from submission to submission)
+    const bool audio = p->rows_tail();        // (the bank part's rows live on the device from submission to submission)
+    const int eo = p->narrow ? 2 : p->esz_out();      // floats per output of the bank part (the narrow Pipe's is complex, its chunk is not)
     if (p->am_dc || nfm || audio) cs = e.compute[0];
     const HostStream::Route route = !direct ? HostStream::kCopyEngines : (rows > 1 || am) ? HostStream::kSlotStream : HostStream::kInPlace;
-    if ((p->kind == PK_TUNER_BANK || am) && route != HostStream::kInPlace) {
+    if ((p->kind == PK_TUNER_BANK || p->kind == PK_NARROW_BANK || am) && route != HostStream::kInPlace) {
         // the copy may land anywhere in the slot's device buffer: put the banked launch's first window on a 16-byte boundary there,
         // which the staging buffer cannot promise once a block had an odd size
         const int64_t k0 = uniform_seam > 0 ? m_done : m_split;
@@ -325,7 +383,7 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
     // the audio Pipes: the chunk holds the audio outputs that became ready, [a_done, a_end) of every row
     int64_t a_end = p->a_done;
     if (audio) {
-        a_end = sdrhip_audio_tail_ready(p->tail, m_end);
+        a_end = p->narrow ? p->narrow_ready(m_end) : sdrhip_audio_tail_ready(p->tail, m_end);
         if (a_end < p->a_done) a_end = p->a_done;
     }
     const int64_t row_len = audio ? a_end - p->a_done : (m_end - m_done) * p->esz_out();
@@ -353,7 +411,7 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
         int64_t fin_stride = row_len;
         if (audio) {
             if ((r = audio_rows_room(p, p->y_n + count, s)) != SDRHIP_OK) return r;
-            fin = (float*)p->y_rows[p->y_cur].p + p->y_n;
+            fin = (float*)p->y_rows[p->y_cur].p + p->y_n * p->yw();
             fin_stride = p->y_stride;
         }
         float* out = fin;
@@ -375,7 +433,7 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
             iq = (float*)p->am_iq[si].p;
         }
         r = submit_parts(m_done, m_split, m_end, uniform_seam, [&](int64_t k0, int64_t k1, int64_t seam, int64_t off) {
-            float* o = out + off * p->esz_out();
+            float* o = out + off * eo;
             if (form.kind == BankForm::PHASE) {
                 // each launch takes the state its predecessor left and leaves the next one's in the other array
                 form.d_state = (const float*)p->nfm_state[p->nfm_cur].p;
@@ -394,6 +452,7 @@ static int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
                                    out + (size_t)K * (size_t)np, 0);
             SDRHIP_CHECK_HIP(hipGetLastError());
         }
+        if (p->narrow) return narrow_rows_tail(p, s, dout, m_done, count, a_end);
         return audio ? audio_rows_tail(p, s, dout, m_done, count, a_end) : SDRHIP_OK;
     }, audio && m_end > m_done);
     if (rc != SDRHIP_OK) return rc;
@@ -748,6 +807,35 @@ int sdrhip_pipe_nfm_bank_audio(sdrhip_pipe** pp, const sdrhip_nfm_bank* a, const
     return bank_audio_pipe_new(pp, "sdrhip_pipe_nfm_bank_audio", a ? a->tb : nullptr, tail, input_type, PK_NFM_BANK_AUDIO, BankForm::PHASE, 2);
 }
 
+// The narrow bank's Pipe: firDecimator deci1 block_mid >-> firDecimator deci2 block_size_out >-> P.map (magnitude | fmDemod)
+// [>-> dcBlockingFilter] for the K channels.  The narrow bank (and through it the tuner bank and the second decimator) is borrowed.
+int sdrhip_pipe_narrow_bank(sdrhip_pipe** pp, const sdrhip_narrow_bank* nb, int block_mid, int block_size_out, int input_type)
+{
+    const char* who = "sdrhip_pipe_narrow_bank";
+    if (pp != nullptr) *pp = nullptr;
+    if (pp == nullptr || nb == nullptr) {
+        set_error("%s: requirement `a pipe pointer and a narrow bank` violated", who);
+        return SDRHIP_ERR_ARG;
+    }
+    // after a crossover the rest of a block of block_mid still holds one whole second filter (the reference's `assert "decimate 1"`)
+    if (block_mid < nb->d2->Lp + nb->d2->factor) {
+        set_error("%s: requirement `block_mid >= numCoeffs + factor of the second decimator` violated", who);
+        return SDRHIP_ERR_ARG;
+    }
+    int rc = bank_pipe_new(pp, who, nb->tb, block_size_out, input_type, 2, PK_NARROW_BANK, BankForm::IQ, 0);
+    if (rc != SDRHIP_OK) return rc;
+    sdrhip_pipe* p = *pp;
+    p->narrow = nb;
+    p->block_mid = block_mid;
+    p->cplx_out = false;                       // the chunk and the fifo hold one float per stage-2 output
+    const size_t bytes = (size_t)p->rows() * 2 * sizeof(float);
+    if (nb->form == NARROW_FM)
+        for (int i = 0; i < 2 && rc == SDRHIP_OK; i++) rc = pipe_dev_state(pp, p->nfm_state[i], bytes, nullptr, who);
+    else if (nb->dc_block)
+        rc = pipe_dev_state(pp, p->dc_state, bytes, nullptr, who);
+    return rc;
+}
+
 int sdrhip_pipe_rows(const sdrhip_pipe* p)
 {
     SDRHIP_REQUIRE(p != nullptr, "sdrhip_pipe_rows");
@@ -1037,7 +1125,26 @@ static size_t pipe_state_audio_bytes(const sdrhip_pipe* p)
 {
     return p->tail ? sizeof(PipeStateAudio) + (size_t)p->rows() * (size_t)p->y_n * sizeof(float) : 0;
 }
-static size_t pipe_state_am_bytes(const sdrhip_pipe* p) { return pipe_state_am(p).bytes() + pipe_state_audio_bytes(p); }
+// The narrow bank's Pipe appends, behind the (absent) record above: the stage-2 position, what the state may be restored into
+// (block_mid, the second decimator's factor and prepared length, the form, dc_block), n_floats state floats (fmDemod's pairs or
+// dcBlocker's, 2 K; 0 for the plain envelope) and the y_n carried COMPLEX stage-1 outputs of every row, row after row.
+struct PipeStateNarrow {
+    int64_t a_done, y_n, block_mid;
+    int32_t D2, Lp2, form, dc_block, n_floats, reserved;
+};
+static PipeStateNarrow pipe_state_narrow(const sdrhip_pipe* p)
+{
+    const NarrowBankDesc* nb = p->narrow;
+    const bool st = nb->form == NARROW_FM || nb->dc_block;
+    return {p->a_done, p->y_n, p->block_mid, nb->d2->factor, nb->d2->Lp, nb->form, nb->dc_block, st ? 2 * p->rows() : 0, 0};
+}
+static void* pipe_narrow_floats(const sdrhip_pipe* p) { return p->narrow->form == NARROW_FM ? p->nfm_state[p->nfm_cur].p : p->dc_state.p; }
+static size_t pipe_state_narrow_bytes(const sdrhip_pipe* p)
+{
+    if (!p->narrow) return 0;
+    return sizeof(PipeStateNarrow) + (size_t)pipe_state_narrow(p).n_floats * sizeof(float) + (size_t)p->rows() * (size_t)p->y_n * 2 * sizeof(float);
+}
+static size_t pipe_state_am_bytes(const sdrhip_pipe* p) { return pipe_state_am(p).bytes() + pipe_state_audio_bytes(p) + pipe_state_narrow_bytes(p); }
 static size_t pipe_state_header_bytes(const sdrhip_pipe* p) { return sizeof(PipeStateHeader) + (pipe_state_version(p) == 2 ? sizeof(PipeStateRows) : 0); }
 // Version 3: the waterfall Pipe.  This header, the carried tail (tail_n samples in the input's own type), the rows not yet popped
 // (pending floats).  pos = samples pushed so far; the tail starts at stream sample rows_done * group * hop = pos - tail_n (skip == 0)
@@ -1141,6 +1248,19 @@ int sdrhip_pipe_save(sdrhip_pipe* p, void* buf, size_t capacity, size_t* used)
                                          (size_t)p->y_n * sizeof(float), (size_t)p->rows(), hipMemcpyDeviceToHost));
         }
     }
+    if (p->narrow) {
+        const PipeStateNarrow x = pipe_state_narrow(p);
+        memcpy(o, &x, sizeof x);
+        o += sizeof x;
+        SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));
+        if (x.n_floats > 0) {
+            SDRHIP_CHECK_HIP(hipMemcpy(o, pipe_narrow_floats(p), (size_t)x.n_floats * sizeof(float), hipMemcpyDeviceToHost));
+            o += (size_t)x.n_floats * sizeof(float);
+        }
+        if (p->y_n > 0)
+            SDRHIP_CHECK_HIP(hipMemcpy2D(o, (size_t)p->y_n * 2 * sizeof(float), p->y_rows[p->y_cur].p, (size_t)p->y_stride * sizeof(float),
+                                         (size_t)p->y_n * 2 * sizeof(float), (size_t)p->rows(), hipMemcpyDeviceToHost));
+    }
     *used = need;
     return SDRHIP_OK;
 }
@@ -1192,7 +1312,7 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
     SDRHIP_REQUIRE(h.hist_n >= 0 && h.hist_n <= h.head_cap && h.pending >= 0 && h.n_blocks >= 0 && h.E_prev >= h.hist_n && h.m_done >= 0,
                    "sdrhip_pipe_restore: inconsistent state");
     if (p->kind == PK_FILTER || p->kind == PK_DECIMATOR || p->kind == PK_RESAMPLER || p->kind == PK_TUNER || p->kind == PK_TUNER_BANK ||
-        p->am_kind() || p->nfm_kind()) {
+        p->am_kind() || p->nfm_kind() || p->kind == PK_NARROW_BANK) {
         // the next pending output must start inside what the pipe has seen, every output computable from those elements must be
         // done at most once, and the history must reach back to its first input (3 elements of alignment slack, 7 of u8, fir_submit):
         // otherwise the kernels would be sent in front of the staging buffer
@@ -1205,7 +1325,8 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
     }
     const size_t am_at = pipe_state_header_bytes(p) + p->eng.state_bytes(h.hist_n, h.pending) + (size_t)h.n_blocks * sizeof(int32_t);
     const PipeAmRecord am = pipe_state_am(p);
-    SDRHIP_REQUIRE(bytes >= am_at + am.bytes() + (p->tail ? sizeof(PipeStateAudio) : 0), "sdrhip_pipe_restore: truncated state");
+    SDRHIP_REQUIRE(bytes >= am_at + am.bytes() + (p->tail ? sizeof(PipeStateAudio) : 0) + (p->narrow ? sizeof(PipeStateNarrow) : 0),
+                   "sdrhip_pipe_restore: truncated state");
     if (am.present) {
         PipeStateAm x;
         memcpy(&x, (const unsigned char*)buf + am_at, sizeof x);
@@ -1230,9 +1351,29 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
                        "sdrhip_pipe_restore: truncated state");
         au_floats = (const unsigned char*)buf + am_at + am.bytes() + sizeof au;
     }
+    PipeStateNarrow nx;
+    memset(&nx, 0, sizeof nx);
+    const unsigned char* nx_floats = nullptr;
+    if (p->narrow) {
+        memcpy(&nx, (const unsigned char*)buf + am_at, sizeof nx);
+        const PipeStateNarrow mine = pipe_state_narrow(p);
+        SDRHIP_REQUIRE(nx.block_mid == mine.block_mid, "sdrhip_pipe_restore: the state belongs to a narrow bank pipe of another block_mid");
+        SDRHIP_REQUIRE(nx.D2 == mine.D2 && nx.Lp2 == mine.Lp2,
+                       "sdrhip_pipe_restore: the state belongs to a narrow bank pipe of another second decimator (factor or tap count)");
+        SDRHIP_REQUIRE(nx.form == mine.form && nx.dc_block == mine.dc_block && nx.n_floats == mine.n_floats,
+                       "sdrhip_pipe_restore: the state belongs to a narrow bank pipe of another form, dc_block or row count");
+        // every stage-2 output the whole blocks of stage-1 outputs so far complete is done, and the carried rows reach back to the
+        // next one's first input
+        const int64_t first = nx.a_done * (int64_t)mine.D2;
+        SDRHIP_REQUIRE(nx.a_done == p->narrow_ready(h.m_done) && nx.y_n >= 0 && nx.y_n <= h.m_done && (first >= h.m_done || nx.y_n >= h.m_done - first),
+                       "sdrhip_pipe_restore: inconsistent state");
+        SDRHIP_REQUIRE((bytes - (am_at + sizeof nx)) / sizeof(float) >= (size_t)nx.n_floats + (size_t)p->rows() * (size_t)nx.y_n * 2,
+                       "sdrhip_pipe_restore: truncated state");
+        nx_floats = (const unsigned char*)buf + am_at + sizeof nx;
+    }
     // (the one step that can fail for want of memory comes before anything is put back: a failed restore leaves the pipe fresh)
-    if (p->tail) {
-        int rc = audio_rows_room(p, au.y_n + 1, p->eng.compute[0]);
+    if (p->rows_tail()) {
+        int rc = audio_rows_room(p, (p->narrow ? nx.y_n : au.y_n) + 1, p->eng.compute[0]);
         if (rc != SDRHIP_OK) return rc;
     }
     const unsigned char* in = p->eng.restore((const unsigned char*)buf + pipe_state_header_bytes(p), h.hist_n, h.pending);
@@ -1258,6 +1399,17 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
             SDRHIP_CHECK_HIP(hipMemcpy2D(p->y_rows[p->y_cur].p, (size_t)p->y_stride * sizeof(float), au_floats, (size_t)au.y_n * sizeof(float),
                                          (size_t)au.y_n * sizeof(float), (size_t)p->rows(), hipMemcpyHostToDevice));
         p->y_n = au.y_n;
+    }
+    if (p->narrow) {
+        SDRHIP_CHECK_HIP(hipStreamSynchronize(p->eng.compute[0]));       // the create call's memsets
+        if (nx.n_floats > 0)
+            SDRHIP_CHECK_HIP(hipMemcpy(pipe_narrow_floats(p), nx_floats, (size_t)nx.n_floats * sizeof(float), hipMemcpyHostToDevice));
+        p->a_done = nx.a_done;
+        if (nx.y_n > 0)
+            SDRHIP_CHECK_HIP(hipMemcpy2D(p->y_rows[p->y_cur].p, (size_t)p->y_stride * sizeof(float), nx_floats + (size_t)nx.n_floats * sizeof(float),
+                                         (size_t)nx.y_n * 2 * sizeof(float), (size_t)nx.y_n * 2 * sizeof(float), (size_t)p->rows(),
+                                         hipMemcpyHostToDevice));
+        p->y_n = nx.y_n;
     }
     return ready_blocks(p);
 }

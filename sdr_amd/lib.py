@@ -152,6 +152,19 @@ lib.sdrhip_debug_nfm_bank_launches.argtypes = []
 lib.sdrhip_debug_nfm_bank_launches.restype = C.c_longlong
 lib.sdrhip_debug_nfm_bank_cross_launches.argtypes = []
 lib.sdrhip_debug_nfm_bank_cross_launches.restype = C.c_longlong
+lib.sdrhip_narrow_bank_create.argtypes = [C.POINTER(_vp), _vp, _vp, C.c_int, C.c_int]
+lib.sdrhip_narrow_bank_destroy.argtypes = [_vp]
+lib.sdrhip_narrow_bank_destroy.restype = None
+lib.sdrhip_narrow_bank_channels.argtypes = [_vp]
+lib.sdrhip_narrow_bank_set_route.argtypes = [_vp, C.c_int]
+lib.sdrhip_narrow_bank_workspace_bytes.argtypes = [_vp, _i64]
+lib.sdrhip_narrow_bank_workspace_bytes.restype = C.c_size_t
+lib.sdrhip_narrow_bank_stage1_range.argtypes = [_vp, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)]
+for _n in ("sdrhip_narrow_bank_run", "sdrhip_narrow_bank_run_u8", "sdrhip_narrow_bank_run_i16"):
+    getattr(lib, _n).argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, C.c_size_t]
+lib.sdrhip_debug_narrow_bank_launches.argtypes = []
+lib.sdrhip_debug_narrow_bank_launches.restype = C.c_longlong
+lib.sdrhip_debug_narrow_bank_tile.argtypes = [C.c_int]
 
 lib.sdrhip_resampler_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.c_int]
 lib.sdrhip_resampler_num_coeffs.argtypes = [_vp]
@@ -385,6 +398,7 @@ lib.sdrhip_pipe_am_bank.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int]
 lib.sdrhip_pipe_nfm_bank.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int]
 lib.sdrhip_pipe_am_bank_audio.argtypes = [C.POINTER(_vp), _vp, _vp, C.c_int]
 lib.sdrhip_pipe_nfm_bank_audio.argtypes = [C.POINTER(_vp), _vp, _vp, C.c_int]
+lib.sdrhip_pipe_narrow_bank.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int, C.c_int]
 lib.sdrhip_pipe_push_i16.argtypes = [_vp, _i16p, C.c_int]
 lib.sdrhip_pipe_input_buffer_i16.argtypes = [_vp, C.c_int]
 lib.sdrhip_pipe_input_buffer_i16.restype = _vp
@@ -1198,6 +1212,81 @@ class NfmBank(_Handle):
                   state, final, workspace, workspace_bytes, stream)
 
 
+NARROW_ENV, NARROW_FM = 0, 1
+
+
+def narrow_bank_launches():
+    """Launches of the narrow-channel bank's kernel so far: one per run on its fused route (sdrhip_debug_narrow_bank_launches)."""
+    return int(lib.sdrhip_debug_narrow_bank_launches())
+
+
+def narrow_bank_tile(form):
+    """Outputs a tile of the narrow-channel bank's kernel advances by: 256 for NARROW_ENV, 255 for NARROW_FM."""
+    return int(lib.sdrhip_debug_narrow_bank_tile(int(form)))
+
+
+class NarrowBank(_Handle):
+    """A second complex decimator and the demodulator behind every channel of a TunerBank: row j of a run holds the stage-2 outputs
+    [k_begin, k_end) of  TunerBank.run -> Decimator.run_rows -> am_demod_rows | fm_demod_rows [-> dc_blocker_rows], bit for bit on
+    every route (sdr_hip.h, sdrhip_narrow_bank_*).  form: NARROW_ENV (magnitude; dc_block adds dcBlocker from `dc_state`, 2 K device
+    floats that belong to output k_begin) or NARROW_FM (fmDemod; `state` / `final` as NfmBank's, of STAGE-2 outputs).  seam_block is
+    the first decimator Pipe's block in input samples, seam_block2 the second one's in stage-1 outputs.  Tuner bank and decimator
+    are borrowed: the object keeps references to them."""
+    _destroy = lib.sdrhip_narrow_bank_destroy
+    ROUTE_AUTO, ROUTE_FUSED, ROUTE_COMPOSED = 0, 1, 2
+
+    def __init__(self, tuner_bank, decimator, form, dc_block=False):
+        super().__init__()
+        self.tuner_bank = tuner_bank
+        self.decimator = decimator
+        self.form = int(form)
+        self.dc_block = bool(dc_block)
+        check(lib.sdrhip_narrow_bank_create(C.byref(self.h), tuner_bank.h, decimator.h, self.form, int(self.dc_block)),
+              "sdrhip_narrow_bank_create")
+
+    @property
+    def channels(self):
+        return check(lib.sdrhip_narrow_bank_channels(self.h), "sdrhip_narrow_bank_channels")
+
+    def set_route(self, route):
+        """0 = auto (sdr_hip.h), 1 = fused: the tuner bank, then ONE launch of the narrow kernel (a run it does not serve is an
+        error), 2 = composed: the calls of the definition."""
+        check(lib.sdrhip_narrow_bank_set_route(self.h, int(route)), "sdrhip_narrow_bank_set_route")
+
+    def workspace_bytes(self, count):
+        """For the current route setting; route 2's figure serves every route."""
+        return int(lib.sdrhip_narrow_bank_workspace_bytes(self.h, int(count)))
+
+    def stage1_range(self, k_begin, k_end):
+        """(j_begin, j_end): the stage-1 outputs that stage-2 outputs [k_begin, k_end) read."""
+        j0, j1 = _i64(0), _i64(0)
+        check(lib.sdrhip_narrow_bank_stage1_range(self.h, int(k_begin), int(k_end), C.byref(j0), C.byref(j1)),
+              "sdrhip_narrow_bank_stage1_range")
+        return int(j0.value), int(j1.value)
+
+    def _run(self, fn, name, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block, seam_block2, state, final, dc_state, workspace,
+             workspace_bytes, stream):
+        check(fn(self.h, stream, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block, seam_block2, state, final, dc_state, workspace,
+                 workspace_bytes), name)
+
+    def run(self, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block=0, seam_block2=0, state=None, final=None, dc_state=None,
+            workspace=None, workspace_bytes=0, stream=None):
+        """cfloat input; channel j's floats [k_begin, k_end) -> d_out + 4 * j * out_stride bytes.  Pointers are device addresses."""
+        self._run(lib.sdrhip_narrow_bank_run, "sdrhip_narrow_bank_run", d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block,
+                  seam_block2, state, final, dc_state, workspace, workspace_bytes, stream)
+
+    def run_u8(self, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block=0, seam_block2=0, state=None, final=None, dc_state=None,
+               workspace=None, workspace_bytes=0, stream=None):
+        self._run(lib.sdrhip_narrow_bank_run_u8, "sdrhip_narrow_bank_run_u8", d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block,
+                  seam_block2, state, final, dc_state, workspace, workspace_bytes, stream)
+
+    def run_i16(self, d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block=0, seam_block2=0, state=None, final=None, dc_state=None,
+                workspace=None, workspace_bytes=0, stream=None):
+        """interleaved int16 IQ input (4 bytes per sample); rows as run."""
+        self._run(lib.sdrhip_narrow_bank_run_i16, "sdrhip_narrow_bank_run_i16", d_in, in_base, d_out, out_stride, k_begin, k_end, seam_block,
+                  seam_block2, state, final, dc_state, workspace, workspace_bytes, stream)
+
+
 class FmChain(_Handle):
     """The FM receiver of examples/fm/fm.hs:34-41 as one device-resident object."""
     _destroy = lib.sdrhip_fm_chain_destroy
@@ -1707,6 +1796,14 @@ class Pipe(_Handle):
             check(fn(C.byref(self.h), bank.h, tail.h, 2 if input_i16 else int(bool(input_u8))), "sdrhip_pipe_" + kind)
             self.input_u8, self.input_i16 = bool(input_u8), bool(input_i16)
             self.complex_in = True
+        elif kind == "narrow_bank":
+            if input_u8 and input_i16:
+                raise ValueError("Pipe.narrow_bank: input_u8 and input_i16 exclude each other")
+            bank, block_mid = desc
+            check(lib.sdrhip_pipe_narrow_bank(C.byref(self.h), bank.h, int(block_mid), block_size_out, 2 if input_i16 else int(bool(input_u8))),
+                  "sdrhip_pipe_narrow_bank")
+            self.input_u8, self.input_i16 = bool(input_u8), bool(input_i16)
+            self.complex_in = True
         elif kind == "spectrum":
             hop, group, reduce, unit, floor_db = spectrum_args
             check(lib.sdrhip_pipe_spectrum(C.byref(self.h), desc.h, int(hop), int(group), int(reduce), int(unit), float(floor_db)),
@@ -1755,6 +1852,13 @@ class Pipe(_Handle):
         """The AM bank and its audio stages on host blocks: IQ blocks in, every channel's audio -- Pipe.am_bank's blocks >->
         firResampler >-> firFilter >-> (* gain), all with the AudioTail's block -- in blocks of tail.block floats out."""
         return Pipe("am_bank_audio", (am_bank, tail), tail.block, input_u8=input_u8, input_i16=input_i16)
+
+    @staticmethod
+    def narrow_bank(narrow_bank, block_mid, block_size_out, input_u8=False, input_i16=False):
+        """The narrow-channel bank on host blocks: IQ blocks in, every channel's  firDecimator deci1 block_mid >-> firDecimator deci2
+        block_size_out >-> magnitude | fmDemod [>-> dcBlockingFilter]  in blocks of block_size_out floats out (sdr_hip.h,
+        sdrhip_pipe_narrow_bank).  The NarrowBank is borrowed: the pipe keeps a reference to it."""
+        return Pipe("narrow_bank", (narrow_bank, block_mid), block_size_out, input_u8=input_u8, input_i16=input_i16)
 
     @staticmethod
     def nfm_bank_audio(nfm_bank, tail, input_u8=False, input_i16=False):
@@ -1858,7 +1962,7 @@ class Pipe(_Handle):
         return self._pop(check(lib.sdrhip_pipe_restore(self.h, state, len(state)), "sdrhip_pipe_restore"))
 
     def _pop(self, ready):
-        if self.kind in ("tuner_bank", "am_bank", "nfm_bank", "am_bank_audio", "nfm_bank_audio"):
+        if self.kind in ("tuner_bank", "am_bank", "nfm_bank", "am_bank_audio", "nfm_bank_audio", "narrow_bank"):
             if ready <= 0:
                 return []
             got = self.pop_rows(ready)
