@@ -958,6 +958,8 @@ int sdrhip_fm_chain_join(sdrhip_fm_chain *c, void *stream);
  * three; longer runs are faster on the stage kernels (every stage is VALU-bound, and a one-tile run is one workgroup).
  * Same bits. */
 int sdrhip_fm_chain_set_fused_tail(sdrhip_fm_chain *c, int mode);
+/* launches of that kernel so far, process-wide (tests assert that this path, not the stage kernels or the one-kernel chain, ran) */
+long long sdrhip_debug_fused_tail_launches(void);
 /* The WHOLE chain (convert + decimator -> fmDemod -> resampler -> audio filter * gain) as ONE kernel for launch-bound runs
  * -- BASELINE configs[4]'s 2^20-sample shard, a push of a few source blocks -- when the chain has the FM receiver's shape
  * (decimation 8 with 128 padded taps, 3/10 resampler with 64-float groups, 64 half-tap symmetric filter, AVX order, 16-byte

@@ -307,6 +307,7 @@ constexpr int kTailTileOutputs = 2046;   // audio outputs one workgroup of the f
 bool fm_tail_fused_fits(int rLp, int64_t seam);
 void launch_fm_tail_fused(hipStream_t s, const float* d_d, int64_t kd0, int64_t kd1, int64_t ky0, int64_t ky1, float* d_audio,
                           int64_t q0, int64_t q1, const FmTailTables& t);
+long long fm_tail_launch_count();   // diagnostics: launches of k_fm_tail
 // kernels_tail_rows.hip: the same tile over ROWS of real y (the audio tail behind the AM / narrow-band FM bank, audio_tail.cpp):
 // 3/10 resampler -> symmetric filter (* gain), one launch for all rows, the row on the grid's second axis.  Row r's y[0] is its
 // stream element y_base, n_y elements readable (others are read as zeros); its outputs [q0, q1) go to d_audio + r * audio_stride.

@@ -22,6 +22,8 @@
 #include "demod.hpp"
 #include "kernels.hpp"
 
+#include <atomic>
+
 namespace sdrhip {
 
 namespace {
@@ -241,8 +243,11 @@ __global__ void __launch_bounds__(TAIL_NT, 4) k_fm_tail(const float* __restrict_
     }
 }
 
+std::atomic<long long> g_tail_launches{0};
 
 }  // namespace
+
+long long fm_tail_launch_count() { return g_tail_launches.load(); }
 
 bool fm_tail_shape_ok(int ngroups, int nloop, int I, int D, const int* increments, int rLp, int ntaps, int nhalf)
 {
@@ -265,6 +270,7 @@ void launch_fm_tail_fused(hipStream_t s, const float* d_d, int64_t kd0, int64_t 
     const int64_t qa0 = (q0 / 3) * 3;
     const int64_t tiles = (q1 - qa0 + TAIL_A - 1) / TAIL_A;
     hipLaunchKernelGGL(k_fm_tail, dim3((unsigned)tiles), dim3(TAIL_NT), 0, s, d_d, d_audio, t.d_groups, t.d_rplain, t.d_fhalf, t.d_fplain, p);
+    g_tail_launches++;
 }
 
 }  // namespace sdrhip

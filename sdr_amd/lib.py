@@ -228,6 +228,8 @@ lib.sdrhip_debug_fm_bank_launches.restype = C.c_longlong
 lib.sdrhip_fm_bank_run_i16.argtypes = [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, C.c_size_t]
 lib.sdrhip_debug_fm_bank_i16_launches.argtypes = []
 lib.sdrhip_debug_fm_bank_i16_launches.restype = C.c_longlong
+lib.sdrhip_debug_fused_tail_launches.argtypes = []
+lib.sdrhip_debug_fused_tail_launches.restype = C.c_longlong
 lib.sdrhip_debug_resample_cycle_launches.restype = C.c_longlong
 lib.sdrhip_debug_decimate_real16_launches.restype = C.c_longlong
 lib.sdrhip_debug_systolic_launches.restype = C.c_longlong

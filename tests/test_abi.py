@@ -240,7 +240,8 @@ def test_route_counters_are_declared_exported_and_bound(L):
     """The route counters the GPU tests read to prove which kernel a launch size took (tests/test_gpu_bench_size.py): declared in
     sdr_hip.h, exported, and bound with a 64-bit result."""
     names = ["sdrhip_debug_systolic_launches", "sdrhip_debug_systolic_plain_launches", "sdrhip_debug_decimator_crossfix_launches",
-             "sdrhip_debug_small_chain_launches", "sdrhip_debug_fused_demod_launches", "sdrhip_debug_record_copied_calls"]
+             "sdrhip_debug_small_chain_launches", "sdrhip_debug_fused_demod_launches", "sdrhip_debug_record_copied_calls",
+             "sdrhip_debug_fused_tail_launches"]
     declared = declared_functions()
     for n in names:
         assert n in declared, f"{n} is not declared in sdr_hip.h"
