@@ -538,7 +538,7 @@ long long sdrhip_debug_spectrum_reduce_split_launches(void) { return g_spectrum_
 
 }  // extern "C"
 
-// what the waterfall Pipe (pipes.cpp) asks of the object it borrows
+// what the waterfall Pipe (pipes_spectrum.cpp) asks of the object it borrows
 namespace sdrhip {
 int spectrum_size_of(const sdrhip_spectrum* s) { return s->n; }
 int spectrum_format_of(const sdrhip_spectrum* s) { return s->format; }

@@ -87,7 +87,7 @@ bool count_ok(const NarrowBankDesc* b, int64_t count)
 // fused launch), its element 0 is stage-1 output in_base, n_in elements readable.  fused: ONE launch of k_narrow_rows; else
 // sdrhip_decimator_run_rows (route 0) into complex rows of the workspace and the demodulator's rows form.  With dc_block the envelope
 // rows pass through the workspace into sdrhip_dc_blocker_run_rows.  d_ws: narrow_stage2_bytes, 16-byte aligned.  narrow_bank_run and
-// the bank's Pipe (pipes.cpp) both end here.
+// the bank's Pipe (rows_tail, pipes_fir.cpp) both end here.
 size_t narrow_stage2_bytes(const NarrowBankDesc* b, int K, int64_t count, bool fused)
 {
     return (fused ? 0 : (size_t)K * 2 * (size_t)row_floats(count) * sizeof(float)) + dc_bytes(K, count, b->dc_block != 0);

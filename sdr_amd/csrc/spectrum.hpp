@@ -54,7 +54,7 @@ hipError_t launch_spectrum_accumulate(hipStream_t stream, const double2* work, i
 
 }  // namespace sdrhip
 
-// what the waterfall Pipe (sdrhip_pipe_spectrum, pipes.cpp) asks of the object it borrows (fft.cpp): its size, its SDRHIP_IQ_*
+// what the waterfall Pipe (sdrhip_pipe_spectrum, pipes_spectrum.cpp) asks of the object it borrows (fft.cpp): its size, its SDRHIP_IQ_*
 // format, and whether a reduce run of this group length goes through the object's one scratch buffer (the hipFFT route, or layers)
 struct sdrhip_spectrum;
 namespace sdrhip {

@@ -265,7 +265,7 @@ def test_pipe_agc_with_save_and_restore(hip):
 
 def test_save_bytes_of_a_dc_blocker_pipe_unchanged(hip):
     """The header of a Pipe state keeps its layout and version: 112 bytes, then the history, the output not yet popped and the
-    block lengths (sdrhip_pipe_state_bytes in pipes.cpp)."""
+    block lengths (sdrhip_pipe_state_bytes in pipes_state.cpp)."""
     rng = np.random.default_rng(1)
     x = rng.uniform(-1, 1, 1777).astype(np.float32)
     pipe = hip.dcBlockingFilter()

@@ -60,9 +60,10 @@ def test_create_refuses_bad_arguments_before_any_device_work(L):
 
 
 def test_the_kind_is_the_last_of_the_enum():
-    """Saved states hold the kind's number: the new kind goes at the END, so every older number keeps its meaning."""
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "sdr_amd", "csrc", "pipes.cpp")).read()
-    line = next(l for l in src.splitlines() if l.startswith("enum PipeKind"))
-    kinds = [k.strip() for k in line[line.index("{") + 1:line.index("}")].split(",")]
-    assert kinds == ["PK_FILTER", "PK_DECIMATOR", "PK_RESAMPLER", "PK_DEMOD", "PK_DCBLOCK", "PK_AGC", "PK_TUNER", "PK_TUNER_BANK", "PK_AM",
-                     "PK_AM_BANK"]
+    """Saved states hold the kind's number: the ten kinds up to the AM bank's keep theirs, 0 .. 9, the AM bank's being the last of
+    them, and every kind behind them has a number of its own."""
+    from pipe_kind_table import KIND_NUMBERS, pipe_kind_table
+    table = pipe_kind_table()
+    assert table[:10] == [(k, n) for k, n in KIND_NUMBERS.items() if n <= 9] and table[9] == ("PK_AM_BANK", 9)
+    assert len({n for _, n in table}) == len(table) == len({k for k, _ in table}), "a number or a name stands twice"
+    assert all(n >= 10 for _, n in table[10:])

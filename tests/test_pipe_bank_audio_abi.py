@@ -77,8 +77,9 @@ def test_create_refuses_bad_arguments_before_any_device_work(L, which):
 
 
 def test_the_kind_numbers_stand_behind_the_older_ones():
-    """Saved states hold the kind's number: the list of the ten oldest kinds is untouched (tests/test_pipe_am_bank_abi.py pins it), the
-    waterfall's and the narrow-band FM bank's numbers follow, and the two audio kinds come behind those."""
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "sdr_amd", "csrc", "pipes.cpp")).read()
-    assert "PK_SPECTRUM = static_cast<PipeKind>(PK_AM_BANK + 1)" in src and "PK_NFM_BANK = static_cast<PipeKind>(PK_SPECTRUM + 1)" in src
-    assert "PK_AM_BANK_AUDIO = static_cast<PipeKind>(PK_NFM_BANK + 1)" in src and "PK_NFM_BANK_AUDIO = static_cast<PipeKind>(PK_NFM_BANK + 2)" in src
+    """Saved states hold the kind's number: the ten oldest kinds keep 0 .. 9, the waterfall's (10) and the narrow-band FM bank's (11)
+    follow, the two audio kinds come behind those (12, 13), and the narrow bank's (14) is the last."""
+    from pipe_kind_table import KIND_NUMBERS, pipe_kind_table
+    table = pipe_kind_table()
+    assert table == list(KIND_NUMBERS.items()), "the whole table, name by name and number by number, in the order of the numbers"
+    assert dict(table)["PK_AM_BANK_AUDIO"] == 12 and dict(table)["PK_NFM_BANK_AUDIO"] == 13

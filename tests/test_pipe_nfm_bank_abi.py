@@ -1,9 +1,8 @@
 """The narrow-band FM bank's Pipe (sdrhip_pipe_nfm_bank) on a host without a GPU: the name is declared, exported and bound, every
-create refusal comes before any device work and leaves *p null, and the kind line of pipes.cpp is unchanged (the new kind stands
-behind it).  What the pipe COMPUTES is held to the models on the device (tests/test_gpu_pipe_nfm_bank.py)."""
+create refusal comes before any device work and leaves *p null, and the kind table of pipe.hpp gives the older kinds their numbers and this one the
+next.  What the pipe COMPUTES is held to the models on the device (tests/test_gpu_pipe_nfm_bank.py)."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -55,10 +54,8 @@ def test_create_refuses_bad_arguments_before_any_device_work(L):
 
 
 def test_the_kind_line_is_unchanged_and_the_new_kind_stands_behind_it():
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "sdr_amd", "csrc", "pipes.cpp")).read()
-    line = next(l for l in src.splitlines() if l.startswith("enum PipeKind"))
-    kinds = [k.strip() for k in line[line.index("{") + 1:line.index("}")].split(",")]
-    assert kinds == ["PK_FILTER", "PK_DECIMATOR", "PK_RESAMPLER", "PK_DEMOD", "PK_DCBLOCK", "PK_AGC", "PK_TUNER", "PK_TUNER_BANK", "PK_AM",
-                     "PK_AM_BANK"]
-    assert re.search(r"constexpr PipeKind PK_SPECTRUM = static_cast<PipeKind>\(PK_AM_BANK \+ 1\);", src)
-    assert re.search(r"constexpr PipeKind PK_NFM_BANK = static_cast<PipeKind>\(PK_SPECTRUM \+ 1\);", src), "the next number after PK_SPECTRUM"
+    """The kind table (sdr_amd/csrc/pipe.hpp) as written: the ten older kinds keep 0 .. 9, the waterfall's is 10 and this Pipe's 11."""
+    from pipe_kind_table import KIND_NUMBERS, pipe_kind_table
+    table = pipe_kind_table()
+    assert table[:12] == [(k, n) for k, n in KIND_NUMBERS.items() if n <= 11]
+    assert dict(table)["PK_SPECTRUM"] == 10 and dict(table)["PK_NFM_BANK"] == 11
