@@ -873,6 +873,36 @@ int sdrhip_audio_tail_run_rows(const sdrhip_audio_tail *t, void *stream, const f
                                int64_t n_y, float *d_audio, int64_t audio_stride, int rows, int64_t q0, int64_t q1,
                                void *d_workspace, size_t workspace_bytes);
 long long sdrhip_debug_audio_tail_launches(void);   /* launches of k_audio_tail_rows (route 1: exactly one per run), process-wide */
+/* The general fused kernel, k_audio_tail_rows_any: the same contract and the same bits in ONE launch for every down-sampling ratio a
+ * narrow receiver uses (4/5, 3/5, 2/5, 2/3, 3/4, 7/8, 8/9, 1/5, 3/10 ...) with short resamplers and small blocks.  Routes 1 and 2
+ * and sdrhip_audio_tail_fused_fits mean what they meant; the general kernel is reached on route 0 only, and only where the rule
+ * for route 1 above did not take the run: route 0 decides (1) route 1 by its rule, unchanged, (2) else the general kernel by the
+ * mode below, (3) else the composition.  Routes 0 and 2 ask for the workspace whichever way that goes.
+ * sdrhip_audio_tail_general_fits: 1 where the general kernel serves this tail, shape and block, else 0 (SDRHIP_ERR_ARG on a null
+ * handle).  It serves: real data, resampler and filter in the AVX order, a symmetric filter of at most 128 prepared taps;
+ * interpolation <= 8 with gcd(interpolation, decimation) = 1, polyphase groups of at most 64 padded floats, numCoeffsR >=
+ * decimation; a tile's y window (840 outputs: decimation * (ceil((840 + numCoeffsF - 1) / interpolation) - 1) + the last group's
+ * offset + the group length + 8 floats) within 5120 floats, i.e. decimation / interpolation up to about 5; block 0 or ANY block
+ * sdrhip_audio_tail_create admits, up to 2^27 -- a tile may hold any number of buffer boundaries of both stages, so there is no
+ * tighter lower bound.
+ * sdrhip_audio_tail_set_general(mode), stored as the route is; SDRHIP_ERR_ARG on a null handle or a mode outside 0 .. 2:
+ *   0 (default) the measured rule: the general kernel exactly at the points of its sweep where its slowest round was below route
+ *               2's fastest (tools/audio_tail_any_bench.py, profiles/audio_tail_any_bench.txt: 1 / 2 / 8 / 32 rows x 51 / 204 / 3276 /
+ *               52428 audio outputs per row, block 0 and 256, the three row layouts above, on the tails 4/5 x 63 taps and 2/5 x 127
+ *               taps with 2 x 64 audio taps); between measured points every neighbour must be ahead, a block other than 0 and 256
+ *               must hold in both block tables, every other tail shape and everything outside the sweep is composed, and a tail of
+ *               route 1's shape never takes the general kernel.  The general kernel was ahead at all 192 points -- general / composed,
+ *               medians: 4/5 x 63 back to back and y strided 0.37 .. 0.78 (one row of 51 outputs, block 256: 7.6 against 11.3 us;
+ *               32 rows of 52428: 52 against 87 us), audio strided 0.05 .. 0.77; 2/5 x 127 back to back and y strided 0.56 .. 0.96
+ *               (the closest point: 32 rows of 51 outputs, block 0, 8.9 against 9.3 us), audio strided 0.06 .. 0.87 -- so on those two
+ *               tails, 1 .. 32 rows of 51 .. 52428 outputs at any block, mode 0 is the general kernel in every layout.  Not measured,
+ *               hence composed: every other ratio, tap count and audio filter length, fewer than 51 or more than 52428 outputs per
+ *               row, more than 32 rows;
+ *   1           the general kernel wherever it fits;
+ *   2           never. */
+int sdrhip_audio_tail_general_fits(const sdrhip_audio_tail *t);
+int sdrhip_audio_tail_set_general(sdrhip_audio_tail *t, int mode);
+long long sdrhip_debug_audio_tail_general_launches(void);   /* launches of k_audio_tail_rows_any, process-wide */
 
 /* ---- the record seam on HOST vectors (hs_sources/SDR/Filter.hs:116-144) ---- */
 /* The closures a Haskell constructor puts into the reference's own Filter / Decimator / Resampler records, so that
@@ -1500,6 +1530,26 @@ int sdrhip_pipe_nfm_bank_audio(sdrhip_pipe **p, const sdrhip_nfm_bank *b, const 
  * or bank, block_size_out < 1, an input_type outside 0 .. 2, block_mid < numCoeffs + factor of the second decimator (the reference's
  * `assert "decimate 1"`: after a crossover a block still holds one whole filter). */
 int sdrhip_pipe_narrow_bank(sdrhip_pipe **p, const sdrhip_narrow_bank *b, int block_mid, int block_size_out, int input_type);
+/* The narrow-channel bank with the audio stages behind it, on host blocks:
+ *     firDecimator deci1 block_mid >-> firDecimator deci2 block >-> P.map (magnitude | fmDemod) [>-> dcBlockingFilter]
+ *     >-> firResampler(block) >-> firFilter(block) >-> (* gain)
+ * for the K channels, `block` the block the tail was created with (at least 1); every channel's AUDIO out in blocks of exactly
+ * `block` floats through sdrhip_pipe_pop_rows / _pop.  Definition: channel j's blocks are those of sdrhip_pipe_narrow_bank with
+ * block_size_out = block, popped and pushed through sdrhip_pipe_fir_resampler(block) and sdrhip_pipe_fir_filter(block) and scaled by
+ * the gain, bit for bit, for every sequence of push sizes, coalesced or adaptive.
+ * Per submission: the bank part and the narrow run are the narrow Pipe's, but stage 2 writes its REAL rows behind the carried history
+ * of a second device rows buffer instead of into the result; ONE sdrhip_audio_tail_run_rows then computes the audio outputs that
+ * became ready -- sdrhip_audio_tail_ready of the stage-2 outputs so far -- into the result on the tail's route (route 0: the general
+ * fused kernel where sdrhip_audio_tail_set_general's rule or mode 1 says so); then both carries step.  A submission that completes no
+ * stage-2 output runs the bank part only; one that completes stage-2 outputs but no audio output runs no tail launch.  Every launch
+ * goes to ONE compute stream.
+ * Save / restore: the kind number stays 14.  The narrow record's last field (always 0 so far) is has_tail = 1, and an audio record
+ * follows it: the audio position, sdrhip_audio_tail_shape, and the carried real stage-2 rows.  A plain narrow pipe's state keeps every
+ * byte.  Restore refuses, with the pipe left fresh: a tailed state on a plain narrow pipe and the reverse, another tail shape, every
+ * mismatch the narrow record refuses, and a truncated state.  SDRHIP_ERR_ARG (and *p = NULL), before any device work: a null
+ * pointer, bank or tail, a tail of block 0, an input_type outside 0 .. 2, block_mid < numCoeffs + factor of the second decimator.
+ * The bank and the tail are borrowed and must outlive the pipe. */
+int sdrhip_pipe_narrow_bank_audio(sdrhip_pipe **p, const sdrhip_narrow_bank *b, const sdrhip_audio_tail *tail, int block_mid, int input_type);
 int sdrhip_pipe_push_i16(sdrhip_pipe *p, const int16_t *iq, int n_samples);
 int16_t *sdrhip_pipe_input_buffer_i16(sdrhip_pipe *p, int n_samples);
 

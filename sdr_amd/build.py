@@ -39,7 +39,7 @@ FILE_FLAGS = {"kernels_chain.hip": ["-fno-slp-vectorize"], "kernels_split.hip": 
               # packed operations written out as 2-vectors; the vectoriser would undo the DPP-fused additions
               "kernels_systolic.hip": ["-fno-slp-vectorize"],
               "kernels_tuner.hip": ["-fno-slp-vectorize"], "kernels_tuner_bank.hip": ["-fno-slp-vectorize"],
-              "kernels_narrow.hip": ["-fno-slp-vectorize"]}
+              "kernels_narrow.hip": ["-fno-slp-vectorize"], "kernels_tail_any.hip": ["-fno-slp-vectorize"]}
 
 
 def sources():

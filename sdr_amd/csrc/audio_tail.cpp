@@ -3,8 +3,10 @@
 // Route 2 is the definition: sdrhip_resampler_run_rows, sdrhip_filter_run_rows and sdrhip_scale_run through the C ABI, as a caller
 // without this object composes them, the z and filter rows in the caller's workspace.  Route 1 is k_audio_tail_rows
 // (kernels_tail_rows.hip): one launch, no workspace, the shape and fit of the FM chain's fused tail.  Route 0 = auto: the measured
-// rule below.  The plan functions are host arithmetic (tail_plan.hpp, shared with chain.cpp) and need no device.  Every refusal
-// comes before any device work, the descriptors' first-use upload included.
+// rule below; where that rule does not take it, k_audio_tail_rows_any (kernels_tail_any.hip: any down-sampling ratio, any number of
+// seams per tile) by sdrhip_audio_tail_set_general's mode and its own measured rule.  The plan functions are host arithmetic
+// (tail_plan.hpp, shared with chain.cpp) and need no device.  Every refusal comes before any device work, the descriptors' first-use
+// upload included.
 #include <atomic>
 
 #include "descriptors.hpp"
@@ -19,6 +21,8 @@ struct sdrhip_audio_tail {
     int64_t block = 0;                   // the one block size of every Pipe of the tail (0 = contiguous)
     bool fm_tail = false;                // the shape k_audio_tail_rows is written for (fm_tail_shape_ok, AVX orders)
     std::atomic<int> route{0};
+    TailAnyShape any = {};               // what audio_tail_any_fits reads (increments: the resampler's, owned above)
+    std::atomic<int> general{0};         // route 0 only: 0 = the measured rule, 1 = k_audio_tail_rows_any wherever it fits, 2 = never
     ~sdrhip_audio_tail()
     {
         sdrhip_resampler_destroy(res);
@@ -27,6 +31,7 @@ struct sdrhip_audio_tail {
     int64_t first_y(int64_t q) const { return tail_first_y(*res, q); }
     int64_t end_y(int64_t q) const { return tail_end_y(*res, *fil, q); }
     bool fused_fits() const { return fm_tail && fm_tail_fused_fits(res->Lp, block); }
+    bool general_fits() const { return audio_tail_any_fits(any, block); }
     // floats of a z row / a filter row that any range inside n_y readable inputs can need: a resampler output per D / I inputs
     int64_t max_outputs(int64_t n_y) const { return n_y * res->I / res->D + 2; }
 };
@@ -34,6 +39,7 @@ struct sdrhip_audio_tail {
 namespace {
 
 enum { ROUTE_AUTO = 0, ROUTE_FUSED = 1, ROUTE_COMPOSED = 2 };
+enum { GENERAL_AUTO = 0, GENERAL_ALWAYS = 1, GENERAL_NEVER = 2 };
 
 // The auto rule (sdr_hip.h states it beside the routes; tools/audio_tail_bench.py, profiles/audio_tail_bench.txt).  Measured:
 // 1 / 2 / 8 / 32 rows x 153 / 2458 / 39322 / 314574 audio outputs per row, block 0 and 8192, in three row layouts, route 1 against
@@ -76,6 +82,48 @@ bool auto_fuses(int rows, int64_t outputs, int64_t block, int layout)
     return true;
 }
 
+// The general kernel's rule (mode 0; tools/audio_tail_any_bench.py, profiles/audio_tail_any_bench.txt).  The sweep: 1 / 2 / 8 / 32 rows x
+// 51 / 204 / 3276 / 52428 audio outputs per row, block 0 and 256, the three layouts above, on two tails -- 4/5 x 63 taps and 2/5 x 127
+// taps, each with 2 x 64 audio taps -- k_audio_tail_rows_any against route 2 alternating in one process, 7 rounds.
+// kGeneral[shape][layout][seamed][rows][size]: the general kernel's slowest round was below route 2's fastest at that point.  Between
+// measured row counts or sizes every measured neighbour must be ahead; a block > 0 other than 256 takes both block tables; any other
+// tail shape, fewer than 51 or more than 52428 outputs per row and more than 32 rows were not measured and are composed.  A tail of
+// k_audio_tail_rows' shape never takes the general kernel under this rule: its own rule above has measured it.
+// Measured: the general kernel was ahead at all 192 points -- general / composed, medians: 4/5 x 63 back to back and y strided 0.37 ..
+// 0.78 (one row of 51 outputs, block 256: 7.6 against 11.3 us; 32 rows of 52428: 52 against 87 us), audio strided 0.05 .. 0.77;
+// 2/5 x 127 back to back and y strided 0.56 .. 0.96 (the closest point: 32 rows of 51 outputs, block 0, 8.9 against 9.3 us, every
+// round of either within 0.1 us of its median), audio strided 0.06 .. 0.87.
+constexpr int64_t kGeneralSizes[4] = {51, 204, 3276, 52428};
+#define ALL_AHEAD {{true, true, true, true}, {true, true, true, true}, {true, true, true, true}, {true, true, true, true}}
+constexpr bool kGeneral[2][3][2][4][4] = {       // the general kernel was ahead at every point of the sweep
+    /* 4/5 x 63:  back to back, y strided, audio strided; block 0, 256 */ {{ALL_AHEAD, ALL_AHEAD}, {ALL_AHEAD, ALL_AHEAD}, {ALL_AHEAD, ALL_AHEAD}},
+    /* 2/5 x 127: back to back, y strided, audio strided; block 0, 256 */ {{ALL_AHEAD, ALL_AHEAD}, {ALL_AHEAD, ALL_AHEAD}, {ALL_AHEAD, ALL_AHEAD}},
+};
+#undef ALL_AHEAD
+
+// the swept tails: their ratio, taps and 2 x 64 audio taps (-1: another shape)
+int general_shape_of(const TailAnyShape& s)
+{
+    if (s.fLp != 128 || s.D != 5) return -1;
+    return s.I == 4 && s.ntaps == 63 ? 0 : s.I == 2 && s.ntaps == 127 ? 1 : -1;
+}
+
+bool auto_general(int shape, int rows, int64_t outputs, int64_t block, int layout)
+{
+    if (shape < 0 || rows < kAutoRows[0] || rows > kAutoRows[3] || outputs < kGeneralSizes[0] || outputs > kGeneralSizes[3]) return false;
+    int rhi = 0, shi = 0;
+    while (kAutoRows[rhi] < rows) rhi++;
+    while (kGeneralSizes[shi] < outputs) shi++;
+    const int rlo = kAutoRows[rhi] == rows ? rhi : rhi - 1, slo = kGeneralSizes[shi] == outputs ? shi : shi - 1;
+    for (int seamed = 0; seamed < 2; seamed++) {
+        if (block == 0 ? seamed == 1 : (block == 256 && seamed == 0)) continue;
+        for (int r = rlo; r <= rhi; r++)
+            for (int i = slo; i <= shi; i++)
+                if (!kGeneral[shape][layout][seamed][r][i]) return false;
+    }
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -100,6 +148,7 @@ int sdrhip_audio_tail_create(sdrhip_audio_tail** t, int order, int interpolation
     const FirDesc& f = *a->fil;
     a->fm_tail = !r.cplx && r.lanes == 8 && !f.cplx && f.sym && f.lanes == 8 && f.factor == 1 &&
                  fm_tail_shape_ok(r.num_groups, r.nloop, r.I, r.D, r.increments.data(), r.Lp, r.ntaps, f.ntaps_kernel);
+    a->any = {r.cplx, r.lanes, f.lanes, f.sym, f.factor, r.I, r.D, r.num_groups, r.nloop, r.row_stride, r.ntaps, r.Lp, r.increments.data(), f.Lp};
     *t = a;
     return SDRHIP_OK;
 }
@@ -148,6 +197,18 @@ int sdrhip_audio_tail_set_route(sdrhip_audio_tail* t, int route)
 
 long long sdrhip_debug_audio_tail_launches(void) { return audio_tail_launch_count(); }
 
+int sdrhip_audio_tail_general_fits(const sdrhip_audio_tail* t) { return t ? (t->general_fits() ? 1 : 0) : SDRHIP_ERR_ARG; }
+
+int sdrhip_audio_tail_set_general(sdrhip_audio_tail* t, int mode)
+{
+    SDRHIP_REQUIRE(t != nullptr, "sdrhip_audio_tail_set_general");
+    SDRHIP_REQUIRE(mode >= GENERAL_AUTO && mode <= GENERAL_NEVER, "sdrhip_audio_tail_set_general");
+    t->general.store(mode, std::memory_order_relaxed);
+    return SDRHIP_OK;
+}
+
+long long sdrhip_debug_audio_tail_general_launches(void) { return audio_tail_any_launch_count(); }
+
 int sdrhip_audio_tail_run_rows(const sdrhip_audio_tail* t, void* stream, const float* d_y, int64_t y_stride, int64_t y_base, int64_t n_y,
                                float* d_audio, int64_t audio_stride, int rows, int64_t q0, int64_t q1, void* d_workspace,
                                size_t workspace_bytes)
@@ -169,16 +230,22 @@ int sdrhip_audio_tail_run_rows(const sdrhip_audio_tail* t, void* stream, const f
         set_error("%s: route 1 on a tail the fused kernel does not serve (shape or block)", what);
         return SDRHIP_ERR_ARG;
     }
-    const bool fused = fits && (route == ROUTE_FUSED || (route == ROUTE_AUTO && auto_fuses(rows, nq, t->block, layout_of(rows, y_stride, n_y, audio_stride, nq))));
+    const int layout = layout_of(rows, y_stride, n_y, audio_stride, nq);
+    const bool fused = fits && (route == ROUTE_FUSED || (route == ROUTE_AUTO && auto_fuses(rows, nq, t->block, layout)));
+    // route 0 only, behind the existing rule: the general kernel by its mode (mode 0 never on k_audio_tail_rows' own shape)
+    const int mode = t->general.load(std::memory_order_relaxed);
+    const bool general = !fused && route == ROUTE_AUTO && mode != GENERAL_NEVER && t->general_fits() &&
+                         (mode == GENERAL_ALWAYS || (!t->fm_tail && auto_general(general_shape_of(t->any), rows, nq, t->block, layout)));
     // routes 0 and 2 ask for the workspace whichever way auto goes: what a call needs does not depend on a measured table
     SDRHIP_REQUIRE(route == ROUTE_FUSED || (d_workspace != nullptr && workspace_bytes >= sdrhip_audio_tail_workspace_bytes(t, rows, n_y)), what);
     hipStream_t s = (hipStream_t)stream;
     int rc;
-    if (fused) {
+    if (fused || general) {
         if ((rc = t->res->ensure_device()) != SDRHIP_OK || (rc = t->fil->ensure_device()) != SDRHIP_OK) return rc;
         const FmTailTables tt = {t->res->d_groups, t->res->row_stride, t->res->d_plain, t->res->ntaps, t->res->Lp,
                                  t->fil->d_taps, t->fil->d_cross, t->gain, t->block};
-        launch_audio_tail_rows(s, d_y, y_stride, y_base, n_y, d_audio, audio_stride, rows, q0, q1, tt);
+        if (fused) launch_audio_tail_rows(s, d_y, y_stride, y_base, n_y, d_audio, audio_stride, rows, q0, q1, tt);
+        else launch_audio_tail_rows_any(s, d_y, y_stride, y_base, n_y, d_audio, audio_stride, rows, q0, q1, t->any, tt);
         SDRHIP_CHECK_HIP(hipGetLastError());
         return SDRHIP_OK;
     }

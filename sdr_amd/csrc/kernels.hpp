@@ -315,6 +315,25 @@ long long fm_tail_launch_count();   // diagnostics: launches of k_fm_tail
 void launch_audio_tail_rows(hipStream_t s, const float* d_y, int64_t y_stride, int64_t y_base, int64_t n_y, float* d_audio,
                             int64_t audio_stride, int rows, int64_t q0, int64_t q1, const FmTailTables& t);
 long long audio_tail_launch_count();   // diagnostics: launches of k_audio_tail_rows
+// kernels_tail_any.hip: the same contract for any down-sampling ratio of a narrow receiver -- I / D, the group length, the tap counts
+// and the block are run-time numbers, and a tile may hold any number of buffer boundaries of both stages.  A tile is
+// kTailAnyTileOutputs = 840 audio outputs of one row (a multiple of every I <= 8: it starts on a polyphase cycle).
+// audio_tail_any_fits is the ONE predicate, shape and block: real data, both stages in the AVX order (8 lanes), a symmetric filter of
+// factor 1 and at most 128 prepared taps; I <= 8 groups (gcd(I, D) = 1) of at most 64 padded floats, Lp >= D; a tile's y window --
+// D * (ceil((840 + Lf - 1) / I) - 1) + pre[I - 1] + nloop + 8 floats -- within kTailAnyWindowFloats (D / I up to about 5); block 0 or
+// any block sdrhip_audio_tail_create admits (block * I >= Lp, block >= Lf: there is no tighter lower bound) up to 2^27.
+// launch_audio_tail_rows_any launches unconditionally and counts; t.d_fhalf / t.d_fplain hold s.fLp / 2 and s.fLp taps.
+constexpr int kTailAnyTileOutputs = 840, kTailAnyMaxFilter = 128, kTailAnyMaxGroup = 64, kTailAnyMaxInterp = 8, kTailAnyWindowFloats = 5120;
+struct TailAnyShape {
+    bool cplx; int rlanes, flanes; bool fsym; int ffactor;      // data and orders of the two descriptors
+    int I, D, ngroups, nloop, row_stride, ntaps, rLp;           // the resampler
+    const int* increments;                                      // per group, from group 0 (ngroups of them)
+    int fLp;                                                    // the filter's prepared length (2 x half-taps)
+};
+bool audio_tail_any_fits(const TailAnyShape& s, int64_t block);
+void launch_audio_tail_rows_any(hipStream_t st, const float* d_y, int64_t y_stride, int64_t y_base, int64_t n_y, float* d_audio,
+                                int64_t audio_stride, int rows, int64_t q0, int64_t q1, const TailAnyShape& s, const FmTailTables& t);
+long long audio_tail_any_launch_count();   // diagnostics: launches of k_audio_tail_rows_any
 // kernels_small.hip: the WHOLE chain (u8 IQ -> /8 decimator -> fmDemod -> 3/10 resampler -> symmetric filter * gain) as one
 // kernel for launch-bound runs; d_in holds samples [s0, s0 + n_in).  tile_outputs: audio outputs per workgroup (0 = chosen
 // from the size of the run, < 0 = the largest).  fits (given fm_tail_shape_ok): /8 decimator with 128 padded taps in the AVX

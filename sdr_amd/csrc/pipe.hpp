@@ -152,8 +152,20 @@ struct sdrhip_pipe {
     const sdrhip_audio_tail* tail = nullptr;
     const NarrowBankDesc* narrow = nullptr;
     int64_t block_mid = 0;
-    RowsCarry y;
+    // narrow AND tail (sdrhip_pipe_narrow_bank_audio, still PK_NARROW_BANK): stage 2 writes its real rows behind the carried history of a
+    // SECOND carry, y2, instead of into the chunk, one sdrhip_audio_tail_run_rows computes the audio outputs [y2.a_done, audio_ready)
+    // into the chunk, then both carries step.  y2's row element 0 is stage-2 output (y.a_done - y2.n) of the stream; block_out is the
+    // tail's block.
+    RowsCarry y, y2;
     bool rows_tail() const { return tail != nullptr || narrow != nullptr; }
+    bool narrow_audio() const { return tail != nullptr && narrow != nullptr; }
+    // floats per row a submission leaves in the chunk once a_end outputs of the (first) rows tail are done, and with it the audio position
+    int64_t chunk_outputs(int64_t a_end, int64_t* q_end) const
+    {
+        if (!narrow_audio()) return a_end - y.a_done;
+        *q_end = std::max(y2.a_done, sdrhip_audio_tail_ready(tail, a_end));
+        return *q_end - y2.a_done;
+    }
     // what the two rows tails differ in besides their run: outputs ready after m bank outputs, first bank output that output a needs
     int64_t tail_ready(int64_t m) const
     {

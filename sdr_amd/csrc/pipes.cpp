@@ -212,6 +212,28 @@ int sdrhip_pipe_narrow_bank(sdrhip_pipe** pp, const sdrhip_narrow_bank* nb, int 
     return SDRHIP_OK;
 }
 
+// The narrow bank's Pipe with the audio tail behind it on the device: ... >-> firResampler(block) >-> firFilter(block) >-> (* gain), block
+// = the tail's block, which is the second decimator's output block too.  The kind stays PK_NARROW_BANK: it is a narrow-bank pipe with
+// `tail` set as well as `narrow` (the second rows carry, pipe.hpp).  Every refusal comes before any device work.
+int sdrhip_pipe_narrow_bank_audio(sdrhip_pipe** pp, const sdrhip_narrow_bank* nb, const sdrhip_audio_tail* tail, int block_mid, int input_type)
+{
+    const char* who = "sdrhip_pipe_narrow_bank_audio";
+    if (pp != nullptr) *pp = nullptr;
+    const int64_t block = sdrhip_audio_tail_block(tail);
+    if (pp == nullptr || nb == nullptr || tail == nullptr || block < 1 || block > (int64_t)0x7fffffff) {
+        set_error("%s: requirement `a pipe pointer, a narrow bank, an audio tail, and a tail created with a block of at least 1` violated", who);
+        return SDRHIP_ERR_ARG;
+    }
+    int rc = sdrhip_pipe_narrow_bank(pp, nb, block_mid, (int)block, input_type);
+    if (rc != SDRHIP_OK) {
+        if (rc == SDRHIP_ERR_ARG)
+            set_error("%s: refused as sdrhip_pipe_narrow_bank refuses it: block_mid >= numCoeffs + factor of the second decimator, input_type 0 .. 2", who);
+        return rc;
+    }
+    (*pp)->tail = tail;
+    return SDRHIP_OK;
+}
+
 int sdrhip_pipe_rows(const sdrhip_pipe* p)
 {
     SDRHIP_REQUIRE(p != nullptr, "sdrhip_pipe_rows");

@@ -5,7 +5,10 @@
 // Behind the bank part of a submission that wrote outputs [m_done, m_done + count) of every row behind the carried ones: the tail's
 // outputs [a_done, a_end) into the chunk by ONE run (none when a_end == a_done), then the carry.  The narrow Pipe's run is the fused
 // launch wherever it fits, whatever the bank's route setting and auto rule (those belong to sdrhip_narrow_bank_run).
-static int rows_tail(sdrhip_pipe* p, hipStream_t s, float* d_chunk, int64_t m_done, int64_t count, int64_t a_end)
+// With an audio tail behind the narrow bank (narrow_audio) stage 2 writes behind the carried history of the second carry instead, ONE
+// sdrhip_audio_tail_run_rows (route 0: the general fused kernel where its rule or mode 1 says so) computes the audio outputs
+// [y2.a_done, q_end) into the chunk -- no tail launch when there is none -- and both carries step.
+static int rows_tail(sdrhip_pipe* p, hipStream_t s, float* d_chunk, int64_t m_done, int64_t count, int64_t a_end, int64_t q_end)
 {
     RowsCarry& y = p->y;
     const int K = p->rows();
@@ -15,14 +18,33 @@ static int rows_tail(sdrhip_pipe* p, hipStream_t s, float* d_chunk, int64_t m_do
         return SDRHIP_OK;
     }
     int rc;
+    float* d_out2 = d_chunk;
+    int64_t stride2 = n;
+    if (p->narrow_audio()) {
+        if ((rc = p->y2.room(K, p->y2.n + n, s)) != SDRHIP_OK) return rc;
+        d_out2 = p->y2.data() + p->y2.n;
+        stride2 = p->y2.stride;
+    }
     if (const NarrowBankDesc* nb = p->narrow) {
         const bool fm = nb->form == NARROW_FM, fused = narrow_stage2_fits(nb, K, y.data(), y.stride, y_base, y.a_done, a_end, p->block_mid);
         const size_t ws = narrow_stage2_bytes(nb, K, n, fused);
         if ((rc = grow(y.ws, ws > 16 ? ws : 16, s)) != SDRHIP_OK) return rc;
         if (fused && (rc = nb->d2->ensure_device()) != SDRHIP_OK) return rc;
-        rc = narrow_stage2(nb, s, fused, y.data(), y.stride, y_base, n_y, d_chunk, n, y.a_done, a_end, p->block_mid, fm ? p->fm.latest() : nullptr,
+        rc = narrow_stage2(nb, s, fused, y.data(), y.stride, y_base, n_y, d_out2, stride2, y.a_done, a_end, p->block_mid, fm ? p->fm.latest() : nullptr,
                            fm ? p->fm.out() : nullptr, nb->dc_block ? p->dc.out() : nullptr, (float*)y.ws.p, ws);
         if (rc == SDRHIP_OK && fm) p->fm.ran();
+        if (rc == SDRHIP_OK && p->narrow_audio()) {
+            RowsCarry& z = p->y2;
+            const int64_t n_z = z.n + n, z_base = y.a_done - z.n, nq = q_end - z.a_done;
+            if (nq == 0) {
+                z.n = n_z;
+            } else {
+                const size_t wz = sdrhip_audio_tail_workspace_bytes(p->tail, K, n_z);
+                if ((rc = grow(z.ws, wz, s)) != SDRHIP_OK) return rc;
+                rc = sdrhip_audio_tail_run_rows(p->tail, s, z.data(), z.stride, z_base, n_z, d_chunk, nq, K, z.a_done, q_end, z.ws.p, wz);
+                if (rc == SDRHIP_OK) rc = z.carry(K, n_z, a_end - sdrhip_audio_tail_first_input(p->tail, q_end), s);
+            }
+        }
     } else {
         const size_t ws = sdrhip_audio_tail_workspace_bytes(p->tail, K, n_y);
         if ((rc = grow(y.ws, ws, s)) != SDRHIP_OK) return rc;
@@ -64,7 +86,8 @@ static int one_row_body(sdrhip_pipe* p, hipStream_t s, const float* din, float* 
 // The banks: every row [cross | one] in the Pipe's form, row_len apart (dev_skew has aligned the tile part's first window).
 // IQ: the bank's own rule picks the banked launch or channel by channel.  Envelopes and phases, one float per output: the
 // fused launch (set) where it fits, else tuner bank + amDemod / fmDemod rows through the slot's complex scratch.
-static int bank_body(sdrhip_pipe* p, hipStream_t s, int si, const void* d_in, float* dout, const Span& x, int64_t row_len, int64_t a_end)
+static int bank_body(sdrhip_pipe* p, hipStream_t s, int si, const void* d_in, float* dout, const Span& x, int64_t row_len, int64_t a_end,
+                     int64_t q_end)
 {
     const int K = p->rows();
     const int64_t count = x.m_end - x.m_done, np = row_floats(count);
@@ -115,7 +138,7 @@ static int bank_body(sdrhip_pipe* p, hipStream_t s, int si, const void* d_in, fl
         launch_dc_blocker_rows(s, K, count, out, np, fin, fin_stride, p->dc.latest(), p->dc.out(), out + (size_t)K * (size_t)np, 0);
         SDRHIP_CHECK_HIP(hipGetLastError());
     }
-    return p->rows_tail() ? rows_tail(p, s, dout, x.m_done, count, a_end) : SDRHIP_OK;
+    return p->rows_tail() ? rows_tail(p, s, dout, x.m_done, count, a_end, q_end) : SDRHIP_OK;
 }
 
 // Submit the n elements staged in the current slot's pinned buffer.  uniform_seam > 0: they are whole blocks of that size
@@ -162,15 +185,17 @@ int fir_submit(sdrhip_pipe* p, int n, int64_t uniform_seam)
     const bool tailed = p->rows_tail();
     int64_t a_end = p->y.a_done;
     if (tailed) a_end = std::max(a_end, p->tail_ready(x.m_end));
-    const int64_t row_len = tailed ? a_end - p->y.a_done : (x.m_end - x.m_done) * p->esz_out();
+    int64_t q_end = p->y2.a_done;                 // (narrow_audio: the audio outputs the stage-2 outputs so far complete)
+    const int64_t row_len = tailed ? p->chunk_outputs(a_end, &q_end) : (x.m_end - x.m_done) * p->esz_out();
     int rc = e.submit(route, cs, first, (size_t)(tail + n) * ein, p->rows() * row_len, [&](hipStream_t s, const void* d_in, void* d_out) {
         if (p->bank == nullptr) return one_row_body(p, s, (const float*)d_in, (float*)d_out, x);
-        return bank_body(p, s, si, d_in, (float*)d_out, x, row_len, a_end);
+        return bank_body(p, s, si, d_in, (float*)d_out, x, row_len, a_end, q_end);
     }, tailed && x.m_end > x.m_done);
     if (rc != SDRHIP_OK) return rc;
     p->m_done = x.m_end;
     p->E_prev = E;
     p->y.a_done = a_end;
+    p->y2.a_done = q_end;
     return SDRHIP_OK;
 }
 

@@ -9,9 +9,11 @@
 //   3. the engine's history and fifo   HostStream::save: hist_n elements in the input's own type, then pending floats row after row
 //   4. n_blocks int32 block lengths    the map stages' output blocks not yet popped
 //   5. the bank record (the AM and NFM kinds)   6. the audio record (the audio Pipes)   7. the narrow record (the narrow bank's Pipe)
-// Each of these trailing records is [a fixed part | n_floats floats of a ChannelState | the rows carry's K * y_n elements]: one Trailer
-// says what this pipe writes as the fixed part, where the floats live, whether rows follow, and how a state's fixed part is checked
-// against this pipe.  state_bytes, save and restore walk the same list (Trailers).  Version 3 (the waterfall) is a header of its own
+//   8. the audio record again, behind the narrow record: the narrow bank's Pipe with an audio tail (has_tail = 1 in record 7), whose
+//      rows are the carried REAL stage-2 outputs of the second carry
+// Each of these trailing records is [a fixed part | n_floats floats of a ChannelState | a rows carry's K * y_n elements]: one Trailer
+// says what this pipe writes as the fixed part, where the floats live, which carry's rows follow, and how a state's fixed part is
+// checked against this pipe.  state_bytes, save and restore walk the same list (Trailers).  Version 3 (the waterfall) is a header of its own
 // plus the engine's state: pipes_spectrum.cpp.
 #include "pipe.hpp"
 
@@ -32,17 +34,19 @@ size_t pipe_state_header_bytes(const sdrhip_pipe* p) { return sizeof(PipeStateHe
 // save), or with dc_block = 0 the NFM kinds' last decimated (re, im) of every channel (2 K: the array the last fmDemod-form launch wrote)
 struct PipeStateAm { int32_t dc_block, n_floats; };
 // 6. the audio position, the tail's shape (so that a state is restored only into a pipe of the same resampler ratio and tap counts) and
-// the y_n carried demodulated elements of every row, row after row
+// the y_n carried demodulated elements of every row, row after row.  Behind a narrow record (8.) the positions count in stage-2 outputs:
+// y_n carried real stage-2 outputs of every row, a_done audio outputs done
 struct PipeStateAudio {
     int64_t a_done, y_n;
     int32_t shape[4];        // sdrhip_audio_tail_shape: interpolation, decimation, numCoeffsR, numCoeffsF
 };
 // 7. the stage-2 position, what the state may be restored into (block_mid, the second decimator's factor and prepared length, the form,
 // dc_block), n_floats state floats (fmDemod's pairs or dcBlocker's, 2 K; 0 for the plain envelope) and the y_n carried COMPLEX stage-1
-// outputs of every row, row after row
+// outputs of every row, row after row.  has_tail: 1 = an audio record follows (sdrhip_pipe_narrow_bank_audio); a plain narrow pipe writes
+// the 0 the field always held
 struct PipeStateNarrow {
     int64_t a_done, y_n, block_mid;
-    int32_t D2, Lp2, form, dc_block, n_floats, reserved;
+    int32_t D2, Lp2, form, dc_block, n_floats, has_tail;
 };
 
 struct Trailer {
@@ -50,11 +54,12 @@ struct Trailer {
     size_t fixed_bytes;
     float* floats;                // the n_floats floats behind it, on the device
     int32_t n_floats;
-    const int64_t* rows;          // {a_done, y_n} inside the fixed part where the rows carry's K * y_n elements follow, else null
+    const int64_t* rows;          // {a_done, y_n} inside the fixed part where a rows carry's K * y_n elements follow, else null
+    RowsCarry* carry;             // ... that carry
     int (*check)(const sdrhip_pipe* p, const unsigned char* in, const PipeStateHeader& h, void* mine);
     size_t bytes(const sdrhip_pipe* p) const
     {
-        return fixed_bytes + (size_t)n_floats * sizeof(float) + (rows ? (size_t)p->rows() * p->y.span(rows[1]) : 0);
+        return fixed_bytes + (size_t)n_floats * sizeof(float) + (rows ? (size_t)p->rows() * carry->span(rows[1]) : 0);
     }
 };
 
@@ -77,9 +82,11 @@ int check_audio(const sdrhip_pipe* p, const unsigned char* in, const PipeStateHe
     SDRHIP_REQUIRE(memcmp(au.shape, mine.shape, sizeof mine.shape) == 0,
                    "sdrhip_pipe_restore: the state belongs to an audio pipe of another resampler ratio or other tail tap counts");
     // every audio output the demodulated outputs so far complete is done, and the carried rows reach back to the next one's first input
-    SDRHIP_REQUIRE(au.a_done == sdrhip_audio_tail_ready(p->tail, h.m_done) && au.y_n >= 0 && au.y_n <= h.m_done &&
-                       sdrhip_audio_tail_first_input(p->tail, au.a_done) >= h.m_done - au.y_n &&
-                       au.y_n <= h.m_done - sdrhip_audio_tail_first_input(p->tail, au.a_done) + sdrhip_audio_tail_max_halo(p->tail),
+    // (behind a narrow record the demodulated outputs are the stage-2 outputs, which check_narrow has tied to the header already)
+    const int64_t m = p->narrow ? p->tail_ready(h.m_done) : h.m_done;
+    SDRHIP_REQUIRE(au.a_done == sdrhip_audio_tail_ready(p->tail, m) && au.y_n >= 0 && au.y_n <= m &&
+                       sdrhip_audio_tail_first_input(p->tail, au.a_done) >= m - au.y_n &&
+                       au.y_n <= m - sdrhip_audio_tail_first_input(p->tail, au.a_done) + sdrhip_audio_tail_max_halo(p->tail),
                    "sdrhip_pipe_restore: inconsistent state");
     mine = au;
     return SDRHIP_OK;
@@ -90,6 +97,8 @@ int check_narrow(const sdrhip_pipe* p, const unsigned char* in, const PipeStateH
     PipeStateNarrow& mine = *(PipeStateNarrow*)fixed;
     PipeStateNarrow nx;
     memcpy(&nx, in, sizeof nx);
+    SDRHIP_REQUIRE(nx.has_tail == mine.has_tail, mine.has_tail ? "sdrhip_pipe_restore: the state belongs to a narrow bank pipe without an audio tail"
+                                                               : "sdrhip_pipe_restore: the state belongs to a narrow bank pipe with an audio tail");
     SDRHIP_REQUIRE(nx.block_mid == mine.block_mid, "sdrhip_pipe_restore: the state belongs to a narrow bank pipe of another block_mid");
     SDRHIP_REQUIRE(nx.D2 == mine.D2 && nx.Lp2 == mine.Lp2,
                    "sdrhip_pipe_restore: the state belongs to a narrow bank pipe of another second decimator (factor or tap count)");
@@ -109,7 +118,7 @@ struct Trailers {
     PipeStateAm am;
     PipeStateAudio au;
     PipeStateNarrow nx;
-    Trailer t[2];
+    Trailer t[3];
     int n = 0;
     Trailers(const Trailers&) = delete;
     explicit Trailers(const sdrhip_pipe* p)
@@ -118,18 +127,24 @@ struct Trailers {
         const bool nfm = p->form == BankForm::PHASE;
         if (p->form != BankForm::IQ) {
             am = {p->am_dc ? 1 : 0, p->am_dc || nfm ? 2 * p->rows() : 0};
-            t[n++] = {&am, sizeof am, (nfm ? p->fm : p->dc).latest(), am.n_floats, nullptr, check_bank};
+            t[n++] = {&am, sizeof am, (nfm ? p->fm : p->dc).latest(), am.n_floats, nullptr, nullptr, check_bank};
         }
-        if (p->tail) {
-            au = {y.a_done, y.n, {0, 0, 0, 0}};
-            (void)sdrhip_audio_tail_shape(p->tail, au.shape);
-            t[n++] = {&au, sizeof au, nullptr, 0, &au.a_done, check_audio};
-        }
+        RowsCarry* const first = const_cast<RowsCarry*>(&p->y);
+        RowsCarry* const audio = p->narrow ? const_cast<RowsCarry*>(&p->y2) : first;      // the carry in front of the audio tail
+        if (p->tail && !p->narrow) audio_record(p, audio);
         if (const NarrowBankDesc* nb = p->narrow) {
             const bool fm = nb->form == NARROW_FM;
-            nx = {y.a_done, y.n, p->block_mid, nb->d2->factor, nb->d2->Lp, nb->form, nb->dc_block, fm || nb->dc_block ? 2 * p->rows() : 0, 0};
-            t[n++] = {&nx, sizeof nx, (fm ? p->fm : p->dc).latest(), nx.n_floats, &nx.a_done, check_narrow};
+            nx = {y.a_done, y.n, p->block_mid, nb->d2->factor, nb->d2->Lp, nb->form, nb->dc_block, fm || nb->dc_block ? 2 * p->rows() : 0,
+                  p->tail ? 1 : 0};
+            t[n++] = {&nx, sizeof nx, (fm ? p->fm : p->dc).latest(), nx.n_floats, &nx.a_done, first, check_narrow};
+            if (p->tail) audio_record(p, audio);
         }
+    }
+    void audio_record(const sdrhip_pipe* p, RowsCarry* carry)
+    {
+        au = {carry->a_done, carry->n, {0, 0, 0, 0}};
+        (void)sdrhip_audio_tail_shape(p->tail, au.shape);
+        t[n++] = {&au, sizeof au, nullptr, 0, &au.a_done, carry, check_audio};
     }
     Trailer* begin() { return t; }
     Trailer* end() { return t + n; }
@@ -154,7 +169,7 @@ int trailer_copy(const sdrhip_pipe* p, const Trailer& t, unsigned char* host, hi
     const bool out = kind == hipMemcpyDeviceToHost;
     const size_t fb = (size_t)t.n_floats * sizeof(float);
     if (fb > 0) SDRHIP_CHECK_HIP(hipMemcpy(out ? (void*)host : t.floats, out ? (const void*)t.floats : host, fb, kind));
-    return t.rows ? p->y.host_copy(p->rows(), host + fb, t.rows[1], kind) : SDRHIP_OK;
+    return t.rows ? t.carry->host_copy(p->rows(), host + fb, t.rows[1], kind) : SDRHIP_OK;
 }
 }  // namespace
 
@@ -251,10 +266,10 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
     for (Trailer& t : trailers) {
         if ((rc = t.check(p, front + at, h, t.fixed)) != SDRHIP_OK) return rc;
         const size_t y_n = t.rows ? (size_t)t.rows[1] : 0;
-        SDRHIP_REQUIRE((bytes - at - t.fixed_bytes) / sizeof(float) >= (size_t)t.n_floats + (size_t)p->rows() * y_n * p->y.width,
+        SDRHIP_REQUIRE((bytes - at - t.fixed_bytes) / sizeof(float) >= (size_t)t.n_floats + (size_t)p->rows() * y_n * (t.rows ? t.carry->width : 1),
                        "sdrhip_pipe_restore: truncated state");
         at += t.bytes(p);
-        if (t.rows && (rc = p->y.room(p->rows(), t.rows[1] + 1, p->eng.compute[0])) != SDRHIP_OK) return rc;
+        if (t.rows && (rc = t.carry->room(p->rows(), t.rows[1] + 1, p->eng.compute[0])) != SDRHIP_OK) return rc;
     }
     // Phase 2: put it back.
     const unsigned char* in = p->eng.restore(front + pipe_state_header_bytes(p), h.hist_n, h.pending);
@@ -267,7 +282,7 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
     if (p->map_state.p) SDRHIP_CHECK_HIP(hipMemcpy(p->map_state.p, h.dc, sizeof h.dc, hipMemcpyHostToDevice));
     for (const Trailer& t : trailers) {
         if ((rc = trailer_copy(p, t, const_cast<unsigned char*>(in) + t.fixed_bytes, hipMemcpyHostToDevice)) != SDRHIP_OK) return rc;
-        if (t.rows) { p->y.a_done = t.rows[0]; p->y.n = t.rows[1]; }
+        if (t.rows) { t.carry->a_done = t.rows[0]; t.carry->n = t.rows[1]; }
         in += t.bytes(p);
     }
     return ready_blocks(p);

@@ -362,6 +362,10 @@ lib.sdrhip_audio_tail_set_route.argtypes = [_vp, C.c_int]
 lib.sdrhip_audio_tail_run_rows.argtypes = [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, C.c_int, _i64, _i64, _vp, C.c_size_t]
 lib.sdrhip_debug_audio_tail_launches.argtypes = []
 lib.sdrhip_debug_audio_tail_launches.restype = C.c_longlong
+lib.sdrhip_audio_tail_general_fits.argtypes = [_vp]
+lib.sdrhip_audio_tail_set_general.argtypes = [_vp, C.c_int]
+lib.sdrhip_debug_audio_tail_general_launches.argtypes = []
+lib.sdrhip_debug_audio_tail_general_launches.restype = C.c_longlong
 
 lib.sdrhip_fm_stream_create.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int]
 lib.sdrhip_fm_stream_destroy.argtypes = [_vp]
@@ -401,6 +405,7 @@ lib.sdrhip_pipe_nfm_bank.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int]
 lib.sdrhip_pipe_am_bank_audio.argtypes = [C.POINTER(_vp), _vp, _vp, C.c_int]
 lib.sdrhip_pipe_nfm_bank_audio.argtypes = [C.POINTER(_vp), _vp, _vp, C.c_int]
 lib.sdrhip_pipe_narrow_bank.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int, C.c_int]
+lib.sdrhip_pipe_narrow_bank_audio.argtypes = [C.POINTER(_vp), _vp, _vp, C.c_int, C.c_int]
 lib.sdrhip_pipe_push_i16.argtypes = [_vp, _i16p, C.c_int]
 lib.sdrhip_pipe_input_buffer_i16.argtypes = [_vp, C.c_int]
 lib.sdrhip_pipe_input_buffer_i16.restype = _vp
@@ -919,6 +924,14 @@ def audio_tail_launches():
     return int(lib.sdrhip_debug_audio_tail_launches())
 
 
+AUDIO_TAIL_GENERAL_AUTO, AUDIO_TAIL_GENERAL_ALWAYS, AUDIO_TAIL_GENERAL_NEVER = 0, 1, 2
+
+
+def audio_tail_general_launches():
+    """sdrhip_debug_audio_tail_general_launches: launches of the general fused audio-tail kernel in this process."""
+    return int(lib.sdrhip_debug_audio_tail_general_launches())
+
+
 class AudioTail(_Handle):
     """sdrhip_audio_tail: firResampler(block) >-> firFilter(block) >-> (* gain) over rows of real demodulated samples -- the audio
     stages behind AmBank / NfmBank.  Arguments as FmChain's tail; block = the one block size of every Pipe (0 = contiguous).
@@ -950,6 +963,13 @@ class AudioTail(_Handle):
     def set_route(self, route):
         """0 = auto, 1 = the fused kernel (one launch, no workspace), 2 = the composition of the row forms (the definition)"""
         check(lib.sdrhip_audio_tail_set_route(self.h, route), "sdrhip_audio_tail_set_route")
+
+    def general_fits(self):
+        return bool(check(lib.sdrhip_audio_tail_general_fits(self.h), "sdrhip_audio_tail_general_fits"))
+
+    def set_general(self, mode):
+        """route 0 only, behind route 1's rule: 0 = the general fused kernel by its measured rule, 1 = wherever it fits, 2 = never"""
+        check(lib.sdrhip_audio_tail_set_general(self.h, mode), "sdrhip_audio_tail_set_general")
 
     def run_rows(self, y, audio, q0, q1, y_base=0, n_y=None, workspace=None, workspace_bytes=None, stream=None, y_stride=None,
                  audio_stride=None, rows=None):
@@ -1806,6 +1826,14 @@ class Pipe(_Handle):
                   "sdrhip_pipe_narrow_bank")
             self.input_u8, self.input_i16 = bool(input_u8), bool(input_i16)
             self.complex_in = True
+        elif kind == "narrow_bank_audio":
+            if input_u8 and input_i16:
+                raise ValueError("Pipe.narrow_bank_audio: input_u8 and input_i16 exclude each other")
+            bank, tail, block_mid = desc
+            check(lib.sdrhip_pipe_narrow_bank_audio(C.byref(self.h), bank.h, tail.h, int(block_mid), 2 if input_i16 else int(bool(input_u8))),
+                  "sdrhip_pipe_narrow_bank_audio")
+            self.input_u8, self.input_i16 = bool(input_u8), bool(input_i16)
+            self.complex_in = True
         elif kind == "spectrum":
             hop, group, reduce, unit, floor_db = spectrum_args
             check(lib.sdrhip_pipe_spectrum(C.byref(self.h), desc.h, int(hop), int(group), int(reduce), int(unit), float(floor_db)),
@@ -1861,6 +1889,13 @@ class Pipe(_Handle):
         block_size_out >-> magnitude | fmDemod [>-> dcBlockingFilter]  in blocks of block_size_out floats out (sdr_hip.h,
         sdrhip_pipe_narrow_bank).  The NarrowBank is borrowed: the pipe keeps a reference to it."""
         return Pipe("narrow_bank", (narrow_bank, block_mid), block_size_out, input_u8=input_u8, input_i16=input_i16)
+
+    @staticmethod
+    def narrow_bank_audio(narrow_bank, tail, block_mid, input_u8=False, input_i16=False):
+        """The narrow-channel bank and its audio stages on host blocks: IQ blocks in, every channel's audio -- Pipe.narrow_bank's blocks
+        >-> firResampler >-> firFilter >-> (* gain), all with the AudioTail's block -- in blocks of tail.block floats out
+        (sdrhip_pipe_narrow_bank_audio).  The NarrowBank and the AudioTail are borrowed: the pipe keeps references to them."""
+        return Pipe("narrow_bank_audio", (narrow_bank, tail, block_mid), tail.block, input_u8=input_u8, input_i16=input_i16)
 
     @staticmethod
     def nfm_bank_audio(nfm_bank, tail, input_u8=False, input_i16=False):
@@ -1964,7 +1999,7 @@ class Pipe(_Handle):
         return self._pop(check(lib.sdrhip_pipe_restore(self.h, state, len(state)), "sdrhip_pipe_restore"))
 
     def _pop(self, ready):
-        if self.kind in ("tuner_bank", "am_bank", "nfm_bank", "am_bank_audio", "nfm_bank_audio", "narrow_bank"):
+        if self.kind in ("tuner_bank", "am_bank", "nfm_bank", "am_bank_audio", "nfm_bank_audio", "narrow_bank", "narrow_bank_audio"):
             if ready <= 0:
                 return []
             got = self.pop_rows(ready)
