@@ -9,8 +9,10 @@ restated in tests/stream_slice_cases.py) -- no product code runs here, so these 
   * the late first output of an output block (late_output_is_one) cannot occur with seam block = output block = B >= I: output k B
     starts B (k D mod I) into its buffer of B I upsampled units, a multiple of B, never one of the last I - 1 positions -- checked by
     search over every launch and over every block up to 1100 for every shape;
-  * the blocks, ends, starts, layouts and gains the GPU test names are in the table, and the one block at which the reference's
-    Pipe asserts (block * I == numCoeffsR: 8/9 x 511 at 64) is the only one without expected values."""
+  * the blocks, ends, starts, layouts and gains the GPU test names are in the table, and the one block of this table at which the
+    reference's Pipe asserts (8/9 x 511 at 64, where block * I == numCoeffsR) is the only one without expected values.  That equality
+    is not the rule: the reference asserts wherever some buffer boundary k has (-k block I) mod D > block I - numCoeffsR, a zone of up
+    to ceil((D - 1) / I) blocks (tests/tail_any_family_cases.py `asserts`; tests/test_tail_any_family_cases.py finds it by search)."""
 import numpy as np
 import pytest
 

@@ -3,7 +3,9 @@
 For every launch of tests/audio_tail_any_cases.py -- nine down-sampling shapes with 64, 32 and 8 half-taps, blocks 0, 200, 250, 256,
 1000 and the lowest block the predicate admits -- route 0 with mode 1 is held bit for bit, NaN by position, to the restated Pipes'
 composition (oracle/pipes_model.py: firResampler(block) >-> firFilter(block) >-> (* gain) on that row's y stream): no device code
-in the expected values.  The one block at which the reference's Pipe asserts (8/9 x 511 at block 64) is held route against route.
+in the expected values.  The one block of this table at which the reference's Pipe asserts (8/9 x 511 at block 64) is held route
+against route; over the family the reference asserts on a zone of blocks above the lowest one, not on one block
+(tests/tail_any_family_cases.py states the rule, tests/test_gpu_tail_any_family.py runs the family).
 The y rows hold exactly what the launch may read, NaN between and around them; the audio buffer starts as canaries and every float
 outside the rows' outputs is a canary afterwards.  Launch counters: a mode-1 run is exactly one launch of the general kernel, none
 of k_audio_tail_rows and none of the row forms; mode 2 and route 2 the reverse.  tests/test_audio_tail_any_cases.py shows on the CPU
