@@ -1,7 +1,8 @@
 /* fm_replay.c -- the FM receiver of the reference's examples/fm/fm.hs:30-41 fed from a file instead of a radio
  * ("file replay source feeding pinned buffers"), in plain C over the C ABI of libsdr_hip.so.
  *
- *     fm_replay [--s16] [--shift NUM/DEN | --stations NUM/DEN[,NUM/DEN...]] <iq_file | udp:PORT> <audio_f32_file> [blocks_per_push] [taps_prefix]
+ *     fm_replay [--s16] [--shift NUM/DEN | --stations NUM/DEN[,NUM/DEN...]] [--deemph TAU_US --audio-rate HZ]
+ *               <iq_file | udp:PORT> <audio_f32_file> [blocks_per_push] [taps_prefix]
  *
  * Reads interleaved unsigned 8-bit IQ (what rtl_sdr writes, what RTLSDRStream.hs:48-67 yields) in source blocks of
  * 8192 samples, `blocks_per_push` of them at a time, straight into the stream operator's pinned staging buffer
@@ -20,7 +21,10 @@
  * FM side through a bank, so the receiver is then always a bank and an int16 stream over it (sdrhip_fm_stream_create_bank_i16,
  * sdrhip_fm_stream_push_i16): the --stations given, or ONE station -- the --shift table, or {1, 0} when neither is given, which is
  * the plain receiver (a converted int16 sample times 1 + 0i keeps its bits) -- whose audio goes to <audio_f32_file> itself.
- * Output is bit-identical to the reference pipeline's (tests/test_gpu_examples.py). */
+ * --deemph TAU_US --audio-rate HZ (both or neither): the popped audio blocks of every station go through a de-emphasis Pipe
+ * (sdrhip_pipe_deemph, alpha = sdrhip_deemph_alpha(TAU_US * 1e-6, HZ); 75 us in the Americas, 50 us elsewhere; 48000 Hz for a 1.28 MHz
+ * capture), one Pipe per station, chained behind the stream the way am_replay.c chains its Pipes.  Without the flags nothing changes.
+ * Output is bit-identical to the reference pipeline's (tests/test_gpu_examples.py); with --deemph, to tests/deemph_model.py on it. */
 #define _POSIX_C_SOURCE 200809L
 #include <arpa/inet.h>
 #include <netinet/in.h>
@@ -93,12 +97,24 @@ static int push(sdrhip_fm_stream *st, const uint8_t *buf, int n_samples)
     return s16 ? sdrhip_fm_stream_push_i16(st, (const int16_t *)buf, n_samples) : sdrhip_fm_stream_push(st, buf, n_samples);
 }
 
+/* the `ready` blocks of a de-emphasis Pipe, popped into `tmp` (SOURCE_BLOCK floats) and written to f */
+static void drain(sdrhip_pipe *p, int ready, float *tmp, FILE *f)
+{
+    for (int i = 0; i < ready; i++) {
+        int len = sdrhip_pipe_pop(p, tmp, SOURCE_BLOCK);
+        check(len, "sdrhip_pipe_pop");
+        fwrite(tmp, sizeof(float), (size_t)len, f);
+    }
+}
+
 int main(int argc, char **argv)
 {
     /* --shift NUM/DEN or --stations NUM/DEN[,...], anywhere on the line; what is left are the positional arguments */
     long long shift_num = 0, shift_den = 0;
     long long st_num[SDRHIP_FM_BANK_MAX_STATIONS], st_den[SDRHIP_FM_BANK_MAX_STATIONS];
     int stations = 0;
+    double deemph_us = 0.0, audio_rate = 0.0;
+    int have_deemph = 0, have_rate = 0;
     {
         int w = 1;
         for (int i = 1; i < argc; i++) {
@@ -107,6 +123,16 @@ int main(int argc, char **argv)
                     fprintf(stderr, "fm_replay: --shift NUM/DEN with 1 <= DEN <= 65536\n");
                     return 2;
                 }
+                i++;
+            } else if (strcmp(argv[i], "--deemph") == 0 || strcmp(argv[i], "--audio-rate") == 0) {
+                const int is_tau = argv[i][2] == 'd';
+                char *end = NULL;
+                const double v = i + 1 < argc ? strtod(argv[i + 1], &end) : 0.0;
+                if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !(v > 0.0) || v > 1e12) {
+                    fprintf(stderr, "fm_replay: --deemph TAU_US --audio-rate HZ, both positive\n");
+                    return 2;
+                }
+                if (is_tau) { deemph_us = v; have_deemph = 1; } else { audio_rate = v; have_rate = 1; }
                 i++;
             } else if (strcmp(argv[i], "--s16") == 0) {
                 s16 = 1;
@@ -132,7 +158,8 @@ int main(int argc, char **argv)
         argc = w;
     }
     if (stations > 0 && shift_den > 0) { fprintf(stderr, "fm_replay: --shift or --stations, not both\n"); return 2; }
-    if (argc < 3) { fprintf(stderr, "usage: fm_replay [--s16] [--shift NUM/DEN | --stations NUM/DEN[,NUM/DEN...]] <iq_file | udp:PORT> <audio_f32_file> [blocks_per_push] [taps_prefix]\n"); return 2; }
+    if (have_deemph != have_rate) { fprintf(stderr, "fm_replay: --deemph TAU_US and --audio-rate HZ go together: both or neither\n"); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: fm_replay [--s16] [--shift NUM/DEN | --stations NUM/DEN[,NUM/DEN...]] [--deemph TAU_US --audio-rate HZ] <iq_file | udp:PORT> <audio_f32_file> [blocks_per_push] [taps_prefix]\n"); return 2; }
     const int bpp = argc > 3 ? atoi(argv[3]) : 64;
     if (bpp < 1) { fprintf(stderr, "fm_replay: blocks_per_push must be >= 1\n"); return 2; }
     int n_decim, n_resamp, n_audio;
@@ -176,6 +203,13 @@ int main(int argc, char **argv)
     sdrhip_fm_stream *st = NULL;
     check(make_stream(&st, chain, bank, bpp), "sdrhip_fm_stream_create");
     const int rows = sdrhip_fm_stream_rows(st);
+    /* --deemph: one de-emphasis Pipe per row behind the stream; its blocks come out at the length they went in */
+    sdrhip_pipe *de[SDRHIP_FM_BANK_MAX_STATIONS] = {NULL};
+    if (have_deemph) {
+        const float alpha = sdrhip_deemph_alpha(deemph_us * 1e-6, audio_rate);
+        for (int j = 0; j < rows; j++) check(sdrhip_pipe_deemph(&de[j], alpha), "sdrhip_pipe_deemph");
+        fprintf(stderr, "fm_replay: de-emphasis %g us at %g Hz: alpha = %.9g\n", deemph_us, audio_rate, (double)alpha);
+    }
 
     source src = {NULL, -1};
     if (is_udp) {
@@ -219,6 +253,7 @@ int main(int argc, char **argv)
     }
     if (!src.f && src.sock < 0) { fprintf(stderr, "fm_replay: cannot open input/output\n"); return 2; }
     float *block = (float *)malloc((size_t)rows * SOURCE_BLOCK * sizeof(float));
+    float *deemphasised = (float *)malloc(SOURCE_BLOCK * sizeof(float));
     long long samples = 0, audio = 0;
     for (;;) {
         uint8_t *buf = input_buffer(st);   /* pinned: the upload needs no intermediate copy */
@@ -236,10 +271,23 @@ int main(int argc, char **argv)
         }
         for (int i = 0; i < ready; i++) {
             check(sdrhip_fm_stream_pop_rows(st, block, SOURCE_BLOCK, 1), "sdrhip_fm_stream_pop_rows");   /* one block of every row */
-            for (int j = 0; j < rows; j++) fwrite(block + (size_t)j * SOURCE_BLOCK, sizeof(float), SOURCE_BLOCK, out[j]);
+            for (int j = 0; j < rows; j++) {
+                float *row = block + (size_t)j * SOURCE_BLOCK;
+                if (!de[j]) { fwrite(row, sizeof(float), SOURCE_BLOCK, out[j]); continue; }
+                int done = sdrhip_pipe_push(de[j], row, SOURCE_BLOCK);
+                check(done, "sdrhip_pipe_push");
+                drain(de[j], done, deemphasised, out[j]);
+            }
             audio += SOURCE_BLOCK;
         }
         if (got < (size_t)bpp) break;
+    }
+    for (int j = 0; j < rows; j++) {
+        if (!de[j]) continue;
+        int done = sdrhip_pipe_flush(de[j]);
+        check(done, "sdrhip_pipe_flush");
+        drain(de[j], done, deemphasised, out[j]);
+        sdrhip_pipe_destroy(de[j]);
     }
     if (per_station_files) fprintf(stderr, "fm_replay: %lld IQ samples in, %lld audio samples out for each of %d stations\n", samples, audio, rows);
     else fprintf(stderr, "fm_replay: %lld IQ samples in, %lld audio samples out\n", samples, audio);
@@ -247,6 +295,7 @@ int main(int argc, char **argv)
     if (src.sock >= 0) close(src.sock);
     for (int j = 0; j < rows; j++) fclose(out[j]);
     free(block);
+    free(deemphasised);
     sdrhip_fm_stream_destroy(st);
     sdrhip_fm_bank_destroy(bank);
     sdrhip_fm_chain_destroy(chain);

@@ -514,6 +514,54 @@ int sdrhip_fm_demod_run_rows(void *stream, const float *d_in_iq, int64_t in_stri
  * call (speculate, three repair rounds, settle) with chunks. */
 long long sdrhip_debug_rows_launches(void);
 
+/* ---- de-emphasis: the one-pole low-pass behind an FM receiver's audio, one row or every row of a bank ----
+ *     y[i] = y[i-1] + alpha * (x[i] - y[i-1])        y[-1] = state
+ * Three f32 operations per sample, each rounded to nearest, in this order: subtract, multiply, add; no FMA.  The final state is
+ * y[n-1], with n == 0 the state.  The reference has no de-emphasis: the definition is this library's, written as the reference
+ * writes agc (a mapAccum at Float), and tests/deemph_model.py is its model.  Bit-identical to the sequential loop, final states
+ * included, on every input whose trajectory stays finite; where the sequential loop holds a NaN the device holds a NaN, payload and
+ * sign unspecified (an Inf sample, or an x - y that overflows, turns the state into NaN one or two steps later).
+ * sdrhip_deemph_alpha is host arithmetic: (float)(1.0 - exp(-1.0 / (tau_seconds * sample_rate))) computed in double; 0.0f, a value the
+ * run calls refuse, when either argument is not finite and positive.  75e-6 s at 48 kHz gives 0.2425..., at 256 kHz 0.0507....
+ * Contract: that of the dcBlocker row form above.  Everything is ordered on `stream`, no host synchronisation; not in-place; states
+ * are device arrays of `rows` floats on both sides and d_final may be d_state; n == 0 copies the states and touches nothing else;
+ * floats outside the rows' [0, n) are untouched; rows 1 .. SDRHIP_ROWS_MAX; run_in = 0 is the default, ceil(40 / alpha) (about 1.5
+ * times the slowest meeting of two trajectories seen, tests/test_deemph_model.py), any other value is rounded up to a multiple of 4,
+ * and the result never depends on it.  sdrhip_deemph_run is the rows call with one row and `state` by value.
+ * Routes (the auto rule).  1 SEQ: one workgroup per row, one lane walks the row; n < 2 * run-in, and n > 65536 without a workspace.  2 WG: ONE launch,
+ * one workgroup per row, lane j owns chunk j (max(16, n / 1024 rounded up to 4) samples, at most 1024 chunks): it runs in, writes its
+ * chunk, and the workgroup repeats rounds in which every chunk whose start state differs from its predecessor's end state is
+ * recomputed, until a round finds no difference (at most `chunks` rounds); it fits 2 * run-in <= n <= 65536 and needs no workspace; auto
+ * takes it there, except with a workspace from n = 32768 on.  3 LS: the dcBlocker rows launch set (speculate, three repair rounds,
+ * settle; 5 launches), with a workspace, for n >= 32768 (and >= 2 * run-in).  The edge at 32768 is read from the sweep
+ * (profiles/deemph_bench.txt: WG ahead of LS at 16384, LS ahead at 32768 and 65536, at 1 and 32 rows); the lower edge and the bound of
+ * 65536 are the starting values, which the sweep could not move (README.md "And for de-emphasis").  An exactly constant row (silence, padding) does not let
+ * trajectories meet; it is repaired chunk by chunk, up to the time of a sequential walk.
+ * The access width is one for all rows: 16 / 8 / 4 bytes as the base pointers and, with rows > 1, the strides * 4 allow.
+ * d_workspace is needed by LS only (*_workspace_bytes; NULL is fine on SEQ and WG).  When given it starts with rows x four uint32
+ * statistics on every route.  SEQ: zeros.  LS: the dcBlocker's words.  WG: {rounds that recomputed a chunk, 0, chunks whose start
+ * state was replaced summed over the rounds, chunks}.
+ * SDRHIP_ERR_ARG, before any device work and with nothing written: alpha outside (0, 1] or not finite, rows out of range, a null
+ * pointer other than d_workspace, n < 0, run_in < 0, d_in == d_out, with rows > 1 a stride shorter than n, a workspace smaller than
+ * *_workspace_bytes, and a forced route (below) that does not fit. */
+float sdrhip_deemph_alpha(double tau_seconds, double sample_rate);
+size_t sdrhip_deemph_workspace_bytes(int64_t n);
+int sdrhip_deemph_run(void *stream, const float *d_in, float *d_out, int64_t n, float alpha, float state,
+                      float *d_final /* 1 float, device */, void *d_workspace, size_t workspace_bytes, int run_in);
+size_t sdrhip_deemph_rows_workspace_bytes(int rows, int64_t n);
+int sdrhip_deemph_run_rows(void *stream, const float *d_in, int64_t in_stride, float *d_out, int64_t out_stride,
+                           int rows, int64_t n, float alpha, const float *d_state /* rows floats, device */,
+                           float *d_final /* rows floats, device */, void *d_workspace, size_t workspace_bytes, int run_in);
+/* Diagnostics.  The plan the run calls follow for these arguments and the route in force: returns the chunks per row (0 = SEQ),
+ * *route (1 SEQ, 2 WG, 3 LS), *chunk and *run_in_used (each may be NULL); SDRHIP_ERR_ARG where the run call would refuse. */
+int sdrhip_debug_deemph_plan(int rows, int64_t n, float alpha, int run_in, int has_workspace,
+                             int *route, int64_t *chunk, int64_t *run_in_used);
+/* 0 auto (the default), 1 SEQ, 2 WG, 3 LS, process-wide, for tests and tools: a forced route that does not fit a call (WG past its
+ * bound, LS without a workspace, either below two run-ins) makes that call SDRHIP_ERR_ARG.  Pipes always follow the auto rule. */
+void sdrhip_debug_set_deemph_route(int route);
+/* kernel launches of the de-emphasis calls, process-wide: 1 per SEQ or WG call, 5 (one launch set) per LS call */
+long long sdrhip_debug_deemph_launches(void);
+
 /* amDemod over rows: row r's n samples at d_in_iq + r * in_stride -> n floats at d_out + r * out_stride, bit for bit the
  * one-row call (sdrhip_am_demod_run) on that row, whatever the other rows hold; it is the same kernel with the row on
  * the grid's second axis.  Exactly one launch for any rows and n > 0 (the workgroups loop over a row's samples, so no
@@ -1404,6 +1452,13 @@ int sdrhip_pipe_dc_blocker(sdrhip_pipe **p);                                    
 /* complex blocks in, complex blocks out at the length they came in; the state starts at 1 and is carried across blocks on the
  * device (sdrhip_agc_run).  save / restore carry the state; mu and reference are the constructor's, not part of it. */
 int sdrhip_pipe_agc(sdrhip_pipe **p, float mu, float reference);                 /* agcPipe, Util.hs:344-348 */
+/* De-emphasis (sdrhip_deemph_run) on host blocks: float blocks in, float blocks out at the length they came in, a map stage like
+ * sdrhip_pipe_dc_blocker: staged blocks go out as ONE run over all of them, from and to the state on the device (one float, starting
+ * at 0), never read in place.  alpha as sdrhip_deemph_run takes it (SDRHIP_ERR_ARG otherwise, *p NULL).  It is a second form of the
+ * one-pole map kind, not a kind of its own: a saved state holds the dcBlocker's kind number, the state in the first of its four
+ * state floats and alpha in the third (a dcBlocker's third is 0, as it always was).  Restore refuses, leaving the pipe fresh, a
+ * dcBlocker state into a de-emphasis pipe, the reverse, and a de-emphasis state of another alpha (compared as bits). */
+int sdrhip_pipe_deemph(sdrhip_pipe **p, float alpha);
 /* `P.map (VG.zipWith (*) osc) >-> firDecimator deci n` with osc indexed by the stream position: cfloat blocks in, blocks of exactly
  * block_size_out decimated samples out.  Push, pop, coalesce, adaptive, input_buffer, save and restore behave as for
  * sdrhip_pipe_fir_decimator; the stream position that selects the oscillator phase is part of the saved state (the table and

@@ -217,6 +217,8 @@ struct sdrhip_pipe {
     std::deque<int> demod_blocks;      // output block lengths (one per input block)
     DevBuf map_state, map_ws;
     float agc_mu = 0.0f, agc_ref = 0.0f;
+    // PK_DCBLOCK's second form (sdrhip_pipe_deemph): not 0 = a de-emphasis pipe of this alpha, whose map_state is {y, 0, alpha, 0}
+    float deemph_alpha = 0.0f;
     bool is_map() const { return kind == PK_DEMOD || kind == PK_DCBLOCK || kind == PK_AGC || kind == PK_AM; }
 
     int esz_in() const { return cplx_in ? 2 : 1; }

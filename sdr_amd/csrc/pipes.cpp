@@ -23,6 +23,7 @@
 // it, placed in device memory so that the banked launch's first window is 16-byte aligned (HostStream::dev_skew).
 //
 // The waterfall Pipe (sdrhip_pipe_spectrum), the spectrum operator's reducing form on the same engine: pipes_spectrum.cpp.
+#include "deemph.hpp"
 #include "pipe.hpp"
 
 int pipe_new(sdrhip_pipe** out, PipeKind kind, const FirDesc* fir, const ResampDesc* rs, int block_out, bool cplx_in, bool cplx_out, int I,
@@ -279,7 +280,21 @@ int sdrhip_pipe_agc(sdrhip_pipe** pp, float mu, float reference)
     return pipe_dev_state(pp, (*pp)->map_state, sizeof init, init, "sdrhip_pipe_agc");
 }
 
-// ---- map stages (fmDemod, amDemod, dcBlockingFilter, agcPipe): one output vector per input vector ------------------------------
+// De-emphasis: a second form of the one-pole map kind (PK_DCBLOCK with deemph_alpha set), as sdrhip_pipe_narrow_bank_audio is a form of
+// kind 14.  The state on the device is {y, 0, alpha, 0}: the kernels read and write the first float only, and alpha in the third is what
+// tells a saved state from a dcBlocker's (whose third float is 0) and from one of another alpha (pipes_state.cpp).
+int sdrhip_pipe_deemph(sdrhip_pipe** pp, float alpha)
+{
+    if (pp != nullptr) *pp = nullptr;
+    SDRHIP_REQUIRE(pp != nullptr && alpha > 0.0f && alpha <= 1.0f, "sdrhip_pipe_deemph: a pipe pointer and 0 < alpha <= 1");
+    int rc = pipe_new(pp, PK_DCBLOCK, nullptr, nullptr, 0, false, false, 1, 1, 1);
+    if (rc != SDRHIP_OK) return rc;
+    (*pp)->deemph_alpha = alpha;
+    const float init[4] = {0.0f, 0.0f, alpha, 0.0f};
+    return pipe_dev_state(pp, (*pp)->map_state, sizeof init, init, "sdrhip_pipe_deemph");
+}
+
+// ---- map stages (fmDemod, amDemod, dcBlockingFilter, agcPipe, de-emphasis): one output vector per input vector ---------------------
 // Blocks are staged one behind the other in the slot's pinned buffer and go out as ONE run over all of them -- the carry of a
 // block is its predecessor's last sample (fmDemod, Demod.hs:41,46) / the filter's running pair kept on the device
 // (dcBlockingFilter, Filter.hs:730-739), which is exactly what a run over the concatenation computes (amDemod carries nothing); the block lengths are
@@ -308,6 +323,14 @@ static int map_submit(sdrhip_pipe* p)
             if (rc != SDRHIP_OK) return rc;
             launch_agc(s, n, p->agc_mu, p->agc_ref, 1.0f, (const float*)d_in, (float*)d_out, (float*)p->map_state.p, p->map_ws.p, 0,
                        (const float*)p->map_state.p);
+        } else if (p->deemph_alpha != 0.0f) {
+            // the auto rule with a workspace, whatever route a test has forced: a forced route need not fit a submission
+            int rc = grow(p->map_ws, deemph_rows_workspace_bytes(1, n), s);
+            if (rc != SDRHIP_OK) return rc;
+            DeemphPlan plan;
+            (void)deemph_plan(1, n, p->deemph_alpha, 0, true, DEEMPH_AUTO, &plan);
+            launch_deemph_rows(s, plan, 1, n, p->deemph_alpha, 0.0f, (const float*)p->map_state.p, (const float*)d_in, n, (float*)d_out, n,
+                               (float*)p->map_state.p, p->map_ws.p);
         } else {
             int rc = grow(p->map_ws, dc_blocker_workspace_bytes(n), s);
             if (rc != SDRHIP_OK) return rc;

@@ -11,6 +11,9 @@
 //   5. the bank record (the AM and NFM kinds)   6. the audio record (the audio Pipes)   7. the narrow record (the narrow bank's Pipe)
 //   8. the audio record again, behind the narrow record: the narrow bank's Pipe with an audio tail (has_tail = 1 in record 7), whose
 //      rows are the carried REAL stage-2 outputs of the second carry
+// The header's dc[4] is the map stage's 16 bytes of device state as they stand: dcBlocker {lastSample, lastOutput, 0, 0}, agc {state, 0, 0,
+// 0}, and de-emphasis (the one-pole map kind's second form: the header's kind is the dcBlocker's) {y, 0, alpha, 0}.  dc[2] as bits tells
+// the two forms apart -- 0 = dcBlocker, whose states keep every byte they had -- and one alpha from another; restore compares it.
 // Each of these trailing records is [a fixed part | n_floats floats of a ChannelState | a rows carry's K * y_n elements]: one Trailer
 // says what this pipe writes as the fixed part, where the floats live, which carry's rows follow, and how a state's fixed part is
 // checked against this pipe.  state_bytes, save and restore walk the same list (Trailers).  Version 3 (the waterfall) is a header of its own
@@ -245,6 +248,14 @@ int sdrhip_pipe_restore(sdrhip_pipe* p, const void* buf, size_t bytes)
     SDRHIP_REQUIRE(h.kind == (int32_t)p->kind && h.block_out == p->block_out && h.I == p->I && h.D == p->D && h.Lp == p->Lp &&
                        h.cplx_in == (int32_t)p->cplx_in && h.cplx_out == (int32_t)p->cplx_out && h.head_cap == p->eng.head_cap,
                    "sdrhip_pipe_restore: the state belongs to a pipe of another kind or geometry");
+    if (p->kind == PK_DCBLOCK) {             // the two forms of the one-pole map kind: dc[2] holds alpha, 0 in a dcBlocker's state
+        uint32_t theirs, mine;
+        memcpy(&theirs, &h.dc[2], sizeof theirs);
+        memcpy(&mine, &p->deemph_alpha, sizeof mine);
+        SDRHIP_REQUIRE(theirs == 0 || mine != 0, "sdrhip_pipe_restore: the state belongs to a de-emphasis pipe, this is a dcBlocker pipe");
+        SDRHIP_REQUIRE(theirs != 0 || mine == 0, "sdrhip_pipe_restore: the state belongs to a dcBlocker pipe, this is a de-emphasis pipe");
+        SDRHIP_REQUIRE(theirs == mine, "sdrhip_pipe_restore: the state belongs to a de-emphasis pipe of another alpha");
+    }
     SDRHIP_REQUIRE(h.hist_n >= 0 && h.hist_n <= h.head_cap && h.pending >= 0 && h.n_blocks >= 0 && h.E_prev >= h.hist_n && h.m_done >= 0,
                    "sdrhip_pipe_restore: inconsistent state");
     if (!p->is_map()) {

@@ -331,6 +331,19 @@ lib.sdrhip_dc_blocker_rows_workspace_bytes.restype = C.c_size_t
 lib.sdrhip_dc_blocker_run_rows.argtypes = [_vp, _vp, _i64, _vp, _i64, C.c_int, _i64, _vp, _vp, _vp, C.c_size_t, C.c_int]
 lib.sdrhip_debug_dc_rows_plan.argtypes = [C.c_int, C.c_int64, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]
 lib.sdrhip_fm_demod_run_rows.argtypes = [_vp, _vp, _i64, _i64, _vp, _i64, C.c_int, _i64, _i64, _vp, _vp]
+lib.sdrhip_deemph_alpha.argtypes = [C.c_double, C.c_double]
+lib.sdrhip_deemph_alpha.restype = C.c_float
+lib.sdrhip_deemph_workspace_bytes.argtypes = [C.c_int64]
+lib.sdrhip_deemph_workspace_bytes.restype = C.c_size_t
+lib.sdrhip_deemph_run.argtypes = [_vp, _vp, _vp, C.c_int64, C.c_float, C.c_float, _vp, _vp, C.c_size_t, C.c_int]
+lib.sdrhip_deemph_rows_workspace_bytes.argtypes = [C.c_int, C.c_int64]
+lib.sdrhip_deemph_rows_workspace_bytes.restype = C.c_size_t
+lib.sdrhip_deemph_run_rows.argtypes = [_vp, _vp, _i64, _vp, _i64, C.c_int, _i64, C.c_float, _vp, _vp, _vp, C.c_size_t, C.c_int]
+lib.sdrhip_debug_deemph_plan.argtypes = [C.c_int, C.c_int64, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(_i64), C.POINTER(_i64)]
+lib.sdrhip_debug_set_deemph_route.argtypes = [C.c_int]
+lib.sdrhip_debug_set_deemph_route.restype = None
+lib.sdrhip_debug_deemph_launches.argtypes = []
+lib.sdrhip_debug_deemph_launches.restype = C.c_longlong
 lib.sdrhip_am_demod_run.argtypes = [_vp, _vp, _vp, _i64]
 lib.sdrhip_am_demod_run_rows.argtypes = [_vp, _vp, _i64, _vp, _i64, C.c_int, _i64]
 lib.sdrhip_debug_am_demod_launches.argtypes = []
@@ -393,6 +406,7 @@ lib.sdrhip_pipe_fm_demod.argtypes = [C.POINTER(_vp)]
 lib.sdrhip_pipe_am_demod.argtypes = [C.POINTER(_vp)]
 lib.sdrhip_pipe_dc_blocker.argtypes = [C.POINTER(_vp)]
 lib.sdrhip_pipe_agc.argtypes = [C.POINTER(_vp), C.c_float, C.c_float]
+lib.sdrhip_pipe_deemph.argtypes = [C.POINTER(_vp), C.c_float]
 lib.sdrhip_pipe_tuner.argtypes = [C.POINTER(_vp), _vp, C.c_int]
 lib.sdrhip_pipe_tuner_bank.argtypes = [C.POINTER(_vp), _vp, C.c_int, C.c_int]
 lib.sdrhip_pipe_rows.argtypes = [_vp]
@@ -700,6 +714,67 @@ def dc_blocker_rows(x, states, run_in=0, out=None, final=None, workspace="auto")
     check(lib.sdrhip_dc_blocker_run_rows(torch.cuda.current_stream().cuda_stream, _dptr(x), in_stride, _dptr(out), out_stride,
                                          rows, n, states.data_ptr(), final.data_ptr(), ws_ptr, ws_bytes, run_in),
           "sdrhip_dc_blocker_run_rows")
+    return out, final
+
+
+# ---- de-emphasis (sdr_hip.h "de-emphasis") ---------------------------------------------------------------------------------------
+DEEMPH_AUTO, DEEMPH_SEQ, DEEMPH_WG, DEEMPH_LS = 0, 1, 2, 3
+
+
+def deemph_alpha(tau_seconds, sample_rate):
+    """sdrhip_deemph_alpha: float32(1 - exp(-1 / (tau * rate))) as a Python float; 0.0 for arguments that are not finite and positive."""
+    return float(lib.sdrhip_deemph_alpha(tau_seconds, sample_rate))
+
+
+def deemph_plan(rows, n, alpha, run_in=0, has_workspace=True):
+    """sdrhip_debug_deemph_plan: (chunks per row, route, chunk length, run-in); route 1 SEQ (chunks == 0), 2 WG, 3 LS."""
+    r, c, w = C.c_int(), _i64(), _i64()
+    chunks = check(lib.sdrhip_debug_deemph_plan(rows, n, alpha, run_in, int(bool(has_workspace)), C.byref(r), C.byref(c), C.byref(w)),
+                   "sdrhip_debug_deemph_plan")
+    return chunks, r.value, c.value, w.value
+
+
+def set_deemph_route(route):
+    """sdrhip_debug_set_deemph_route: 0 auto, 1 SEQ, 2 WG, 3 LS, process-wide; a forced route that does not fit a call is refused."""
+    lib.sdrhip_debug_set_deemph_route(int(route))
+
+
+def deemph_launches():
+    """sdrhip_debug_deemph_launches: kernel launches of the de-emphasis calls in this process (1 per SEQ or WG call, 5 per LS call)."""
+    return int(lib.sdrhip_debug_deemph_launches())
+
+
+def deemph_rows(x, alpha, states, run_in=0, out=None, final=None, workspace="auto"):
+    """sdrhip_deemph_run_rows on the current stream -> (out, final).  x: rows x n float32 on the device, rows contiguous, any row
+    stride (a view into a bank's audio will do).  states: rows float32 on the device; final likewise (default: new; may be `states`).
+    workspace: "auto" = allocate, None = none, or a device tensor of bytes.  No synchronisation."""
+    import torch
+    rows, n, in_stride = _rows_of(x, "deemph_rows")
+    if out is None:
+        out = _rows_empty(rows, n, torch.float32, x.device)
+    orows, on, out_stride = _rows_of(out, "deemph_rows")
+    if (orows, on) != (rows, n) or states.numel() != rows or states.dtype != torch.float32 or not states.is_contiguous():
+        raise ValueError("deemph_rows: out and states must match x's rows")
+    if final is None:
+        final = torch.empty(rows, dtype=torch.float32, device=x.device)
+    ws, ws_ptr, ws_bytes = _rows_workspace(workspace, lib.sdrhip_deemph_rows_workspace_bytes(rows, n), x.device)
+    check(lib.sdrhip_deemph_run_rows(torch.cuda.current_stream().cuda_stream, _dptr(x), in_stride, _dptr(out), out_stride, rows, n,
+                                     alpha, states.data_ptr(), final.data_ptr(), ws_ptr or None, ws_bytes, run_in), "sdrhip_deemph_run_rows")
+    return out, final
+
+
+def deemph(x, alpha, state=0.0, run_in=0):
+    """sdrhip_deemph_run on the current stream -> (out, final): x a 1-D float32 device tensor, final a device tensor of one float.
+    No synchronisation."""
+    import torch
+    x = x.contiguous()
+    n = x.numel()
+    out = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)[:n]
+    final = torch.empty(1, dtype=torch.float32, device=x.device)
+    wsb = lib.sdrhip_deemph_workspace_bytes(n)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
+    check(lib.sdrhip_deemph_run(torch.cuda.current_stream().cuda_stream, _dptr(x), _dptr(out), n, alpha, state, final.data_ptr(),
+                                ws.data_ptr(), wsb, run_in), "sdrhip_deemph_run")
     return out, final
 
 
@@ -1846,6 +1921,8 @@ class Pipe(_Handle):
             check(lib.sdrhip_pipe_am_demod(C.byref(self.h)), "sdrhip_pipe_am_demod")
         elif kind == "dc_blocker":
             check(lib.sdrhip_pipe_dc_blocker(C.byref(self.h)), "sdrhip_pipe_dc_blocker")
+        elif kind == "deemph":
+            check(lib.sdrhip_pipe_deemph(C.byref(self.h), mu), "sdrhip_pipe_deemph")
         elif kind == "agc":
             if mu is None or reference is None:
                 raise ValueError("Pipe('agc') needs mu and reference")
@@ -1908,6 +1985,12 @@ class Pipe(_Handle):
         int16 arrays; an array of another dtype is refused), rows of n float32 out -- output row R reducing input rows R*group ..
         R*group+group-1 of the whole stream, as Spectrum.reduce_device over the concatenated pushes.  hop defaults to n."""
         return Pipe("spectrum", spectrum, spectrum.n, spectrum_args=(spectrum.n if hop is None else hop, group, reduce, unit, floor_db))
+
+    @staticmethod
+    def deemph(alpha):
+        """De-emphasis on host blocks (sdrhip_pipe_deemph): float32 blocks in, blocks of the same length out, the state (starting at 0)
+        carried on the device."""
+        return Pipe("deemph", mu=alpha)
 
     @staticmethod
     def am_demod():
