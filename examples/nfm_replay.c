@@ -10,7 +10,8 @@
  * demodulated samples go to OUT_PREFIX.chJ.f32 as float32, whole blocks of N (default 1024) only, as the Pipe yields them.  The
  * capture is pushed SAMPLES (default 8192) at a time, the rest in one shorter push.  ONE Pipe for all channels (sdrhip_pipe_nfm_bank
  * over sdrhip_nfm_bank over sdrhip_tuner_bank): one copy over the link per push, K float rows back.  What follows the demodulator
- * in a receiver (de-emphasis, squelch) is the caller's; a second decimator in FRONT of the demodulator is --narrow, below.
+ * in a receiver is the caller's (de-emphasis: sdrhip_deemph_run_rows; squelch: sdrhip_squelch_run_rows, as examples/squelch_scan.c
+ * uses it); a second decimator in FRONT of the demodulator is --narrow, below.
  * With --audio the files hold AUDIO instead: the demodulated samples resampled by I/D (default 3/10: 160 ksample/s to 48 k) with the
  * taps of RESAMP_TAPS.f32, filtered with the symmetric filter whose first half is AUDIO_HALF_TAPS.f32 and multiplied by G (default
  * 1), every Pipe of those stages with blocks of N -- sdrhip_pipe_nfm_bank_audio over an sdrhip_audio_tail, still ONE Pipe, one copy

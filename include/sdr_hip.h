@@ -562,6 +562,67 @@ void sdrhip_debug_set_deemph_route(int route);
 /* kernel launches of the de-emphasis calls, process-wide: 1 per SEQ or WG call, 5 (one launch set) per LS call */
 long long sdrhip_debug_deemph_launches(void);
 
+/* ---- squelch: a gate decision per block from the block's mean power, one row or every row of a bank ----
+ * A detector row (real, or complex when det_complex = 1; it may be the signal row itself) is cut into n_blocks blocks of block_det
+ * samples, the signal row into as many blocks of block_sig floats.  The reference has no squelch: the definition is this library's,
+ * and tests/squelch_model.py is its model.  Every operation is f32 and rounded, no FMA.
+ * Power of a sample: x * x; complex: a = re * re, b = im * im, a + b.  Level of a block: 256 slots, slot[j] = the sum of the block's
+ * powers p_i with i mod 256 == j in ascending i (an empty slot is +0); fold slot[j] += slot[j + w] (j < w) for w = 128, 64 .. 1;
+ * level = slot[0] * (float)(1.0 / block_det).
+ * Gate, block after block of a row, state {det, hang_left} (int32; a fresh stream starts from {0, 0}; on entry det is read as
+ * det != 0 and hang_left is clamped into 0 .. hang_blocks):
+ *     open_above = 1: want_open = level >= open_level, want_close = level <  close_level      (close_level <= open_level)
+ *     open_above = 0: want_open = level <= open_level, want_close = level >  close_level      (close_level >= open_level)
+ *     if want_open: det = 1; else if want_close: det = 0;            (a NaN level, or one between the two levels: det stays)
+ *     if det: hang_left = hang_blocks, gate = 1; else if hang_left > 0: hang_left -= 1, gate = 1; else gate = 0
+ * Output: with gate 1 the block's block_sig signal floats are copied bit for bit (NaN payloads included), with gate 0 they are +0.0f.
+ * d_levels / d_gates, when given, receive every block's level and gate (rows x n_blocks, rows contiguous).  Consecutive calls over
+ * consecutive whole blocks that hand d_final on as d_state are one stream and give the bits of one call.
+ * Contract.  Everything is ordered on `stream`, no host synchronisation.  Row r is read and written at d_det + r * det_stride,
+ * d_in + r * in_stride, d_out + r * out_stride (strides in floats); floats outside the rows' [0, n_blocks * block_sig) are untouched.
+ * d_in == NULL && d_out == NULL is detect-only: state, levels and gates are written, block_sig is ignored.  n_blocks == 0 copies the
+ * states (read as above) and touches nothing else.  d_det == d_in is self-detection.  d_out == d_in gates in place and needs
+ * out_stride == in_stride; the levels are those of the samples as they were before the call.  d_out == d_det is allowed only when
+ * d_det == d_in as well, and then the detector is real with block_det == block_sig and det_stride == in_stride (the rows coincide
+ * block for block).  d_state NULL = {0, 0} for every row; d_final may be NULL, and may be d_state.  sdrhip_squelch_run is the rows
+ * call with one row and the state by value.
+ * Access width: 16 / 8 / 4 bytes, chosen on its own for the detector (from d_det, with rows > 1 det_stride, and with n_blocks > 1
+ * the floats of a block), the signal and the output (from the pointer and, with rows > 1, the stride).
+ * Routes.  1 WG: ONE launch, one workgroup of 16 waves per row, no workspace: one wave per block takes the levels (lane l holds
+ * slots 4l .. 4l + 3), the workgroup finds the gates of up to 1024 blocks by two max-scans in LDS, copies the signal and writes the
+ * state; a row of more than 1024 blocks is walked in groups of 1024 inside the workgroup.  2 LS: three launches (two when
+ * detect-only): levels over blocks x rows, gate with one workgroup per row, apply over signal tiles x rows; it needs a workspace
+ * (levels and gates: rows * n_blocks * 5 bytes + 64).  Auto rule: WG while n_blocks <= 1024 and a row's detector plus signal bytes
+ * are <= 256 KiB; past either, LS when a workspace is given, WG when not.  Both edges are the starting values: README.md "And for
+ * squelch" says what profiles/squelch_bench.txt could and could not tell about them.
+ * SDRHIP_ERR_ARG, before any device work and with nothing written: rows outside 1 .. SDRHIP_ROWS_MAX; block_det or block_sig outside
+ * 1 .. 2^20; n_blocks < 0 or a row of more than 2^40 floats; a level that is not finite or is negative; the levels in the wrong
+ * order for the polarity; hang_blocks outside 0 .. 2^30; open_above or det_complex other than 0 / 1; a null d_det; one of d_in /
+ * d_out null without the other; an odd det_stride with a complex detector; with rows > 1 a stride shorter than the row; the
+ * aliasings not allowed above; a workspace smaller than *_workspace_bytes; a forced route (below) that does not fit. */
+size_t sdrhip_squelch_rows_workspace_bytes(int rows, int64_t n_blocks);
+int sdrhip_squelch_run_rows(void *stream, const float *d_det, int64_t det_stride, int det_complex, int block_det,
+                            const float *d_in, int64_t in_stride, float *d_out, int64_t out_stride, int block_sig,
+                            int rows, int64_t n_blocks, float open_level, float close_level, int hang_blocks, int open_above,
+                            const int32_t *d_state /* rows x {det, hang_left}; NULL = {0, 0} */,
+                            int32_t *d_final /* NULL, or rows x 2; may be d_state */,
+                            float *d_levels /* NULL, or rows x n_blocks */, uint8_t *d_gates /* NULL, or rows x n_blocks */,
+                            void *d_workspace, size_t workspace_bytes);
+int sdrhip_squelch_run(void *stream, const float *d_det, int det_complex, int block_det, const float *d_in, float *d_out,
+                       int block_sig, int64_t n_blocks, float open_level, float close_level, int hang_blocks, int open_above,
+                       int32_t det, int32_t hang_left, int32_t *d_final /* NULL, or 2 int32 on the device */,
+                       float *d_levels, uint8_t *d_gates, void *d_workspace, size_t workspace_bytes);
+/* Diagnostics.  The route the run calls take for these arguments and the route in force (block_sig = 0: detect-only): returns the
+ * kernel launches of such a call (1 on WG; 3 on LS, 2 when detect-only) and *route (1 WG, 2 LS; may be NULL); SDRHIP_ERR_ARG where
+ * the run call would refuse the sizes or the route. */
+int sdrhip_debug_squelch_plan(int rows, int64_t n_blocks, int block_det, int det_complex, int block_sig, int has_workspace,
+                              int *route);
+/* 0 auto (the default), 1 WG, 2 LS, process-wide, for tests and tools: forced LS without a workspace makes a call SDRHIP_ERR_ARG
+ * (n_blocks == 0 is always the one state-copying launch). */
+void sdrhip_debug_set_squelch_route(int route);
+/* kernel launches of the squelch calls, process-wide */
+long long sdrhip_debug_squelch_launches(void);
+
 /* amDemod over rows: row r's n samples at d_in_iq + r * in_stride -> n floats at d_out + r * out_stride, bit for bit the
  * one-row call (sdrhip_am_demod_run) on that row, whatever the other rows hold; it is the same kernel with the row on
  * the grid's second axis.  Exactly one launch for any rows and n > 0 (the workgroups loop over a row's samples, so no

@@ -344,6 +344,17 @@ lib.sdrhip_debug_set_deemph_route.argtypes = [C.c_int]
 lib.sdrhip_debug_set_deemph_route.restype = None
 lib.sdrhip_debug_deemph_launches.argtypes = []
 lib.sdrhip_debug_deemph_launches.restype = C.c_longlong
+lib.sdrhip_squelch_rows_workspace_bytes.argtypes = [C.c_int, C.c_int64]
+lib.sdrhip_squelch_rows_workspace_bytes.restype = C.c_size_t
+lib.sdrhip_squelch_run_rows.argtypes = [_vp, _vp, _i64, C.c_int, C.c_int, _vp, _i64, _vp, _i64, C.c_int, C.c_int, _i64, C.c_float, C.c_float,
+                                        C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t]
+lib.sdrhip_squelch_run.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _i64, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int32,
+                                   C.c_int32, _vp, _vp, _vp, _vp, C.c_size_t]
+lib.sdrhip_debug_squelch_plan.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+lib.sdrhip_debug_set_squelch_route.argtypes = [C.c_int]
+lib.sdrhip_debug_set_squelch_route.restype = None
+lib.sdrhip_debug_squelch_launches.argtypes = []
+lib.sdrhip_debug_squelch_launches.restype = C.c_longlong
 lib.sdrhip_am_demod_run.argtypes = [_vp, _vp, _vp, _i64]
 lib.sdrhip_am_demod_run_rows.argtypes = [_vp, _vp, _i64, _vp, _i64, C.c_int, _i64]
 lib.sdrhip_debug_am_demod_launches.argtypes = []
@@ -776,6 +787,93 @@ def deemph(x, alpha, state=0.0, run_in=0):
     check(lib.sdrhip_deemph_run(torch.cuda.current_stream().cuda_stream, _dptr(x), _dptr(out), n, alpha, state, final.data_ptr(),
                                 ws.data_ptr(), wsb, run_in), "sdrhip_deemph_run")
     return out, final
+
+
+# ---- squelch (sdr_hip.h "squelch") -----------------------------------------------------------------------------------------------
+SQUELCH_AUTO, SQUELCH_WG, SQUELCH_LS = 0, 1, 2
+
+
+def squelch_plan(rows, n_blocks, block_det, det_complex=False, block_sig=0, has_workspace=True):
+    """sdrhip_debug_squelch_plan: (kernel launches, route); route 1 WG, 2 LS; block_sig = 0 is detect-only."""
+    r = C.c_int()
+    launches = check(lib.sdrhip_debug_squelch_plan(rows, n_blocks, block_det, int(bool(det_complex)), block_sig, int(bool(has_workspace)),
+                                                   C.byref(r)), "sdrhip_debug_squelch_plan")
+    return launches, r.value
+
+
+def set_squelch_route(route):
+    """sdrhip_debug_set_squelch_route: 0 auto, 1 WG, 2 LS, process-wide; forced LS without a workspace is refused."""
+    lib.sdrhip_debug_set_squelch_route(int(route))
+
+
+def squelch_launches():
+    """sdrhip_debug_squelch_launches: kernel launches of the squelch calls in this process."""
+    return int(lib.sdrhip_debug_squelch_launches())
+
+
+def squelch_run_rows(det, block_det, sig, block_sig, open_level, close_level, hang_blocks=0, open_above=True, states=None, out=None,
+                     final=None, levels=None, gates=None, workspace="auto", n_blocks=None):
+    """sdrhip_squelch_run_rows on the current stream -> (out, final, levels, gates).  det: rows x m complex64 (a complex detector) or
+    rows x m float32 (a real one) on the device, rows contiguous, any row stride.  sig: rows x (n_blocks * block_sig) float32, `det`
+    itself for self-detection, or None for detect-only (out is None then).  out: default a new tensor; `sig` gates in place.
+    states: rows x 2 int32 on the device or None ({0, 0}); final likewise (default: new; may be `states`).  levels / gates: True for
+    new tensors, a tensor to fill, or None.  n_blocks defaults to the whole blocks of det.  No synchronisation."""
+    import torch
+    cplx = det.is_complex()
+    rows, m, det_stride = _rows_of(det, "squelch_run_rows")
+    if n_blocks is None:
+        n_blocks = m // block_det
+    in_stride = out_stride = 0
+    if sig is not None:
+        srows, sn, in_stride = _rows_of(sig, "squelch_run_rows")
+        if srows != rows or sn < n_blocks * block_sig or sig.dtype != torch.float32:
+            raise ValueError("squelch_run_rows: sig must be float32 with det's rows and n_blocks * block_sig floats in each")
+        if out is None:
+            out = _rows_empty(rows, n_blocks * block_sig, torch.float32, sig.device)
+        orows, on, out_stride = _rows_of(out, "squelch_run_rows")
+        if orows != rows or on < n_blocks * block_sig:
+            raise ValueError("squelch_run_rows: out must match sig")
+    if states is not None and (states.numel() != 2 * rows or states.dtype != torch.int32 or not states.is_contiguous()):
+        raise ValueError("squelch_run_rows: states must be rows x 2 int32")
+    if final is None:
+        final = torch.empty((rows, 2), dtype=torch.int32, device=det.device)
+    if levels is True:
+        levels = _rows_empty(rows, n_blocks, torch.float32, det.device)
+    if gates is True:
+        gates = _rows_empty(rows, n_blocks, torch.uint8, det.device)
+    ws, ws_ptr, ws_bytes = _rows_workspace(workspace, lib.sdrhip_squelch_rows_workspace_bytes(rows, n_blocks), det.device)
+    check(lib.sdrhip_squelch_run_rows(torch.cuda.current_stream().cuda_stream, _dptr(det), det_stride, int(cplx), block_det,
+                                      _dptr(sig) if sig is not None else None, in_stride, _dptr(out) if sig is not None else None,
+                                      out_stride, block_sig, rows, n_blocks, open_level, close_level, hang_blocks, int(bool(open_above)),
+                                      states.data_ptr() if states is not None else None, final.data_ptr(),
+                                      _dptr(levels) if levels is not None else None, _dptr(gates) if gates is not None else None,
+                                      ws_ptr or None, ws_bytes), "sdrhip_squelch_run_rows")
+    return (out if sig is not None else None), final, levels, gates
+
+
+def squelch_run(det, block_det, sig, block_sig, open_level, close_level, hang_blocks=0, open_above=True, state=(0, 0), levels=None,
+                gates=None):
+    """sdrhip_squelch_run on the current stream -> (out, final, levels, gates): det a 1-D complex64 or float32 device tensor, sig a
+    1-D float32 device tensor (`det` itself for self-detection) or None for detect-only; final a device tensor of two int32."""
+    import torch
+    cplx = det.is_complex()
+    n_blocks = det.numel() // block_det
+    out = None
+    if sig is not None:
+        out = torch.empty(max(n_blocks * block_sig, 1), dtype=torch.float32, device=det.device)[:n_blocks * block_sig]
+    final = torch.empty(2, dtype=torch.int32, device=det.device)
+    if levels is True:
+        levels = torch.empty(max(n_blocks, 1), dtype=torch.float32, device=det.device)[:n_blocks]
+    if gates is True:
+        gates = torch.empty(max(n_blocks, 1), dtype=torch.uint8, device=det.device)[:n_blocks]
+    wsb = lib.sdrhip_squelch_rows_workspace_bytes(1, n_blocks)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=det.device)
+    check(lib.sdrhip_squelch_run(torch.cuda.current_stream().cuda_stream, _dptr(det), int(cplx), block_det,
+                                 _dptr(sig) if sig is not None else None, _dptr(out) if sig is not None else None, block_sig, n_blocks,
+                                 open_level, close_level, hang_blocks, int(bool(open_above)), int(state[0]), int(state[1]), final.data_ptr(),
+                                 _dptr(levels) if levels is not None else None, _dptr(gates) if gates is not None else None,
+                                 ws.data_ptr(), wsb), "sdrhip_squelch_run")
+    return out, final, levels, gates
 
 
 def fm_demod_rows(x, last=None, out=None, last_out=None, in_base=0, k_begin=None, k_end=None):
